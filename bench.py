@@ -11,16 +11,26 @@ A "step" = one pass of the hot path over one batch of 32 synthetic lines per GPU
 all-gather of those records when N > 1).  Workload = BASELINE.json configs[1]: Latin model (C=166), bf16, bs=32, 128x2048,
 random-init name-seeded weights with trained-like head margins (generator v2; no checkpoint ships with the reference).
 Rank 0 prints ONE JSON line on stdout, kept below 6 KB (compact_line: the contract's keys, `roofline` of the dominant kernel, `roofline_msda`,
-`cpu_baseline`, `distributed`, six numbers per engine in `by_dtype`); the FULL result -- everything described below -- is written to
-gpurun_out/bench_detail.json (or ./bench_detail.json) and to stderr.
+`cpu_baseline`, `distributed`, six numbers per engine in `by_dtype`).
 
-timing       : W warm-up steps, then blocks of exactly K steps, each bracketed by barrier + torch.cuda.synchronize() on both
-               sides and reduced with MAX over ranks.  The block is repeated until >= 2 s have been timed (a 20-step block is
-               0.2 s: one clock ramp away from noise) and the MEDIAN block is reported: ms_per_step = median block / K,
-               value = global lines per block / median block time.  `block_ms` lists every block.
+plain run    : set up, W warm-up steps, the K timed steps, --dump-outputs if given, the result line (metric, value, unit,
+               higher_is_better, dtype, ms_per_step, config, ...).  Nothing else runs: no HIP events are recorded in the timed steps.
+--full       : after the timed steps, everything described below from `data-parallel` on (the dp self-check, rooflines, the
+               MSDA offset-scale sweep, single-line latency, the parity legs, the other engines, the CPU baseline; the
+               deformable-sampling launches are timed with HIP events inside the timed steps); the FULL result is written as JSON
+               (see --detail and write_detail) and to stderr.
+--dump-outputs DIR : what the last timed step computed, as float32 .npy files in DIR (write_outputs): `labels` [n_gpus x B, nq]
+               and `lengths` [n_gpus x B] -- the decode records the step returns, -1 padded -- and rank 0's `pred_logits` /
+               `pred_boxes`.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
+timing       : W warm-up steps, then ONE block of exactly K steps, bracketed by barrier + torch.cuda.synchronize() on both
+               sides and reduced with MAX over ranks: ms_per_step = block / K, value = global lines per block / block time.
+               --min-seconds S repeats the block until >= S s have been timed and reports the MEDIAN block (`block_ms`
+               lists every block); the timed steps are then K x timed_blocks.
 data-parallel: the global batch is ONE seeded list of n_gpus x 32 lines; rank r owns the contiguous shard shard_bounds(r)
                (dtlr_amd/dist.py).  After the timed region rank 0 recomputes every shard itself and compares the all-gathered
-               records bit for bit (`dp_verified`): N-rank output == single-process output on the same lines, in order.
+               records bit for bit (`dp_verified`; --full only, null otherwise): N-rank output == single-process output on the
+               same lines, in order.
 parity       : `parity_vs_oracle` (oracle/parity.py): the CPU oracle runs --parity-lines (16) lines of the benched batch ONCE, with its
                own two-stage selection; every engine is compared against that run twice: `free_running` = the engine's decoded strings
                (its own selection) against the oracle's, as they come out -- `strings_identical_free_running: k/n`, no tolerance, no
@@ -69,7 +79,8 @@ def log(msg: str) -> None:
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 MFMA_PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak (no sparsity); fp32 MFMA (16x16x4_f32) class: 157
 MFMA_PEAK_F32_TFLOPS = 157.0
-MIN_TIMED_SECONDS = 2.0
+MIN_TIMED_SECONDS = 0.0          # one block of exactly --steps steps
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 
 
 def msda_algorithmic_bytes_per_line(S: int, Lq: int, value_elem: int, M=8, D=32, L=4, P=4, ref_dim=2) -> int:
@@ -359,6 +370,26 @@ def parity_vs_oracle(ob, engine_name, out, rows, chinese=False):
     return ob.compare(engine_name, out["pred_logits"][rows], out["pred_boxes"][rows], d["topk_idx"][rows], d["topk_scores"][rows], chinese=chinese)
 
 
+def write_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """--dump-outputs: every array as float32 `out_dir/<name>.npy`.  When they hold more than `limit` bytes in all, each keeps the same
+    fraction of its elements: a fixed seeded sample (sorted flat indices, written beside it as `<name>_sample_index.npy`, float64).
+    Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size * 4 for a in host.values())
+    keep = 1.0 if total <= limit else 0.95 * limit / (total + 8 * sum(a.size for a in host.values()))   # room for the indices
+    written = {}
+    for name, a in host.items():
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * keep)), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = list(a.shape)
+    return written
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher in the environment: start the N ranks ourselves, exactly as the documented
     command does (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...);
@@ -405,7 +436,11 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the parity_vs_oracle legs (an oracle forward of --parity-lines lines on the host)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL); gloo for the single-GPU DP test")
     ap.add_argument("--single-device", action="store_true", help="all ranks use cuda:0 (tests: two ranks on one GPU need gloo)")
-    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS)
+    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS,
+                    help="repeat the block of --steps steps until this many seconds are timed and report the median block (default: one block)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the dp self-check, rooflines, latency, parity legs, the "
+                                                        "other engines and the CPU baseline (each --no-* flag still skips its part)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-bs1", action="store_true", help="skip the single-line latency leg (latency_ms_bs1)")
     ap.add_argument("--detail", default="", help="where the FULL result (roofline_by_kernel, gemm_by_shape, parity objects ...) is written as JSON; "
                                                  "default gpurun_out/bench_detail.json, else ./bench_detail.json.  stdout carries the compact line only")
@@ -531,23 +566,27 @@ def main():
         x, mask = to_batch(imgs)
     padded = chinese or mixed or bool(mask.any().item())
     observed = None
-    if args.weights or args.images:
+    if args.full and (args.weights or args.images):
         # what the synthetic generator only assumes: the backbone's activation peak (fp16 / split engines need < 65504)
         # and how far the encoder's offset heads look (the LDS-window sampler's far fraction at a halo of 8 columns, per layer after calibration)
         f_, l_, _hw = eng.features(x)
         observed = {"backbone_activation_peak": float(max(t.float().abs().max() for t in list(f_) + [l_])), "canvas": [int(x.shape[2]), int(x.shape[3])]}
         del f_, l_
 
+    last_out = {}                        # --dump-outputs: the head outputs of a block's last step (no other step's outputs are kept)
+
     # --single-device: all ranks drive cuda:0 (the 2-ranks-on-one-GPU test; gloo, because RCCL refuses duplicate devices).  Their kernels
     # interleave freely on the device -- round 2 serialised the ranks through a file lock here because ~10% of forwards then differed;
     # the cause (a lane-mask sequence of the decoder's deformable-sampling kernel) is fixed and the lock is gone.
-    def local_step(xx=None, mm=None, debug=False):
+    def local_step(xx=None, mm=None, debug=False, keep=False):
         out = eng.forward(x if xx is None else xx, mask if mm is None else mm, has_padding=padded, return_debug=debug)
         rec = decode_blank_records(out)
+        if keep:
+            last_out["out"] = out
         return (rec, out) if debug else rec
 
-    def step():
-        labels, lengths = local_step()
+    def step(keep=False):
+        labels, lengths = local_step(keep=keep)
         return ddist.all_gather_records(labels, lengths, n_total)
 
     for i in range(args.warmup):
@@ -556,16 +595,17 @@ def main():
         log(f"warm-up step {i} done")
 
     def timed_block():
+        last_out.clear()
         ddist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            r = step()
+        for i in range(args.steps):
+            r = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         torch.cuda.synchronize()
         ddist.barrier()
         return ddist.max_over_ranks(time.perf_counter() - t0, dev), r
 
-    ops.MSDA_EVENTS = []
+    ops.MSDA_EVENTS = [] if args.full else None              # --full: the deformable-sampling launches are timed inside the blocks (roofline)
     first, rec = timed_block()
     blocks = [first]
     # every rank derives the same repeat count from the max-reduced first block
@@ -573,9 +613,49 @@ def main():
     for _ in range(repeats - 1):
         t, rec = timed_block()
         blocks.append(t)
-    events, ops.MSDA_EVENTS = ops.MSDA_EVENTS, None
+    events, ops.MSDA_EVENTS = ops.MSDA_EVENTS or [], None
     elapsed = sorted(blocks)[len(blocks) // 2]
     log(f"timed {len(blocks)} blocks of {args.steps} steps: median {elapsed:.4f}s (min {min(blocks):.4f}, max {max(blocks):.4f})")
+    if args.dump_outputs and rank == 0:
+        o = last_out["out"]
+        written = write_outputs(args.dump_outputs, {"labels": rec[0], "lengths": rec[1], "pred_logits": o["pred_logits"], "pred_boxes": o["pred_boxes"]})
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {written}")
+    last_out.clear()
+
+    line = {
+        "metric": ("text-lines/sec (Chinese 7356-class head, mixed-length 128x2560, bs=32)" if chinese else
+                   "text-lines/sec (Latin, mixed widths padded to 128x2048, bs=32)" if mixed else
+                   f"text-lines/sec (Latin, eval transform: 128x2048 uint8 lines -> {x.shape[2]}x{x.shape[3]} canvases, bs=32)" if evalshape else
+                   "text-lines/sec (128x2048, bs=32)"),
+        "value": round(n_total * args.steps / elapsed, 2), "unit": "lines/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic" if not args.images else f"user images ({os.path.basename(os.path.normpath(args.images))})",
+        "timed_blocks": len(blocks), "block_ms": [round(b * 1e3, 2) for b in blocks],
+        "config": {"workload": (f"Latin DTLR (C=166) forward+decode, {B} synthetic lines per GPU, widths seeded from {{{canvas_w - 768}..{canvas_w}}}, zero-padded to {args.height}x{canvas_w} with masks"
+                                if mixed else
+                                f"Latin DTLR (C=166) forward+decode on the eval-transformed canvas ({x.shape[2]}x{x.shape[3]}; preprocessing {preproc_ms:.3f} ms per batch, outside the timed step), {B} synthetic uint8 {args.height}x{canvas_w} lines per GPU"
+                                if evalshape else
+                                f"Latin DTLR (ResNet-50 + 6/6 deformable DETR, C=166) forward+decode, {B} synthetic {args.height}x{canvas_w} lines per GPU"
+                                if not chinese else
+                                f"Chinese DTLR (C=7356) forward+decode, {B} synthetic lines per GPU, widths seeded from {{{canvas_w - 1024}..{canvas_w}}}, zero-padded to {args.height}x{canvas_w} with masks")
+                               + f", random-init name-seeded weights (generator v{weights.GENERATOR_VERSION})",
+                   "weights": args.weights or f"synthetic, generator v{weights.GENERATOR_VERSION}", "images": args.images or "synthetic noise lines (seed 1000)",
+                   "canvas": [int(x.shape[2]), int(x.shape[3])], "num_classes": cfg.num_classes,
+                   "backbone": cfg.backbone, "engine_opts": args.engine_opt, "global_batch": n_total, "parallelism": f"dp{world}",
+                   "library_backed_ops": sorted(ops.LIBRARY_BACKED)},
+        "distributed": {"backend": tdist.get_backend() if (tdist.is_available() and tdist.is_initialized()) else None,
+                        "world_size": tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized()) else 1,
+                        # ranks in the RCCL communicator as torch.distributed reports them (backend "nccl" IS RCCL on ROCm): a first multi-GPU run describes itself
+                        "rccl_ranks": (tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized() and tdist.get_backend() == "nccl") else 0),
+                        "devices_visible": torch.cuda.device_count(),
+                        "dp_verified": None, "host_placement": placement},
+    }
+    if not args.full:                    # a plain run ends here: the headline line only
+        if rank == 0:
+            print(json.dumps(compact_line(line)), flush=True)
+        ddist.finalize()
+        return
 
     # ---- data-parallel self-check: rank 0 recomputes every shard and compares with the gathered records, bit for bit ----
     dp_verified = None
@@ -697,40 +777,14 @@ def main():
     gemm_by_shape.sort(key=lambda r: -r["ms_per_step"])
     # `roofline` = the single KERNEL with the largest share of the step (class rows aggregate many instantiations: never the headline)
     dominant = next((r for r in by_kernel if r.get("symbol")), by_kernel[0] if by_kernel else None)
-    line = {
-        "metric": ("text-lines/sec (Chinese 7356-class head, mixed-length 128x2560, bs=32)" if chinese else
-                   "text-lines/sec (Latin, mixed widths padded to 128x2048, bs=32)" if mixed else
-                   f"text-lines/sec (Latin, eval transform: 128x2048 uint8 lines -> {x.shape[2]}x{x.shape[3]} canvases, bs=32)" if evalshape else
-                   "text-lines/sec (128x2048, bs=32)"),
-        "value": round(n_total * args.steps / elapsed, 2), "unit": "lines/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic" if not args.images else f"user images ({os.path.basename(os.path.normpath(args.images))})",
-        "timed_blocks": len(blocks), "block_ms": [round(b * 1e3, 2) for b in blocks],
-        "config": {"workload": (f"Latin DTLR (C=166) forward+decode, {B} synthetic lines per GPU, widths seeded from {{{canvas_w - 768}..{canvas_w}}}, zero-padded to {args.height}x{canvas_w} with masks"
-                                if mixed else
-                                f"Latin DTLR (C=166) forward+decode on the eval-transformed canvas ({x.shape[2]}x{x.shape[3]}; preprocessing {preproc_ms:.3f} ms per batch, outside the timed step), {B} synthetic uint8 {args.height}x{canvas_w} lines per GPU"
-                                if evalshape else
-                                f"Latin DTLR (ResNet-50 + 6/6 deformable DETR, C=166) forward+decode, {B} synthetic {args.height}x{canvas_w} lines per GPU"
-                                if not chinese else
-                                f"Chinese DTLR (C=7356) forward+decode, {B} synthetic lines per GPU, widths seeded from {{{canvas_w - 1024}..{canvas_w}}}, zero-padded to {args.height}x{canvas_w} with masks")
-                               + f", random-init name-seeded weights (generator v{weights.GENERATOR_VERSION})",
-                   "weights": args.weights or f"synthetic, generator v{weights.GENERATOR_VERSION}", "images": args.images or "synthetic noise lines (seed 1000)",
-                   "canvas": [int(x.shape[2]), int(x.shape[3])], "num_classes": cfg.num_classes,
-                   "backbone": cfg.backbone, "engine_opts": args.engine_opt, "global_batch": n_total, "parallelism": f"dp{world}",
-                   "library_backed_ops": sorted(ops.LIBRARY_BACKED)},
-        "distributed": {"backend": tdist.get_backend() if (tdist.is_available() and tdist.is_initialized()) else None,
-                        "world_size": tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized()) else 1,
-                        # ranks in the RCCL communicator as torch.distributed reports them (backend "nccl" IS RCCL on ROCm): a first multi-GPU run describes itself
-                        "rccl_ranks": (tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized() and tdist.get_backend() == "nccl") else 0),
-                        "devices_visible": torch.cuda.device_count(),
-                        "dp_verified": dp_verified, "host_placement": placement},
+    line["distributed"]["dp_verified"] = dp_verified
+    line.update({
         "roofline": dominant,
         # `traffic` figures are PMC measurements looked up from profiles/ (not taken in this run): the file and the commit they were measured at
         "traffic_source": {"file": traffic_file, "measured_at_commit": traffic_db.get("_commit"), "attached": bool(traffic_ok)},
         "roofline_by_kernel": by_kernel,
         "gemm_by_shape": gemm_by_shape[:24],
-    }
+    })
     if world == 1 and args.dtype in ("bf16", "f16") and not cfg.is_swin:
         try:                                                    # the MSDA figure above is the synthetic weights' best case: show the other cases beside it
             lhw = [tuple(int(v) for v in hw) for hw in eng._shape_cache[next(iter(eng._shape_cache))]["level_hw"]] if eng._shape_cache else None

@@ -603,7 +603,7 @@ def test_data_parallel_two_ranks_on_one_gpu_equals_single_process():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3",
-           "--backend", "gloo", "--single-device", "--no-cpu-baseline", "--no-parity", "--min-seconds", "0"]
+           "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline", "--no-parity", "--min-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -621,7 +621,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3",
-           "--backend", "gloo", "--single-device", "--no-cpu-baseline", "--no-parity", "--min-seconds", "0"]
+           "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline", "--no-parity", "--min-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -632,6 +632,41 @@ def test_bench_gpus_n_starts_its_own_ranks():
     # a failing rank's exit code propagates
     bad = subprocess.run(cmd + ["--engine-opt", "no_such_attribute=1"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert bad.returncode != 0
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py` (no --full): ONE block of exactly --steps timed steps, the contract's keys and nothing that --full adds;
+    --dump-outputs writes what the last timed step computed (decode records, head outputs) as float32 .npy, and those are the engine's
+    outputs for the same seeded batch, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from dtlr_amd.engine import DTLREngine
+    from dtlr_amd.evaluation import decode_blank_records
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["timed_blocks"] == 1 and "timed 1 blocks of 3 steps" in r.stderr
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 2) < 1e-2          # 2 lines per step, one step = ms_per_step
+    assert line["value"] > 0 and line["unit"] == "lines/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["roofline"] is None and line["distributed"]["dp_verified"] is None
+    assert not {"by_dtype", "cpu_baseline", "latency_ms_bs1", "parity_grade"} & set(line)
+    got = {k: np.load(out_dir / f"{k}.npy") for k in ("labels", "lengths", "pred_logits", "pred_boxes")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    cfg = DTLRConfig.latin()
+    eng = DTLREngine(cfg, weights.synthetic_state_dict(cfg, seed=0), "cuda:0", torch.bfloat16)
+    x = torch.stack(synth.noise_lines(2, 128, [2048, 2048], seed=1000, start=0)).cuda()
+    out = eng.forward(x, torch.zeros((2, 128, 2048), dtype=torch.bool, device="cuda:0"), has_padding=False)
+    labels, lengths = decode_blank_records(out)
+    want = {"labels": labels, "lengths": lengths, "pred_logits": out["pred_logits"], "pred_boxes": out["pred_boxes"]}
+    for k, v in want.items():
+        assert np.array_equal(got[k], v.float().cpu().numpy()), k
 
 
 @pytest.mark.parametrize("engine", [torch.float32, "f32s", torch.bfloat16], ids=["f32", "f32s", "bf16"])
@@ -706,7 +741,7 @@ def test_bench_accepts_a_user_checkpoint_and_an_image_folder(tmp_path):
         Image.fromarray(preproc_image(96 + 8 * (k % 2), 1400 + 100 * k, 50 + k), "RGB").save(img_dir / f"line{k:02d}.png")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--dtype", "f32", "--weights",
-           str(tmp_path / "checkpoint.pth"), "--images", str(img_dir), "--no-cpu-baseline", "--no-other-dtypes", "--no-bs1", "--parity-lines", "2",
+           str(tmp_path / "checkpoint.pth"), "--images", str(img_dir), "--full", "--no-cpu-baseline", "--no-other-dtypes", "--no-bs1", "--parity-lines", "2",
            "--min-seconds", "0", "--detail", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

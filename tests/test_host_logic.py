@@ -98,12 +98,15 @@ def test_state_dict_schema_and_determinism():
     m.load_state_dict(extra, strict=True)
 
 
-def test_reference_config_files_parse():
+def test_reference_config_files_parse(tmp_path, golden_dir):
+    """G10 (tests/golden/make_golden_configs.py): the reference's Latin_CTC.py / Chinese.py and their `_base_` file, written back as
+    plain assignment files from the stored settings, parse (with the inheritance) into the Latin / Chinese configurations."""
+    import json
+    g = json.load(open(os.path.join(golden_dir, "g10_reference_configs.json")))
+    for fn, assigns in g["files"].items():
+        (tmp_path / fn).write_text("".join(f"{k} = {v!r}\n" for k, v in assigns.items()))
     for name, C in (("Latin_CTC.py", 166), ("Chinese.py", 7356)):
-        p = os.path.join("/root/reference/config", name)
-        if not os.path.exists(p):
-            pytest.skip("reference configs not present")
-        cfg = DTLRConfig.from_reference_file(p)
+        cfg = DTLRConfig.from_reference_file(str(tmp_path / name))
         assert cfg.num_classes == C and cfg.num_queries == 900 and cfg.enc_layers == 6 and cfg.pe_temperatureH == 20
 
 
@@ -732,6 +735,33 @@ def test_bench_stdout_line_stays_below_6kb_whatever_the_detail_holds():
     broken["by_dtype"]["f32"] = {"error": "RuntimeError(" + "x" * 5000 + ")"}
     assert len(json.dumps(bench.compact_line(broken))) < bench.STDOUT_LINE_LIMIT
     assert "error" in bench.compact_line(broken)["by_dtype"]["f32"]
+
+
+def test_bench_write_outputs_float32_and_a_fixed_sample_above_the_limit(tmp_path):
+    """bench.py --dump-outputs (bench.write_outputs): every array as float32 <name>.npy, values as given (int32 records included); above
+    the byte limit each array keeps the same fraction of its elements, a seeded sample written beside its sorted flat indices (float64),
+    identical from run to run, and the files stay within the limit."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(3)
+    arrays = {"labels": torch.randint(-1, 166, (4, 900), generator=g, dtype=torch.int32),
+              "pred_logits": torch.randn((4, 900, 166), generator=g).bfloat16()}
+    small = bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert small == {"labels": [4, 900], "pred_logits": [4, 900, 166]}
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    assert not any(p.name.endswith("_sample_index.npy") for p in (tmp_path / "a").iterdir())
+    limit = 400_000
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), arrays, limit=limit)
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= limit
+    for k, v in arrays.items():
+        vals, idx = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}_sample_index.npy")
+        assert vals.dtype == np.float32 and idx.dtype == np.float64 and 0 < len(vals) == len(idx) < v.numel()
+        assert np.all(np.diff(idx) > 0) and np.array_equal(vals, v.float().numpy().reshape(-1)[idx.astype(np.int64)])
+        assert np.array_equal(vals, np.load(tmp_path / "c" / f"{k}.npy"))
 
 
 def test_split_gemm_lds_swizzle_is_conflict_free_in_the_bank_model():

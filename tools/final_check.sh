@@ -4,6 +4,7 @@
 # usage: [BENCH_EXTRA="--no-cpu-baseline"] [ROUND=r04] bash tools/final_check.sh <tag> [prof-only|no-tests]
 TAG=${1:-vX}
 R4=${ROUND:-r06}
+BENCH_EXTRA="--full $BENCH_EXTRA"             # the bench line with rooflines, parity legs, other engines and the CPU baseline
 cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p gpurun_out
 if [ "$2" != "prof-only" ]; then
@@ -17,7 +18,7 @@ if [ "$2" != "prof-only" ]; then
     timeout 200 python tools/profile_ops.py --dtype $dt --top 60 > gpurun_out/${R4}_ops_by_shape_${dt}_$TAG.txt 2>/dev/null; head -4 gpurun_out/${R4}_ops_by_shape_${dt}_$TAG.txt
   done
   for cfgx in "chinese:--config chinese" "latin_mixed:--config latin-mixed" "latin_eval:--config latin-eval" "swinT:--backbone swin_T_224_1k"; do
-    nm=${cfgx%%:*}; fl=${cfgx#*:}
+    nm=${cfgx%%:*}; fl="--full ${cfgx#*:}"          # the parity legs printed below come with --full
     timeout 400 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-other-dtypes $fl > gpurun_out/${R4}_bench_${nm}_$TAG.json 2>/dev/null
     python - <<P
 import json
