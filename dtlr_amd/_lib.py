@@ -120,6 +120,17 @@ _SIGNATURES = {
     "dtlr_blank_emissions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "dtlr_blank_emissions_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
     "dtlr_decode_blank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    # per-line batching
+    "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dtlr_zero_outside_extent_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dtlr_maxpool3x3s2_nhwc_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dtlr_groupnorm_tokens_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "dtlr_geometry_ext": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtlr_topk_rows_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dtlr_decoder_query_prep_per_line": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dtlr_dec_query_stage_per_line": (c_int, [c_void_p] * 16 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

@@ -126,7 +126,8 @@ __device__ __forceinline__ void dq_sine_quarter(unsigned char* dst, float c, con
     }
 }
 
-template <int NTT>
+// UNSCALED_SINE: the per-line form (dtlr_dec_query_stage_per_line) -- sine embedding of the unscaled reference, ref_in still scaled
+template <int NTT, bool UNSCALED_SINE = false>
 __global__ __launch_bounds__(512) void dec_query_stage_kernel(
     const float* __restrict__ ref, const float* __restrict__ vr, const float* __restrict__ dim_t, const uint16_t* __restrict__ tgt,
     const uint16_t* __restrict__ W0, const float* __restrict__ b0, const uint16_t* __restrict__ W1, const float* __restrict__ b1,
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
             }
         }
     }
-    const float vx0 = vr[(bs * L) * 2], vy0 = vr[(bs * L) * 2 + 1];
+    const float vx0 = UNSCALED_SINE ? 1.f : vr[(bs * L) * 2], vy0 = UNSCALED_SINE ? 1.f : vr[(bs * L) * 2 + 1];
     const float scale = 6.283185307179586f;
     const float cq[4] = {rr.y * vy0 * scale, rr.x * vx0 * scale, rr.z * vx0 * scale, rr.w * vy0 * scale};   // order y, x, w, h
     __syncthreads();                                              // rcp table
@@ -284,10 +285,11 @@ extern "C" int dtlr_dq_pack_weights(const unsigned short* w_host, unsigned short
     return DTLR_OK;
 }
 
-extern "C" int dtlr_dec_query_stage(const float* ref, const float* valid_ratios, const float* dim_t, const void* tgt,
-                                    const void* W0, const float* b0, const void* W1, const float* b1,
-                                    const void* Wqk, const float* bqk, const void* Wv, const float* bv,
-                                    float* ref_in, void* qpos, void* qk, void* v, int B, int nq, int L, int dtype, void* stream)
+template <bool UNSCALED_SINE>
+static int dec_query_stage_launch(const float* ref, const float* valid_ratios, const float* dim_t, const void* tgt,
+                                  const void* W0, const float* b0, const void* W1, const float* b1,
+                                  const void* Wqk, const float* bqk, const void* Wv, const float* bv,
+                                  float* ref_in, void* qpos, void* qk, void* v, int B, int nq, int L, int dtype, void* stream)
 {
     clear_stale_error();
     if (!ref || !valid_ratios || !dim_t || !tgt || !W0 || !b0 || !W1 || !b1 || !Wqk || !bqk || !Wv || !bv || !ref_in || !qpos || !qk || !v)
@@ -301,16 +303,32 @@ extern "C" int dtlr_dec_query_stage(const float* ref, const float* valid_ratios,
         // small batches (round 5; one line = 900 queries = 8 workgroups of 128): workgroups of 32 queries -- the four dependent GEMM stages,
         // the sine quarters and the 64 KB of output per workgroup shrink four-fold, the per-workgroup weight fetch from L2 does not grow
         static DevOnce attrs;
-        if (attrs.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, DqCfg<2>::LDS); (void)hipGetLastError(); }
-        hipLaunchKernelGGL(dec_query_stage_kernel<2>, dim3((unsigned)((Q + 31) / 32)), dim3(512), DqCfg<2>::LDS, (hipStream_t)stream,
+        if (attrs.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<2, UNSCALED_SINE>, hipFuncAttributeMaxDynamicSharedMemorySize, DqCfg<2>::LDS); (void)hipGetLastError(); }
+        hipLaunchKernelGGL((dec_query_stage_kernel<2, UNSCALED_SINE>), dim3((unsigned)((Q + 31) / 32)), dim3(512), DqCfg<2>::LDS, (hipStream_t)stream,
                            ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
                            (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
         return check_launch();
     }
     static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL(dec_query_stage_kernel<8>, dim3((unsigned)grid), dim3(512), DQ_LDS, (hipStream_t)stream,
+    if (attr.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<8, UNSCALED_SINE>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS); (void)hipGetLastError(); }
+    hipLaunchKernelGGL((dec_query_stage_kernel<8, UNSCALED_SINE>), dim3((unsigned)grid), dim3(512), DQ_LDS, (hipStream_t)stream,
                        ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
                        (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
     return check_launch();
+}
+
+extern "C" int dtlr_dec_query_stage(const float* ref, const float* valid_ratios, const float* dim_t, const void* tgt,
+                                    const void* W0, const float* b0, const void* W1, const float* b1,
+                                    const void* Wqk, const float* bqk, const void* Wv, const float* bv,
+                                    float* ref_in, void* qpos, void* qk, void* v, int B, int nq, int L, int dtype, void* stream)
+{
+    return dec_query_stage_launch<false>(ref, valid_ratios, dim_t, tgt, W0, b0, W1, b1, Wqk, bqk, Wv, bv, ref_in, qpos, qk, v, B, nq, L, dtype, stream);
+}
+
+extern "C" int dtlr_dec_query_stage_per_line(const float* ref, const float* valid_ratios, const float* dim_t, const void* tgt,
+                                             const void* W0, const float* b0, const void* W1, const float* b1,
+                                             const void* Wqk, const float* bqk, const void* Wv, const float* bv,
+                                             float* ref_in, void* qpos, void* qk, void* v, int B, int nq, int L, int dtype, void* stream)
+{
+    return dec_query_stage_launch<true>(ref, valid_ratios, dim_t, tgt, W0, b0, W1, b1, Wqk, bqk, Wv, bv, ref_in, qpos, qk, v, B, nq, L, dtype, stream);
 }

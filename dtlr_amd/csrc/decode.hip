@@ -15,6 +15,14 @@ __device__ __forceinline__ uint32_t f32_sortable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// selection key of row element i: (~sortable(score) << 32) | i.  An excluded element (excl_row[i] != 0, dtlr_topk_rows_masked) gets the
+// largest score part, 0xffffffff: it ranks after every score and is never selected while at least k elements are not excluded (with
+// fewer, the excluded ones fill the tail in index order -- indices stay in range).
+__device__ __forceinline__ unsigned long long topk_key(float v, long i, const uint8_t* __restrict__ excl_row) {
+    const uint32_t hi = (excl_row && excl_row[i]) ? 0xffffffffu : ~f32_sortable(v);
+    return ((unsigned long long)hi << 32) | (unsigned long long)i;
+}
+
 // in-LDS bitonic sort of n = power of two 64-bit keys, ascending.  A thread owns compare-exchange PAIRS (pair t of stage j is
 // i = the index with bit j cleared, i | j), four at a time, and reads all eight keys before it writes any: one LDS round trip
 // per stage instead of one per element (the element-wise form serialised 8 dependent read->write trips per stage at n = 8192
@@ -51,7 +59,7 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int n
 // instead of the 8192-key one, 91 stages at 8x the traffic: the full sort was LDS-bandwidth bound at ~80 us).
 // KP2 = next_pow2(k) ; when KP2 >= npow2 the row is simply sorted whole.
 __global__ __launch_bounds__(1024) void topk_rows_kernel(const float* __restrict__ scores, long* __restrict__ idx_out,
-                                                         int S, int k, int npow2, int kp2)
+                                                         int S, int k, int npow2, int kp2, const uint8_t* __restrict__ excl)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // [npow2] row keys, then [kp2] candidates
     __shared__ int hist[256];
@@ -59,8 +67,9 @@ __global__ __launch_bounds__(1024) void topk_rows_kernel(const float* __restrict
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* row = scores + (long)b * S;
+    const uint8_t* erow = excl ? excl + (long)b * S : nullptr;
     for (int i = threadIdx.x; i < npow2; i += blockDim.x)
-        keys[i] = i < S ? (((unsigned long long)(~f32_sortable(row[i]))) << 32) | (unsigned)i : ~0ull;
+        keys[i] = i < S ? topk_key(row[i], i, erow) : ~0ull;
     if (kp2 >= npow2) {
         bitonic_sort_u64(keys, npow2);
         for (int i = threadIdx.x; i < k; i += blockDim.x) idx_out[(long)b * k + i] = (long)(keys[i] & 0xffffffffull);
@@ -123,7 +132,8 @@ __global__ __launch_bounds__(1024) void topk_rows_kernel(const float* __restrict
 // the probabilities, descending, with ties ordered by logit and then by lower index).  k <= 8192 (the survivors' sort lives in LDS).
 // Also the large-S path of dtlr_topk_rows (rows too long for an LDS copy), with values == nullptr.
 __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict__ x, float* __restrict__ values, long* __restrict__ idx_out,
-                                                         long n, int k, int kp2, int index_bytes, int apply_sigmoid)
+                                                         long n, int k, int kp2, int index_bytes, int apply_sigmoid,
+                                                         const uint8_t* __restrict__ excl = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long cand[];      // [kp2]
     __shared__ int hist[256];
@@ -131,6 +141,7 @@ __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* row = x + (long)b * n;
+    const uint8_t* erow = excl ? excl + (long)b * n : nullptr;
     unsigned long long pref = 0ull, mask = 0ull;
     int rem = k;
     const int npass = 4 + index_bytes;
@@ -139,7 +150,7 @@ __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict
         if (threadIdx.x < 256) hist[threadIdx.x] = 0;
         __syncthreads();
         for (long i = threadIdx.x; i < n; i += blockDim.x) {
-            const unsigned long long key = (((unsigned long long)(~f32_sortable(row[i]))) << 32) | (unsigned long long)i;
+            const unsigned long long key = topk_key(row[i], i, erow);
             if ((key & mask) == pref) atomicAdd(&hist[(int)(key >> (8 * byte)) & 255], 1);
         }
         __syncthreads();
@@ -167,7 +178,7 @@ __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict
     __syncthreads();
     for (long i0 = 0; i0 < n; i0 += blockDim.x) {
         const long i = i0 + threadIdx.x;
-        const unsigned long long key = i < n ? (((unsigned long long)(~f32_sortable(row[i]))) << 32) | (unsigned long long)i : ~0ull;
+        const unsigned long long key = i < n ? topk_key(row[i], i, erow) : ~0ull;
         const bool sel = key <= pref;
         const unsigned long long m = __ballot(sel);
         int base = 0;
@@ -490,7 +501,7 @@ static inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p;
 
 using namespace dtlr;
 
-extern "C" int dtlr_topk_rows(const float* scores, long* idx_out, int B, int S, int k, void* stream)
+static int topk_rows_launch(const float* scores, const unsigned char* excl, long* idx_out, int B, int S, int k, void* stream)
 {
     clear_stale_error();
     if (!scores || !idx_out) return DTLR_EINVAL;
@@ -505,14 +516,26 @@ extern "C" int dtlr_topk_rows(const float* scores, long* idx_out, int B, int S, 
         while (index_bytes < 4 && ((long)S - 1) >> (8 * index_bytes)) ++index_bytes;
         const size_t fl = (size_t)kp * 8;
         if (fl > 48 * 1024) { (void)hipFuncSetAttribute((const void*)topk_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl); (void)hipGetLastError(); }
-        hipLaunchKernelGGL(topk_flat_kernel, dim3(B), dim3(1024), fl, (hipStream_t)stream, scores, (float*)nullptr, idx_out, (long)S, k, kp, index_bytes, 0);
+        hipLaunchKernelGGL(topk_flat_kernel, dim3(B), dim3(1024), fl, (hipStream_t)stream, scores, (float*)nullptr, idx_out, (long)S, k, kp, index_bytes, 0,
+                           excl);
         return check_launch();
     }
     (void)hipGetLastError();                                   // do not inherit a stale error from an earlier API call
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)topk_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, scores, idx_out, S, k, np, kp);
+    hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, scores, idx_out, S, k, np, kp, excl);
     return check_launch();
+}
+
+extern "C" int dtlr_topk_rows(const float* scores, long* idx_out, int B, int S, int k, void* stream)
+{
+    return topk_rows_launch(scores, nullptr, idx_out, B, S, k, stream);
+}
+
+extern "C" int dtlr_topk_rows_masked(const float* scores, const unsigned char* excl, long* idx_out, int B, int S, int k, void* stream)
+{
+    if (!excl) return DTLR_EINVAL;
+    return topk_rows_launch(scores, excl, idx_out, B, S, k, stream);
 }
 
 extern "C" int dtlr_decode_blank(const float* logits, const float* boxes, int* labels, int* lengths,

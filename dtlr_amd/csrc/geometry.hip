@@ -42,29 +42,45 @@ template <> struct GeoOut<uint16_t> {
 
 // mask [B,H,W] uint8 (1 = padding) ; level_embed [4,256] fp32 ; dim_t [128] fp32 (temperature^(2 (i/2) / 128): y table then x table
 // are passed separately) ; outputs: see dtlr_geometry in include/dtlr_hip.h
-template <typename OutT>
+// EXT (dtlr_geometry_ext, per-line batches): the level masks are not interpolated from `mask` but are the line extents at the level's
+// stride, ext [B,2] (h, w) -> level q pads token (i, j) iff i >= ceil(h / 2^(s0+q)) or j >= ceil(w / 2^(s0+q)): the convolution output
+// extent, so the valid ratios are w_q / W_q exactly and every in-extent token gets the values of the line run alone.
+template <typename OutT, bool EXT = false>
 __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict__ mask, int H, int W, GeoLevels lv, int S,
                                                        const float* __restrict__ level_embed, const float* __restrict__ dim_ty,
                                                        const float* __restrict__ dim_tx,
                                                        uint8_t* __restrict__ mask_flat, uint8_t* __restrict__ keep, OutT* __restrict__ pos,
                                                        float* __restrict__ valid_ratios, float* __restrict__ enc_ref,
-                                                       float* __restrict__ proposals)
+                                                       float* __restrict__ proposals, const int* __restrict__ ext = nullptr, int s0 = 0)
 {
     __shared__ int s_cnt[8];
     __shared__ int s_wtot[4];
     __shared__ float s_xe[256], s_ye[256];
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t* mb = mask + (long)b * H * W;
+    const uint8_t* mb = EXT ? nullptr : mask + (long)b * H * W;
 
     // which (level, row) is this workgroup?
     int l = 0, row = blockIdx.x;
     while (l < 3 && row >= lv.H[l]) { row -= lv.H[l]; ++l; }
     const int h = lv.H[l], w = lv.W[l];
+    int eh = 0, ew = 0;                                          // EXT: this level's extent
+    if constexpr (EXT) {
+        const int sl = s0 + l;
+        eh = min((ext[2 * b] + (1 << sl) - 1) >> sl, h);
+        ew = min((ext[2 * b + 1] + (1 << sl) - 1) >> sl, w);
+    }
 
     // ---- valid width (row 0) / height (column 0) of every level ----------------------------------------------------
     if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
     __syncthreads();
+    if constexpr (EXT) {
+        if (threadIdx.x < 4) {
+            const int q = threadIdx.x, sq = s0 + q;
+            s_cnt[2 * q] = min((ext[2 * b + 1] + (1 << sq) - 1) >> sq, lv.W[q]);
+            s_cnt[2 * q + 1] = min((ext[2 * b] + (1 << sq) - 1) >> sq, lv.H[q]);
+        }
+    } else {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int hq = lv.H[q], wq = lv.W[q];
@@ -75,6 +91,7 @@ __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { cw += __shfl_xor(cw, o, 64); ch += __shfl_xor(ch, o, 64); }
         if (lane == 0) { if (cw) atomicAdd(&s_cnt[2 * q], cw); if (ch) atomicAdd(&s_cnt[2 * q + 1], ch); }
+    }
     }
     __syncthreads();
     float vrw[4], vrh[4];
@@ -99,15 +116,15 @@ __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict
 #pragma unroll
     for (int e = 0; e < 8; ++e) le[e] = level_embed[l * 256 + cg * 8 + e];
 
-    const int sy = nearest_src(row, H, h);
+    const int sy = EXT ? 0 : nearest_src(row, H, h);
     const float scale = 6.283185307179586f;                      // 2 * math.pi as the fp32 scalar torch multiplies with
     const float wh_l = 0.05f * (float)(1 << l);
     int carry = 0;
     for (int c0 = 0; c0 < w; c0 += 256) {
         const int j = c0 + threadIdx.x;
         const bool live = j < w;
-        const int sx = live ? nearest_src(j, W, w) : 0;
-        const bool pad = live ? mb[(long)sy * W + sx] != 0 : true;
+        const int sx = (live && !EXT) ? nearest_src(j, W, w) : 0;
+        const bool pad = live ? (EXT ? (row >= eh || j >= ew) : mb[(long)sy * W + sx] != 0) : true;
         // x_embed: inclusive count of unpadded pixels of this row up to j
         const unsigned long long bal = __ballot(live && !pad);
         const int within = __popcll(bal & ((2ull << lane) - 1ull));
@@ -116,7 +133,7 @@ __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict
         int ycum = 0, ytot = 0;
         if (live)
             for (int i = 0; i < h; ++i) {
-                const int v = mb[(long)nearest_src(i, H, h) * W + sx] ? 0 : 1;
+                const int v = EXT ? (i < eh && j < ew ? 1 : 0) : (mb[(long)nearest_src(i, H, h) * W + sx] ? 0 : 1);
                 ytot += v;
                 if (i <= row) ycum += v;
             }
@@ -157,7 +174,7 @@ __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict
         int rowtot = carry;
         for (int c1 = c0 + 256; c1 < w; c1 += 256) {
             const int j1 = c1 + threadIdx.x;
-            const bool v1 = j1 < w && mb[(long)sy * W + nearest_src(j1, W, w)] == 0;
+            const bool v1 = j1 < w && (EXT ? (row < eh && j1 < ew) : mb[(long)sy * W + nearest_src(j1, W, w)] == 0);
             const unsigned long long b1 = __ballot(v1);
             if (lane == 0) s_wtot[wave] = __popcll(b1);
             __syncthreads();
@@ -188,15 +205,16 @@ __global__ __launch_bounds__(256) void geometry_kernel(const uint8_t* __restrict
 
 using namespace dtlr;
 
-extern "C" int dtlr_geometry(const unsigned char* mask, int B, int H, int W, const int* level_hw,
-                             const float* level_embed, const float* dim_ty, const float* dim_tx, int pos_dtype,
-                             unsigned char* mask_flat, unsigned char* keep, void* pos, float* valid_ratios,
-                             float* enc_ref, float* proposals, void* stream)
+template <bool EXT>
+static int geometry_launch(const unsigned char* mask, const int* ext, int s0, int B, int H, int W, const int* level_hw,
+                           const float* level_embed, const float* dim_ty, const float* dim_tx, int pos_dtype,
+                           unsigned char* mask_flat, unsigned char* keep, void* pos, float* valid_ratios,
+                           float* enc_ref, float* proposals, void* stream)
 {
     clear_stale_error();
-    if (!mask || !level_hw || !level_embed || !dim_ty || !dim_tx || !mask_flat || !keep || !pos || !valid_ratios || !enc_ref || !proposals)
+    if ((EXT ? !ext : !mask) || !level_hw || !level_embed || !dim_ty || !dim_tx || !mask_flat || !keep || !pos || !valid_ratios || !enc_ref || !proposals)
         return DTLR_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0) return DTLR_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || s0 < 0 || s0 > 12) return DTLR_EINVAL;
     GeoLevels lv;
     int S = 0, rows = 0;
     for (int l = 0; l < 4; ++l) {
@@ -208,12 +226,30 @@ extern "C" int dtlr_geometry(const unsigned char* mask, int B, int H, int W, con
     if (B > 65535) return DTLR_ESHAPE;
     const dim3 grid(rows, B);
     if (pos_dtype == DTLR_H16)
-        hipLaunchKernelGGL(geometry_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
-                           mask_flat, keep, (uint16_t*)pos, valid_ratios, enc_ref, proposals);
+        hipLaunchKernelGGL((geometry_kernel<uint16_t, EXT>), grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
+                           mask_flat, keep, (uint16_t*)pos, valid_ratios, enc_ref, proposals, ext, s0);
     else if (pos_dtype == DTLR_F32)
-        hipLaunchKernelGGL(geometry_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
-                           mask_flat, keep, (float*)pos, valid_ratios, enc_ref, proposals);
+        hipLaunchKernelGGL((geometry_kernel<float, EXT>), grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
+                           mask_flat, keep, (float*)pos, valid_ratios, enc_ref, proposals, ext, s0);
     else
         return DTLR_EDTYPE;
     return check_launch();
+}
+
+extern "C" int dtlr_geometry(const unsigned char* mask, int B, int H, int W, const int* level_hw,
+                             const float* level_embed, const float* dim_ty, const float* dim_tx, int pos_dtype,
+                             unsigned char* mask_flat, unsigned char* keep, void* pos, float* valid_ratios,
+                             float* enc_ref, float* proposals, void* stream)
+{
+    return geometry_launch<false>(mask, nullptr, 0, B, H, W, level_hw, level_embed, dim_ty, dim_tx, pos_dtype, mask_flat, keep, pos,
+                                  valid_ratios, enc_ref, proposals, stream);
+}
+
+extern "C" int dtlr_geometry_ext(const int* ext, int s0, int B, const int* level_hw,
+                                 const float* level_embed, const float* dim_ty, const float* dim_tx, int pos_dtype,
+                                 unsigned char* mask_flat, unsigned char* keep, void* pos, float* valid_ratios,
+                                 float* enc_ref, float* proposals, void* stream)
+{
+    return geometry_launch<true>(nullptr, ext, s0, B, 1, 1, level_hw, level_embed, dim_ty, dim_tx, pos_dtype, mask_flat, keep, pos,
+                                 valid_ratios, enc_ref, proposals, stream);
 }

@@ -9,7 +9,9 @@ namespace dtlr {
 //   sine[q, :]      = [emb(y) | emb(x) | emb(w) | emb(h)] of ref_in[q, 0, :],  emb(c)[i] = sin/cos(c * 2pi / dim_t[i])
 // one thread per (query, frequency pair): 64 pairs x 4 coordinates; dim_t comes from the host so it is
 // bit-identical to the table torch builds (10000 ** (2*(i//2)/128) in fp32).
-template <typename OT>
+// UNSCALED_SINE (per-line batches): the sine embedding of the UNscaled reference -- the line alone has valid ratios 1 -- while
+// ref_in keeps ref * valid_ratios, the same pixel coordinates in the canvas as alone.
+template <typename OT, bool UNSCALED_SINE = false>
 __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict__ ref, const float* __restrict__ vr,
                                                          const float* __restrict__ dim_t, float* __restrict__ ref_in,
                                                          OT* __restrict__ sine, int nq, int L, long total)
@@ -24,7 +26,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
         const float vx = vr[(b * L + pair) * 2], vy = vr[(b * L + pair) * 2 + 1];
         *reinterpret_cast<float4*>(ref_in + (q * L + pair) * 4) = make_float4(r.x * vx, r.y * vy, r.z * vx, r.w * vy);
     }
-    const float vx0 = vr[(b * L) * 2], vy0 = vr[(b * L) * 2 + 1];
+    const float vx0 = UNSCALED_SINE ? 1.f : vr[(b * L) * 2], vy0 = UNSCALED_SINE ? 1.f : vr[(b * L) * 2 + 1];
     const float scale = 6.283185307179586f;           // 2*pi, as `scale = 2 * math.pi` rounded to fp32 by torch
     const float c[4] = {r.y * vy0 * scale, r.x * vx0 * scale, r.z * vx0 * scale, r.w * vy0 * scale};   // order y, x, w, h
     const float d0 = dim_t[2 * pair], d1 = dim_t[2 * pair + 1];
@@ -167,8 +169,9 @@ extern "C" int dtlr_box_head_refine(const float* h, const float* W, const float*
     return check_launch();
 }
 
-extern "C" int dtlr_decoder_query_prep(const float* ref, const float* valid_ratios, const float* dim_t,
-                                       float* ref_in, void* sine, int B, int nq, int L, int sine_dtype, void* stream)
+template <bool UNSCALED_SINE>
+static int query_prep_launch(const float* ref, const float* valid_ratios, const float* dim_t,
+                             float* ref_in, void* sine, int B, int nq, int L, int sine_dtype, void* stream)
 {
     clear_stale_error();
     if (!ref || !valid_ratios || !dim_t || !ref_in || !sine) return DTLR_EINVAL;
@@ -177,11 +180,23 @@ extern "C" int dtlr_decoder_query_prep(const float* ref, const float* valid_rati
     const long grid = (total + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
     if (sine_dtype == DTLR_H16)
-        hipLaunchKernelGGL((query_prep_kernel<uint16_t>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (uint16_t*)sine, nq, L, total);
+        hipLaunchKernelGGL((query_prep_kernel<uint16_t, UNSCALED_SINE>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (uint16_t*)sine, nq, L, total);
     else if (sine_dtype == DTLR_F32)
-        hipLaunchKernelGGL((query_prep_kernel<float>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (float*)sine, nq, L, total);
+        hipLaunchKernelGGL((query_prep_kernel<float, UNSCALED_SINE>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (float*)sine, nq, L, total);
     else return DTLR_EDTYPE;
     return check_launch();
+}
+
+extern "C" int dtlr_decoder_query_prep(const float* ref, const float* valid_ratios, const float* dim_t,
+                                       float* ref_in, void* sine, int B, int nq, int L, int sine_dtype, void* stream)
+{
+    return query_prep_launch<false>(ref, valid_ratios, dim_t, ref_in, sine, B, nq, L, sine_dtype, stream);
+}
+
+extern "C" int dtlr_decoder_query_prep_per_line(const float* ref, const float* valid_ratios, const float* dim_t,
+                                                float* ref_in, void* sine, int B, int nq, int L, int sine_dtype, void* stream)
+{
+    return query_prep_launch<true>(ref, valid_ratios, dim_t, ref_in, sine, B, nq, L, sine_dtype, stream);
 }
 
 extern "C" int dtlr_box_refine(const float* delta, const float* ref, float* out, long n, void* stream)

@@ -172,15 +172,30 @@ extern "C" int dtlr_layernorm(const void* x, const void* residual, const float* 
 // ---------------------------------------------------------------------------------------------
 namespace dtlr {
 
-template <typename T>
-__global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, float2* __restrict__ part, int T_tokens, int rows_per_slab)
+// EXT (per-line batches): the level is [Hl, Wl] tokens (T = Hl Wl) and only line b's extent at stride 2^s -- tokens (y, x) with
+// y < ceil(h / 2^s), x < ceil(w / 2^s) -- enters the statistics; tokens outside it are written as 0 (finite padding rows in 16-bit).
+struct GnExt {
+    const int* ext; int s, Wl;
+    __device__ __forceinline__ int eh(int b) const { return (ext[2 * b] + (1 << s) - 1) >> s; }
+    __device__ __forceinline__ int ew(int b) const { return (ext[2 * b + 1] + (1 << s) - 1) >> s; }
+};
+
+template <typename T, bool EXT = false>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, float2* __restrict__ part, int T_tokens, int rows_per_slab,
+                                                         GnExt ge = GnExt{nullptr, 0, 1})
 {
     __shared__ float2 red[4][32];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slab = blockIdx.x, b = blockIdx.y;
     const int r0 = slab * rows_per_slab, r1 = min(r0 + rows_per_slab, T_tokens);
     float s = 0.f, q = 0.f;
+    int eh = 0, ew = 0;
+    if constexpr (EXT) { eh = ge.eh(b); ew = ge.ew(b); }
     for (int r = r0 + wave; r < r1; r += 4) {
+        if constexpr (EXT) {
+            const int ty = r / ge.Wl;
+            if (ty >= eh || r - ty * ge.Wl >= ew) continue;
+        }
         float v[4];
         IO<T>::load4(x + ((long)b * T_tokens + r) * 256 + 4 * lane, v);
 #pragma unroll
@@ -198,11 +213,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
     }
 }
 
-template <typename T>
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, const float2* __restrict__ part,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        T* __restrict__ y, int T_tokens, int nslab, int rows_per_block, float eps,
-                                                       long y_bstride)
+                                                       long y_bstride, GnExt ge = GnExt{nullptr, 0, 1})
 {
     __shared__ float2 stat[32];                     // (mean, rstd) per group
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -210,7 +225,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
     if (threadIdx.x < 32) {
         double s = 0.0, q = 0.0;
         for (int k = 0; k < nslab; ++k) { const float2 p = part[((long)b * nslab + k) * 32 + threadIdx.x]; s += (double)p.x; q += (double)p.y; }
-        const double n = (double)T_tokens * 8.0;
+        const double n = EXT ? (double)max(ge.eh(b) * ge.ew(b), 1) * 8.0 : (double)T_tokens * 8.0;
         const double mean = s / n;
         double var = q / n - mean * mean;
         if (var < 0.0) var = 0.0;
@@ -234,6 +249,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
             if (r + 4 * u >= r1) break;
             float o[4] = {(v[u][0] - st.x) * st.y * ga.x + be.x, (v[u][1] - st.x) * st.y * ga.y + be.y,
                           (v[u][2] - st.x) * st.y * ga.z + be.z, (v[u][3] - st.x) * st.y * ga.w + be.w};
+            if constexpr (EXT) {
+                const int rr = r + 4 * u, ty = rr / ge.Wl;
+                if (ty >= ge.eh(b) || rr - ty * ge.Wl >= ge.ew(b)) o[0] = o[1] = o[2] = o[3] = 0.f;
+            }
             IO<T>::store4(y + (long)b * y_bstride + (long)(r + 4 * u) * 256 + 4 * lane, o);
         }
     }
@@ -241,9 +260,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 
 // 3x3 stride-2 pad-1 max pooling on NHWC (torchvision resnet50.maxpool as run by backbone.py:97-106);
 // a thread owns VEC channels of one output pixel; padding behaves as -inf.
-template <typename T, int VEC>
+// EXT (per-line batches): line b's input extent at stride 2^s_in is ceil(ext / 2^s_in); taps past it behave as padding (the line alone
+// has no such pixels) and outputs past the output extent (stride 2^(s_in + 1)) are written as 0.  An in-extent output always has an
+// in-extent tap (2 ho < ceil(eh_in / 2) * 2 <= eh_in + 1).
+template <typename T, int VEC, bool EXT = false>
 __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ bias,
-                                                           int relu, int H, int W, int C, int Ho, int Wo, long total)
+                                                           int relu, int H, int W, int C, int Ho, int Wo, long total,
+                                                           const int* __restrict__ ext = nullptr, int s_in = 0)
 {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= total) return;
@@ -253,6 +276,14 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
     const int wo = (int)(p % Wo); p /= Wo;
     const int ho = (int)(p % Ho);
     const long b = p / Ho;
+    int eh = H, ew = W;
+    bool out_ok = true;
+    if constexpr (EXT) {
+        const int lh = ext[2 * b], lw = ext[2 * b + 1];
+        eh = (lh + (1 << s_in) - 1) >> s_in;
+        ew = (lw + (1 << s_in) - 1) >> s_in;
+        out_ok = ho < ((lh + (2 << s_in) - 1) >> (s_in + 1)) && wo < ((lw + (2 << s_in) - 1) >> (s_in + 1));
+    }
     float m[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) m[i] = -INFINITY;
@@ -261,12 +292,12 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
         const int hi = 2 * ho - 1 + kh;
-        const bool hok = hi >= 0 && hi < H;
+        const bool hok = hi >= 0 && hi < H && (!EXT || hi < eh);
         const int hc = min(max(hi, 0), H - 1);
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
             const int wi = 2 * wo - 1 + kw;
-            const bool ok = hok && wi >= 0 && wi < W;
+            const bool ok = hok && wi >= 0 && wi < W && (!EXT || wi < ew);
             float v[VEC];
             const T* src = x + ((b * H + hc) * W + min(max(wi, 0), W - 1)) * C + c0;
             if constexpr (VEC == 8 && sizeof(T) == 2) {               // one 16-byte load (8-byte accesses run at ~0.6x the 16-byte rate)
@@ -290,6 +321,10 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
     if (relu) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) m[i] = fmaxf(m[i], 0.f);
+    }
+    if (EXT && !out_ok) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) m[i] = 0.f;
     }
     T* dst = y + ((b * Ho + ho) * Wo + wo) * C + c0;
     if constexpr (VEC == 8 && sizeof(T) == 2) {
@@ -336,6 +371,55 @@ extern "C" int dtlr_groupnorm_tokens_strided(const void* x, const float* gamma, 
         hipLaunchKernelGGL((gn_partial_kernel<uint16_t>), dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab);
         hipLaunchKernelGGL((gn_apply_kernel<uint16_t>), dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta, (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs);
     } else return DTLR_EDTYPE;
+    return check_launch();
+}
+
+extern "C" int dtlr_groupnorm_tokens_ext(const void* x, const float* gamma, const float* beta, void* y, long y_batch_stride,
+                                         void* workspace, const int* ext, int s, int Hl, int Wl, int B, int C, int groups, float eps,
+                                         int dtype, void* stream)
+{
+    clear_stale_error();
+    if (!x || !gamma || !beta || !y || !workspace || !ext) return DTLR_EINVAL;
+    if (B <= 0 || Hl <= 0 || Wl <= 0 || s < 0 || s > 16) return DTLR_EINVAL;
+    if (C != 256 || groups != 32) return DTLR_ESHAPE;
+    const int T_tokens = Hl * Wl;
+    const long ybs = y_batch_stride > 0 ? y_batch_stride : (long)T_tokens * 256;
+    if (ybs < (long)T_tokens * 256) return DTLR_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows_per_slab = 64;
+    const int nslab = (T_tokens + rows_per_slab - 1) / rows_per_slab;
+    const int rows_per_block = 32;
+    const int nblk = (T_tokens + rows_per_block - 1) / rows_per_block;
+    const GnExt ge{ext, s, Wl};
+    if (dtype == DTLR_F32) {
+        hipLaunchKernelGGL((gn_partial_kernel<float, true>), dim3(nslab, B), dim3(256), 0, st, (const float*)x, (float2*)workspace, T_tokens, rows_per_slab, ge);
+        hipLaunchKernelGGL((gn_apply_kernel<float, true>), dim3(nblk, B), dim3(256), 0, st, (const float*)x, (const float2*)workspace, gamma, beta, (float*)y,
+                           T_tokens, nslab, rows_per_block, eps, ybs, ge);
+    } else if (dtype == DTLR_H16) {
+        hipLaunchKernelGGL((gn_partial_kernel<uint16_t, true>), dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab, ge);
+        hipLaunchKernelGGL((gn_apply_kernel<uint16_t, true>), dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta,
+                           (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs, ge);
+    } else return DTLR_EDTYPE;
+    return check_launch();
+}
+
+extern "C" int dtlr_maxpool3x3s2_nhwc_ext(const void* x, void* y, const float* bias, int relu, const int* ext, int s_in,
+                                          int B, int H, int W, int C, int dtype, void* stream)
+{
+    clear_stale_error();
+    if (!x || !y || !ext) return DTLR_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || s_in < 0 || s_in > 15) return DTLR_EINVAL;
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DTLR_H16 && C % 8 == 0) {
+        const long total = (long)B * Ho * Wo * (C / 8);
+        hipLaunchKernelGGL((maxpool3x3s2_kernel<uint16_t, 8, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           (const uint16_t*)x, (uint16_t*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
+    } else if (dtype == DTLR_F32 && C % 4 == 0) {
+        const long total = (long)B * Ho * Wo * (C / 4);
+        hipLaunchKernelGGL((maxpool3x3s2_kernel<float, 4, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           (const float*)x, (float*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
+    } else return (dtype == DTLR_H16 || dtype == DTLR_F32) ? DTLR_ESHAPE : DTLR_EDTYPE;
     return check_launch();
 }
 

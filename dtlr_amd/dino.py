@@ -13,7 +13,7 @@ forward is executed by the HIP/ROCm operators on the GPU.  There is no CPU path.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -26,14 +26,16 @@ from .ms_deform_attn import MSDeformAttn
 
 # ------------------------------------------------------------------------------- util/misc.py
 class NestedTensor(object):
-    def __init__(self, tensors, mask: Optional[torch.Tensor], has_padding: bool = True):
+    def __init__(self, tensors, mask: Optional[torch.Tensor], has_padding: bool = True, sizes: Optional[List[Tuple[int, int]]] = None):
         self.tensors, self.mask = tensors, mask
         # host-side knowledge that mask is all-False lets the engine skip the value masked_fill
         # (ms_deform_attn.py:95-96) without a device sync; True = unknown / padded
         self.has_padding = has_padding
+        # host list of every image's (h, w) inside the canvas, when the producer knows it (None = unknown)
+        self.sizes = None if sizes is None else [(int(h), int(w)) for h, w in sizes]
 
     def to(self, device):
-        return NestedTensor(self.tensors.to(device), None if self.mask is None else self.mask.to(device))
+        return NestedTensor(self.tensors.to(device), None if self.mask is None else self.mask.to(device), sizes=self.sizes)
 
     def decompose(self):
         return self.tensors, self.mask
@@ -51,7 +53,8 @@ def nested_tensor_from_tensor_list(tensor_list) -> NestedTensor:
         if tensor_list.ndim != 4:
             raise ValueError("not supported")
         b, c, h, w = tensor_list.shape
-        return NestedTensor(tensor_list, torch.zeros((b, h, w), dtype=torch.bool, device=tensor_list.device), has_padding=False)
+        return NestedTensor(tensor_list, torch.zeros((b, h, w), dtype=torch.bool, device=tensor_list.device), has_padding=False,
+                            sizes=[(h, w)] * b)
     if tensor_list[0].ndim != 3:
         raise ValueError("not supported")
     c = tensor_list[0].shape[0]
@@ -64,7 +67,7 @@ def nested_tensor_from_tensor_list(tensor_list) -> NestedTensor:
         tensor[i, :, : img.shape[1], : img.shape[2]].copy_(img)
         mask[i, : img.shape[1], : img.shape[2]] = False
     padded = any(tuple(t.shape[1:]) != (h, w) for t in tensor_list)
-    return NestedTensor(tensor, mask, has_padding=padded)
+    return NestedTensor(tensor, mask, has_padding=padded, sizes=[(int(t.shape[1]), int(t.shape[2])) for t in tensor_list])
 
 
 # ------------------------------------------------------------------- parameter containers
@@ -300,9 +303,10 @@ class DINO(nn.Module):
 
     @torch.no_grad()
     def forward(self, samples, targets: List = None, forced_topk: Optional[torch.Tensor] = None,
-                return_debug: bool = False) -> Dict[str, torch.Tensor]:
+                return_debug: bool = False, per_line: bool = False) -> Dict[str, torch.Tensor]:
         """samples: NestedTensor | Tensor[B,3,H,W] | list[Tensor[3,h,w]] (models/dino/dino.py:270-288).
-        targets must be None (inference; denoising queries are training-only, dn_components.py:135-140)."""
+        targets must be None (inference; denoising queries are training-only, dn_components.py:135-140).
+        per_line: every line gets the result it would get alone (DTLREngine.forward); the reference's padded-batch semantics otherwise."""
         if targets is not None:
             raise NotImplementedError("dtlr_amd.DINO is inference-only: targets must be None")
         if self.training:
@@ -313,7 +317,7 @@ class DINO(nn.Module):
         x, mask = samples.decompose()
         ops.require_cuda(x, "samples")
         out = eng.forward(x.float(), mask, forced_topk=forced_topk, want_aux=self.return_aux, return_debug=return_debug,
-                          has_padding=getattr(samples, "has_padding", True))
+                          has_padding=getattr(samples, "has_padding", True), per_line=per_line, sizes=getattr(samples, "sizes", None))
         if not self.return_aux:
             out["aux_outputs"] = []
         return out

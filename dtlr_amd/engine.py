@@ -426,7 +426,7 @@ class DTLREngine:
         h = self._lin(q + "ff1", x, relu=True)
         return self._ln(q + norm, self._lin(q + "ff2", h), residual=x)
 
-    def backbone(self, x_nchw) -> List[torch.Tensor]:
+    def backbone(self, x_nchw, ext=None) -> List[torch.Tensor]:
         """torchvision resnet50 (v1.5) body with FrozenBN folded; returns layer2/3/4 maps, NHWC
         (models/dino/backbone.py:97-106,118-120)."""
         # stem: own kernels for both engines, reading the NCHW fp32 image directly (bf16: MFMA; fp32: exact direct convolution);
@@ -435,11 +435,13 @@ class DTLREngine:
         # (Round 5 tried the HBM-heavy front -- stem + layer1 + layer2, 268 MB maps at B = 32 -- per group of 4 / 8 / 16 images so that a
         # producer's map would still be in the 256 MiB Infinity Cache when its consumer reads it: 8.66 -> 9.74 / 9.08 / 8.86 ms per step;
         # the smaller launches lose more than the cache returns.  tools/experiments/gpu_calls/r05_call3.sh, profiles/r05_bb_group_c3.txt.)
-        x = self._stem(x_nchw)
-        return self._backbone_layers(x, 1, len(self.cfg.backbone_blocks))
+        x = self._stem(x_nchw, ext)
+        return self._backbone_layers(x, 1, len(self.cfg.backbone_blocks), ext)
 
-    def _stem(self, x_nchw):
-        if "conv1.frag" in self.w and self.use_stem_pool:
+    def _stem(self, x_nchw, ext=None):
+        """ext (per-line batches, [B, 2] line extents): the pool window skips stem outputs past each line's stride-2 extent -- they are
+        not padding (the 7x7 receptive field still covers image pixels), but the line alone has no such outputs."""
+        if "conv1.frag" in self.w and self.use_stem_pool and ext is None:
             return ops.stem_conv7x7_pool(x_nchw, self.w["conv1.frag"], self.w["conv1.b"], self.dtype)
         if "conv1.frag" in self.w:
             x = ops.stem_conv7x7(x_nchw, self.w["conv1.frag"], self.dtype)
@@ -447,18 +449,23 @@ class DTLREngine:
             x = ops.stem_conv7x7_f32s(x_nchw, self.w["conv1.fh"], self.w["conv1.fl"])
         else:
             x = ops.stem_conv7x7_f32(x_nchw, self.w["conv1.wk"])
+        if ext is not None:
+            return ops.maxpool_nhwc_ext(x, ext, 1, bias=self.w["conv1.b"], relu=True)
         return ops.maxpool_nhwc(x, bias=self.w["conv1.b"], relu=True)
 
-    def _backbone_layers(self, x, li_from, li_to):
-        """bottleneck layers li_from..li_to (1-based, inclusive) on the NHWC map x; returns the maps of layers >= 2 among them"""
+    def _backbone_layers(self, x, li_from, li_to, ext=None):
+        """bottleneck layers li_from..li_to (1-based, inclusive) on the NHWC map x; returns the maps of layers >= 2 among them.
+        ext (per-line batches): every 3x3 conv2 input is zeroed outside the lines' extents first (after conv + BN + ReLU the padded
+        region is not zero, and conv2 would read it at a line's right / bottom border where the line alone reads zero padding)."""
         outs = []
+        s = max(2, li_from)              # log2 of the stride of x (the pooled stem map: 4)
         pre = None                       # the NEXT bottleneck's conv1 output when the previous tail already computed it (layer1 chain)
         for li, nblocks in enumerate(self.cfg.backbone_blocks, start=1):
             if li < li_from or li > li_to:
                 continue
             if li == 1 and self.use_l1_chain and x.dtype in ops.H16 and x.shape[-1] == 64 and x.numel() // 64 >= 16384 \
                     and self.w["l1.0.c3.w"].shape == (256, 64) and self.w["l1.0.ds.w"].shape == (256, 64):
-                x, pre = self._layer1_chain(x, nblocks)
+                x, pre = self._layer1_chain(x, nblocks, ext)
                 continue
             for bi in range(nblocks):
                 q = f"l{li}.{bi}."
@@ -479,6 +486,8 @@ class DTLREngine:
                     idt = self._conv(q + "ds", x, stride, 0)
                 o = pre if pre is not None else self._conv(q + "c1", x, 1, 0, relu=True)
                 pre = None
+                if ext is not None:
+                    ops.zero_outside_extent(o, ext, s)
                 o = self._conv(q + "c2", o, stride, 1, relu=True)
                 if join is not None:
                     cur.wait_stream(join)
@@ -489,11 +498,12 @@ class DTLREngine:
                     x = ops.gemm_kres_cat_s2(o, x, self.w[q + "cat.wk"], self.w[q + "cat.b"], relu=True)
                 else:
                     x = self._conv(q + "c3", o, 1, 0, relu=True, residual=idt)
+                s += stride - 1
             if li >= 2:
                 outs.append(x)
         return outs
 
-    def _layer1_chain(self, x0, nblocks):
+    def _layer1_chain(self, x0, nblocks, ext=None):
         """layer1 (64-channel bottlenecks on the full-resolution pooled map: the HBM-heaviest part of the backbone) with the 1x1
         convolutions chained (ops.gemm_kres_chain): the first block's `downsample` shortcut is K columns 64..127 of its conv3 GEMM
         ([t | x] . [W3 | Wd]^T, bias b3 + bd: the 256-channel shortcut map is neither written nor read back), and every tail also
@@ -515,6 +525,8 @@ class DTLREngine:
         for bi in range(nblocks):
             if o is None:                       # the previous tail could not produce this block's conv1
                 o = self._conv(f"l1.{bi}.c1", x, 1, 0, relu=True)
+            if ext is not None:
+                ops.zero_outside_extent(o, ext, 2)
             o = self._conv(f"l1.{bi}.c2", o, 1, 1, relu=True)
             nm = nxt[bi]
             if nm is not None and (w[nm + ".w"].shape != (n2[bi], 256) or (bi == 0 and n2[bi] != 64)):
@@ -528,13 +540,17 @@ class DTLREngine:
                 x, o = self._conv(f"l1.{bi}.c3", o, 1, 0, relu=True, residual=x), None
         return x, o
 
-    def _geometry(self, mask, level_hw, has_padding=True):
+    def _geometry(self, mask, level_hw, has_padding=True, ext=None):
         """Everything that depends only on the padding masks, ONE HIP launch per forward (ops.geometry): per-level masks
         (backbone.py:103, dino.py:304-307), pos + level embeds (position_encoding.py:79-108, deformable_transformer.py:281-285),
-        valid ratios (:239-246), encoder reference points (:479-492), proposals and their validity (models/dino/utils.py:31-62)."""
+        valid ratios (:239-246), encoder reference points (:479-492), proposals and their validity (models/dino/utils.py:31-62).
+        ext (per-line batches): level masks from the line extents at strides 8..64 (ops.geometry_ext), not the interpolated mask."""
         cfg, dev = self.cfg, mask.device
         level_hw = [(int(h), int(w)) for h, w in level_hw]
-        g = ops.geometry(mask, level_hw, self.w["level_embed"], cfg.pe_temperatureH, cfg.pe_temperatureW, self.dtype)
+        if ext is not None:
+            g = ops.geometry_ext(ext, 3, level_hw, self.w["level_embed"], cfg.pe_temperatureH, cfg.pe_temperatureW, self.dtype)
+        else:
+            g = ops.geometry(mask, level_hw, self.w["level_embed"], cfg.pe_temperatureH, cfg.pe_temperatureW, self.dtype)
         key = (dev, tuple(level_hw))
         if key not in self._level_cache:                              # int64 shapes / level starts for the B1 operator: once per shape
             shapes = torch.as_tensor(level_hw, dtype=torch.long, device=dev)
@@ -716,7 +732,7 @@ class DTLREngine:
             src = self._ffn(q, "norm2", src)
         return src
 
-    def two_stage(self, memory, g, forced_topk=None):
+    def two_stage(self, memory, g, forced_topk=None, per_line=False):
         """deformable_transformer.py:320-363 with gen_encoder_output_proposals (utils.py:15-64).
         The box MLP runs only on the selected rows (selection uses class scores only)."""
         cfg = self.cfg
@@ -756,7 +772,12 @@ class DTLREngine:
                 # selection scores are computed in fp32: the projection writes fp32 straight from its accumulators
                 om = self._ln("enc_output_norm", self._lin("enc_output", om, out_dtype=torch.float32))
             scores = ops.linear_rowmax(om, w["enc_class.w"], w["enc_class.b"])
-        idx = ops.topk_rows(scores, cfg.num_queries) if forced_topk is None else forced_topk
+        if forced_topk is not None:
+            idx = forced_topk
+        elif per_line:                  # a padded token scores the bare bias, like an in-image token with an invalid proposal: never selected
+            idx = ops.topk_rows_masked(scores, g["mask_flat"], cfg.num_queries)
+        else:
+            idx = ops.topk_rows(scores, cfg.num_queries)
         sel_raw, sel_x, prop_sel, init_box = ops.two_stage_gather(om, g["proposals"], idx)      # one launch for all the gathers
         ref_unsig = self._box_mlp("enc_bbox", sel_raw if sel_x is None else sel_x, prop_sel, mode=1)
         ts = dict(topk_idx=idx, topk_scores=scores, ref_unsig=ref_unsig, init_box=init_box)
@@ -836,10 +857,11 @@ class DTLREngine:
             return True
         return False
 
-    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None):
+    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False):
         """TransformerDecoder.forward + DeformableTransformerDecoderLayer
         (deformable_transformer.py:652-766, 882-997), batch-first.  vall: value_proj(memory) of all layers when the caller already
-        computed it (forward() does, on a side stream under the two-stage selection)."""
+        computed it (forward() does, on a side stream under the two-stage selection).  per_line: the query position embedding is the
+        sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios."""
         cfg = self.cfg
         B = memory.shape[0]
         ref = ts["ref_unsig"].sigmoid()
@@ -863,9 +885,10 @@ class DTLREngine:
                     if nm + ".dq" not in w:                    # fragment-order images, packed once
                         w[nm + ".dq"] = ops.dq_pack(w[nm + ".w"])
                 ref_in, qpos, qk, v = ops.dec_query_stage(ref, g["valid_ratios"], tgt, w["dec.rph0.dq"], w["dec.rph0.b"], w["dec.rph1.dq"],
-                                                          w["dec.rph1.b"], w[q + "sa.qk.dq"], w[q + "sa.qk.b"], w[q + "sa.v.dq"], w[q + "sa.v.b"])
+                                                          w["dec.rph1.b"], w[q + "sa.qk.dq"], w[q + "sa.qk.b"], w[q + "sa.v.dq"], w[q + "sa.v.b"],
+                                                          per_line=per_line)
             else:
-                ref_in, sine = ops.decoder_query_prep(ref, g["valid_ratios"], self.dtype)      # [B,nq,L,4], [B,nq,512]
+                ref_in, sine = ops.decoder_query_prep(ref, g["valid_ratios"], self.dtype, per_line)      # [B,nq,L,4], [B,nq,512]
                 qpos = self._lin("dec.rph1", self._lin("dec.rph0", sine, relu=True))
                 # self attention (q = k = tgt + query_pos, v = tgt)
                 qk = self._lin(q + "sa.qk", tgt, a2=qpos)
@@ -888,10 +911,13 @@ class DTLREngine:
                 hs.append(None)
         return hs, refs
 
-    def features(self, x):
-        """backbone maps (NHWC) + the extra stride-2 level's convolution (dino.py:290-311) and the level sizes."""
-        feats = self.backbone_swin(x.float()) if self.cfg.is_swin else self.backbone(x.float())
+    def features(self, x, ext=None):
+        """backbone maps (NHWC) + the extra stride-2 level's convolution (dino.py:290-311) and the level sizes.
+        ext (per-line batches, ResNet only): the backbone's extent handling, and C5 zeroed outside the extents before the 3x3/s2 conv."""
+        feats = self.backbone_swin(x.float()) if self.cfg.is_swin else self.backbone(x.float(), ext)
         level_hw = [(f.shape[1], f.shape[2]) for f in feats]
+        if ext is not None:
+            ops.zero_outside_extent(feats[-1], ext, 2 + len(feats))
         last = self._conv(f"ip{len(feats)}", feats[-1], 2, 1)
         level_hw.append((last.shape[1], last.shape[2]))
         return feats, last, level_hw
@@ -948,9 +974,10 @@ class DTLREngine:
                 self._shape_cache[gkey] = g
         return g
 
-    def tokens(self, feats, last, level_hw):
+    def tokens(self, feats, last, level_hw, ext=None):
         """input_proj + GroupNorm of every level (dino.py:115-136), each level normalised straight into its rows of the
-        concatenated token matrix (no torch.cat pass)."""
+        concatenated token matrix (no torch.cat pass).  ext (per-line batches): statistics over each line's extent only (level l at
+        stride 2^(3 + l)), 0 outside it."""
         B = last.shape[0]
         S_tot = sum(h * w for h, w in level_hw)
         src = torch.empty((B, S_tot, self.cfg.hidden_dim), dtype=self.dtype, device=last.device)
@@ -958,7 +985,10 @@ class DTLREngine:
         for l, f in enumerate(list(feats) + [last]):
             t = self._lin(f"ip{l}", f.flatten(1, 2)) if l < len(feats) else f.flatten(1, 2)
             T_l = t.shape[1]
-            ops.groupnorm_tokens(t, 32, self.w[f"ip{l}.gn.w"], self.w[f"ip{l}.gn.b"], out=src[:, off:off + T_l])
+            if ext is not None:
+                ops.groupnorm_tokens_ext(t, level_hw[l], ext, 3 + l, 32, self.w[f"ip{l}.gn.w"], self.w[f"ip{l}.gn.b"], out=src[:, off:off + T_l])
+            else:
+                ops.groupnorm_tokens(t, 32, self.w[f"ip{l}.gn.w"], self.w[f"ip{l}.gn.b"], out=src[:, off:off + T_l])
             off += T_l
         return src
 
@@ -989,26 +1019,49 @@ class DTLREngine:
         return out
 
     # ------------------------------------------------------------------------------ forward
+    def per_line_tokens(self, h: int, w: int) -> int:
+        """encoder tokens of an h x w line run alone (levels at strides 8, 16, 32, 64)"""
+        return sum(-(-h // (1 << s)) * -(-w // (1 << s)) for s in range(3, 3 + self.cfg.num_feature_levels))
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor, mask: torch.Tensor, forced_topk: Optional[torch.Tensor] = None,
-                want_aux: bool = False, return_debug: bool = False, has_padding: bool = True) -> Dict[str, torch.Tensor]:
+                want_aux: bool = False, return_debug: bool = False, has_padding: bool = True, per_line: bool = False,
+                sizes: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
         """x [B,3,H,W] fp32 (zero-padded), mask [B,H,W] bool (True = padding)  ->  DINO.forward's
-        dict (models/dino/dino.py:270-415): pred_logits [B,nq,C] raw, pred_boxes [B,nq,4] cxcywh."""
+        dict (models/dino/dino.py:270-415): pred_logits [B,nq,C] raw, pred_boxes [B,nq,4] cxcywh.
+        per_line: every line of the padded batch gets the result it would get alone (up to rounding and the order of near-tied
+        queries): its extent -- the unpadded top-left rectangle of `mask` -- is carried through the backbone, the GroupNorm statistics,
+        the level masks, the two-stage selection and the decoder's query embedding (per-line batching).  The batch is always
+        treated as padded and runs on one stream.  `sizes`: the host's (h, w) of every line, when known -- a line with fewer encoder
+        tokens than queries cannot run alone and raises ValueError."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
+        ext = None
+        if per_line:
+            if cfg.is_swin:
+                raise NotImplementedError("per_line: the Swin backbone's patch-merge arithmetic has no extent form")
+            if cfg.num_feature_levels != 4 or len(cfg.backbone_blocks) != 4:
+                raise NotImplementedError("per_line: written for the 4-level ResNet configuration")
+            if sizes is not None:
+                for i, (h, w) in enumerate(sizes):
+                    n = self.per_line_tokens(int(h), int(w))
+                    if n < cfg.num_queries:
+                        raise ValueError(f"per_line: line {i} ({int(h)}x{int(w)}) has {n} encoder tokens, fewer than num_queries = {cfg.num_queries}")
+            ext = ops.line_extents(mask)
+            has_padding = True
         st = torch.cuda.current_stream(self.device).cuda_stream
         if st not in self._ws_streams and not torch.cuda.is_current_stream_capturing():
             # the library's split-K / hidden-split scratch of THIS stream, sized once before anything can be captured on it: a captured
             # forward then allocates nothing and dispatches exactly as an eager one (dtlr_hip.h, dtlr_workspace_reserve)
             ops.workspace_reserve(self.dtype)
             self._ws_streams.add(st)
-        overlap = self.overlap_streams and not cfg.is_swin
+        overlap = self.overlap_streams and not cfg.is_swin and not per_line
         src = None
         if overlap:
             feats, last, level_hw, src = self._features_tokens_overlapped(x)
         else:
-            feats, last, level_hw = self.features(x)
+            feats, last, level_hw = self.features(x, ext)
         if self._range_check_pending:
             # fp16 storage / split fp16 operands saturate at 65504 (the conversions do not clamp: a larger backbone activation becomes inf and
             # poisons a whole GroupNorm group).  No trained checkpoint ships with the reference, so the range assumption is CHECKED on the
@@ -1018,9 +1071,9 @@ class DTLREngine:
             if not (peak < 6.0e4):
                 raise RuntimeError(f"DTLREngine({'f32s' if self.split else 'float16'}): backbone activations reach {peak:.3g}, beyond fp16's range "
                                    "(65504) -- run this checkpoint on the bfloat16 or the exact float32 engine")
-        g = self.geometry_for(x, mask, level_hw, has_padding)
+        g = self._geometry(mask, level_hw, True, ext) if per_line else self.geometry_for(x, mask, level_hw, has_padding)
         if src is None:
-            src = self.tokens(feats, last, level_hw)
+            src = self.tokens(feats, last, level_hw, ext)
         if self.msda_auto and self.use_lds_msda and ("enc0.attn", tuple((int(h), int(w)) for h, w in level_hw)) not in self._msda_state:
             self._calibrate_msda(x.shape, level_hw)            # once per canvas shape
         memory = self.encoder(src, g)
@@ -1034,10 +1087,10 @@ class DTLREngine:
                 done = self._value_all_into(memory, g, vall)
             if not done:
                 vall = None
-        ts = self.two_stage(memory, g, forced_topk)
+        ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall)
+        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line)
         out = self.heads(hs, refs, ts, want_aux)
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,

@@ -13,6 +13,8 @@ What differs from the reference loop, and why the numbers do not:
     identical are batched together WITHOUT padding (`--batching exact`, default): the per-line arithmetic is exactly the
     bs = 1 arithmetic, only the launch is shared.  `--batching padded` pads mixed sizes into one canvas (faster, but a padded
     line is not bit-identical to the same line alone: the backbone sees the canvas's zero padding instead of its own border);
+    `--batching ragged` pads mixed sizes the same way but runs the forward per line (each line's result is its bs = 1 result up to
+    rounding and the order of near-tied queries; DESIGN.md, per-line batching);
   * lines are sharded over the ranks of a torch.distributed job (contiguous shards of the size-sorted list), decoded records
     are all-gathered, rank 0 computes the metrics in dataset order -- the running CER series (the figure the reference reports
     is the MEAN of the running sum(dist)/sum(len) series, evaluation.py:521-529,547) is order dependent;
@@ -117,19 +119,21 @@ def image_size(path: str) -> Tuple[int, int]:
 def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optional[float] = None,
                    NM: Optional[float] = None, postprocessor=None, device="cuda", size: int = EVAL_SIZE,
                    max_size: int = EVAL_MAX_SIZE, rank: int = 0, world: int = 1, sizes: Optional[Sequence[Tuple[int, int]]] = None,
-                   skip_errors: bool = True) -> List[Optional[List[int]]]:
+                   skip_errors: bool = True, per_line: bool = False) -> List[Optional[List[int]]]:
     """convert_output_to_pred (evaluation.py:94-158) for a list of RGB uint8 images -> one label list per image, dataset
     order.  TH / NM given: the NMS decoder; otherwise the blank/argmax decoder with eps = 0.03 / C.
     `images`: a sequence of [h, w, 3] uint8 arrays, or (with `sizes` = the (h, w) of every line) a callable i -> array that is
     invoked only for the lines of this rank's shard.  skip_errors (the reference's behaviour, evaluation.py:498-504): a line whose
-    load / forward / decode raises is reported and returned as None; KeyboardInterrupt always propagates."""
+    load / forward / decode raises is reported and returned as None; KeyboardInterrupt always propagates.
+    per_line (`--batching ragged`): mixed sizes share a padded batch as with exact=False, and the forward runs per line
+    (DINO.forward(per_line=True)): every line gets the result it gets alone."""
     lazy = callable(images)
     if lazy and sizes is None:
         raise ValueError("predict_labels: a loader callable needs `sizes`")
     sizes = list(sizes) if sizes is not None else [im.shape[:2] for im in images]
     n = len(sizes)
     load = images if lazy else (lambda i: images[i])
-    batches = plan_batches(sizes, batch, exact, size, max_size)
+    batches = plan_batches(sizes, batch, exact and not per_line, size, max_size)
     lo, hi = ddist.shard_bounds(len(batches), rank, world)
     tf = EvalTransform(size, max_size)
     nq = model.num_queries
@@ -137,7 +141,7 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
 
     def run(idx):
         samples = tf([load(i) for i in idx], device=device)
-        out = model(samples)
+        out = model(samples, per_line=True) if per_line else model(samples)
         preds = E.decode_nms(out, postprocessor, TH, NM) if (TH is not None and NM is not None) else E.decode_blank(out)
         for i, p in zip(idx, preds):
             rec[i, : len(p)] = torch.tensor(p, dtype=torch.int32)
@@ -255,7 +259,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--charset", default=None, help="charset file (.json list / .pkl list); default datasets/default_charset.json")
     ap.add_argument("--out", default="stats_dect")
     ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--batching", default="exact", choices=["exact", "padded"])
+    ap.add_argument("--batching", default="exact", choices=["exact", "padded", "ragged"],
+                    help="exact: same-size lines only (bs = 1 results); padded: mixed sizes in one canvas (the reference's padded-batch "
+                         "results); ragged: mixed sizes in one canvas, each line with its bs = 1 result")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32s", "f32"],
                     help="bf16 / f16: the 16-bit engines; f32s: fp32 activations, split fp16 products (parity-grade, ~1/3 of the 16-bit rate); f32: exact-fp32 MFMA")
     ap.add_argument("--limit", type=int, default=0, help="evaluate only the first N lines")
@@ -308,7 +314,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     for TH in list_TH:
         for NM in list_NM:
             preds = predict_labels(model, images, args.batch, args.batching == "exact", TH, NM, post, dev, args.size, args.max_size,
-                                   rank=rank, world=world, sizes=sizes)
+                                   rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged")
             if rank == 0:
                 res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
                 d = write_outputs(res, args.out, args.dataset, TH, NM)

@@ -1136,8 +1136,9 @@ def mha(qk, v, n_heads: int, split: bool = False):
 _DIM_T = {}
 
 
-def decoder_query_prep(ref, valid_ratios, out_dtype):
-    """ref [B,nq,4] fp32, valid_ratios [B,L,2] fp32 -> (ref_in [B,nq,L,4] fp32, sine [B,nq,512] out_dtype)."""
+def decoder_query_prep(ref, valid_ratios, out_dtype, per_line: bool = False):
+    """ref [B,nq,4] fp32, valid_ratios [B,L,2] fp32 -> (ref_in [B,nq,L,4] fp32, sine [B,nq,512] out_dtype).
+    per_line: the sine embedding of the unscaled reference (dtlr_decoder_query_prep_per_line); ref_in is still scaled."""
     B, nq, _ = ref.shape
     L = valid_ratios.shape[1]
     key = ref.device
@@ -1148,7 +1149,8 @@ def decoder_query_prep(ref, valid_ratios, out_dtype):
     valid_ratios = valid_ratios.contiguous()
     ref_in = torch.empty((B, nq, L, 4), dtype=torch.float32, device=ref.device)
     sine = torch.empty((B, nq, 512), dtype=out_dtype, device=ref.device)
-    code = _L(out_dtype).dtlr_decoder_query_prep(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), ref_in.data_ptr(),
+    fn = _L(out_dtype).dtlr_decoder_query_prep_per_line if per_line else _L(out_dtype).dtlr_decoder_query_prep
+    code = fn(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), ref_in.data_ptr(),
                                               sine.data_ptr(), B, nq, L, _DT[out_dtype], _lib.current_stream())
     _lib.check(code, "dtlr_decoder_query_prep")
     return ref_in, sine
@@ -1163,11 +1165,12 @@ def dq_pack(w):
     return v.permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)                   # u, ks, t, [g, m] = lane, e
 
 
-def dec_query_stage(ref, valid_ratios, tgt, w0, b0, w1, b1, wqk, bqk, wv, bv):
+def dec_query_stage(ref, valid_ratios, tgt, w0, b0, w1, b1, wqk, bqk, wv, bv, per_line: bool = False):
     """The query stage of a decoder layer in ONE launch (dtlr_dec_query_stage, 16-bit engines): reference boxes per level, sine
     embedding, ref_point_head MLP, and the q | k (on tgt + query_pos) and v (on tgt) input projections of the self-attention.
     ref [B,nq,4] fp32, valid_ratios [B,L,2] fp32, tgt [B,nq,256] 16-bit; weights = dq_pack of the 16-bit [256,512] / [256,256] /
-    [512,256] / [256,256] matrices, biases fp32 -> (ref_in [B,nq,L,4] fp32, qpos [B,nq,256], qk [B,nq,512], v [B,nq,256])."""
+    [512,256] / [256,256] matrices, biases fp32 -> (ref_in [B,nq,L,4] fp32, qpos [B,nq,256], qk [B,nq,512], v [B,nq,256]).
+    per_line: the sine embedding of the unscaled reference (dtlr_dec_query_stage_per_line)."""
     require_cuda(tgt, "tgt")
     B, nq, C = tgt.shape
     L = valid_ratios.shape[1]
@@ -1187,7 +1190,8 @@ def dec_query_stage(ref, valid_ratios, tgt, w0, b0, w1, b1, wqk, bqk, wv, bv):
     M = B * nq
     with _Timed("gemm_bf16", 2.0 * M * (512 * 256 + 256 * 256 + 256 * 512 + 256 * 256), float(M) * (256 + 256 + 512 + 256) * 2 + 393216.0 * 2,
                 f"dec_query_stage M{M}"):
-        code = _L(tgt).dtlr_dec_query_stage(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), tgt.data_ptr(),
+        fn = _L(tgt).dtlr_dec_query_stage_per_line if per_line else _L(tgt).dtlr_dec_query_stage
+        code = fn(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), tgt.data_ptr(),
                                             w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), wqk.data_ptr(), bqk.data_ptr(),
                                             wv.data_ptr(), bv.data_ptr(), ref_in.data_ptr(), qpos.data_ptr(), qk.data_ptr(), v.data_ptr(),
                                             B, nq, L, _DT[tgt.dtype], _lib.current_stream())
@@ -1367,3 +1371,97 @@ for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "gemm
               "topk_flat", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
     globals()[_name] = _device_scoped(globals()[_name])
 del _name
+
+
+# ------------------------------------------------------------------------------ per-line batching (csrc/extent.hip and the extent forms)
+# A line's extent (h, w) is its unpadded top-left rectangle in the input mask; at stride 2^s it is (ceil(h / 2^s), ceil(w / 2^s)).
+# The extents stay on the device ([B, 2] int32): none of these wrappers reads anything back.
+
+def line_extents(mask):
+    """mask [B,H,W] bool (True = padding) -> [B,2] int32 (h, w): unmasked rows of column 0, unmasked columns of row 0."""
+    require_cuda(mask, "mask")
+    assert mask.dtype == torch.bool and mask.dim() == 3
+    mask = mask if mask.is_contiguous() else mask.contiguous()
+    B, H, W = mask.shape
+    ext = torch.empty((B, 2), dtype=torch.int32, device=mask.device)
+    code = _lib.lib().dtlr_line_extents(mask.data_ptr(), ext.data_ptr(), B, H, W, _lib.current_stream())
+    _lib.check(code, "dtlr_line_extents")
+    return ext
+
+
+def zero_outside_extent(x, ext, s: int):
+    """In place: zero the positions of the NHWC map x [B,H,W,C] outside each line's stride-2^s extent.  Returns x."""
+    require_cuda(x, "x")
+    assert x.dim() == 4 and x.is_contiguous() and ext.dtype == torch.int32 and tuple(ext.shape) == (x.shape[0], 2)
+    B, H, W, C = x.shape
+    code = _L(x).dtlr_zero_outside_extent_nhwc(x.data_ptr(), ext.data_ptr(), int(s), B, H, W, C, _DT[x.dtype], _lib.current_stream())
+    _lib.check(code, "dtlr_zero_outside_extent_nhwc")
+    return x
+
+
+def maxpool_nhwc_ext(x, ext, s_in: int, bias=None, relu: bool = False):
+    """maxpool_nhwc whose window skips taps outside the input's stride-2^s_in extent; 0 outside the output's extent."""
+    B, H, W, C = x.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    assert ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2)
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
+    code = _L(x).dtlr_maxpool3x3s2_nhwc_ext(x.data_ptr(), y.data_ptr(), 0 if bias is None else bias.data_ptr(), 1 if relu else 0,
+                                            ext.data_ptr(), int(s_in), B, H, W, C, _DT[x.dtype], _lib.current_stream())
+    _lib.check(code, "dtlr_maxpool3x3s2_nhwc_ext")
+    return y
+
+
+def groupnorm_tokens_ext(x, hw, ext, s: int, groups: int, w, b, eps: float = 1e-5, out=None):
+    """groupnorm_tokens over a level of hw = (Hl, Wl) tokens, statistics over each line's stride-2^s extent only, 0 written outside it."""
+    B, T, C = x.shape
+    Hl, Wl = int(hw[0]), int(hw[1])
+    assert T == Hl * Wl and ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2)
+    x = x if x.is_contiguous() else x.contiguous()
+    L_ = _L(x)
+    ws = torch.empty(L_.dtlr_groupnorm_workspace_bytes(B, T), dtype=torch.uint8, device=x.device)
+    y = torch.empty_like(x) if out is None else out
+    assert y.shape == x.shape and y.dtype == x.dtype and y.stride(2) == 1 and y.stride(1) == C
+    code = L_.dtlr_groupnorm_tokens_ext(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), ws.data_ptr(), ext.data_ptr(),
+                                        int(s), Hl, Wl, B, C, groups, eps, _DT[x.dtype], _lib.current_stream())
+    _lib.check(code, "dtlr_groupnorm_tokens_ext")
+    return y
+
+
+def geometry_ext(ext, s0: int, level_hw, level_embed, temperature_h: float, temperature_w: float, pos_dtype):
+    """geometry() with the level masks taken from the line extents (level q: stride 2^(s0 + q)) instead of the interpolated mask."""
+    require_cuda(ext, "ext")
+    assert ext.dtype == torch.int32 and ext.dim() == 2 and ext.shape[1] == 2 and len(level_hw) == 4
+    ext = ext.contiguous()
+    B = ext.shape[0]
+    dev = ext.device
+    key = (dev, float(temperature_h), float(temperature_w))
+    if key not in _POS_TABLES:
+        i = torch.arange(128, dtype=torch.float32, device=dev)
+        e = 2 * torch.div(i, 2, rounding_mode="floor") / 128
+        _POS_TABLES[key] = ((temperature_h ** e).contiguous(), (temperature_w ** e).contiguous())
+    dim_ty, dim_tx = _POS_TABLES[key]
+    S = sum(int(h) * int(w) for h, w in level_hw)
+    hw = (ctypes.c_int * 8)(*[int(v) for pair in level_hw for v in pair])
+    mask_flat = torch.empty((B, S), dtype=torch.bool, device=dev)
+    keep = torch.empty((B, S), dtype=torch.bool, device=dev)
+    pos = torch.empty((B, S, 256), dtype=pos_dtype, device=dev)
+    vr = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
+    enc_ref = torch.empty((B, S, 4, 2), dtype=torch.float32, device=dev)
+    prop = torch.empty((B, S, 4), dtype=torch.float32, device=dev)
+    code = _L(pos_dtype).dtlr_geometry_ext(ext.data_ptr(), int(s0), B, ctypes.cast(hw, ctypes.c_void_p), level_embed.data_ptr(),
+                                           dim_ty.data_ptr(), dim_tx.data_ptr(), _DT[pos_dtype], mask_flat.data_ptr(), keep.data_ptr(),
+                                           pos.data_ptr(), vr.data_ptr(), enc_ref.data_ptr(), prop.data_ptr(), _lib.current_stream())
+    _lib.check(code, "dtlr_geometry_ext")
+    return dict(mask_flat=mask_flat, keep=keep, pos=pos, valid_ratios=vr, enc_ref=enc_ref, proposals=prop)
+
+
+def topk_rows_masked(scores, excl, k: int):
+    """topk_rows that never returns an element with excl[b, i] True (as long as k elements of the row are not excluded)."""
+    B, S = scores.shape
+    assert excl.dtype in (torch.bool, torch.uint8) and tuple(excl.shape) == (B, S)
+    scores = scores.float().contiguous()
+    excl = excl.contiguous()
+    idx = torch.empty((B, k), dtype=torch.int64, device=scores.device)
+    code = _L(scores).dtlr_topk_rows_masked(scores.data_ptr(), excl.data_ptr(), idx.data_ptr(), B, S, k, _lib.current_stream())
+    _lib.check(code, "dtlr_topk_rows_masked")
+    return idx

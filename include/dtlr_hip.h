@@ -627,6 +627,46 @@ int dtlr_nms(const float *boxes, const float *scores, float iou_threshold, long 
  *   x [B,n] fp32 ; values [B,k] fp32 ; idx_out [B,k] int64 (flat positions: box = idx / C, label = idx % C) ; k <= 8192. */
 int dtlr_topk_flat(const float *x, float *values, long *idx_out, int B, long n, int k, int apply_sigmoid, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-line batching (csrc/extent.hip and extent forms of existing kernels): a padded batch in which every line gets the result it
+ * would get alone.  A line's extent (h, w) is its unpadded top-left rectangle in the input mask (the reference's valid_H / valid_W,
+ * models/dino/deformable_transformer.py:239-246); at stride 2^s it is (ceil(h / 2^s), ceil(w / 2^s)), the output size of every
+ * stride-2 stage of the ResNet path applied s times.  Every entry below reads the extents from a device int32 [B, 2] and a shift s:
+ * nothing synchronises with the host (a per-line forward can be captured in a HIP graph).
+ *
+ * dtlr_line_extents: ext [B,2] int32 (h, w) = unmasked rows of column 0, unmasked columns of row 0 of mask [B,H,W] (1 = padding). */
+int dtlr_line_extents(const unsigned char *mask, int *ext, int B, int H, int W, void *stream);
+/* Zero, in place, the positions of x [B,H,W,C] outside each line's stride-2^s extent; in-extent bytes are not touched (the input of a
+ * 3x3 convolution then reads zeros past the line's border, as the zero padding of the line alone).  16-byte stores: C * element size
+ * a multiple of 16 and x 16-byte aligned.  dtype DTLR_F32, DTLR_BF16 or DTLR_F16. */
+int dtlr_zero_outside_extent_nhwc(void *x, const int *ext, int s, int B, int H, int W, int C, int dtype, void *stream);
+/* dtlr_maxpool3x3s2_nhwc whose window skips taps outside the input's stride-2^s_in extent; outputs outside the stride-2^(s_in+1)
+ * extent are written as 0.  The stem: s_in = 1. */
+int dtlr_maxpool3x3s2_nhwc_ext(const void *x, void *y, const float *bias, int relu, const int *ext, int s_in,
+                               int B, int H, int W, int C, int dtype, void *stream);
+/* dtlr_groupnorm_tokens_strided over a level of Hl x Wl tokens whose statistics are taken over each line's stride-2^s extent only;
+ * tokens outside it are written as 0.  workspace >= dtlr_groupnorm_workspace_bytes(B, Hl * Wl). */
+int dtlr_groupnorm_tokens_ext(const void *x, const float *gamma, const float *beta, void *y, long y_batch_stride,
+                              void *workspace, const int *ext, int s, int Hl, int Wl, int B, int C, int groups, float eps,
+                              int dtype, void *stream);
+/* The outputs of dtlr_geometry with the level masks taken from the extents: level q pads token (i, j) iff it lies outside the
+ * stride-2^(s0+q) extent (s0 = 3 for the ResNet levels), so valid ratios are w_q / W_q exactly. */
+int dtlr_geometry_ext(const int *ext, int s0, int B, const int *level_hw,
+                      const float *level_embed, const float *dim_ty, const float *dim_tx, int pos_dtype,
+                      unsigned char *mask_flat, unsigned char *keep, void *pos, float *valid_ratios,
+                      float *enc_ref, float *proposals, void *stream);
+/* dtlr_topk_rows that never returns a row element with excl[b, i] != 0 (excl [B,S] uint8: dtlr_geometry_ext's mask_flat), as long as
+ * at least k elements of the row are not excluded.  Same tie rule. */
+int dtlr_topk_rows_masked(const float *scores, const unsigned char *excl, long *idx_out, int B, int S, int k, void *stream);
+/* Per-line forms of dtlr_decoder_query_prep / dtlr_dec_query_stage: the sine embedding of the UNscaled reference (the line alone
+ * has valid ratios 1); ref_in is still ref * valid_ratios.  Same signatures. */
+int dtlr_decoder_query_prep_per_line(const float *ref, const float *valid_ratios, const float *dim_t,
+                                     float *ref_in, void *sine, int B, int nq, int L, int sine_dtype, void *stream);
+int dtlr_dec_query_stage_per_line(const float *ref, const float *valid_ratios, const float *dim_t, const void *tgt,
+                                  const void *W0, const float *b0, const void *W1, const float *b1,
+                                  const void *Wqk, const float *bqk, const void *Wv, const float *bv,
+                                  float *ref_in, void *qpos, void *qk, void *v, int B, int nq, int L, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
