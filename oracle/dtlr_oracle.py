@@ -261,7 +261,7 @@ def position_embedding_sine_hw(mask: Tensor, num_pos_feats: int = 128, tH: float
 # ======================================================================================
 # models/dino/ops : the MSDeformAttn operator and module
 # ======================================================================================
-def ms_deform_attn_core(value: Tensor, spatial_shapes, sampling_locations: Tensor, attention_weights: Tensor) -> Tensor:
+def ms_deform_attn_core(value: Tensor, spatial_shapes, sampling_locations: Tensor, attention_weights: Tensor, fma_im: bool = False) -> Tensor:
     """Line-by-line restatement of the CUDA forward kernel's arithmetic
     (ops/src/cuda/ms_deform_im2col_cuda.cuh:33-84 bilinear, :237-299 loop) with torch gathers:
         h_im = loc_y*H - 0.5 ; w_im = loc_x*W - 0.5 ; sampled iff -1 < h_im < H and -1 < w_im < W
@@ -269,7 +269,9 @@ def ms_deform_attn_core(value: Tensor, spatial_shapes, sampling_locations: Tenso
         out[b,q,m,:] = sum_l sum_p A[b,q,m,l,p] * bilinear(...)
     which the reference states is equivalent to ms_deform_attn_core_pytorch
     (ops/functions/ms_deform_attn_func.py:41-61; ops/test.py:31-60).
-    value [N,S,M,D], locations [N,Lq,M,L,P,2] (x,y), weights [N,Lq,M,L,P] -> [N,Lq,M*D]."""
+    value [N,S,M,D], locations [N,Lq,M,L,P,2] (x,y), weights [N,Lq,M,L,P] -> [N,Lq,M*D].
+    fma_im: h_im / w_im rounded ONCE to the locations' dtype from the exact loc * H - 0.5, as a compiler that contracts the expression
+    into one fused multiply-add computes it (hipcc and nvcc do by default), instead of rounding the product and then the difference."""
     N, S, M, D = value.shape
     _, Lq, _, L, P, _ = sampling_locations.shape
     shapes = [(int(h), int(w)) for h, w in (spatial_shapes.tolist() if isinstance(spatial_shapes, Tensor) else spatial_shapes)]
@@ -281,8 +283,12 @@ def ms_deform_attn_core(value: Tensor, spatial_shapes, sampling_locations: Tenso
         v = value[:, start:start + H * W]                       # [N, HW, M, D]
         loc = sampling_locations[:, :, :, l]                    # [N, Lq, M, P, 2]
         aw = attention_weights[:, :, :, l]                      # [N, Lq, M, P]
-        w_im = loc[..., 0] * W - 0.5
-        h_im = loc[..., 1] * H - 0.5
+        if fma_im:
+            w_im = (loc[..., 0].double() * W - 0.5).to(loc.dtype)
+            h_im = (loc[..., 1].double() * H - 0.5).to(loc.dtype)
+        else:
+            w_im = loc[..., 0] * W - 0.5
+            h_im = loc[..., 1] * H - 0.5
         inside = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
         h_low = torch.floor(h_im)
         w_low = torch.floor(w_im)

@@ -823,3 +823,60 @@ def test_ffn4_inline_asm_mfmas_have_no_valu_written_sources():
     for defs in ("", "-DDTLR_HALF_IS_F16"):
         n, bad = mod.lint(defs)
         assert n >= 300 and not bad, bad[:3]
+
+
+def test_msda_encoder_plan_restatement_matches_the_library_and_the_plan_cases_reach_every_plan():
+    """tests/util.py::msda_enc_plan (the Python restatement of make_plan in msda_enc.hip) agrees with dtlr_msda_encoder_plan_ok of both
+    libraries on fit / no fit over heights 8..600, the canvas widths the engine meets, both value element sizes and every halo; and
+    the canvases tests/test_gpu_msda_plans.py runs reach all 16 (element size, TW0, LDS cap) plans, so a plan change that leaves one of
+    the kernel's tile layouts unreached fails here instead of silently going untested."""
+    from dtlr_amd import _lib, build
+    from tests.util import MSDA_HALOS, canvas_level_hw, msda_enc_plan, msda_plan_coverage
+    build.build(verbose=False)
+    libs = ((_lib.lib(), _lib.DTLR_BF16), (_lib.lib(torch.float16), _lib.DTLR_F16))
+    seen = set()
+    for H in range(8, 601, 8):
+        for W in (256, 512, 1024, 1328, 1333, 2048, 2560, 4096):
+            lhw = canvas_level_hw(H, W)
+            hw = (ctypes.c_int * 8)(*[v for pair in lhw for v in pair])
+            for elem in (2, 4):
+                for halo in MSDA_HALOS:
+                    p = msda_enc_plan(lhw, elem, halo)
+                    for L, h16 in libs:
+                        rc = L.dtlr_msda_encoder_plan_ok(ctypes.cast(hw, ctypes.c_void_p), _lib.DTLR_F32 if elem == 4 else h16, halo)
+                        assert rc == (p is not None), (H, W, elem, halo, rc, p)
+                    if p is not None:
+                        assert p["lds"] <= p["cap"] and all(w <= hw_[1] for w, hw_ in zip(p["wmax"], lhw))
+                        seen.add((elem, p["TW0"], p["cap"]))
+    assert (4, 4, 160 * 1024) in seen and (2, 4, 160 * 1024) in seen          # the grid itself reaches the narrowest tiles
+    # the worked examples of the plan rule (16-bit / fp32 values at Latin 128x2048; taller 16-bit lines at halo 24)
+    latin = canvas_level_hw(128, 2048)
+    assert [(msda_enc_plan(latin, 2, h)["TW0"], msda_enc_plan(latin, 2, h)["cap"] // 1024) for h in (8, 16, 24)] == [(32, 80), (64, 160), (32, 160)]
+    assert (msda_enc_plan(latin, 4, 16)["TW0"], msda_enc_plan(latin, 4, 16)["cap"] // 1024) == (8, 160) and msda_enc_plan(latin, 4, 24) is None
+    assert msda_enc_plan(canvas_level_hw(200, 2048), 2, 24)["TW0"] == 4 and msda_enc_plan(canvas_level_hw(184, 2048), 2, 24)["TW0"] == 8
+    want = {(e, tw, 80 * 1024) for e in (2, 4) for tw in (16, 32, 64)} | {(e, tw, 160 * 1024) for e in (2, 4) for tw in (4, 8, 16, 32, 64)}
+    cov = msda_plan_coverage()
+    assert set(cov) == want, sorted(want - set(cov))
+
+
+def test_msda_offset_sweep_crosses_every_border():
+    """The dense-sweep regime of tests/util.py::msda_offsets, through the oracle's fp32 location arithmetic on a Latin 128x2048 line:
+    x offsets span +-(24 + 3) columns and y offsets +-(H_l + 1) rows of every level on a 1/8-px grid, and h_im / w_im land exactly on
+    -1 and on H / W (the kernels' `inside` test) at every level; the other two regimes have sigma 8 and 40 px."""
+    from tests.util import canvas_level_hw, msda_offsets
+    lhw = canvas_level_hw(128, 2048)
+    shapes = torch.tensor(lhw)
+    S = sum(h * w for h, w in lhw)
+    off = msda_offsets(1, S, 8, lhw, seed=7)
+    assert torch.equal(off, msda_offsets(1, S, 8, lhw, seed=7))
+    ref = O.encoder_reference_points(shapes, torch.ones((1, 4, 2)))
+    loc = O.msda_sampling_locations(ref, off, shapes, 4)
+    sweep = off[:, :, :4]
+    assert torch.equal(sweep * 8, torch.round(sweep * 8))
+    for l, (H, W) in enumerate(lhw):
+        assert sweep[..., l, :, 0].min() == -27 and sweep[..., l, :, 0].max() == 27
+        assert sweep[..., l, :, 1].min() == -(H + 1) and sweep[..., l, :, 1].max() == H + 1
+        w_im, h_im = loc[:, :, :4, l, :, 0] * W - 0.5, loc[:, :, :4, l, :, 1] * H - 0.5
+        for t, n in ((w_im, W), (h_im, H)):
+            assert bool((t == -1).any()) and bool((t == n).any()) and bool(((t > -1) & (t < 0)).any()) and bool(((t > n - 1) & (t < n)).any())
+    assert 7 < off[:, :, 4:6].std().item() < 9 and 37 < off[:, :, 6:].std().item() < 43
