@@ -131,6 +131,9 @@ _SIGNATURES = {
     "dtlr_topk_rows_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_decoder_query_prep_per_line": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dtlr_dec_query_stage_per_line": (c_int, [c_void_p] * 16 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "dtlr_swin_patch_embed_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "dtlr_swin_window_attn_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dtlr_swin_patch_merge_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
 }
 
 

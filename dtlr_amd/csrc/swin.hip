@@ -9,6 +9,10 @@
 //                           after it are GEMMs (gemm.hip).
 //   dtlr_swin_patch_merge   PatchMerging (:250-288): 2x2 neighbourhood gather (zero padding for odd sizes) + LayerNorm(4C); the
 //                           4C -> 2C reduction that follows is a GEMM.
+// Per-line batching (engine.forward(per_line=True)): the three kernels have an extent form (template flag EXT; entry points *_ext) in
+// which every line of a canvas batch is processed at ITS OWN size -- (ceil(h / 2^s), ceil(w / 2^s)) at stride 2^s, from the device-side
+// extent array of extent.hip -- while addressing keeps the canvas pitch: a position outside the line's extent is a padding position
+// whatever the tensor holds there, and every output position outside the extent is written as zero.
 // The MLP's GELU is an epilogue of the GEMM (EPI_GELU), LayerNorm of arbitrary C the generic row kernel of norm.hip.
 #include "dtlr_common.h"
 
@@ -20,22 +24,35 @@ typedef __attribute__((ext_vector_type(4))) float sw_f32x4_t;
 // ------------------------------------------------------------------------------------------------------------- patch embed
 // x [B,3,H,W] fp32 ; w [48][E] fp32 (k = (c*4 + dy)*4 + dx, k-major) ; b, gamma, beta [E] ; out [B,Hp,Wp,E], Hp = ceil(H/4).
 // Workgroup = 64 output pixels of one row; thread (pixel, quarter) accumulates EQ = E/4 channels; LayerNorm over the 4 threads.
-template <typename OT, int EQ>
+// EXT: pixels outside line b's (h, w) read as zero (what F.pad gives the line alone), tokens outside (ceil(h/4), ceil(w/4)) are written as 0.
+template <typename OT, int EQ, bool EXT = false>
 __global__ __launch_bounds__(256) void swin_patch_embed_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                const float* __restrict__ bias, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, OT* __restrict__ out,
-                                                               int H, int W, int Hp, int Wp, float eps)
+                                                               int H, int W, int Hp, int Wp, float eps,
+                                                               const int* __restrict__ ext = nullptr)
 {
     constexpr int E = 4 * EQ;
     extern __shared__ __attribute__((aligned(16))) float sw_pe[];
     float* patch = sw_pe;                 // [64][49] (padded)
     float* wl = sw_pe + 64 * 49;          // [48][E]
     const int b = blockIdx.z, i = blockIdx.y, j0 = blockIdx.x * 64;
+    int eh = H, ew = W;                       // the image rectangle this line's patches read
+    if constexpr (EXT) {
+        eh = min(ext[2 * b], H); ew = min(ext[2 * b + 1], W);
+        if (4 * i >= eh || 4 * j0 >= ew) {    // a whole workgroup of tokens outside the extent
+            for (int t = threadIdx.x; t < 64 * E; t += 256) {
+                const int px = t / E;
+                if (j0 + px < Wp) out[(((long)b * Hp + i) * Wp + j0 + px) * E + t % E] = OT(0);
+            }
+            return;
+        }
+    }
     for (int t = threadIdx.x; t < 64 * 48; t += 256) {
         const int px = t / 48, k = t % 48;
         const int c = k >> 4, dy = (k >> 2) & 3, dx = k & 3;
         const int y = 4 * i + dy, xx = 4 * (j0 + px) + dx;
-        patch[px * 49 + k] = (y < H && xx < W && j0 + px < Wp) ? x[(((long)b * 3 + c) * H + y) * W + xx] : 0.f;
+        patch[px * 49 + k] = (y < eh && xx < ew && j0 + px < Wp) ? x[(((long)b * 3 + c) * H + y) * W + xx] : 0.f;
     }
     for (int t = threadIdx.x; t < 48 * E; t += 256) wl[t] = w[t];
     __syncthreads();
@@ -65,7 +82,8 @@ __global__ __launch_bounds__(256) void swin_patch_embed_kernel(const float* __re
         OT* o = out + (((long)b * Hp + i) * Wp + j0 + px) * E + q * EQ;
 #pragma unroll
         for (int e = 0; e < EQ; ++e) {
-            const float y = (acc[e] - mean) * rstd * gamma[q * EQ + e] + beta[q * EQ + e];
+            float y = (acc[e] - mean) * rstd * gamma[q * EQ + e] + beta[q * EQ + e];
+            if constexpr (EXT) { if (4 * (j0 + px) >= ew) y = 0.f; }
             if constexpr (sizeof(OT) == 2) o[e] = f32_to_bf16(y);
             else o[e] = y;
         }
@@ -75,10 +93,13 @@ __global__ __launch_bounds__(256) void swin_patch_embed_kernel(const float* __re
 // ------------------------------------------------------------------------------------------------------------ patch merging
 // x [B,H,W,C] -> y [B,H2,W2,4C] = LayerNorm(cat(x[2i,2j], x[2i+1,2j], x[2i,2j+1], x[2i+1,2j+1])) (zeros beyond H, W).
 // One wavefront per output token; lane l owns elements 4l + 256 g of the 4C-long row (C % 4 == 0, 4C <= 3072).
-template <typename T>
+// EXT (s = the input's stride exponent): input positions outside line b's stride-2^s extent read as zero, output rows outside its
+// stride-2^(s+1) extent are written as 0.
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(256) void swin_patch_merge_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, T* __restrict__ y,
-                                                               int H, int W, int C, int H2, int W2, long rows, float eps)
+                                                               int H, int W, int C, int H2, int W2, long rows, float eps,
+                                                               const int* __restrict__ ext = nullptr, int s_in = 0)
 {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -86,6 +107,19 @@ __global__ __launch_bounds__(256) void swin_patch_merge_kernel(const T* __restri
     const int C4 = 4 * C;
     const int j = (int)(row % W2), i = (int)((row / W2) % H2);
     const long b = row / ((long)W2 * H2);
+    int eh = H, ew = W;                       // the rectangle of x this line's tokens are gathered from
+    if constexpr (EXT) {
+        const int r = (1 << s_in) - 1;
+        eh = min((ext[2 * b] + r) >> s_in, H); ew = min((ext[2 * b + 1] + r) >> s_in, W);
+        if (2 * i >= eh || 2 * j >= ew) {
+            T* yz = y + row * C4;
+            for (int e = 4 * lane; e < C4; e += 256) {
+                if constexpr (sizeof(T) == 2) *reinterpret_cast<uint2*>(yz + e) = make_uint2(0u, 0u);
+                else *reinterpret_cast<float4*>(yz + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            return;
+        }
+    }
     float v[12][4];
     float s = 0.f;
 #pragma unroll
@@ -95,7 +129,7 @@ __global__ __launch_bounds__(256) void swin_patch_merge_kernel(const T* __restri
         if (e < C4) {
             const int part = e / C, c = e % C;
             const int yy = 2 * i + (part & 1), xx = 2 * j + (part >> 1);
-            if (yy < H && xx < W) {
+            if (yy < eh && xx < ew) {
                 const T* p = x + ((b * H + yy) * W + xx) * (long)C + c;
                 if constexpr (sizeof(T) == 2) {
                     const uint2 t = *reinterpret_cast<const uint2*>(p);
@@ -150,15 +184,33 @@ template <> struct SwinLds<float> {
     static __host__ __device__ int bytes(int NQ, int NK) { return (NQ + 2 * NK) * 33 * 4 + NK * 8; }
 };
 
-template <typename T>
+// EXT (per-line batches): P.H, P.W, P.Hp, P.Wp describe the CANVAS (pitch, launch grid); the window arithmetic -- padding, roll modulus,
+// mask regions, crop -- runs on line b's own (H, W) = its stride-2^s extent.  Every workgroup first zeroes the out-of-extent positions
+// of its own UNSHIFTED canvas window (head h's channels): those positions partition the canvas, and the attention below writes
+// in-extent positions only, so every output element is written exactly once.  A window outside the line's own grid then exits.
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restrict__ qkv, const float* __restrict__ qkv_b,
-                                                               const float* __restrict__ rpb, T* __restrict__ out, SwinAttnP P)
+                                                               const float* __restrict__ rpb, T* __restrict__ out, SwinAttnP P,
+                                                               const int* __restrict__ ext = nullptr, int s = 0)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
     constexpr bool BF = sizeof(T) == 2;
     const int N = P.N, NQ = P.NQ, NK = P.NK, ws = P.ws, C = P.C;
     const int win = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int wy = win / P.nWw, wx = win % P.nWw;
+    int H = P.H, W = P.W, Hp = P.Hp, Wp = P.Wp;                 // the map the windows tile: the launch's, or (EXT) line b's own
+    if constexpr (EXT) {
+        const int r = (1 << s) - 1;
+        H = min((ext[2 * b] + r) >> s, P.H); W = min((ext[2 * b + 1] + r) >> s, P.W);
+        Hp = (H + ws - 1) / ws * ws; Wp = (W + ws - 1) / ws * ws;
+        constexpr int NV = 32 * sizeof(T) / 16;                  // 16-byte vectors of one head's channels
+        for (int i = threadIdx.x; i < N * NV; i += 256) {
+            const int pos = i / NV, y = wy * ws + pos / ws, xx = wx * ws + pos % ws;
+            if (y < P.H && xx < P.W && (y >= H || xx >= W))
+                reinterpret_cast<uint4*>(out + (((long)b * P.H + y) * P.W + xx) * C + h * 32)[i % NV] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        if (wy * ws >= Hp || wx * ws >= Wp) return;              // not a window of this line (uniform over the workgroup)
+    }
     // LDS carve-up
     unsigned char* Qs = sw_smem;
     unsigned char* Ks = Qs + (BF ? NQ * 64 : NQ * 33 * 4);
@@ -172,11 +224,11 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
         if (i < N) {
             const int a = i / ws, c = i % ws;
             const int ys = wy * ws + a, xs = wx * ws + c;                     // shifted-frame coordinates
-            const int y = (ys + P.shift) % P.Hp, xx = (xs + P.shift) % P.Wp;   // torch.roll(x, -shift): shifted[i] = x[(i + shift) mod Hp]
-            t = (y < P.H && xx < P.W) ? y * P.W + xx : -2;                     // -2: padding position (projects to the biases)
+            const int y = (ys + P.shift) % Hp, xx = (xs + P.shift) % Wp;       // torch.roll(x, -shift): shifted[i] = x[(i + shift) mod Hp]
+            t = (y < H && xx < W) ? y * P.W + xx : -2;                         // -2: padding position (projects to the biases); row pitch P.W
             if (P.shift > 0) {
-                const int rh = ys < P.Hp - ws ? 0 : (ys < P.Hp - P.shift ? 1 : 2);
-                const int rw = xs < P.Wp - ws ? 0 : (xs < P.Wp - P.shift ? 1 : 2);
+                const int rh = ys < Hp - ws ? 0 : (ys < Hp - P.shift ? 1 : 2);
+                const int rw = xs < Wp - ws ? 0 : (xs < Wp - P.shift ? 1 : 2);
                 r = 3 * rh + rw;
             }
         }
@@ -334,8 +386,9 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
 
 using namespace dtlr;
 
-extern "C" int dtlr_swin_patch_embed(const float* x, const float* w_kE, const float* bias, const float* gamma, const float* beta,
-                                     void* out, int B, int H, int W, int E, float eps, int out_dtype, void* stream)
+// ext == nullptr: the whole-map forms; otherwise the per-line forms (ext [B,2] int32 on the device, extent.hip)
+static int swin_patch_embed_launch(const float* x, const float* w_kE, const float* bias, const float* gamma, const float* beta,
+                                   void* out, int B, int H, int W, int E, float eps, int out_dtype, const int* ext, void* stream)
 {
     clear_stale_error();
     if (!x || !w_kE || !bias || !gamma || !beta || !out) return DTLR_EINVAL;
@@ -346,8 +399,11 @@ extern "C" int dtlr_swin_patch_embed(const float* x, const float* w_kE, const fl
     const dim3 grid((Wp + 63) / 64, Hp, B);
     const size_t lds = (size_t)(64 * 49 + 48 * E) * 4;
     hipStream_t st = (hipStream_t)stream;
-#define PE_LAUNCH(OT, EQ) hipLaunchKernelGGL((swin_patch_embed_kernel<OT, EQ>), grid, dim3(256), lds, st, x, w_kE, bias, gamma, beta, (OT*)out, H, W, Hp, Wp, eps)
-#define PE_CASE(EQ) case 4 * EQ: if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ); else PE_LAUNCH(float, EQ); break;
+#define PE_LAUNCH(OT, EQ, X) hipLaunchKernelGGL((swin_patch_embed_kernel<OT, EQ, X>), grid, dim3(256), lds, st, x, w_kE, bias, gamma, beta, (OT*)out, H, W, Hp, Wp, eps, ext)
+#define PE_CASE(EQ) case 4 * EQ: \
+        if (ext) { if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ, true); else PE_LAUNCH(float, EQ, true); } \
+        else { if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ, false); else PE_LAUNCH(float, EQ, false); } \
+        break;
     switch (E) {
         PE_CASE(8) PE_CASE(16) PE_CASE(24) PE_CASE(32) PE_CASE(48)
     default: return DTLR_ESHAPE;                               // embed_dim 32 / 64 / 96 / 128 / 192
@@ -357,31 +413,57 @@ extern "C" int dtlr_swin_patch_embed(const float* x, const float* w_kE, const fl
     return check_launch();
 }
 
-extern "C" int dtlr_swin_patch_merge(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C,
-                                     float eps, int dtype, void* stream)
+extern "C" int dtlr_swin_patch_embed(const float* x, const float* w_kE, const float* bias, const float* gamma, const float* beta,
+                                     void* out, int B, int H, int W, int E, float eps, int out_dtype, void* stream)
+{
+    return swin_patch_embed_launch(x, w_kE, bias, gamma, beta, out, B, H, W, E, eps, out_dtype, nullptr, stream);
+}
+
+extern "C" int dtlr_swin_patch_embed_ext(const float* x, const float* w_kE, const float* bias, const float* gamma, const float* beta,
+                                         void* out, const int* ext, int B, int H, int W, int E, float eps, int out_dtype, void* stream)
+{
+    if (!ext) return DTLR_EINVAL;
+    return swin_patch_embed_launch(x, w_kE, bias, gamma, beta, out, B, H, W, E, eps, out_dtype, ext, stream);
+}
+
+static int swin_patch_merge_launch(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C,
+                                   float eps, int dtype, const int* ext, int s_in, void* stream)
 {
     clear_stale_error();
     if (!x || !gamma || !beta || !y) return DTLR_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return DTLR_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || s_in < 0 || s_in > 16) return DTLR_EINVAL;
     if ((C & 3) || 4 * C > 3072) return DTLR_ESHAPE;
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
     const long rows = (long)B * H2 * W2;
     const unsigned grid = (unsigned)((rows + 3) / 4);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DTLR_H16)
-        hipLaunchKernelGGL(swin_patch_merge_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t*)x, gamma, beta, (uint16_t*)y, H, W, C, H2, W2, rows, eps);
-    else if (dtype == DTLR_F32)
-        hipLaunchKernelGGL(swin_patch_merge_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, gamma, beta, (float*)y, H, W, C, H2, W2, rows, eps);
+#define PM_LAUNCH(T, X) hipLaunchKernelGGL((swin_patch_merge_kernel<T, X>), dim3(grid), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, H, W, C, H2, W2, rows, eps, ext, s_in)
+    if (dtype == DTLR_H16) { if (ext) PM_LAUNCH(uint16_t, true); else PM_LAUNCH(uint16_t, false); }
+    else if (dtype == DTLR_F32) { if (ext) PM_LAUNCH(float, true); else PM_LAUNCH(float, false); }
     else return DTLR_EDTYPE;
+#undef PM_LAUNCH
     return check_launch();
 }
 
-extern "C" int dtlr_swin_window_attn(const void* qkv, const float* qkv_bias, const float* rpb, void* out,
-                                     int B, int H, int W, int C, int n_heads, int window, int shift, int dtype, void* stream)
+extern "C" int dtlr_swin_patch_merge(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C,
+                                     float eps, int dtype, void* stream)
+{
+    return swin_patch_merge_launch(x, gamma, beta, y, B, H, W, C, eps, dtype, nullptr, 0, stream);
+}
+
+extern "C" int dtlr_swin_patch_merge_ext(const void* x, const float* gamma, const float* beta, void* y, const int* ext, int s_in,
+                                         int B, int H, int W, int C, float eps, int dtype, void* stream)
+{
+    if (!ext) return DTLR_EINVAL;
+    return swin_patch_merge_launch(x, gamma, beta, y, B, H, W, C, eps, dtype, ext, s_in, stream);
+}
+
+static int swin_window_attn_launch(const void* qkv, const float* qkv_bias, const float* rpb, void* out, int B, int H, int W, int C,
+                                   int n_heads, int window, int shift, int dtype, const int* ext, int s, void* stream)
 {
     clear_stale_error();
     if (!qkv || !qkv_bias || !rpb || !out) return DTLR_EINVAL;
-    if (B <= 0 || H <= 0 || W <= 0 || window <= 0 || shift < 0 || shift >= window || n_heads <= 0) return DTLR_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || window <= 0 || shift < 0 || shift >= window || n_heads <= 0 || s < 0 || s > 16) return DTLR_EINVAL;
     if (C != 32 * n_heads) return DTLR_ESHAPE;                  // head_dim 32 (every reference variant)
     SwinAttnP P;
     P.H = H; P.W = W; P.C = C; P.nH = n_heads; P.ws = window; P.shift = shift;
@@ -393,15 +475,34 @@ extern "C" int dtlr_swin_window_attn(const void* qkv, const float* qkv_bias, con
     const int nW = (P.Hp / window) * P.nWw;
     if (n_heads > 65535 || B > 65535) return DTLR_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
+#define WA_LAUNCH(T, X) hipLaunchKernelGGL((swin_window_attn_kernel<T, X>), dim3(nW, n_heads, B), dim3(256), lds, st, (const T*)qkv, qkv_bias, rpb, (T*)out, P, ext, s)
     if (dtype == DTLR_H16) {
         const int lds = SwinLds<uint16_t>::bytes(P.NQ, P.NK);
-        hipLaunchKernelGGL(swin_window_attn_kernel<uint16_t>, dim3(nW, n_heads, B), dim3(256), lds, st, (const uint16_t*)qkv, qkv_bias, rpb, (uint16_t*)out, P);
+        if (ext) WA_LAUNCH(uint16_t, true); else WA_LAUNCH(uint16_t, false);
     } else if (dtype == DTLR_F32) {
         const int lds = SwinLds<float>::bytes(P.NQ, P.NK);
         static DevOnce once;
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)swin_window_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); (void)hipGetLastError(); }
+        if (once.first()) {
+            (void)hipFuncSetAttribute((const void*)swin_window_attn_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            (void)hipFuncSetAttribute((const void*)swin_window_attn_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            (void)hipGetLastError();
+        }
         if (lds > 96 * 1024) return DTLR_ESHAPE;
-        hipLaunchKernelGGL(swin_window_attn_kernel<float>, dim3(nW, n_heads, B), dim3(256), lds, st, (const float*)qkv, qkv_bias, rpb, (float*)out, P);
+        if (ext) WA_LAUNCH(float, true); else WA_LAUNCH(float, false);
     } else return DTLR_EDTYPE;
+#undef WA_LAUNCH
     return check_launch();
+}
+
+extern "C" int dtlr_swin_window_attn(const void* qkv, const float* qkv_bias, const float* rpb, void* out,
+                                     int B, int H, int W, int C, int n_heads, int window, int shift, int dtype, void* stream)
+{
+    return swin_window_attn_launch(qkv, qkv_bias, rpb, out, B, H, W, C, n_heads, window, shift, dtype, nullptr, 0, stream);
+}
+
+extern "C" int dtlr_swin_window_attn_ext(const void* qkv, const float* qkv_bias, const float* rpb, void* out, const int* ext, int s,
+                                         int B, int H, int W, int C, int n_heads, int window, int shift, int dtype, void* stream)
+{
+    if (!ext) return DTLR_EINVAL;
+    return swin_window_attn_launch(qkv, qkv_bias, rpb, out, B, H, W, C, n_heads, window, shift, dtype, ext, s, stream);
 }

@@ -181,12 +181,16 @@ class DTLREngine:
                 self._put(f"swin.norm{i}.w", sd[f"{b}norm{i}.weight"], f32)
                 self._put(f"swin.norm{i}.b", sd[f"{b}norm{i}.bias"], f32)
 
-    def backbone_swin(self, x_nchw) -> List[torch.Tensor]:
-        """SwinTransformer.forward (models/dino/swin_transformer.py:633-673) -> the NHWC maps of return_interm_indices."""
+    def backbone_swin(self, x_nchw, ext=None) -> List[torch.Tensor]:
+        """SwinTransformer.forward (models/dino/swin_transformer.py:633-673) -> the NHWC maps of return_interm_indices.
+        ext (per-line batches, [B, 2] line extents): every line runs at its own size -- stage i on (ceil(h / 2^(2+i)), ceil(w / 2^(2+i))).
+        The canvas enters a line at the patch embedding, the window attention (padding, roll modulus, mask regions) and the patch
+        merging (odd sizes): each has an extent form.  Everything between them is row-local, so out-of-extent rows carry values no
+        line reads; the returned maps are zeroed there."""
         cfg, w = self.cfg, self.w
         sp = cfg.swin_params()
         ws = sp["window_size"]
-        x = ops.swin_patch_embed(x_nchw, w["swin.pe.w"], w["swin.pe.b"], w["swin.pe.ln.w"], w["swin.pe.ln.b"], self.dtype)
+        x = ops.swin_patch_embed(x_nchw, w["swin.pe.w"], w["swin.pe.b"], w["swin.pe.ln.w"], w["swin.pe.ln.b"], self.dtype, ext=ext)
 
         def padk(t, wname):                       # zero-pad the last dim to the packed weight's K (16-bit engines, C = 96: see _pack_swin)
             kp = w[wname].shape[1]
@@ -204,17 +208,18 @@ class DTLREngine:
                 # index arithmetic inside the attention kernel; the residual add is the projection's epilogue
                 y = ops.layernorm(x, w[q + "norm1.w"], w[q + "norm1.b"], 1e-5)
                 qkv = ops.linear(padk(y, q + "qkv.w"), w[q + "qkv.w"], w[q + "qkv.b"])
-                a = ops.swin_window_attn(qkv, w[q + "qkv.b"], w[q + "rpb"], nh, ws, 0 if j % 2 == 0 else ws // 2)
+                a = ops.swin_window_attn(qkv, w[q + "qkv.b"], w[q + "rpb"], nh, ws, 0 if j % 2 == 0 else ws // 2, ext=ext, s=2 + i)
                 x = ops.linear(padk(a, q + "proj.w"), w[q + "proj.w"], w[q + "proj.b"], residual=x)
                 # x = x + fc2(gelu(fc1(norm2(x))))  (:244-247)
                 y = ops.layernorm(x, w[q + "norm2.w"], w[q + "norm2.b"], 1e-5)
                 hdn = ops.linear(padk(y, q + "fc1.w"), w[q + "fc1.w"], w[q + "fc1.b"], relu=3)
                 x = ops.linear(padk(hdn, q + "fc2.w"), w[q + "fc2.w"], w[q + "fc2.b"], residual=x)
             if i in cfg.return_interm_indices:
-                outs.append(ops.layernorm(x, w[f"swin.norm{i}.w"], w[f"swin.norm{i}.b"], 1e-5))
+                o = ops.layernorm(x, w[f"swin.norm{i}.w"], w[f"swin.norm{i}.b"], 1e-5)
+                outs.append(o if ext is None else ops.zero_outside_extent(o, ext, 2 + i))
             if i < 3:
                 q = f"swin.{i}.merge."
-                x = ops.linear(padk(ops.swin_patch_merge(x, w[q + "ln.w"], w[q + "ln.b"]), q + "w"), w[q + "w"], None)
+                x = ops.linear(padk(ops.swin_patch_merge(x, w[q + "ln.w"], w[q + "ln.b"], ext=ext, s=2 + i), q + "w"), w[q + "w"], None)
         return outs
 
     def _pack(self, sd):
@@ -913,8 +918,8 @@ class DTLREngine:
 
     def features(self, x, ext=None):
         """backbone maps (NHWC) + the extra stride-2 level's convolution (dino.py:290-311) and the level sizes.
-        ext (per-line batches, ResNet only): the backbone's extent handling, and C5 zeroed outside the extents before the 3x3/s2 conv."""
-        feats = self.backbone_swin(x.float()) if self.cfg.is_swin else self.backbone(x.float(), ext)
+        ext (per-line batches): the backbone's extent handling, and the last map zeroed outside the extents before the 3x3/s2 conv."""
+        feats = self.backbone_swin(x.float(), ext) if self.cfg.is_swin else self.backbone(x.float(), ext)
         level_hw = [(f.shape[1], f.shape[2]) for f in feats]
         if ext is not None:
             ops.zero_outside_extent(feats[-1], ext, 2 + len(feats))
@@ -1039,8 +1044,6 @@ class DTLREngine:
         B = x.shape[0]
         ext = None
         if per_line:
-            if cfg.is_swin:
-                raise NotImplementedError("per_line: the Swin backbone's patch-merge arithmetic has no extent form")
             if cfg.num_feature_levels != 4 or len(cfg.backbone_blocks) != 4:
                 raise NotImplementedError("per_line: written for the 4-level ResNet configuration")
             if sizes is not None:

@@ -975,28 +975,48 @@ def msda_fused(value, spatial_shapes, level_start_index, ow, ref):
 MSDA_HALO = 8            # columns staged beyond a tile's own (level-0 pixels); tools/msda_sweep.py varies it
 
 
-def swin_patch_embed(x_nchw, w_kE, b, ln_w, ln_b, out_dtype, eps: float = 1e-5):
+def _check_ext(ext, B):
+    assert ext.is_cuda and ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2) and ext.is_contiguous()
+
+
+def swin_patch_embed(x_nchw, w_kE, b, ln_w, ln_b, out_dtype, eps: float = 1e-5, ext=None):
     """PatchEmbed of a Swin backbone (dtlr_swin_patch_embed): x [B,3,H,W] fp32 -> [B, ceil(H/4), ceil(W/4), E] out_dtype
-    (4x4/s4 convolution with zero padding + LayerNorm).  w_kE [48, E] fp32 = proj.weight.reshape(E, 48).t()."""
+    (4x4/s4 convolution with zero padding + LayerNorm).  w_kE [48, E] fp32 = proj.weight.reshape(E, 48).t().
+    ext ([B,2] int32 line extents, per-line batches: dtlr_swin_patch_embed_ext): every line embedded as alone -- pixels outside its
+    (h, w) read as zero, tokens outside (ceil(h/4), ceil(w/4)) are 0."""
     require_cuda(x_nchw, "images")
     assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.shape[1] == 3 and w_kE.shape[0] == 48
     x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
     B, _, H, W = x.shape
     E = w_kE.shape[1]
     out = torch.empty((B, (H + 3) // 4, (W + 3) // 4, E), dtype=out_dtype, device=x.device)
+    if ext is not None:
+        _check_ext(ext, B)
+        code = _L(out_dtype).dtlr_swin_patch_embed_ext(x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), out.data_ptr(),
+                                                       ext.data_ptr(), B, H, W, E, eps, _DT[out_dtype], _lib.current_stream())
+        _lib.check(code, "dtlr_swin_patch_embed_ext")
+        return out
     code = _L(out_dtype).dtlr_swin_patch_embed(x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), out.data_ptr(),
                                             B, H, W, E, eps, _DT[out_dtype], _lib.current_stream())
     _lib.check(code, "dtlr_swin_patch_embed")
     return out
 
 
-def swin_window_attn(qkv, qkv_bias, rpb, n_heads: int, window: int, shift: int):
-    """Attention core of a Swin block (dtlr_swin_window_attn): qkv [B,H,W,3C] -> [B,H,W,C]; rpb = swin_dense_bias(table, window)."""
+def swin_window_attn(qkv, qkv_bias, rpb, n_heads: int, window: int, shift: int, ext=None, s: Optional[int] = None):
+    """Attention core of a Swin block (dtlr_swin_window_attn): qkv [B,H,W,3C] -> [B,H,W,C]; rpb = swin_dense_bias(table, window).
+    ext, s (per-line batches: dtlr_swin_window_attn_ext): padding, roll, mask regions and crop of every line at its own stride-2^s
+    extent; positions outside it are padding on input and 0 on output."""
     require_cuda(qkv, "qkv")
     B, H, W, C3 = qkv.shape
     C = C3 // 3
     assert qkv.is_contiguous() and qkv_bias.dtype == torch.float32 and rpb.dtype == torch.float32 and rpb.is_contiguous()
     out = torch.empty((B, H, W, C), dtype=qkv.dtype, device=qkv.device)
+    if ext is not None:
+        _check_ext(ext, B)
+        code = _L(qkv).dtlr_swin_window_attn_ext(qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), ext.data_ptr(), int(s),
+                                                 B, H, W, C, n_heads, window, shift, _DT[qkv.dtype], _lib.current_stream())
+        _lib.check(code, "dtlr_swin_window_attn_ext")
+        return out
     code = _L(qkv).dtlr_swin_window_attn(qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), B, H, W, C, n_heads, window, shift,
                                             _DT[qkv.dtype], _lib.current_stream())
     _lib.check(code, "dtlr_swin_window_attn")
@@ -1019,12 +1039,20 @@ def swin_dense_bias(table, window: int):
     return out.contiguous()
 
 
-def swin_patch_merge(x, ln_w, ln_b, eps: float = 1e-5):
-    """PatchMerging up to its LayerNorm (dtlr_swin_patch_merge): x [B,H,W,C] -> [B, ceil(H/2), ceil(W/2), 4C]."""
+def swin_patch_merge(x, ln_w, ln_b, eps: float = 1e-5, ext=None, s: Optional[int] = None):
+    """PatchMerging up to its LayerNorm (dtlr_swin_patch_merge): x [B,H,W,C] -> [B, ceil(H/2), ceil(W/2), 4C].
+    ext, s (per-line batches: dtlr_swin_patch_merge_ext; s = the stride exponent of x): zeros for every input position outside a
+    line's extent, 0 written outside its stride-2^(s+1) extent."""
     require_cuda(x, "x")
     B, H, W, C = x.shape
     x = x if x.is_contiguous() else x.contiguous()
     y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, 4 * C), dtype=x.dtype, device=x.device)
+    if ext is not None:
+        _check_ext(ext, B)
+        code = _L(x).dtlr_swin_patch_merge_ext(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), ext.data_ptr(), int(s),
+                                               B, H, W, C, eps, _DT[x.dtype], _lib.current_stream())
+        _lib.check(code, "dtlr_swin_patch_merge_ext")
+        return y
     code = _L(x).dtlr_swin_patch_merge(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), B, H, W, C, eps, _DT[x.dtype], _lib.current_stream())
     _lib.check(code, "dtlr_swin_patch_merge")
     return y

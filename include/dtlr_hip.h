@@ -511,6 +511,25 @@ int dtlr_swin_window_attn(const void *qkv, const float *qkv_bias, const float *r
                           int B, int H, int W, int C, int n_heads, int window, int shift, int dtype, void *stream);
 int dtlr_swin_patch_merge(const void *x, const float *gamma, const float *beta, void *y, int B, int H, int W, int C,
                           float eps, int dtype, void *stream);
+/* Per-line forms (engine.forward(per_line=True) on a Swin backbone): the same kernels, the same arithmetic in the same order, with
+ * every line b of the canvas batch processed at its own size.  ext [B,2] int32 (h, w) on the device (dtlr_line_extents); at stride 2^s
+ * a line covers (ceil(h / 2^s), ceil(w / 2^s)) positions (clamped to the map).  B, H, W describe the canvas and addressing keeps its
+ * row pitch.  A position outside the line's extent is a padding position whatever the tensor holds there, and EVERY output position
+ * outside the output's extent is written as 0.  Nothing synchronises with the host.
+ * dtlr_swin_patch_embed_ext  PatchEmbed.forward (swin_transformer.py:416-432) of each line alone: pixels outside (h, w) read as the
+ *     zeros of F.pad ; tokens outside (ceil(h/4), ceil(w/4)) are 0.
+ * dtlr_swin_window_attn_ext  SwinTransformerBlock.forward :191-243 + BasicLayer.forward :357-376 of each line alone, s = the stage's
+ *     stride exponent (2..5): F.pad to the line's own multiple of the window (a position outside the extent projects to the bare
+ *     biases), torch.roll modulo the line's own padded size, the nine mask regions cut at the line's own padded size, crop to the
+ *     extent.  A workgroup whose window lies outside the line's own window grid does no attention work.
+ * dtlr_swin_patch_merge_ext  PatchMerging.forward :262-286 of each line alone, s_in = the INPUT's stride exponent: the F.pad zeros
+ *     of an odd H_l / W_l instead of the canvas neighbour ; output rows outside the stride-2^(s_in+1) extent are 0. */
+int dtlr_swin_patch_embed_ext(const float *x, const float *w_kE, const float *bias, const float *gamma, const float *beta,
+                              void *out, const int *ext, int B, int H, int W, int E, float eps, int out_dtype, void *stream);
+int dtlr_swin_window_attn_ext(const void *qkv, const float *qkv_bias, const float *rpb, void *out, const int *ext, int s,
+                              int B, int H, int W, int C, int n_heads, int window, int shift, int dtype, void *stream);
+int dtlr_swin_patch_merge_ext(const void *x, const float *gamma, const float *beta, void *y, const int *ext, int s_in,
+                              int B, int H, int W, int C, float eps, int dtype, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mask-derived geometry of one forward, ONE launch (a workgroup per row of a level of an image).

@@ -2,16 +2,17 @@
 """Batching modes on an IAM-like size set: `exact` (same resized size only), `padded` (mixed sizes in one canvas, the reference's
 padded-batch results) and `ragged` (the same canvases, forward(per_line=True): every line gets its bs = 1 result).
 
-    python tools/per_line_bench.py [--lines 256] [--batch 32] [--engines bf16,f32s] [--seed 0] [--repeats 2]
+    python tools/per_line_bench.py [--lines 256] [--batch 32] [--engines bf16,f32s] [--seed 0] [--repeats 2] [--backbone swin_T_224_1k]
 
 The size set: crops of 40-200 x 1000-2600 px (uniform, seeded) through the eval transform's resize (short side 800, long side capped
 at 1333), i.e. lines of ~24-160 x ~1330 px, nearly every one its own size.  Synthetic stroke lines at those sizes, Latin config,
-synthetic weights.  One JSON line per engine: lines/s of each mode (one untimed pass first: it calibrates the encoder kernels for every
+synthetic weights (`--backbone`: the same configuration on another backbone, e.g. swin_T_224_1k).  One JSON line per engine: lines/s of each mode (one untimed pass first: it calibrates the encoder kernels for every
 canvas shape), mean batch size, canvas fill (image pixels / canvas pixels), and the largest difference between `ragged` and
 `exact` per line (max |logit| and |box| difference, lines whose blank-decoded string differs).  Free-running: near-tied queries may
 take each other's slots (the per-line GPU tests compare teacher-forced).
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -49,8 +50,11 @@ def main():
     ap.add_argument("--engines", default="bf16,f32s")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--backbone", default=None, help="replace the Latin configuration's backbone (e.g. swin_T_224_1k)")
     args = ap.parse_args()
     cfg = DTLRConfig.latin()
+    if args.backbone:
+        cfg = dataclasses.replace(cfg, backbone=args.backbone)
     sd = weights.synthetic_state_dict(cfg, 0)
     crops, resized = iam_like_sizes(args.lines, args.seed)
     lines = [synth.stroke_lines(1, h, w, seed=1000 + i)[0].cuda() for i, (h, w) in enumerate(resized)]
@@ -60,7 +64,7 @@ def main():
         m = DINO(cfg, compute_dtype={"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "f32s": "f32s"}[eng])
         m.load_state_dict(sd)
         m.eval().cuda()
-        rec = {"engine": eng, "lines": args.lines, "batch": args.batch, "seed": args.seed}
+        rec = {"engine": eng, "backbone": cfg.backbone, "lines": args.lines, "batch": args.batch, "seed": args.seed}
         outs = {}
         for mode, plan in plans.items():
             outs[mode] = run_mode(m, lines, plan, mode == "ragged")                # untimed: per-canvas-shape calibration, allocator warm-up
