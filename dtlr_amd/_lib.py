@@ -29,6 +29,13 @@ class K256sSlice(ctypes.Structure):
                 ("ldc", c_int), ("ldr", c_int), ("n_valid", c_int), ("relu", c_int)]
 
 
+class NgramLM(ctypes.Structure):
+    """include/dtlr_hip.h: dtlr_ngram_lm"""
+    _fields_ = [("tok", c_void_p), ("child_lo", c_void_p), ("child_hi", c_void_p), ("suffix", c_void_p), ("ctx", c_void_p),
+                ("logp", c_void_p), ("bo", c_void_p), ("n_nodes", c_int), ("order", c_int), ("bos_state", c_int), ("eos_tok", c_int),
+                ("unk", ctypes.c_double)]
+
+
 # name -> (restype, argtypes): every symbol include/dtlr_hip.h declares
 _SIGNATURES = {
     "dtlr_strerror": (c_char_p, [c_int]),
@@ -119,6 +126,9 @@ _SIGNATURES = {
     "dtlr_nms": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dtlr_blank_emissions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "dtlr_blank_emissions_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
+    "dtlr_ngram_beam": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, c_int, c_int,
+                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtlr_ngram_beam_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
     "dtlr_decode_blank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     # per-line batching
     "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -119,14 +119,16 @@ def image_size(path: str) -> Tuple[int, int]:
 def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optional[float] = None,
                    NM: Optional[float] = None, postprocessor=None, device="cuda", size: int = EVAL_SIZE,
                    max_size: int = EVAL_MAX_SIZE, rank: int = 0, world: int = 1, sizes: Optional[Sequence[Tuple[int, int]]] = None,
-                   skip_errors: bool = True, per_line: bool = False) -> List[Optional[List[int]]]:
+                   skip_errors: bool = True, per_line: bool = False, ngram: Optional[Dict] = None) -> List[Optional[List[int]]]:
     """convert_output_to_pred (evaluation.py:94-158) for a list of RGB uint8 images -> one label list per image, dataset
     order.  TH / NM given: the NMS decoder; otherwise the blank/argmax decoder with eps = 0.03 / C.
     `images`: a sequence of [h, w, 3] uint8 arrays, or (with `sizes` = the (h, w) of every line) a callable i -> array that is
     invoked only for the lines of this rank's shard.  skip_errors (the reference's behaviour, evaluation.py:498-504): a line whose
     load / forward / decode raises is reported and returned as None; KeyboardInterrupt always propagates.
     per_line (`--batching ragged`): mixed sizes share a padded batch as with exact=False, and the forward runs per line
-    (DINO.forward(per_line=True)): every line gets the result it gets alone."""
+    (DINO.forward(per_line=True)): every line gets the result it gets alone.
+    ngram (`--ngram-arpa`): the bundle of ngram_bundle(); the batch's lines are then re-scored by the device n-gram beam decoder
+    (ngram.rescored_labels_batch: one launch over every word span of the batch) instead of decoded by the blank / NMS decoder."""
     lazy = callable(images)
     if lazy and sizes is None:
         raise ValueError("predict_labels: a loader callable needs `sizes`")
@@ -142,7 +144,11 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
     def run(idx):
         samples = tf([load(i) for i in idx], device=device)
         out = model(samples, per_line=True) if per_line else model(samples)
-        preds = E.decode_nms(out, postprocessor, TH, NM) if (TH is not None and NM is not None) else E.decode_blank(out)
+        if ngram is not None:
+            from . import ngram as NG
+            preds = NG.rescored_labels_batch(out, ngram)
+        else:
+            preds = E.decode_nms(out, postprocessor, TH, NM) if (TH is not None and NM is not None) else E.decode_blank(out)
         for i, p in zip(idx, preds):
             rec[i, : len(p)] = torch.tensor(p, dtype=torch.int32)
             rec[i, nq], rec[i, nq + 1] = len(p), 0
@@ -238,6 +244,47 @@ def write_outputs(res: Dict, out_dir: str, dataset: str, TH, NM) -> str:
     return stats_dir
 
 
+def default_ngram_tokens(charset: Sequence) -> List[str]:
+    """The token table of the n-gram side, indexed by emission channel: the CTC token, then the charset with " " spelled <space>
+    (the layout ngram/preprocessing/get_char_training_text.py:95-100 writes)."""
+    return ["<ctc>"] + ["<space>" if c == " " else str(c) for c in charset]
+
+
+def default_ngram_ignore(charset: Sequence) -> List[int]:
+    """Channels that are never re-scored: the charset's non-alphanumeric characters except the apostrophe (the RIMES / READ rule of
+    ngram/clean_gen_ngram_preds.py:288-311)."""
+    return [i + 1 for i, c in enumerate(charset) if not str(c).isalnum() and str(c) != "'"]
+
+
+def ngram_bundle(args, charset: Sequence, device) -> Optional[Dict]:
+    """What predict_labels(ngram=...) takes, from the command line; None without --ngram-arpa."""
+    if not args.ngram_arpa:
+        return None
+    from . import ngram as NG
+    if args.ngram_tokens:
+        with open(args.ngram_tokens, encoding="utf-8") as f:
+            tokens = [line.rstrip("\n") for line in f if line.rstrip("\n")]
+    else:
+        tokens = default_ngram_tokens(charset)
+    if len(tokens) != len(charset) + 1:
+        raise SystemExit(f"--ngram-tokens: {len(tokens)} tokens for {len(charset)} characters + the CTC token")
+    if len(set(tokens)) != len(tokens):
+        dup = sorted({t for t in tokens if tokens.count(t) > 1})
+        raise SystemExit(f"--ngram-tokens: repeated token(s) {dup}: a token must name one emission channel")
+    ngram_charset = ["<ctc>"] + [str(c) for c in charset]
+    if args.ngram_ignore is None:
+        ignore = default_ngram_ignore(charset)
+    else:
+        missing = [c for c in args.ngram_ignore if c not in ngram_charset[1:]]
+        if missing:
+            raise SystemExit(f"--ngram-ignore: {missing} not in the charset")
+        ignore = [ngram_charset.index(c, 1) for c in args.ngram_ignore]
+    dec = NG.DeviceNgramDecoder(tokens, NG.ArpaLM(args.ngram_arpa), args.ngram_weight, args.ngram_beam, args.ngram_beam_token,
+                                blank_token=tokens[0], device=device)
+    return dict(decoder=dec, ignore=ignore, ngram_charset=ngram_charset, no_uppercase_words=args.no_uppercase_words,
+                no_digits=args.no_digits, no_dash=args.no_dash, multiply_pred_logits_by=args.multiply_pred_logits_by)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m dtlr_amd.evaluation", description=__doc__.split("\n\n")[0])
     # the reference's flags (evaluation.py:15-27)
@@ -267,6 +314,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--limit", type=int, default=0, help="evaluate only the first N lines")
     ap.add_argument("--size", type=int, default=EVAL_SIZE, help="eval resize: short side (config/coco_transformer.py:1)")
     ap.add_argument("--max_size", type=int, default=EVAL_MAX_SIZE, help="eval resize: long-side cap (config/coco_transformer.py:2)")
+    # n-gram re-scoring (the reference's ngram/ path; ngram/IAM.yaml: 6-gram character model, weight 0.25, per word)
+    ap.add_argument("--ngram-arpa", default=None, help="character n-gram in ARPA text: switches re-scoring by the device beam decoder on")
+    ap.add_argument("--ngram-weight", type=float, default=0.25)
+    ap.add_argument("--ngram-beam", type=int, default=50, help="beam size, 1..64")
+    ap.add_argument("--ngram-beam-token", type=int, default=None, help="tokens extended per frame (default: all)")
+    ap.add_argument("--ngram-tokens", default=None, help="token table, one per line, channel order (default: <ctc> + the charset, ' ' as <space>)")
+    ap.add_argument("--ngram-ignore", default=None, help="characters never re-scored (default: the charset's non-alphanumerics except ')")
+    ap.add_argument("--multiply_pred_logits_by", type=float, default=1.0)
+    ap.add_argument("--no_uppercase_words", action="store_true")
+    ap.add_argument("--no_digits", action="store_true")
+    ap.add_argument("--no_dash", action="store_true")
     return ap
 
 
@@ -310,11 +368,13 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     images = lambda i: read_rgb(paths[i])                      # noqa: E731
     texts = [t for _, t in rows]
     post = PostProcess(num_select=cfg.num_select, nms_iou_threshold=cfg.nms_iou_threshold)
+    bundle = ngram_bundle(args, charset, dev)
+    extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
     for TH in list_TH:
         for NM in list_NM:
             preds = predict_labels(model, images, args.batch, args.batching == "exact", TH, NM, post, dev, args.size, args.max_size,
-                                   rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged")
+                                   rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", **extra)
             if rank == 0:
                 res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
                 d = write_outputs(res, args.out, args.dataset, TH, NM)

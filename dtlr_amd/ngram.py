@@ -12,9 +12,19 @@ and sends every word's emissions through torchaudio's lexicon CTC beam decoder w
     decoder is a CALLABLE with torchaudio's interface (`decoder(emissions [1,T,V]) -> [[hypothesis]]`, hypothesis.words), so a
     user holding those packages passes `torchaudio.models.decoder.ctc_decoder(...)` unchanged.  `LexiconCTCDecoder` below is a
     small self-contained stand-in with the same interface -- CTC prefix beam search constrained to a lexicon, scored with an ARPA
-    n-gram (`ArpaLM`) -- restating the published algorithm.  PARITY UNPINNED: nothing in this container can run torchaudio's decoder or
-    KenLM, so `LexiconCTCDecoder` / `ArpaLM` are checked only against hand-computed cases; what IS pinned to the reference (G8: vectors
-    produced by its own function bodies) is everything around the decoder: emissions, span selection, re-assembly.
+    n-gram (`ArpaLM`) -- restating the published algorithm;
+  * the reference's lexicon spells every character by itself (ngram/preprocessing/get_char_training_text.py:102-108), so what runs
+    there is a character-level CTC prefix beam search scored by a back-off character n-gram on the frames of one word.
+    `DeviceNgramDecoder` is that search as a HIP kernel (csrc/ngram_beam.hip, dtlr_ngram_beam): every span of a batch in one launch,
+    fp64 scores, the LM as a sorted trie in device memory (`pack_lm`).  `get_ngram_predictions_batch` is the batched form of
+    `get_ngram_prediction`: one copy of the argmax rows to the host, one launch, one copy of the records back.
+
+WHAT IS PINNED: (a) to the reference, by vectors its own function bodies produced (G8): emissions, span selection, re-assembly;
+(b) the device decoder's semantics, written down in DESIGN.md section 10: the kernel equals a dict-based fp64 restatement of them, and
+that restatement equals an exhaustive enumeration of all alignments on small cases (tests/ngram_beam_ref.py) -- no third party needed.
+WHAT IS NOT: torchaudio / flashlight-text / KenLM are not available here, so flashlight's own scoring conventions (its `log_add`, the
+`sil` token's handling, how it treats a repeated one-token word, its beam threshold) are not compared with; `LexiconCTCDecoder` /
+`ArpaLM` are checked against hand-computed cases only.
 """
 from __future__ import annotations
 
@@ -73,21 +83,59 @@ def get_input_split_indices(model_labels: Sequence[int], ngram_charset: Sequence
     return split, clean
 
 
+def _assemble_words(labels: Sequence[int], indices_to_ignore: Sequence[int], decode_span: Callable) -> list:
+    """The assembly of prediction_helpers.py:49-74 on one argmax row: a list of decoder words (str, from decode_span(first, end)) and
+    of separator channels (int, from the argmax)."""
+    ignore = set(int(i) for i in indices_to_ignore)
+    split = [-1] + [i for i, v in enumerate(labels) if v in ignore] + [len(labels)]
+    items: list = []
+    for i in range(len(split) - 1):
+        if split[i] < split[i + 1] - 1:
+            items += decode_span(split[i] + 1, split[i + 1])
+        if split[i + 1] < len(labels):
+            items.append(int(labels[split[i + 1]]))
+    return items
+
+
+def _assemble_words_2(labels: Sequence[int], indices_to_ignore: Sequence[int], ngram_charset: Sequence[str], no_uppercase_words: bool,
+                      no_digits: bool, no_dash: bool, decode_span: Callable) -> list:
+    """The assembly of prediction_helpers.py:176-224 on one argmax row: decoder words (str) and argmax channels (int)."""
+    split, clean = get_input_split_indices(labels, ngram_charset, indices_to_ignore, no_uppercase_words, no_digits, no_dash)
+    items: list = []
+    max_added = -1
+    inner, head = set(split[1:]), set(split[:-1])
+    clean_set = set(clean)
+    for i in range(len(split) - 1):
+        a, b = split[i], split[i + 1]
+        if a in inner and a > max_added:
+            items.append(int(labels[a]))
+            max_added = a
+        if a < b and a in clean_set:
+            items += decode_span(a + 1, b)
+            max_added = max(b - 1, max_added)
+        else:
+            items += [int(v) for v in labels[a + 1: b] if v > 0]
+            max_added = max(b - 1, max_added)
+        if b in head and b > max_added:
+            items.append(int(labels[b]))
+            max_added = b
+    return items
+
+
+def _join(items: list, table: Sequence[str], shift: int) -> str:
+    """decoder words as they are; an argmax channel c as table[c - shift] (a multi-character entry contributes its characters)."""
+    chars: List[str] = []
+    for it in items:
+        chars += it if isinstance(it, str) else table[it - shift]
+    return "".join(chars)
+
+
 def get_word_per_word_pred(new_pred_logits: torch.Tensor, ctc_decoder: Callable, indices_to_ignore: Sequence[int], charset: Sequence[str]) -> str:
     """prediction_helpers.py:49-74: every span between never-rescored characters goes through the decoder; the separators are copied
     from the argmax (charset[label - 1])."""
     row = new_pred_logits[0]
     labels = row.argmax(-1).tolist()
-    ignore = set(int(i) for i in indices_to_ignore)
-    split = [-1] + [i for i, v in enumerate(labels) if v in ignore] + [len(labels)]
-    chars: List[str] = []
-    for i in range(len(split) - 1):
-        if split[i] < split[i + 1] - 1:
-            word = row[split[i] + 1: split[i + 1]][None, :, :]
-            chars += ctc_decoder(word.cpu())[0][0].words
-        if split[i + 1] < len(labels):
-            chars += charset[labels[split[i + 1]] - 1]
-    return "".join(chars)
+    return _join(_assemble_words(labels, indices_to_ignore, lambda lo, hi: ctc_decoder(row[lo:hi][None, :, :].cpu())[0][0].words), charset, 1)
 
 
 def get_word_per_word_pred_2(new_pred_logits: torch.Tensor, ctc_decoder: Callable, indices_to_ignore: Sequence[int],
@@ -95,26 +143,8 @@ def get_word_per_word_pred_2(new_pred_logits: torch.Tensor, ctc_decoder: Callabl
     """prediction_helpers.py:176-224: like the above, but spans that must not be rescored keep their argmax characters."""
     row = new_pred_logits[0]
     labels = row.argmax(-1).tolist()
-    split, clean = get_input_split_indices(labels, ngram_charset, indices_to_ignore, no_uppercase_words, no_digits, no_dash)
-    chars: List[str] = []
-    max_added = -1
-    inner, head = set(split[1:]), set(split[:-1])
-    clean_set = set(clean)
-    for i in range(len(split) - 1):
-        a, b = split[i], split[i + 1]
-        if a in inner and a > max_added:
-            chars += ngram_charset[labels[a]]
-            max_added = a
-        if a < b and a in clean_set:
-            chars += ctc_decoder(row[a + 1: b][None, :, :].cpu())[0][0].words
-            max_added = max(b - 1, max_added)
-        else:
-            chars += [ngram_charset[v] for v in labels[a + 1: b] if v > 0]
-            max_added = max(b - 1, max_added)
-        if b in head and b > max_added:
-            chars += ngram_charset[labels[b]]
-            max_added = b
-    return "".join(chars)
+    return _join(_assemble_words_2(labels, indices_to_ignore, ngram_charset, no_uppercase_words, no_digits, no_dash,
+                                   lambda lo, hi: ctc_decoder(row[lo:hi][None, :, :].cpu())[0][0].words), ngram_charset, 0)
 
 
 @torch.no_grad()
@@ -247,3 +277,195 @@ class LexiconCTCDecoder:
 
     def __call__(self, emissions: torch.Tensor) -> List[List[_Hypothesis]]:
         return [self._decode_one(e) for e in emissions]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# The device decoder: character-level CTC prefix beam search scored by a back-off character n-gram (csrc/ngram_beam.hip).
+def _lm_word(token: str) -> str:
+    return "<space>" if token == " " else token
+
+
+def pack_lm(lm: ArpaLM, tokens: Sequence[str], blank_token: str = "<ctc>") -> Dict:
+    """The n-gram table as the sorted trie dtlr_ngram_beam reads (include/dtlr_hip.h, dtlr_ngram_lm), as CPU tensors.  Pure host code.
+    An LM word is known by the emission channel that spells it (tokens[c]; " " is the LM's <space>); <s> is V, </s> is V + 1; n-grams
+    with any other word (<unk> among them) cannot be reached from a label sequence and are left out -- a channel the LM does not
+    know misses every look-up and scores the <unk> unigram behind the back-offs of its context, as ArpaLM.score does.  Node 0 is the
+    empty context; nodes are sorted by (length, channels), so the children of a node are contiguous and sorted by channel.  A prefix
+    of an n-gram that is not an n-gram itself gets a node with logp = 1 (never a hit) and back-off 0."""
+    V = len(tokens)
+    word_id = {_lm_word(t): c for c, t in enumerate(tokens) if t != blank_token}
+    word_id["<s>"], word_id["</s>"] = V, V + 1
+    real: Dict[Tuple[int, ...], Tuple[float, float]] = {}
+    for words, (p, bo) in lm.grams.items():
+        ids = tuple(word_id.get(w, -1) for w in words)
+        if min(ids) >= 0:
+            real[ids] = (min(float(p), 0.0), float(bo))
+    nodes = set(real)
+    for g in real:
+        for k in range(1, len(g)):
+            nodes.add(g[:k])
+    order_list = [()] + sorted(nodes, key=lambda g: (len(g), g))
+    index = {g: i for i, g in enumerate(order_list)}
+    n = len(order_list)
+    tok, lo, hi, suf, ctx = [0] * n, [0] * n, [0] * n, [0] * n, [0] * n
+    logp, bo = [1.0] * n, [0.0] * n
+    for i in range(n - 1, 0, -1):                     # descending: the last write of lo[parent] is its first child
+        g = order_list[i]
+        par = index[g[:-1]]
+        lo[par] = i
+        hi[par] = max(hi[par], i + 1)
+        tok[i] = g[-1]
+        if g in real:
+            logp[i], bo[i] = real[g]
+        k = 1
+        while g[k:] not in index:
+            k += 1
+        suf[i] = index[g[k:]]
+    for i in range(1, n):
+        ctx[i] = i if len(order_list[i]) <= lm.order - 1 else suf[i]
+    bos_node = index.get((V,))
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)                # noqa: E731
+    f64 = lambda v: torch.tensor(v, dtype=torch.float64)              # noqa: E731
+    return dict(tok=i32(tok), child_lo=i32(lo), child_hi=i32(hi), suffix=i32(suf), ctx=i32(ctx), logp=f64(logp), bo=f64(bo),
+                order=lm.order, bos_state=ctx[bos_node] if bos_node is not None else 0,
+                eos_tok=V + 1 if ("</s>",) in lm.grams else -1, has_bos=("<s>",) in lm.grams, has_eos=("</s>",) in lm.grams,
+                unk=float(lm.grams.get(("<unk>",), (-10.0, 0.0))[0]), vocab=V)
+
+
+def _host_lists(packed: Dict) -> Dict:
+    h = packed.get("_host")
+    if h is None:
+        h = packed["_host"] = {k: packed[k].tolist() for k in ("tok", "child_lo", "child_hi", "suffix", "ctx", "logp", "bo")}
+    return h
+
+
+def lm_walk(packed: Dict, state: int, token: int) -> Tuple[float, int]:
+    """(log10 P(token | state), the state after token) on the packed trie -- the walk the kernel does, on the host."""
+    h = _host_lists(packed)
+    acc, new_state, s = 0.0, -1, state
+    while True:
+        lo, hi, found = h["child_lo"][s], h["child_hi"][s], -1
+        while lo < hi:
+            mid = (lo + hi) >> 1
+            if h["tok"][mid] == token:
+                found = mid
+                break
+            if h["tok"][mid] < token:
+                lo = mid + 1
+            else:
+                hi = mid
+        if found >= 0:
+            if new_state < 0:
+                new_state = h["ctx"][found]
+            if h["logp"][found] <= 0.0:
+                return acc + h["logp"][found], new_state
+        if s == 0:
+            return acc + packed["unk"], max(new_state, 0)
+        acc += h["bo"][s]
+        s = h["suffix"][s]
+
+
+def lm_state(packed: Dict, context: Sequence[int]) -> int:
+    """The LM state of a context given as channels (V = <s>): the node of its longest suffix, at most order - 1 long, the trie holds."""
+    s = 0
+    for c in context:
+        s = lm_walk(packed, s, int(c))[1]
+    return s
+
+
+class DeviceNgramDecoder:
+    """Character-level CTC prefix beam search with a back-off character n-gram, on the device (dtlr_ngram_beam; the semantics are
+    written down in DESIGN.md section 10).  tokens[c] = the string of emission channel c, tokens[0] = the blank.
+    decode_spans(emissions [B,T,V] CUDA, spans [(line, first, end)]) -> (labels, lengths, scores) on the device, all spans in one launch.
+    __call__(emissions [B,T,V], CUDA or CPU) keeps torchaudio's interface: [[hypothesis]] with .words (token strings) and .score."""
+
+    def __init__(self, tokens: Sequence[str], lm: Optional[ArpaLM] = None, lm_weight: float = 0.0, beam_size: int = 50,
+                 beam_size_token: Optional[int] = None, blank_token: str = "<ctc>", bos: Optional[bool] = None, eos: Optional[bool] = None,
+                 device="cuda"):
+        self.tokens = list(tokens)
+        if not self.tokens or self.tokens[0] != blank_token:
+            raise ValueError("DeviceNgramDecoder: the blank must be emission channel 0 (what dtlr_blank_emissions writes)")
+        if not 1 <= int(beam_size) <= 64:
+            raise ValueError("DeviceNgramDecoder: beam_size must be in 1..64")
+        self.lm_weight, self.beam_size, self.beam_size_token = float(lm_weight), int(beam_size), int(beam_size_token or 0)
+        self.device = torch.device(device)
+        self.packed = pack_lm(lm, self.tokens, blank_token) if lm is not None else None
+        self.bos = bool(self.packed and self.packed["has_bos"]) if bos is None else bool(bos)
+        self.eos = bool(self.packed and self.packed["has_eos"]) if eos is None else bool(eos)
+        self._on: Dict = {}
+
+    def _lm_on(self, device) -> Optional[Dict]:
+        if self.packed is None:
+            return None
+        key = str(device)
+        if key not in self._on:                         # uploaded once per device
+            self._on[key] = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in self.packed.items() if k != "_host"}
+        return self._on[key]
+
+    def decode_spans(self, emissions: torch.Tensor, spans):
+        from . import ops
+        return ops.ngram_beam(emissions, spans, self._lm_on(emissions.device), self.lm_weight, self.beam_size, self.beam_size_token,
+                              self.bos, self.eos)
+
+    def words(self, labels_row: Sequence[int], length: int) -> List[str]:
+        return [self.tokens[int(c)] for c in labels_row[:length]]
+
+    def __call__(self, emissions: torch.Tensor) -> List[List[_Hypothesis]]:
+        B, T = emissions.shape[0], emissions.shape[1]
+        if B == 0 or T == 0:
+            return [[_Hypothesis([], 0.0)] for _ in range(B)]
+        em = emissions if emissions.is_cuda else emissions.to(self.device)
+        labels, lengths, scores = self.decode_spans(em, [(b, 0, T) for b in range(B)])
+        labels, lengths, scores = labels.cpu().tolist(), lengths.cpu().tolist(), scores.cpu().tolist()
+        return [[_Hypothesis(self.words(labels[b], lengths[b]), scores[b])] for b in range(B)]
+
+
+@torch.no_grad()
+def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
+                   multiply_pred_logits_by) -> List[list]:
+    """Per line: the item list of _assemble_words / _assemble_words_2 (decoder words as str, argmax channels as int)."""
+    if not per_word_ngram:
+        raise NotImplementedError("no test support for full sentence n-gram for now")      # as the reference (:108)
+    emissions = get_new_pred_logits(outputs, multiply_pred_logits_by)         # [B, T, V] on the device
+    rows = emissions.argmax(-1).cpu().tolist()                                # the one copy the host span logic needs
+    second = bool(no_uppercase_words or no_digits)
+
+    def assemble(b, decode_span):
+        if second:
+            return _assemble_words_2(rows[b], indices_to_ignore, ngram_charset, no_uppercase_words, no_digits, no_dash, decode_span)
+        return _assemble_words(rows[b], indices_to_ignore, decode_span)
+
+    if not isinstance(decoder, DeviceNgramDecoder):                           # any callable with torchaudio's interface: one call per span
+        host = emissions.cpu()
+        return [assemble(b, lambda lo, hi, b=b: decoder(host[b, lo:hi][None, :, :])[0][0].words) for b in range(len(rows))]
+    spans: List[Tuple[int, int, int]] = []
+    for b in range(len(rows)):                                                # pass 1: which spans go to the decoder
+        assemble(b, lambda lo, hi, b=b: spans.append((b, lo, hi)) or [])
+    labels, lengths, _ = decoder.decode_spans(emissions, spans)
+    labels, lengths = labels.cpu().tolist(), lengths.cpu().tolist()           # the records, one copy each
+    found = {sp: decoder.words(labels[k], lengths[k]) for k, sp in enumerate(spans)}
+    return [assemble(b, lambda lo, hi, b=b: found[(b, lo, hi)]) for b in range(len(rows))]
+
+
+def get_ngram_predictions_batch(outputs, decoder: Callable, indices_to_ignore, charset, ngram_charset, per_word_ngram: bool = True,
+                                no_uppercase_words: bool = False, no_digits: bool = False, no_dash: bool = True,
+                                multiply_pred_logits_by: float = 1.0) -> List[str]:
+    """get_ngram_prediction for a whole batch: emissions by the device kernel, ONE device -> host copy of the [B, T] argmax rows, the
+    host span logic per line, ONE dtlr_ngram_beam launch over every span of every line that goes to the decoder, one copy of the
+    records back, the same assembly.  Each line's string is the one get_ngram_prediction returns for that line alone with the same
+    decoder.  A decoder that is not a DeviceNgramDecoder is called once per span on host emissions."""
+    items = _rescore_batch(outputs, decoder, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
+                           multiply_pred_logits_by)
+    if no_uppercase_words or no_digits:
+        return [_join(it, ngram_charset, 0) for it in items]
+    return [_join(it, charset, 1) for it in items]
+
+
+def rescored_labels_batch(outputs, bundle: Dict) -> List[List[int]]:
+    """The re-scored lines of a batch as LABEL ids (channel - 1), for the evaluation harness: `bundle` = dict(decoder=DeviceNgramDecoder,
+    ignore=[channels], ngram_charset=[...], no_uppercase_words, no_digits, no_dash, multiply_pred_logits_by)."""
+    dec = bundle["decoder"]
+    chan = {t: c for c, t in enumerate(dec.tokens)}
+    items = _rescore_batch(outputs, dec, bundle["ignore"], bundle["ngram_charset"], True, bundle.get("no_uppercase_words", False),
+                           bundle.get("no_digits", False), bundle.get("no_dash", True), bundle.get("multiply_pred_logits_by", 1.0))
+    return [[(chan[it] if isinstance(it, str) else it) - 1 for it in line if isinstance(it, str) or it > 0] for line in items]

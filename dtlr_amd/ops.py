@@ -1308,6 +1308,54 @@ def blank_emissions(logits, boxes, eps: float, scale: float = 1.0):
     return out
 
 
+_NGRAM_LM_FIELDS = ("tok", "child_lo", "child_hi", "suffix", "ctx", "logp", "bo")
+
+
+def ngram_beam(emissions, spans, lm=None, lm_weight: float = 0.0, beam_size: int = 50, beam_size_token: int = 0,
+               bos: bool = True, eos: bool = True):
+    """Character n-gram CTC prefix beam search over every span in ONE launch (dtlr_ngram_beam; semantics: DESIGN.md section 10).
+    emissions [B,T,V] fp32 CUDA probabilities (channel 0 = blank); spans: HOST [n,3] integers (line, first frame, one past the last),
+    checked here before the upload (the kernel only clamps); lm: the packed trie of ngram.pack_lm with its tensors on the emissions'
+    device, or None.  -> (labels [n,Lmax] int32, -1 padded; lengths [n] int32; scores [n] fp64), all on the device.  The library call
+    never synchronises; this wrapper allocates the outputs and the workspace and uploads the span table from pageable host memory (a
+    blocking copy on the current stream)."""
+    require_cuda(emissions, "emissions")
+    if emissions.dim() != 3:
+        raise _lib.DTLRError("ngram_beam: emissions must be [B, T, V]")
+    emissions = emissions.float().contiguous()
+    B, T, V = emissions.shape
+    sp = torch.as_tensor(spans, dtype=torch.int64, device="cpu").reshape(-1, 3)
+    n = int(sp.shape[0])
+    dev = emissions.device
+    if n and (int(sp[:, 0].min()) < 0 or int(sp[:, 0].max()) >= B or int(sp[:, 1].min()) < 0 or int(sp[:, 2].max()) > T
+              or bool((sp[:, 1] > sp[:, 2]).any())):
+        raise _lib.DTLRError(f"ngram_beam: span table outside emissions [{B}, {T}, {V}]")
+    Tmax = int((sp[:, 2] - sp[:, 1]).max()) if n else 0
+    Lmax = max(Tmax, 1)
+    labels = torch.empty((n, Lmax), dtype=torch.int32, device=dev)
+    lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+    scores = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n == 0:
+        return labels, lengths, scores
+    L_ = _lib.lib()
+    st = None
+    if lm is not None:
+        for k in _NGRAM_LM_FIELDS:
+            t = lm[k]
+            want = torch.float64 if k in ("logp", "bo") else torch.int32
+            if not (t.is_cuda and t.device == dev and t.dtype == want and t.is_contiguous() and t.numel() == lm["tok"].numel()):
+                raise _lib.DTLRError(f"ngram_beam: lm['{k}'] must be a contiguous {want} tensor on {dev}")
+        st = _lib.NgramLM(*[lm[k].data_ptr() for k in _NGRAM_LM_FIELDS], int(lm["tok"].numel()), int(lm["order"]),
+                          int(lm["bos_state"]), int(lm["eos_tok"]), float(lm["unk"]))
+    ws = torch.empty(L_.dtlr_ngram_beam_workspace_bytes(n, Tmax, int(beam_size)), dtype=torch.uint8, device=dev)
+    spans_dev = sp.to(torch.int32).to(dev)
+    code = L_.dtlr_ngram_beam(emissions.data_ptr(), B, T, V, spans_dev.data_ptr(), n, Tmax, ctypes.cast(ctypes.pointer(st), ctypes.c_void_p) if st is not None else None,
+                              float(lm_weight), int(beam_size), int(beam_size_token or 0), int(bool(bos)), int(bool(eos)),
+                              labels.data_ptr(), Lmax, lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _lib.current_stream())
+    _lib.check(code, "dtlr_ngram_beam")
+    return labels, lengths, scores
+
+
 def preprocess_lines(src_u8, offsets, dims, Hc: int, Wc: int, max_downscale: float, mean, std):
     """Resize + ToTensor + Normalize + pad of a batch of uint8 RGB images in ONE launch (dtlr_preprocess_lines).
     src_u8: flat uint8 CUDA tensor (images back to back, HWC); offsets [B] int64 CUDA; dims [B,4] int32 CUDA = (h, w, oh, ow).
@@ -1396,7 +1444,7 @@ def _device_scoped(fn):
 for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
               "maxpool_nhwc", "groupnorm_tokens", "msda", "msda_fused", "msda_encoder", "mha", "decoder_query_prep", "box_mlp_refine",
               "box_head_refine", "box_refine", "topk_rows", "decode_blank", "preprocess_lines", "ctc_loss_interleaved", "nms_batched",
-              "topk_flat", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
+              "topk_flat", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
     globals()[_name] = _device_scoped(globals()[_name])
 del _name
 

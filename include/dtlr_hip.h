@@ -632,6 +632,41 @@ int dtlr_blank_emissions(const float *logits, const float *boxes, float *out, fl
                          int B, int nq, int C, float scale, float eps, void *stream);
 long dtlr_blank_emissions_workspace_bytes(int B, int nq);
 
+/* ---------------------------------------------------------------------------------------------
+ * Character n-gram CTC prefix beam search, every span of a batch in one launch (csrc/ngram_beam.hip; semantics: DESIGN.md section 10).
+ * Replaces: torchaudio.models.decoder.ctc_decoder with a one-token-per-word lexicon and a KenLM character n-gram, called on the
+ *           emissions of one word (ngram/prediction_helpers.py:66,82-90,208; lexicon: ngram/preprocessing/get_char_training_text.py:102-108).
+ *   emissions [B,T,V] fp32 probabilities, channel 0 = the CTC blank (what dtlr_blank_emissions writes) ;
+ *   spans [n,3] int32 on the DEVICE: (line, first frame, one past the last frame).  The kernel clamps every line to [0, B), every frame
+ *     to [0, T] and every span to its first Tmax frames: a bad table gives a wrong string, never a fault ;
+ *   Tmax >= 0: the longest span of the table, as the caller states it (0: no span runs a frame and the workspace is not touched) ;
+ *     Lmax >= max(Tmax, 1) (DTLR_ESHAPE / DTLR_EINVAL otherwise) ;
+ *   lm: NULL, or a HOST struct of DEVICE pointers to the packed back-off trie (order <= 6).  Node 0 is the empty context; the children of
+ *     node s are nodes child_lo[s] .. child_hi[s] - 1, sorted by tok (emission channel; V = <s>, V + 1 = </s>); logp / bo are the ARPA
+ *     log10 values (logp > 0: the node is only a prefix of longer n-grams, not an n-gram itself); suffix[s] = the node of the longest
+ *     proper suffix the trie holds; ctx[s] = the LM state after s (s itself, or suffix[s] for an n-gram of full order) ;
+ *   lm_weight w: an extension by c adds w ln(10) log10 P(c | context) ; bos: the context starts with <s> ; eos: the final score adds
+ *     w ln(10) log10 P(</s> | context) ;
+ *   K: beam, 1..64 (DTLR_ESHAPE otherwise) ; N: tokens extended per frame, the N largest E[t, c] (equal: lower channel first);
+ *     N <= 0 or N >= V - 1: all of them.  N <= 1024 and the LDS image ~ 8 (K N + N + 64) + 12 KB <= 150 KB, V <= 65536 (DTLR_ESHAPE) ;
+ *   labels_out [n,Lmax] int32 (channels, -1 padded), len_out [n] int32, score_out [n] fp64 ; an empty span gives length 0 ; n = 0 is a no-op ;
+ *   workspace: the back-pointer arena, the size the _workspace_bytes entry returns for (n, Tmax, K).
+ * Scores are fp64.  Exact ties are cut by candidate index (stay entries in beam order, then extensions by (parent's beam slot,
+ * channel)): the same records on every run.  Asynchronous on `stream`; never synchronises. */
+typedef struct dtlr_ngram_lm {
+    const int *tok, *child_lo, *child_hi, *suffix, *ctx;
+    const double *logp, *bo;
+    int n_nodes, order;
+    int bos_state;      /* LM state of the context (<s>), 0 when the model has none */
+    int eos_tok;        /* V + 1, or -1 when the model has no </s>: with eos set, </s> then scores as any unknown word does
+                           (the <unk> unigram behind the context's back-offs), as ArpaLM.score would */
+    double unk;         /* log10 P(<unk>) */
+} dtlr_ngram_lm;
+int dtlr_ngram_beam(const float *emissions, int B, int T, int V, const int *spans, int n, int Tmax,
+                    const dtlr_ngram_lm *lm, double lm_weight, int K, int N, int bos, int eos,
+                    int *labels_out, int Lmax, int *len_out, double *score_out, void *workspace, void *stream);
+long dtlr_ngram_beam_workspace_bytes(int n, int Tmax, int K);
+
 /* Greedy non-maximum suppression, batched: image b keeps, in descending score order (equal scores: lower index first), every
  * box whose IoU with an already kept box is <= iou_threshold.
  * Replaces: `torchvision.ops.nms(b, s, iou_threshold)` as PostProcess calls it per image (models/dino/dino.py:1029-1033), i.e.
