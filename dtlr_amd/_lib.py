@@ -123,6 +123,16 @@ _SIGNATURES = {
     "dtlr_topk_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_ctc_loss_interleaved": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "dtlr_topk_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_long, c_int, c_int, c_void_p]),
+    # class-head adaptation (csrc/ctc_grad.hip, csrc/head_grad.hip)
+    "dtlr_ctc_loss_interleaved_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                                   c_int, c_float, c_float, c_void_p]),
+    "dtlr_ctc_loss_interleaved_backward_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
+    "dtlr_head_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_void_p]),
+    "dtlr_head_grad_workspace_bytes": (ctypes.c_long, [ctypes.c_long, c_int, c_int]),
+    "dtlr_grad_norm_scale": (c_int, [c_void_p, ctypes.c_long, c_float, c_void_p, c_void_p, c_void_p]),
+    "dtlr_grad_norm_scale_workspace_bytes": (ctypes.c_long, []),
+    "dtlr_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_float, c_float, c_float, c_float, c_float,
+                                c_int, c_void_p]),
     "dtlr_nms": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dtlr_blank_emissions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "dtlr_blank_emissions_workspace_bytes": (ctypes.c_long, [c_int, c_int]),

@@ -6,14 +6,10 @@
 // Both sorts are bitonic networks over 64-bit keys (value bits | index) so the order is total and
 // deterministic: equal scores keep the LOWER index first (torch leaves ties unspecified).
 #include "dtlr_common.h"
+#include "decode_common.h"
 
 namespace dtlr {
 
-// monotone map float -> uint32 (ascending)
-__device__ __forceinline__ uint32_t f32_sortable(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // selection key of row element i: (~sortable(score) << 32) | i.  An excluded element (excl_row[i] != 0, dtlr_topk_rows_masked) gets the
 // largest score part, 0xffffffff: it ranks after every score and is never selected while at least k elements are not excluded (with
@@ -23,35 +19,6 @@ __device__ __forceinline__ unsigned long long topk_key(float v, long i, const ui
     return ((unsigned long long)hi << 32) | (unsigned long long)i;
 }
 
-// in-LDS bitonic sort of n = power of two 64-bit keys, ascending.  A thread owns compare-exchange PAIRS (pair t of stage j is
-// i = the index with bit j cleared, i | j), four at a time, and reads all eight keys before it writes any: one LDS round trip
-// per stage instead of one per element (the element-wise form serialised 8 dependent read->write trips per stage at n = 8192
-// and made the two selection kernels ~100 us each).
-__device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int n) {
-    const int half = n >> 1;
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int t0 = threadIdx.x; t0 < half; t0 += 4 * blockDim.x) {
-                unsigned long long a[4], b[4];
-                int ia[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t = t0 + u * blockDim.x;
-                    ia[u] = t < half ? (((t & ~(j - 1)) << 1) | (t & (j - 1))) : -1;
-                    if (ia[u] >= 0) { a[u] = keys[ia[u]]; b[u] = keys[ia[u] | j]; }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (ia[u] < 0) continue;
-                    const bool up = (ia[u] & k) == 0;
-                    if ((a[u] > b[u]) == up) { keys[ia[u]] = b[u]; keys[ia[u] | j] = a[u]; }
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
 
 // k largest scores of a row, descending (ties: lower index first).  key = (~sortable(score) << 32) | index is unique, so the
 // k-th smallest key K* is found EXACTLY by a radix select (six 8-bit histogram passes over the row in LDS: the four score bytes
@@ -195,10 +162,6 @@ __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict
     }
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); }
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
 
 // Step 1 of the blank decoder, chip-wide: the label of every query (class index, or -1 = blank), 16 lanes per query.
 // logits [B*nq, C] fp32 -> raw [B*nq] int32.  The 16-lane reductions are DPP row operations (xor 1, xor 2, half-mirror, mirror):
@@ -332,20 +295,7 @@ __global__ __launch_bounds__(256) void blank_emissions_kernel(const float* __res
 // Step 1, chip-wide: sum over classes of sigmoid(logit) for every query (16 lanes per query, DPP reductions).
 __global__ __launch_bounds__(256) void query_sum_kernel(const float* __restrict__ logits, float* __restrict__ sums, long nrows, int C)
 {
-    const int l16 = threadIdx.x & 15;
-    const long q = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    const bool live = q < nrows;
-    const float* lr = logits + (live ? q : 0) * C;
-    float sum = 0.f;
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        float x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int c = c0 + 16 * u + l16; x[u] = (live && c < C) ? lr[c] : -INFINITY; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sum += 1.f / (1.f + expf(-x[u]));
-    }
-    sum += dpp_f<0xB1>(sum); sum += dpp_f<0x4E>(sum); sum += dpp_f<0x141>(sum); sum += dpp_f<0x140>(sum);
-    if (live && l16 == 0) sums[q] = sum;
+    query_sum_rows(logits, sums, nrows, C);
 }
 
 // Step 2, one workgroup per line, one thread per state of the blank-extended label sequence l' (S = 2 L + 1 <= blockDim):
@@ -387,21 +337,8 @@ __global__ __launch_bounds__(1024) void ctc_interleaved_kernel(const float* __re
 #pragma unroll
     for (int u = 0; u < CTC_PF; ++u) pf[u] = (lab > 0 && u < nq) ? lrow[(long)(int)(keys[u] & 0xffffffffull) * C] : 0.f;
 
-    auto logp = [&](float x, float sum) -> float {                              // log of the blank-augmented probability
-        float p;
-        if (sum < thr) p = lab == 0 ? 1.f - sum : 1.f / (1.f + expf(-x));
-        else p = lab == 0 ? eps : one_m_eps * (1.f / (1.f + expf(-x))) / sum;
-        return logf(p);
-    };
-    auto step = [&](const float* prev, float* cur, float lp) {
-        if (live) {
-            const float la1 = prev[s], la2 = prev[s - 1], la3 = skip ? prev[s - 2] : -INFINITY;
-            float m = fmaxf(la1, fmaxf(la2, la3));
-            if (m == -INFINITY) m = 0.f;
-            cur[s] = logf(expf(la1 - m) + expf(la2 - m) + expf(la3 - m)) + m + lp;
-        }
-        __syncthreads();
-    };
+    auto logp = [&](float x, float sum) -> float { return ctc_log_prob(lab, x, sum, thr, one_m_eps, eps); };
+    auto step = [&](const float* prev, float* cur, float lp) { ctc_alpha_step(prev, cur, s, live, skip, lp); };
     for (int i0 = 0; i0 < nq; i0 += CTC_PF) {
         float nx[CTC_PF];
 #pragma unroll
@@ -425,10 +362,7 @@ __global__ __launch_bounds__(1024) void ctc_interleaved_kernel(const float* __re
         for (int u = 0; u < CTC_PF; ++u) pf[u] = nx[u];
     }
     if (threadIdx.x == 0) {                                                     // after t = T - 1 the alphas are in a1
-        const float l1 = a1[S - 1], l2 = L > 0 ? a1[S - 2] : -INFINITY;
-        float m = fmaxf(l1, l2);
-        if (m == -INFINITY) m = 0.f;
-        const float v = -(logf(expf(l1 - m) + expf(l2 - m)) + m);
+        const float v = ctc_final_nll(a1, S, L);
         nll[b] = isinf(v) ? 0.f : v;                                            // zero_infinity=True
     }
 }

@@ -377,6 +377,23 @@ class DTLREngine:
             self.w[key] = ops.head_ts_pack(self.w[name + ".w"], self.w[name + ".b"], self.dtype)
         return self.w[key]
 
+    @torch.no_grad()
+    def set_class_head(self, weight, bias) -> None:
+        """Replace the final class head (class_embed: Linear(hidden -> C), the one shared by the decoder layers) in the packed model
+        without re-packing anything else: `class.w` / `class.b` are swapped and the images derived from them (the 16-bit engines'
+        [W_hi | W_lo], the token-stationary image) are dropped, to be rebuilt by the next forward.  The charset size may change.  A
+        forward after this equals, bit for bit, the forward of a fresh engine built from the updated state dict.  The two-stage head
+        (`enc_class`) is untouched."""
+        if weight.dim() != 2 or weight.shape[1] != self.cfg.hidden_dim or tuple(bias.shape) != (weight.shape[0],):
+            raise ValueError(f"set_class_head: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not form a Linear({self.cfg.hidden_dim} -> C)")
+        self._put("class.w", weight.detach().clone(), torch.float32)         # copies: the engine never aliases the caller's buffers
+        self._put("class.b", bias.detach().clone(), torch.float32)
+        if self.split:
+            self.w["class.w"] = ops.split_pack(self.w["class.w"])
+        self.w.pop("class.w2", None)
+        self.w.pop("class.ts", None)
+        self.num_classes = int(weight.shape[0])
+
     def _class_head(self, hs):
         """class_embed on decoder states (models/dino/dino.py:349-352), fp32 logits.  bf16 engine: the states are exact bf16
         values, so [hs | hs] . [W_hi | W_lo]^T on the bf16 matrix cores is the fp32-weight product to ~2^-16 relative -- the
@@ -997,7 +1014,7 @@ class DTLREngine:
             off += T_l
         return src
 
-    def heads(self, hs, refs, ts, want_aux=False):
+    def heads(self, hs, refs, ts, want_aux=False, return_hidden=False):
         """DINO.forward's tail (models/dino/dino.py:339-415): class / box heads of the last (and, on request, every) decoder layer
         and the two-stage intermediate outputs."""
         cfg = self.cfg
@@ -1021,6 +1038,8 @@ class DTLREngine:
         out["interm_outputs"] = {"pred_logits": interm_class, "pred_boxes": ts["ref_unsig"].sigmoid()}
         out["interm_outputs_for_matching_pre"] = {"pred_logits": interm_class, "pred_boxes": ts["init_box"]}
         out["dn_meta"] = None
+        if return_hidden:
+            out["hs"] = hs[n]
         return out
 
     # ------------------------------------------------------------------------------ forward
@@ -1031,14 +1050,16 @@ class DTLREngine:
     @torch.no_grad()
     def forward(self, x: torch.Tensor, mask: torch.Tensor, forced_topk: Optional[torch.Tensor] = None,
                 want_aux: bool = False, return_debug: bool = False, has_padding: bool = True, per_line: bool = False,
-                sizes: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
+                sizes: Optional[Sequence] = None, return_hidden: bool = False) -> Dict[str, torch.Tensor]:
         """x [B,3,H,W] fp32 (zero-padded), mask [B,H,W] bool (True = padding)  ->  DINO.forward's
         dict (models/dino/dino.py:270-415): pred_logits [B,nq,C] raw, pred_boxes [B,nq,4] cxcywh.
         per_line: every line of the padded batch gets the result it would get alone (up to rounding and the order of near-tied
         queries): its extent -- the unpadded top-left rectangle of `mask` -- is carried through the backbone, the GroupNorm statistics,
         the level masks, the two-stage selection and the decoder's query embedding (per-line batching).  The batch is always
         treated as padded and runs on one stream.  `sizes`: the host's (h, w) of every line, when known -- a line with fewer encoder
-        tokens than queries cannot run alone and raises ValueError."""
+        tokens than queries cannot run alone and raises ValueError.
+        return_hidden: also return out["hs"], the last decoder layer's normalised output [B,nq,hidden] in the engine's dtype -- what the
+        class head multiplies (dtlr_amd/adapt.py trains the head on it); no extra launch."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1094,7 +1115,7 @@ class DTLREngine:
         if vall is not None:
             cur.wait_stream(side)
         hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line)
-        out = self.heads(hs, refs, ts, want_aux)
+        out = self.heads(hs, refs, ts, want_aux, return_hidden)
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

@@ -71,6 +71,21 @@ def decode_blank_records(outputs, eps: Optional[float] = None) -> Tuple[torch.Te
     return ops.decode_blank(outputs["pred_logits"], outputs["pred_boxes"], 0.03 / C if eps is None else eps)
 
 
+def _ctc_targets(logits, target_labels, what: str):
+    """label lists -> (targets [B, max(Lmax, 1)] int32 = label + 1, lengths [B] int32, Lmax) on the logits' device"""
+    B = logits.shape[0]
+    if len(target_labels) != B:
+        raise ValueError(f"{what}: {len(target_labels)} label sequences for a batch of {B}")
+    lens = [len(t) for t in target_labels]
+    Lmax = max(lens) if lens else 0
+    tt = torch.zeros((B, max(Lmax, 1)), dtype=torch.int32)
+    for i, t in enumerate(target_labels):
+        if len(t):
+            tt[i, : len(t)] = torch.as_tensor([int(v) for v in t], dtype=torch.int32) + 1
+    tl = torch.tensor(lens, dtype=torch.int32)
+    return tt.to(logits.device), tl.to(logits.device), Lmax
+
+
 def loss_ctc(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.003, filler: float = 1e-5) -> torch.Tensor:
     """Forward value of `SetCriterion.loss_CTC` (models/dino/dino.py:457-551) as engine.evaluate_CTC logs it
     (engine.py:381): HIP kernels (per-query sigmoid sums chip-wide, then one workgroup per line for the reading-order sort
@@ -79,18 +94,27 @@ def loss_ctc(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.003
     (charset positions, WITHOUT the +1 blank shift).  Returns a 0-d fp32 CUDA tensor."""
     from . import ops
     logits = outputs["pred_logits"]
-    B = logits.shape[0]
-    if len(target_labels) != B:
-        raise ValueError(f"loss_ctc: {len(target_labels)} label sequences for a batch of {B}")
-    lens = [len(t) for t in target_labels]
-    Lmax = max(lens) if lens else 0
-    tt = torch.zeros((B, max(Lmax, 1)), dtype=torch.int32)
+    tt, tl, Lmax = _ctc_targets(logits, target_labels, "loss_ctc")
+    nll = ops.ctc_loss_interleaved(logits, outputs["pred_boxes"], tt, tl, Lmax, eps, filler)
+    return (nll / tl.clamp(min=1).float()).mean()
+
+
+def loss_ctc_backward(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.003, filler: float = 1e-5):
+    """`loss_ctc` and its gradient with respect to outputs["pred_logits"], as engine.train_one_epoch_CTC's
+    `criterion.loss_CTC(outputs, targets, None, None)` + backward produce them (engine.py:200-212): HIP kernels
+    (dtlr_ctc_loss_interleaved_backward: the forward's alpha recursion, a beta recursion over the same 2 nq frames, then the
+    blank construction's chain rule chip-wide).  A line whose transcription does not fit 2 nq frames contributes loss 0 and gradient 0
+    (zero_infinity).  A label outside 0..C-1 raises ValueError (the labels are host lists: the check costs no synchronisation).
+    Returns (loss: 0-d fp32 CUDA tensor with loss_ctc's bits, dlogits [B,nq,C] fp32)."""
+    from . import ops
+    logits = outputs["pred_logits"]
+    C = logits.shape[-1]
     for i, t in enumerate(target_labels):
-        if len(t):
-            tt[i, : len(t)] = torch.as_tensor([int(v) for v in t], dtype=torch.int32) + 1
-    tl = torch.tensor(lens, dtype=torch.int32)
-    nll = ops.ctc_loss_interleaved(logits, outputs["pred_boxes"], tt.to(logits.device), tl.to(logits.device), Lmax, eps, filler)
-    return (nll / tl.to(logits.device).clamp(min=1).float()).mean()
+        if any(not 0 <= int(v) < C for v in t):
+            raise ValueError(f"loss_ctc_backward: line {i} has a label outside 0..{C - 1}")
+    tt, tl, Lmax = _ctc_targets(logits, target_labels, "loss_ctc_backward")
+    nll, dlogits = ops.ctc_loss_interleaved_backward(logits, outputs["pred_boxes"], tt, tl, Lmax, eps, filler)
+    return (nll / tl.clamp(min=1).float()).mean(), dlogits
 
 
 def evaluate_ctc_step(outputs, target_labels: Sequence[Sequence[int]]) -> Dict[str, float]:

@@ -1393,6 +1393,78 @@ def ctc_loss_interleaved(logits, boxes, targets, target_lengths, max_target_leng
     return nll
 
 
+def ctc_loss_interleaved_backward(logits, boxes, targets, target_lengths, max_target_length: int, eps: float = 0.003, filler: float = 1e-5):
+    """dtlr_ctc_loss_interleaved_backward: ctc_loss_interleaved's arguments -> (nll [B] fp32, bit-identical to ctc_loss_interleaved;
+    dlogits [B,nq,C] fp32 = the gradient of mean_b(nll_b / max(L_b, 1)) with respect to the logits; 0 for a line without a feasible
+    alignment)."""
+    require_cuda(logits, "pred_logits")
+    B, nq, C = logits.shape
+    logits = logits.float().contiguous()
+    boxes = boxes.float().contiguous()
+    assert targets.dtype == torch.int32 and target_lengths.dtype == torch.int32 and targets.is_cuda and target_lengths.is_cuda
+    targets = targets.contiguous()
+    Lmax = targets.shape[1]
+    L = _L(logits)
+    nll = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty((B, nq, C), dtype=torch.float32, device=logits.device)
+    ws = torch.empty((L.dtlr_ctc_loss_interleaved_backward_workspace_bytes(B, nq, Lmax) // 4,), dtype=torch.float32, device=logits.device)
+    code = L.dtlr_ctc_loss_interleaved_backward(logits.data_ptr(), boxes.data_ptr(), targets.data_ptr() if Lmax > 0 else None,
+                                                target_lengths.data_ptr(), nll.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), B, nq, C, Lmax,
+                                                int(max_target_length), float(eps), float(filler), _lib.current_stream())
+    _lib.check(code, "dtlr_ctc_loss_interleaved_backward")
+    return nll, dlogits
+
+
+def head_grad(g, x, out=None):
+    """dtlr_head_grad: g [M,C] fp32 (dlogits), x [M,D] fp32 (decoder states), D % 64 == 0 -> the flat gradient [C*D + C] fp32 of a
+    Linear(D -> C): dW = g^T x row-major, then db = g.sum(0).  Exact fp32 products; reproducible run to run.  out: a buffer to fill."""
+    require_cuda(g, "dlogits")
+    g = g.float().contiguous()
+    x = x.float().contiguous()
+    M, C = g.shape
+    D = x.shape[1]
+    assert x.shape[0] == M
+    L = _L(g)
+    if out is None:
+        out = torch.empty((C * D + C,), dtype=torch.float32, device=g.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == C * D + C
+    nbytes = L.dtlr_head_grad_workspace_bytes(M, C, D)
+    if M and nbytes <= 0:
+        raise _lib.DTLRError(f"dtlr_head_grad: unsupported shape M={M} C={C} D={D} (D must be a multiple of 64)")
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=g.device)
+    code = L.dtlr_head_grad(g.data_ptr(), x.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * C * D, ws.data_ptr(), M, C, D, _lib.current_stream())
+    _lib.check(code, "dtlr_head_grad")
+    return out
+
+
+def grad_norm_scale(grad, max_norm: float, out=None):
+    """dtlr_grad_norm_scale: flat fp32 grad -> device tensor [2] = (clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)), norm);
+    max_norm <= 0: the coefficient is 1.  No host synchronisation."""
+    require_cuda(grad, "grad")
+    assert grad.dtype == torch.float32 and grad.is_contiguous()
+    L = _L(grad)
+    if out is None:
+        out = torch.empty((2,), dtype=torch.float32, device=grad.device)
+    ws = torch.empty((L.dtlr_grad_norm_scale_workspace_bytes() // 8,), dtype=torch.float64, device=grad.device)
+    code = L.dtlr_grad_norm_scale(grad.data_ptr(), grad.numel(), float(max_norm), out.data_ptr(), ws.data_ptr(), _lib.current_stream())
+    _lib.check(code, "dtlr_grad_norm_scale")
+    return out
+
+
+def adamw_step(param, exp_avg, exp_avg_sq, grad, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+               grad_scale=None):
+    """dtlr_adamw_step: torch.optim.AdamW's update, in place, over flat fp32 buffers; `step` >= 1 is this step's number; grad_scale: a
+    device tensor whose first element multiplies the gradient (ops.grad_norm_scale's output)."""
+    require_cuda(param, "param")
+    for t in (param, exp_avg, exp_avg_sq, grad):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel() and t.device == param.device
+    code = _L(param).dtlr_adamw_step(param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(),
+                                     grad_scale.data_ptr() if grad_scale is not None else None, param.numel(), float(lr), float(betas[0]),
+                                     float(betas[1]), float(eps), float(weight_decay), int(step), _lib.current_stream())
+    _lib.check(code, "dtlr_adamw_step")
+    return param
+
+
 def nms_batched(boxes, scores, iou_threshold: float):
     """Greedy NMS per image on the device (dtlr_nms): boxes [B,n,4] xyxy fp32, scores [B,n] fp32 -> (keep [B,n] int64: kept
     original indices in descending score order, -1 padded; counts [B] int32).  n <= 1024."""
@@ -1444,7 +1516,7 @@ def _device_scoped(fn):
 for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
               "maxpool_nhwc", "groupnorm_tokens", "msda", "msda_fused", "msda_encoder", "mha", "decoder_query_prep", "box_mlp_refine",
               "box_head_refine", "box_refine", "topk_rows", "decode_blank", "preprocess_lines", "ctc_loss_interleaved", "nms_batched",
-              "topk_flat", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
+              "topk_flat", "ctc_loss_interleaved_backward", "head_grad", "grad_norm_scale", "adamw_step", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
     globals()[_name] = _device_scoped(globals()[_name])
 del _name
 

@@ -623,6 +623,44 @@ int dtlr_ctc_loss_interleaved(const float *logits, const float *boxes, const int
                               float eps, float filler, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Class-head adaptation (dtlr_amd/adapt.py): the CTC loss's gradient, the head's weight gradient, clipping and AdamW.
+ * The reference trains the heads of a new charset with engine.train_one_epoch_CTC (engine.py:160-260): loss_CTC on the final
+ * pred_logits only, the optimizer holding only the class heads (finetuning.py:518-539).  pred_logits = class_embed(hs[-1]) is one
+ * shared Linear, so its gradient needs nothing from the trunk.
+ *
+ * dtlr_ctc_loss_interleaved_backward: nll [B] exactly as dtlr_ctc_loss_interleaved writes it, and dlogits [B,nq,C] fp32 = the
+ *   gradient of  mean_b( nll[b] / max(target_lengths[b], 1) )  (nn.CTCLoss(reduction="mean", zero_infinity=True)) with respect to
+ *   the logits.  A line without a feasible alignment contributes 0 and an all-zero gradient.  Same arguments and shape limits as the
+ *   forward (2 max_target_length + 1 <= 1024, LDS cap: DTLR_ESHAPE), plus C <= 15360.  workspace:
+ *   dtlr_ctc_loss_interleaved_backward_workspace_bytes(B, nq, Lmax) bytes (the alphas of the even frames: B nq (2 Lmax + 1) floats).
+ *   Every reduction runs in a fixed order: repeated calls give identical bits.  On inputs the forward leaves undefined this call is
+ *   defined: a target length outside 0..max_target_length is clamped, and a line with a NaN NLL or with a target outside 1..C
+ *   contributes 0 and an all-zero gradient (no out-of-range read). */
+int dtlr_ctc_loss_interleaved_backward(const float *logits, const float *boxes, const int *targets, const int *target_lengths,
+                                       float *nll, float *dlogits, float *workspace, int B, int nq, int C, int Lmax,
+                                       int max_target_length, float eps, float filler, void *stream);
+long dtlr_ctc_loss_interleaved_backward_workspace_bytes(int B, int nq, int Lmax);
+
+/* dW [C,D] = G^T X and db [C] = column sums of G, for G [M,C] (dlogits) and X [M,D] (decoder states), all fp32 row-major; D % 64 == 0
+ *   (else DTLR_ESHAPE); X and workspace 16-byte aligned.  Exact fp32 products (plain fp32 FMAs on the vector units); a stage of 32 rows
+ *   is summed in fp32, a split's stages in fp64 (its partial tile is stored in fp32), the splits and the bias in fp64.  The split over M is reduced
+ *   through `workspace` (dtlr_head_grad_workspace_bytes(M, C, D) bytes) in a fixed order: repeated calls give identical bits. */
+int dtlr_head_grad(const float *G, const float *X, float *dW, float *db, float *workspace, long M, int C, int D, void *stream);
+long dtlr_head_grad_workspace_bytes(long M, int C, int D);
+
+/* scale_out[0] = min(1, max_norm / (||grad||_2 + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s coefficient; 1 when max_norm <= 0 --
+ *   and scale_out[1] = ||grad||_2, over n fp32 values, written to device memory (nothing synchronises with the host).
+ *   workspace: dtlr_grad_norm_scale_workspace_bytes() bytes, 8-byte aligned. */
+int dtlr_grad_norm_scale(const float *grad, long n, float max_norm, float *scale_out, void *workspace, void *stream);
+long dtlr_grad_norm_scale_workspace_bytes(void);
+
+/* One torch.optim.AdamW step over n fp32 values: g = grad * grad_scale[0] (device scalar; NULL = 1), param *= 1 - lr weight_decay,
+ *   exp_avg / exp_avg_sq updated with beta1 / beta2, param -= lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq / (1 - beta2^step)) + eps).
+ *   step >= 1 is the number of THIS step. */
+int dtlr_adamw_step(float *param, float *exp_avg, float *exp_avg_sq, const float *grad, const float *grad_scale, long n,
+                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * CTC-style emissions for the n-gram re-scoring path.
  * Replaces: get_new_pred_logits (ngram/prediction_helpers.py:5-46): queries sorted by box cx, p = scale * sigmoid(logits),
  *           blank channel first with the rule of SetCriterion.loss_CTC (models/dino/dino.py:466-502; eps = 0.003 there).
