@@ -14,12 +14,9 @@
 //        B operand of lane (g,n) = its own 8 probabilities (two key tiles x 4 regs): zero data movement;
 //        the MFMA k-index <-> key permutation this implies is applied identically to the V^T fragment.
 // V^T ([B, H, 32, Lpad], Lpad = 32-multiple, zero padded) is produced by the V projection.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __device__ __forceinline__ uint32_t pack2(float a, float b) { return pack_bf16x2(a, b); }
 
@@ -35,40 +32,40 @@ __global__ __launch_bounds__(256) void mha_fwd_bf16_kernel(const uint16_t* __res
     const int q0 = blockIdx.x * 128 + wave * 32;
     if (q0 >= L) return;                                   // whole wave: no block-level sync is used
     const uint16_t* qkb = qk + (long)b * L * (2 * C);
-    bf16x8 qf[2];
+    h16x8_t qf[2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const int q = min(q0 + qt * 16 + n, L - 1);
-        qf[qt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
+        qf[qt] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
     }
     const uint16_t* vtb = vt + ((long)(b * H + h) * 32) * Lpad;
-    f32x4 o[2][2];
+    f32x4_t o[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
 
     for (int kb = 0; kb < Lpad; kb += 32) {
-        bf16x8 kf[2];
+        h16x8_t kf[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             const int key = min(kb + kt * 16 + n, L - 1);
-            kf[kt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(qkb + (long)key * (2 * C) + C + h * 32 + 8 * g));
+            kf[kt] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(qkb + (long)key * (2 * C) + C + h * 32 + 8 * g));
         }
-        bf16x8 vf[2];
+        h16x8_t vf[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
             const uint16_t* vr = vtb + (long)(dt * 16 + n) * Lpad + kb + 4 * g;
             const uint2 lo = *reinterpret_cast<const uint2*>(vr), hi = *reinterpret_cast<const uint2*>(vr + 16);
-            vf[dt] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+            vf[dt] = __builtin_bit_cast(h16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
         }
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
-            f32x4 s[2];
+            f32x4_t s[2];
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
-                s[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                s[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             float mx = -INFINITY;
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(256) void mha_fwd_bf16_kernel(const uint16_t* __res
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(s[kt][r] - m_new); ps += s[kt][r]; }
             lsum[qt] = lsum[qt] * alpha + ps;
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, make_uint4(pack2(s[0][0], s[0][1]), pack2(s[0][2], s[0][3]),
+            const h16x8_t pf = __builtin_bit_cast(h16x8_t, make_uint4(pack2(s[0][0], s[0][1]), pack2(s[0][2], s[0][3]),
                                                                     pack2(s[1][0], s[1][1]), pack2(s[1][2], s[1][3])));
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(256) void mha_fwd_bf16_kernel(const uint16_t* __res
         if (q < L) {
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const f32x4 v = o[qt][dt] * inv;
+                const f32x4_t v = o[qt][dt] * inv;
                 *reinterpret_cast<uint2*>(out + ((long)b * L + q) * C + h * 32 + dt * 16 + 4 * g) =
                     make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
             }
@@ -181,17 +178,17 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds_kernel(const uint16_t* 
     const int nqb = (L + 31) / 32;                           // query blocks of 32
     for (int qb = wave; qb < nqb; qb += 16) {
         const int q0 = qb * 32;
-        bf16x8 qf[2];
+        h16x8_t qf[2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const int q = min(q0 + qt * 16 + n, L - 1);
-            qf[qt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
+            qf[qt] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
         }
-        f32x4 o[2][2];
+        f32x4_t o[2][2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
         // one 32-key block; MASKED only for the last one (keys >= L are padding).  The softmax scale is folded into one FMA per
         // score (exp2(s*c - m)) and the running maximum is kept in scaled units: 149 -> ~110 VALU instructions per block, and
@@ -199,15 +196,15 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds_kernel(const uint16_t* 
 #define MHA_KEY_BLOCK(J, MASKED)                                                                   \
         {                                                                                          \
             const int kb = (J) * 32;                                                               \
-            bf16x8 kf[2], vf[2];                                                                   \
+            h16x8_t kf[2], vf[2];                                                                   \
             _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                        \
-                kf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
-                vf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(vimg + (2 * (J) + t) * 1024 + lane * 16)); \
+                kf[t] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
+                vf[t] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(vimg + (2 * (J) + t) * 1024 + lane * 16)); \
             }                                                                                      \
             _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                     \
-                f32x4 sc[2];                                                                       \
+                f32x4_t sc[2];                                                                       \
                 _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                                   \
-                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
+                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
                 if (MASKED) {                                                                      \
                     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                               \
                         _Pragma("unroll") for (int r = 0; r < 4; ++r)                              \
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds_kernel(const uint16_t* 
                         ps += sc[kt][r];                                                           \
                     }                                                                              \
                 lsum[qt] = lsum[qt] * alpha + ps;                                                  \
-                const bf16x8 pf = __builtin_bit_cast(bf16x8, make_uint4(pack2(sc[0][0], sc[0][1]), pack2(sc[0][2], sc[0][3]), \
+                const h16x8_t pf = __builtin_bit_cast(h16x8_t, make_uint4(pack2(sc[0][0], sc[0][1]), pack2(sc[0][2], sc[0][3]), \
                                                                         pack2(sc[1][0], sc[1][1]), pack2(sc[1][2], sc[1][3]))); \
                 _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) {                                 \
                     o[qt][dt] *= alpha;                                                            \
@@ -246,7 +243,7 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds_kernel(const uint16_t* 
             if (q < L) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const f32x4 v = o[qt][dt] * inv;
+                    const f32x4_t v = o[qt][dt] * inv;
                     *reinterpret_cast<uint2*>(out + ((long)b * L + q) * C + h * 32 + dt * 16 + 4 * g) =
                         make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
                 }
@@ -300,37 +297,37 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds2_kernel(const uint16_t*
     // a third "d tile" of V^T whose row 0 is all ones: (V^T | 1) P yields the row sums of the ROUNDED probabilities -- the very values the
     // numerator multiplies -- from the idle matrix pipe instead of 16 v_add_f32 per key block
     const uint32_t one2 = n == 0 ? ((uint32_t)H16_ONE | ((uint32_t)H16_ONE << 16)) : 0u;
-    const bf16x8 ones_f = __builtin_bit_cast(bf16x8, make_uint4(one2, one2, one2, one2));
+    const h16x8_t ones_f = __builtin_bit_cast(h16x8_t, make_uint4(one2, one2, one2, one2));
     // query blocks: wave w of workgroup z takes blocks w + 16 z, + 16 gridDim.z, ...  (gridDim.z = 1: the whole head in one workgroup; 2 for
     // small batches (round 5): at ONE line the 8 (head) workgroups each walked two query blocks per wave after staging K / V^T -- 58 us on 8
     // CUs; two workgroups per head stage the images twice and finish in one block per wave)
     for (int qb = wave + 16 * (int)blockIdx.z; qb < nqb; qb += 16 * (int)gridDim.z) {
         const int q0 = qb * 32;
-        bf16x8 qf[2];
+        h16x8_t qf[2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const int q = min(q0 + qt * 16 + n, L - 1);
-            qf[qt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
+            qf[qt] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(qkb + (long)q * (2 * C) + h * 32 + 8 * g));
         }
-        f32x4 o[2][2];
+        f32x4_t o[2][2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         float m[2];
-        f32x4 osum[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};    // row 0 = the row sums of P (see ones_f)
+        f32x4_t osum[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};    // row 0 = the row sums of P (see ones_f)
         // ---- pass 1: row maxima (raw scores; the scale is positive, so it commutes with the maximum) ----
         float mraw[2] = {-INFINITY, -INFINITY};
 #define MHA_MAX_BLOCK(J, MASKED)                                                                   \
         {                                                                                      \
             const int kb = (J) * 32;                                                           \
-            bf16x8 kf[2];                                                                      \
+            h16x8_t kf[2];                                                                      \
             _Pragma("unroll") for (int t = 0; t < 2; ++t)                                      \
-                kf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
+                kf[t] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
             _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                 \
-                f32x4 sc[2];                                                                   \
+                f32x4_t sc[2];                                                                   \
                 _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                               \
-                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
+                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
                 if (MASKED) {                                                                  \
                     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                           \
                         _Pragma("unroll") for (int r = 0; r < 4; ++r)                          \
@@ -349,15 +346,15 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds2_kernel(const uint16_t*
 #define MHA_PV_BLOCK(J, MASKED)                                                                    \
         {                                                                                      \
             const int kb = (J) * 32;                                                           \
-            bf16x8 kf[2], vf[2];                                                               \
+            h16x8_t kf[2], vf[2];                                                               \
             _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                    \
-                kf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
-                vf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(vimg + (2 * (J) + t) * 1024 + lane * 16)); \
+                kf[t] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(kimg + (2 * (J) + t) * 1024 + lane * 16)); \
+                vf[t] = __builtin_bit_cast(h16x8_t, *reinterpret_cast<const uint4*>(vimg + (2 * (J) + t) * 1024 + lane * 16)); \
             }                                                                                  \
             _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                 \
-                f32x4 sc[2];                                                                   \
+                f32x4_t sc[2];                                                                   \
                 _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                               \
-                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
+                    sc[kt] = DTLR_MFMA_16x16x32_H16(kf[kt], qf[qt], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
                 if (MASKED) {                                                                  \
                     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                           \
                         _Pragma("unroll") for (int r = 0; r < 4; ++r)                          \
@@ -366,7 +363,7 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds2_kernel(const uint16_t*
                 _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                               \
                     _Pragma("unroll") for (int r = 0; r < 4; ++r)                              \
                         sc[kt][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][r], scale_log2e, -m[qt])); \
-                const bf16x8 pf = __builtin_bit_cast(bf16x8, make_uint4(pack2(sc[0][0], sc[0][1]), pack2(sc[0][2], sc[0][3]), \
+                const h16x8_t pf = __builtin_bit_cast(h16x8_t, make_uint4(pack2(sc[0][0], sc[0][1]), pack2(sc[0][2], sc[0][3]), \
                                                                         pack2(sc[1][0], sc[1][1]), pack2(sc[1][2], sc[1][3]))); \
                 _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                               \
                     o[qt][dt] = DTLR_MFMA_16x16x32_H16(vf[dt], pf, o[qt][dt], 0, 0, 0);        \
@@ -384,7 +381,7 @@ __global__ __launch_bounds__(1024) void mha_fwd_bf16_lds2_kernel(const uint16_t*
             if (q < L) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const f32x4 v = o[qt][dt] * inv;
+                    const f32x4_t v = o[qt][dt] * inv;
                     *reinterpret_cast<uint2*>(out + ((long)b * L + q) * C + h * 32 + dt * 16 + 4 * g) =
                         make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
                 }
@@ -441,11 +438,11 @@ __global__ __launch_bounds__(256) void mha_fwd_f32_kernel(const float* __restric
         qf[qt][0] = a.x; qf[qt][1] = a.y; qf[qt][2] = a.z; qf[qt][3] = a.w; qf[qt][4] = c.x; qf[qt][5] = c.y; qf[qt][6] = c.z; qf[qt][7] = c.w;
     }
     const float* vtb = vt + ((long)(b * H + h) * 32) * Lpad;
-    f32x4 o[2][2];
+    f32x4_t o[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
 
     for (int kb = 0; kb < Lpad; kb += 32) {
@@ -467,10 +464,10 @@ __global__ __launch_bounds__(256) void mha_fwd_f32_kernel(const float* __restric
             }
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
-            f32x4 s[2];
+            f32x4_t s[2];
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
-                s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                s[kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt][j], qf[qt][j], s[kt], 0, 0, 0);
             }
@@ -516,7 +513,7 @@ __global__ __launch_bounds__(256) void mha_fwd_f32_kernel(const float* __restric
         if (q < L) {
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const f32x4 v = o[qt][dt] * inv;
+                const f32x4_t v = o[qt][dt] * inv;
                 *reinterpret_cast<float4*>(out + ((long)b * L + q) * C + h * 32 + dt * 16 + 4 * g) = make_float4(v[0], v[1], v[2], v[3]);
             }
         }
@@ -534,22 +531,12 @@ __global__ __launch_bounds__(256) void mha_fwd_f32_kernel(const float* __restric
 //                                                                  layout of S^T is still the B-operand layout of the second product)
 // Row sums are taken of the fp32 probabilities (hi + lo reproduces them to 2^-22).  Waves take query blocks w, w + 16, ...; a group of
 // 16 query blocks re-stages the chunks (2 groups at L = 900: 464 KB of L2 reads per (batch, head)).
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2v;
 __device__ __forceinline__ void split8(const float (&x)[8], uint4& hi, uint4& lo) {
     uint32_t h[4], l[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f16x2v hh = __builtin_convertvector(f32x2_hw_t{x[2 * i], x[2 * i + 1]}, f16x2v);
-        const f16x2v ll = __builtin_convertvector(f32x2_hw_t{x[2 * i] - (float)hh[0], x[2 * i + 1] - (float)hh[1]}, f16x2v);
-        h[i] = __builtin_bit_cast(uint32_t, hh);
-        l[i] = __builtin_bit_cast(uint32_t, ll);
-    }
+    for (int i = 0; i < 4; ++i) split2_f16(x[2 * i], x[2 * i + 1], h[i], l[i]);
     hi = make_uint4(h[0], h[1], h[2], h[3]);
     lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ f32x4 mfma_f16(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
 __global__ __launch_bounds__(1024) void mha_fwd_f32s_kernel(const float* __restrict__ qk, const float* __restrict__ v,
@@ -581,11 +568,11 @@ __global__ __launch_bounds__(1024) void mha_fwd_f32s_kernel(const float* __restr
             const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
             split8(x, qh[qt], ql[qt]);
         }
-        f32x4 o[2][2];
+        f32x4_t o[2][2];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int dt = 0; dt < 2; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.f, 0.f};
 
         for (int c0 = 0; c0 < nkb; c0 += kc) {
@@ -627,10 +614,10 @@ __global__ __launch_bounds__(1024) void mha_fwd_f32s_kernel(const float* __restr
                     vl[t] = *reinterpret_cast<const uint4*>(v_lo + (2 * (JL) + t) * 1024 + lane * 16); \
                 }                                                                                  \
                 _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                 \
-                    f32x4 sc[2];                                                                   \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mfma_f16(kh[kt], ql[qt], f32x4{0.f, 0.f, 0.f, 0.f}); \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mfma_f16(kl[kt], qh[qt], sc[kt]); \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mfma_f16(kh[kt], qh[qt], sc[kt]); \
+                    f32x4_t sc[2];                                                                   \
+                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mma16_f16(kh[kt], ql[qt], f32x4_t{0.f, 0.f, 0.f, 0.f}); \
+                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mma16_f16(kl[kt], qh[qt], sc[kt]); \
+                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) sc[kt] = mma16_f16(kh[kt], qh[qt], sc[kt]); \
                     if (MASKED) {                                                                  \
                         _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                           \
                             _Pragma("unroll") for (int r = 0; r < 4; ++r)                          \
@@ -652,9 +639,9 @@ __global__ __launch_bounds__(1024) void mha_fwd_f32s_kernel(const float* __restr
                     uint4 ph, pl;                                                                  \
                     split8(pv, ph, pl);                                                            \
                     _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] *= alpha;           \
-                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mfma_f16(vh[dt], pl, o[qt][dt]); \
-                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mfma_f16(vl[dt], ph, o[qt][dt]); \
-                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mfma_f16(vh[dt], ph, o[qt][dt]); \
+                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mma16_f16(vh[dt], pl, o[qt][dt]); \
+                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mma16_f16(vl[dt], ph, o[qt][dt]); \
+                    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) o[qt][dt] = mma16_f16(vh[dt], ph, o[qt][dt]); \
                 }                                                                                  \
             }
             const bool last_chunk = c0 + cn == nkb;
@@ -671,7 +658,7 @@ __global__ __launch_bounds__(1024) void mha_fwd_f32s_kernel(const float* __restr
                 if (q < L) {
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt) {
-                        const f32x4 r = o[qt][dt] * inv;
+                        const f32x4_t r = o[qt][dt] * inv;
                         *reinterpret_cast<float4*>(out + ((long)b * L + q) * C + h * 32 + dt * 16 + 4 * g) = make_float4(r[0], r[1], r[2], r[3]);
                     }
                 }

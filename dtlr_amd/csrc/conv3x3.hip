@@ -13,29 +13,15 @@
 //   * 4 waves, each a 64-pixel x BN/2-channel sub-tile (16x16x32 MFMAs, fp32 accumulators for the whole K sweep), one barrier per slab;
 //   * bias + ReLU epilogue with the paired 16-byte stores of gemm.hip.
 // L2 -> LDS bytes per 128-pixel x 128-channel tile at Cin = 256: 92 KB patch + 36 x 16 KB weights = 668 KB (0.57x).
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t cp_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float cp_f32x4_t;
 
 constexpr int CP_TH = 8, CP_TW = 16, CP_PW = CP_TW + 2, CP_PH = CP_TH + 2, CP_NPIX = CP_PW * CP_PH;      // 18 x 10 = 180 patch pixels
 constexpr int CP_PLANE = 184 * 128;                         // 23 DMA blocks of 8 pixels x 128 B per channel-block plane
 constexpr int CP_NS = 4;                                    // weight ring stages
 __device__ __attribute__((aligned(16))) unsigned int g_cp_zero_line[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void cp_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void cp_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // CB = Cin / 64, BN = output channels per workgroup (64 or 128).  Wt: [Cout][3][3][Cin] bf16.  grid = (ceil(W / 16), ceil(H / 8), B * Cout / BN)
 // NW = 4 or 8 waves: wave w owns the 64-pixel half w & 1 and channel slice w >> 1 of BN / (NW / 2) channels.  With one workgroup per CU
@@ -69,7 +55,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_patch_kernel(const uint16_
         const bool ok = y >= 0 && y < H && x >= 0 && x < W;
         const int c = slot ^ ((8 * j + pr) & 7);
         const void* src = ok ? (const void*)(Xb + ((long)y * W + x) * Cin + cb * 64 + c * 8) : (const void*)g_cp_zero_line;
-        cp_glds16(src, lds_base + (unsigned)(cb * CP_PLANE + j * 1024));
+        glds16(src, lds_base + (unsigned)(cb * CP_PLANE + j * 1024));
     }
     // ---- weight slabs: slab s = (tap = s / CB, cb = s % CB): rows n0 .. n0 + BN - 1, 128 B each; this wave issues blocks u = wave + 4 i
     auto issue_w = [&](int s) {
@@ -79,20 +65,20 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_patch_kernel(const uint16_
         for (int i = 0; i < P; ++i) {
             const int u = wave + NW * i, r = 8 * u + pr;
             const int c = slot ^ pr;                                      // (r & 7) == pr
-            cp_glds16(Wt + (long)(n0 + r) * K + tap * Cin + cb * 64 + c * 8, dst + (unsigned)(u * 1024));
+            glds16(Wt + (long)(n0 + r) * K + tap * Cin + cb * 64 + c * 8, dst + (unsigned)(u * 1024));
         }
     };
 #pragma unroll
     for (int s = 0; s < CP_NS - 1; ++s)
         if (s < NSL) issue_w(s);
-    cp_wait<0>();
+    wait_vm<0>();
 
     const int wm = wave & 1, wn = wave >> 1;
-    cp_f32x4_t acc[CI][4];
+    f32x4_t acc[CI][4];
 #pragma unroll
     for (int ci = 0; ci < CI; ++ci)
 #pragma unroll
-        for (int ti = 0; ti < 4; ++ti) acc[ci][ti] = cp_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int ti = 0; ti < 4; ++ti) acc[ci][ti] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const unsigned wrow = (unsigned)((wn * CW + n) * 128);                   // this lane's weight row inside a stage (+ ci * 2048)
 
     for (int s = 0; s < NSL; ++s) {
@@ -118,12 +104,12 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_patch_kernel(const uint16_
             for (int ci = 0; ci < CI; ++ci)
 #pragma unroll
                 for (int ti = 0; ti < 4; ++ti)
-                    acc[ci][ti] = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(cp_bf16x8_t, wf[ci]), __builtin_bit_cast(cp_bf16x8_t, xf[ti]),
+                    acc[ci][ti] = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(h16x8_t, wf[ci]), __builtin_bit_cast(h16x8_t, xf[ti]),
                                                                           acc[ci][ti], 0, 0, 0);
         }
         // my pieces of slab s + 1 must have landed before the next barrier; the (NS - 2) slabs issued after it may stay in flight
-        if (s + CP_NS - 1 < NSL) cp_wait<(CP_NS - 2) * P>();
-        else cp_wait<0>();
+        if (s + CP_NS - 1 < NSL) wait_vm<(CP_NS - 2) * P>();
+        else wait_vm<0>();
     }
 
     // ---- epilogue: + bias, ReLU, bf16, paired 16-byte stores (lane (n, g): channels 16 ci + 4 g + r of token n of tile row ti) -------
@@ -168,17 +154,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_patch_kernel(const uint16_
 //     of a row permuted on the source side (chunk c in slot c ^ (row & 15)): conflict-free A-fragment reads at a 256-byte row pitch;
 //   * per (k-quarter, channel tile, pixel row): acc += W_hi X_lo + W_lo X_hi + W_hi X_hi (gemm_k256s.hip's order), fp32 accumulators
 //     for the whole K sweep, bias + ReLU, 16-byte fp32 stores.
-typedef __attribute__((ext_vector_type(8))) _Float16 cps_f16x8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 cps_f16x2_t;
-__device__ __forceinline__ cp_f32x4_t cps_mma(const uint4& a, const uint4& b, cp_f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cps_f16x8_t, a), __builtin_bit_cast(cps_f16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void cps_split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-    const cps_f16x2_t a = __builtin_convertvector(f32x2_hw_t{x0, x1}, cps_f16x2_t);
-    const cps_f16x2_t b = __builtin_convertvector(f32x2_hw_t{x0 - (float)a[0], x1 - (float)a[1]}, cps_f16x2_t);
-    hi = __builtin_bit_cast(uint32_t, a);
-    lo = __builtin_bit_cast(uint32_t, b);
-}
 
 // CB = Cin / 64, BN = output channels per workgroup, NW waves (wave w: 64-pixel half w & 1, channel slice w >> 1), NS ring stages.
 // Wt: the split slab image of [Cout][3][3][Cin] (byte offset of (row, k) slab = (row K + 32 slab) 4).  grid = (ceil(W / 16), ceil(H / 8), B Cout / BN)
@@ -209,7 +184,7 @@ __global__ __launch_bounds__(64 * NW, (CB == 1 && NS <= 2) ? 2 : 1) void conv3x3
         for (int i = 0; i < P; ++i) {
             const int u = wave + NW * i, r = 4 * u + wr;
             const int c = wp ^ (r & 15);
-            cp_glds16(Wt + ((long)(n0 + r) * K + tap * Cin + cb * 64) * 4 + c * 16, dst + (unsigned)(u * 1024));
+            glds16(Wt + ((long)(n0 + r) * K + tap * Cin + cb * 64) * 4 + c * 16, dst + (unsigned)(u * 1024));
         }
     };
 #pragma unroll
@@ -232,20 +207,20 @@ __global__ __launch_bounds__(64 * NW, (CB == 1 && NS <= 2) ? 2 : 1) void conv3x3
             c4 = *reinterpret_cast<const float4*>(src + 4);
         }
         uint4 hi, lo;
-        cps_split2(a.x, a.y, hi.x, lo.x); cps_split2(a.z, a.w, hi.y, lo.y); cps_split2(c4.x, c4.y, hi.z, lo.z); cps_split2(c4.z, c4.w, hi.w, lo.w);
+        split2_f16(a.x, a.y, hi.x, lo.x); split2_f16(a.z, a.w, hi.y, lo.y); split2_f16(c4.x, c4.y, hi.z, lo.z); split2_f16(c4.z, c4.w, hi.w, lo.w);
         unsigned char* dst = cp_smem + (2 * cb) * CP_PLANE + pp * 128 + ((slot ^ (pp & 7)) * 16);
         *reinterpret_cast<uint4*>(dst) = hi;
         *reinterpret_cast<uint4*>(dst + CP_PLANE) = lo;
     }
-    cp_wait<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_vm<0>();
+    DTLR_WAITCNT_LGKM(0);
 
     const int wm = wave & 1, wn = wave >> 1;
-    cp_f32x4_t acc[CI][4];
+    f32x4_t acc[CI][4];
 #pragma unroll
     for (int ci = 0; ci < CI; ++ci)
 #pragma unroll
-        for (int ti = 0; ti < 4; ++ti) acc[ci][ti] = cp_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int ti = 0; ti < 4; ++ti) acc[ci][ti] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const unsigned wrow = (unsigned)((wn * CW + n) * 256);                   // this lane's weight row inside a stage (+ ci * 4096); row & 15 == n
 
     for (int s = 0; s < NSL; ++s) {
@@ -275,14 +250,14 @@ __global__ __launch_bounds__(64 * NW, (CB == 1 && NS <= 2) ? 2 : 1) void conv3x3
             for (int ci = 0; ci < CI; ++ci)
 #pragma unroll
                 for (int ti = 0; ti < 4; ++ti) {
-                    acc[ci][ti] = cps_mma(wh[ci], xl[ti], acc[ci][ti]);
-                    acc[ci][ti] = cps_mma(wl[ci], xh[ti], acc[ci][ti]);
-                    acc[ci][ti] = cps_mma(wh[ci], xh[ti], acc[ci][ti]);
+                    acc[ci][ti] = mma16_f16(wh[ci], xl[ti], acc[ci][ti]);
+                    acc[ci][ti] = mma16_f16(wl[ci], xh[ti], acc[ci][ti]);
+                    acc[ci][ti] = mma16_f16(wh[ci], xh[ti], acc[ci][ti]);
                 }
         }
         // my pieces of slab s + 1 must have landed before the next barrier; the (NS - 2) slabs issued after it may stay in flight
-        if (s + NS - 1 < NSL) cp_wait<(NS - 2) * P>();
-        else cp_wait<0>();
+        if (s + NS - 1 < NSL) wait_vm<(NS - 2) * P>();
+        else wait_vm<0>();
     }
 
     // ---- epilogue: + bias, ReLU, fp32: lane (n, g) stores channels 16 ci + 4 g .. + 3 of pixel n of tile row ti (16 bytes) ----------

@@ -30,12 +30,9 @@
 // two launches, i.e. nothing gained; with the second GEMM as three single-tile passes 54.9 us.  Removed.)
 // Arithmetic identical to the unfused path (same MFMA, k ascending, same roundings: sine, H, qpos, tgt + qpos and the outputs are
 // rounded to the 16-bit format exactly where the separate kernels stored them), so the results are bit-identical to it.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t dq_h16x8_t;
-typedef __attribute__((ext_vector_type(4))) float dq_f32x4_t;
 
 constexpr int DQ_ROWS = 128;                      // queries per workgroup (NTT = 8 query tiles of 16); the small-batch form: 32 (NTT = 2)
 constexpr int DQ_PITCH_Q = 128 * 2 + 16;          // sine quarter tile: 128 channels per row
@@ -49,10 +46,6 @@ template <int NTT> struct DqCfg {
     static constexpr int TPT = 512 / ROWS;        // threads per query in the sine / reference-box stage: 4 or 16
     static constexpr int PPT = 64 / TPT;          // (sin, cos) pairs per thread and quarter: 16 or 4
 };
-
-__device__ __forceinline__ dq_f32x4_t dq_mma(const uint4& a, const uint4& b, dq_f32x4_t c) {
-    return DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(dq_h16x8_t, a), __builtin_bit_cast(dq_h16x8_t, b), c, 0, 0, 0);
-}
 
 // The weight fragments of one GEMM stage of a wave: 2 row tiles x KT / 32 k-steps.  Weights are handed over PACKED in fragment order
 // (ops.dq_pack / dtlr_dq_pack_weights): unit u = output channels [32 u, 32 u + 32), image [unit][k-step][tile 2][lane 64][8 elements],
@@ -72,7 +65,7 @@ __device__ __forceinline__ void dq_fetch(uint4 (&a)[KT / 32][2], const uint16_t*
 // acc[t][tt] += W-fragments . X[16 tt + n][0 .. KT)^T for the wave's NT row tiles and the 8 query tiles; xt: LDS tile (rows = queries),
 // `pitch` bytes per row.  One activation fragment (ds_read_b128) feeds the NT MFMAs of its k-step.
 template <int KT, int NT, int NTT>
-__device__ __forceinline__ void dq_gemm(dq_f32x4_t (&acc)[NT][NTT], const uint4 (&a)[KT / 32][NT], const unsigned char* xt, int pitch, int lane)
+__device__ __forceinline__ void dq_gemm(f32x4_t (&acc)[NT][NTT], const uint4 (&a)[KT / 32][NT], const unsigned char* xt, int pitch, int lane)
 {
     const unsigned char* xp = xt + (lane & 15) * pitch + 16 * (lane >> 4);
 #pragma unroll
@@ -81,7 +74,7 @@ __device__ __forceinline__ void dq_gemm(dq_f32x4_t (&acc)[NT][NTT], const uint4 
         for (int tt = 0; tt < NTT; ++tt) {
             const uint4 b = *reinterpret_cast<const uint4*>(xp + (16 * tt) * pitch + 64 * ks);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t][tt] = dq_mma(a[ks][t], b, acc[t][tt]);
+            for (int t = 0; t < NT; ++t) acc[t][tt] = mma16(a[ks][t], b, acc[t][tt]);
         }
     }
 }
@@ -89,7 +82,7 @@ __device__ __forceinline__ void dq_gemm(dq_f32x4_t (&acc)[NT][NTT], const uint4 
 // Store the wave's two row tiles (32 channels) of one query tile as 16-byte pieces: the tiles are paired with v_permlane16_swap so that a
 // lane holds 8 consecutive channels (even g: channels 8 (g/2).. of tile 0, odd g: the same 8 channels of tile 1) -- 64 contiguous bytes
 // per query and instruction instead of two 32-byte pieces (the output of a workgroup is 262 KB).
-__device__ __forceinline__ void dq_store_pair(uint16_t* __restrict__ row /* &out[q][ch0] */, const dq_f32x4_t& c0, const dq_f32x4_t& c1,
+__device__ __forceinline__ void dq_store_pair(uint16_t* __restrict__ row /* &out[q][ch0] */, const f32x4_t& c0, const f32x4_t& c1,
                                               const float4& b0, const float4& b1, int g, bool live)
 {
     const uint32_t lo0 = pack_bf16x2(c0[0] + b0.x, c0[1] + b0.y), hi0 = pack_bf16x2(c0[2] + b0.z, c0[3] + b0.w);
@@ -100,11 +93,11 @@ __device__ __forceinline__ void dq_store_pair(uint16_t* __restrict__ row /* &out
 }
 
 template <int NT, int NTT>
-__device__ __forceinline__ void dq_zero(dq_f32x4_t (&acc)[NT][NTT]) {
+__device__ __forceinline__ void dq_zero(f32x4_t (&acc)[NT][NTT]) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int tt = 0; tt < NTT; ++tt) acc[t][tt] = dq_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < NTT; ++tt) acc[t][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 }
 
 // one sine quarter: coordinate value c[token] (already x 2 pi), 128 channels = 64 (sin, cos) pairs; thread -> (token = tid / TPT, PPT pairs)
@@ -177,7 +170,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
     dq_sine_quarter<NTT>(r0, cq[0], rcp, tid);
     __syncthreads();
     {
-        dq_f32x4_t acc[2][NTT];
+        f32x4_t acc[2][NTT];
         dq_zero<2, NTT>(acc);
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
             const float4 bb = *reinterpret_cast<const float4*>(b0 + ch);
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
-                const dq_f32x4_t c = acc[t][tt];
+                const f32x4_t c = acc[t][tt];
                 *reinterpret_cast<uint2*>(r1 + (16 * tt + n) * DQ_PITCH + ch * 2) =
                     make_uint2(pack_bf16x2(fmaxf(c[0] + bb.x, 0.f), fmaxf(c[1] + bb.y, 0.f)), pack_bf16x2(fmaxf(c[2] + bb.z, 0.f), fmaxf(c[3] + bb.w, 0.f)));
             }
@@ -207,7 +200,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
     // ---- qpos = H W1^T + b1 ; A = tgt + qpos -> region 0, tgt -> region 1, qpos -> global --------------------------------------
     uint4 wf[8][2];                                               // the [q|k] projection's first half (row tiles 0, 1 of the wave's four)
     {
-        dq_f32x4_t acc[2][NTT];
+        f32x4_t acc[2][NTT];
         dq_zero<2, NTT>(acc);
         dq_fetch<256>(wf, Wqk, 2 * wave, 8, 0, lane);
         // this lane's tgt values (the residual input of A = tgt + qpos and the v projection's operand): requested BEFORE the GEMM so that
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
                 const long q = q0 + 16 * tt + n;
                 const bool live = q < Q;
                 const uint2 tw = tq[t][tt];
-                const dq_f32x4_t c = acc[t][tt];
+                const f32x4_t c = acc[t][tt];
                 const uint2 pw = make_uint2(pack_bf16x2(c[0] + bb.x, c[1] + bb.y), pack_bf16x2(c[2] + bb.z, c[3] + bb.w));
                 if (live) *reinterpret_cast<uint2*>(qpos + q * 256 + ch) = pw;
                 const uint2 aw = make_uint2(pack_bf16x2(h16_lo(tw.x) + h16_lo(pw.x), h16_hi(tw.x) + h16_hi(pw.x)),
@@ -245,7 +238,7 @@ __global__ __launch_bounds__(512) void dec_query_stage_kernel(
     //      stage's weights are always in flight behind the current one -------------------------------------------------------------
 #define DQ_OUT_STAGE(WF, XT, OUT, LDO, CH0, BIAS)                                                  \
     {                                                                                              \
-        dq_f32x4_t acc[2][NTT];                                                                    \
+        f32x4_t acc[2][NTT];                                                                    \
         dq_zero<2, NTT>(acc);                                                                      \
         dq_gemm<256, 2, NTT>(acc, WF, XT, DQ_PITCH, lane);                                         \
         const float4 bb0 = *reinterpret_cast<const float4*>((BIAS) + (CH0) + 4 * g);               \

@@ -189,10 +189,10 @@ __global__ __launch_bounds__(256) void query_label_kernel(const float* __restric
     }
 #define QL_STEP(CTRL)                                                                          \
     {                                                                                          \
-        sum += dpp_f<CTRL>(sum);                                                               \
-        nonfin += dpp_f<CTRL>(nonfin);                                                         \
-        const float ob = dpp_f<CTRL>(best);                                                    \
-        const int oa = dpp_i<CTRL>(arg);                                                       \
+        sum += dpp_f<CTRL, true>(sum);                                                               \
+        nonfin += dpp_f<CTRL, true>(nonfin);                                                         \
+        const float ob = dpp_f<CTRL, true>(best);                                                    \
+        const int oa = dpp_i<CTRL, true>(arg);                                                       \
         if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }                    \
     }
     QL_STEP(0xB1) QL_STEP(0x4E) QL_STEP(0x141) QL_STEP(0x140)       // quad xor 1, quad xor 2, row_half_mirror, row_mirror

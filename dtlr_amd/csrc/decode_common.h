@@ -1,8 +1,8 @@
-// Device helpers shared by decode.hip and ctc_grad.hip: the sortable float key, the in-LDS bitonic sort, DPP lane exchange, the
+// Device helpers shared by decode.hip and ctc_grad.hip: the sortable float key, the in-LDS bitonic sort, the
 // per-query sigmoid sum and the CTC alpha recursion's frame (one code path, so the CTC forward and backward see bit-identical sums,
 // reading orders and alphas).
 #pragma once
-#include "dtlr_common.h"
+#include "gfx950_prims.h"      // dpp_f / dpp_i
 
 namespace dtlr {
 
@@ -42,11 +42,6 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int n
     __syncthreads();
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); }
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
 // sum over classes of sigmoid(logit) for every query: 16 lanes per query, 256 threads = 16 queries per workgroup (DPP reductions)
 __device__ __forceinline__ void query_sum_rows(const float* __restrict__ logits, float* __restrict__ sums, long nrows, int C)
 {
@@ -62,7 +57,7 @@ __device__ __forceinline__ void query_sum_rows(const float* __restrict__ logits,
 #pragma unroll
         for (int u = 0; u < 4; ++u) sum += 1.f / (1.f + expf(-x[u]));
     }
-    sum += dpp_f<0xB1>(sum); sum += dpp_f<0x4E>(sum); sum += dpp_f<0x141>(sum); sum += dpp_f<0x140>(sum);
+    sum += dpp_f<0xB1, true>(sum); sum += dpp_f<0x4E, true>(sum); sum += dpp_f<0x141, true>(sum); sum += dpp_f<0x140, true>(sum);
     if (live && l16 == 0) sums[q] = sum;
 }
 

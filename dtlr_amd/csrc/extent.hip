@@ -8,12 +8,6 @@
 
 namespace dtlr {
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // one workgroup per line: unmasked rows of column 0 and unmasked columns of row 0
 __global__ __launch_bounds__(256) void line_extents_kernel(const uint8_t* __restrict__ mask, int H, int W, int* __restrict__ ext)
 {

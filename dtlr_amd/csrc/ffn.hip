@@ -28,13 +28,10 @@
 //   * epilogue: + b2 + X (the residual is already in registers: W2's rows are assigned to MFMA rows so that a lane's
 //     accumulators are exactly the channels its X fragments hold), LayerNorm over the 256 channels (lane-local
 //     sums, two cross-lane steps, one exchange with the partner wave through LDS), 16-byte stores.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t ffn_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float ffn_f32x4_t;
 
 constexpr int FFN_NS = 4;                                   // ring stages
 constexpr int FFN_STAGE = 32768;                            // W1 chunk image (16 KB) | W2 chunk image (16 KB)
@@ -45,37 +42,10 @@ constexpr int FFN_B1_OFF = FFN_LN_OFF + 4 * 256 * 4;         // (LayerNorm uses 
 constexpr int FFN_MAX_DFF = 2048;
 constexpr int FFN_LDS = FFN_B1_OFF + FFN_MAX_DFF * 4;
 
-// LDS-DMA: 64 lanes x 16 bytes, destination = wave-uniform LDS byte address + 16 * lane.  Invisible to hipcc's
-// waitcnt bookkeeping: completion is counted by hand (cdna_hip_programming.md section 5.7).
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// same with a wave-uniform base in SGPRs and a 32-bit per-lane byte offset (one VGPR instead of a 64-bit address per source)
-__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-__device__ __forceinline__ uint4 ffn_load16(const void* p) {
-    uint4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-
 template <int DBG = 0>
-__device__ __forceinline__ ffn_f32x4_t ffn_mma(const uint4& a, const uint4& b, ffn_f32x4_t c) {
+__device__ __forceinline__ f32x4_t ffn_mma(const uint4& a, const uint4& b, f32x4_t c) {
     if constexpr (DBG & 2) { asm volatile("" :: "v"(a.x), "v"(b.x)); return c; }
-    return DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(ffn_bf16x8_t, a), __builtin_bit_cast(ffn_bf16x8_t, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = h16_lo(w[i]); v[2 * i + 1] = h16_hi(w[i]); }
+    return mma16(a, b, c);
 }
 
 // DBG (timing experiments only, env DTLR_FFN_DBG; results are garbage): 1 = no weight DMA after the prologue,
@@ -123,11 +93,11 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
     for (int tt = 0; tt < 2; ++tt) {
         const long tok = min(tok0 + tt * 16 + n, (long)M - 1);
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) xf[ks][tt] = ffn_load16(X + tok * 256 + ks * 32 + g * 8);
+        for (int ks = 0; ks < 8; ++ks) xf[ks][tt] = load16(X + tok * 256 + ks * 32 + g * 8);
     }
     // The X loads are asm (uncounted) and waited for right here: as compiler-counted loads hipcc kept their waits (down
     // to vmcnt(0)) inside the chunk loop, where every iteration would then drain the DMA queue.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    DTLR_WAITCNT_VM(0);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- DMA sources: wave w moves blocks 4w .. 4w+3 of a chunk image (blocks 0-15: W1, 16-31: W2) ----------
@@ -156,11 +126,11 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
         _Pragma("unroll") for (int u = 0; u < 4; ++u) glds16(src[u] + (long)(C) * cstride, dst_ + u * 1024u); \
     }
 
-    ffn_f32x4_t yacc[8][2];
+    f32x4_t yacc[8][2];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) yacc[i][tt] = ffn_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < 2; ++tt) yacc[i][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     {
         float* b1s = reinterpret_cast<float*>(smem + FFN_B1_OFF);
@@ -170,9 +140,9 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
     FFN_ISSUE(0)
     if (nchunk > 1) FFN_ISSUE(1)
     if (nchunk > 2) FFN_ISSUE(2)
-    if (nchunk > 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if (nchunk > 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (nchunk > 2) DTLR_WAITCNT(8, 0);
+    else if (nchunk > 1) DTLR_WAITCNT(4, 0);
+    else DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();
 
     unsigned char* hbuf = smem + FFN_H_OFF + tg * 4096;
@@ -198,8 +168,8 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
 #define FFN_LOAD_B1(C) const float4 bb = *reinterpret_cast<const float4*>(smem + FFN_B1_OFF + ((C) * 32 + g * 8 + half * 4) * 4);
 #define FFN_MMA_A(C)                                                                               \
     {                                                                                              \
-        ffn_f32x4_t he[2] = {ffn_f32x4_t{0.f, 0.f, 0.f, 0.f}, ffn_f32x4_t{0.f, 0.f, 0.f, 0.f}};    \
-        ffn_f32x4_t ho[2] = {ffn_f32x4_t{0.f, 0.f, 0.f, 0.f}, ffn_f32x4_t{0.f, 0.f, 0.f, 0.f}};    \
+        f32x4_t he[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};    \
+        f32x4_t ho[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};    \
         _Pragma("unroll") for (int ks = 0; ks < 8; ks += 2) {                                      \
             he[0] = ffn_mma<DBG>(wa[ks], xf[ks][0], he[0]);         he[1] = ffn_mma<DBG>(wa[ks], xf[ks][1], he[1]); \
             ho[0] = ffn_mma<DBG>(wa[ks + 1], xf[ks + 1][0], ho[0]); ho[1] = ffn_mma<DBG>(wa[ks + 1], xf[ks + 1][1], ho[1]); \
@@ -225,8 +195,8 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
     {                                                                                              \
         /* the one barrier of the chunk: publishes H(C) to the partner wave; my pieces of chunk C+1 (read by phase */ \
         /* A(C+1)) have landed -- chunk C+2's four may stay in flight; my H writes are done */     \
-        if (!(DBG & 1) && (C) + 2 < nchunk) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); \
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                           \
+        if (!(DBG & 1) && (C) + 2 < nchunk) DTLR_WAITCNT(4, 0); \
+        else DTLR_WAITCNT(0, 0);                           \
         if (!(DBG & 4)) __builtin_amdgcn_s_barrier();                                              \
         if (!(DBG & 1) && (C) + 3 < nchunk) FFN_ISSUE((C) + 3)   /* into the stage of chunk C-1: its last readers (W2(C-1), step C-1) are done */ \
         FFN_LOAD_B1((C) + 1)                                      /* ahead of the pinned region: it would otherwise be scheduled last, in front of the H store */ \
@@ -360,7 +330,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_bf16_kernel(
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             float xr[8];
-            unpack8(half ? xf[4 + kq][tt] : xf[kq][tt], xr);      // (a runtime index into xf would move it to scratch)
+            unpack8_h16(half ? xf[4 + kq][tt] : xf[kq][tt], xr);      // (a runtime index into xf would move it to scratch)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float y = e < 4 ? yacc[2 * kq][tt][e] : yacc[2 * kq + 1][tt][e - 4];
@@ -496,9 +466,9 @@ __global__ __launch_bounds__(256, 1) void ffn2_bf16_kernel(
     for (int tt = 0; tt < TT; ++tt) {
         const long tok = min(tok0 + tt * 16 + n, (long)M - 1);
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) xf[ks][tt] = ffn_load16(X + tok * 256 + ks * 32 + g * 8);
+        for (int ks = 0; ks < 8; ++ks) xf[ks][tt] = load16(X + tok * 256 + ks * 32 + g * 8);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    DTLR_WAITCNT_VM(0);
     __builtin_amdgcn_sched_barrier(0);
 
     // DMA sources: wave w moves blocks 4w .. 4w+3 of each 16-block image.
@@ -542,11 +512,11 @@ __global__ __launch_bounds__(256, 1) void ffn2_bf16_kernel(
     if (nchunk > 2) F2_ISSUE1(2)
     if (nchunk > 1) F2_ISSUE2(1)
 
-    ffn_f32x4_t yacc[16][TT];
+    f32x4_t yacc[16][TT];
 #pragma unroll
     for (int i = 0; i < 16; ++i)
 #pragma unroll
-        for (int tt = 0; tt < TT; ++tt) yacc[i][tt] = ffn_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < TT; ++tt) yacc[i][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     uint4 hb[TT];                                                   // H^T B-fragments of the chunk phase B works on
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) hb[tt] = make_uint4(0u, 0u, 0u, 0u);
@@ -558,8 +528,8 @@ __global__ __launch_bounds__(256, 1) void ffn2_bf16_kernel(
 #define F2_W1F(C, Q) (*reinterpret_cast<const uint4*>(smem + ((C) & (F2_NS - 1)) * F2_RING + (((Q) & 1) * 8 + ((Q) >> 1)) * 1024 + lane * 16))
 #define F2_W2F(C, Q) (*reinterpret_cast<const uint4*>(smem + F2_W2_OFF + ((C) & (F2_NS - 1)) * F2_RING + (Q) * 1024 + lane * 16))
     // W1(0) has to be in registers before the first iteration (the only exposed fragment reads are these and the last W2's)
-    if (nchunk > 1) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (nchunk > 1) DTLR_WAITCNT(16, 0);
+    else DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int q = 0; q < 16; ++q) w[q] = F2_W1F(0, q);
@@ -570,20 +540,20 @@ __global__ __launch_bounds__(256, 1) void ffn2_bf16_kernel(
 #define F2_STEP(C, WITH_B, WITH_NEXT, DMA1, DMA2)                                                  \
     {                                                                                              \
         F2_TL(1)                                                                                   \
-        if (DMA2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");   /* the previous iteration's 8 pieces may stay in flight */ \
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                           \
+        if (DMA2) DTLR_WAITCNT(8, 0);   /* the previous iteration's 8 pieces may stay in flight */ \
+        else DTLR_WAITCNT(0, 0);                           \
         F2_TL(2)                                                                                   \
         __builtin_amdgcn_s_barrier();                                                              \
         F2_TL(3)                                                                                   \
         const float4 bl = *reinterpret_cast<const float4*>(smem + F2_B1_OFF + ((C) * 32 + g * 8) * 4);      \
         const float4 bh = *reinterpret_cast<const float4*>(smem + F2_B1_OFF + ((C) * 32 + g * 8 + 4) * 4);  \
         __builtin_amdgcn_sched_barrier(0);                                                         \
-        ffn_f32x4_t he[2][TT];                                                                     \
+        f32x4_t he[2][TT];                                                                     \
         /* hand-placed stream: one group = TT MFMAs on fragment slot q + the slot's refill (+ a DMA piece every 4th group, + a */ \
         /* sixth of the H epilogue in phase B); sched_barrier(0) between groups keeps hipcc from re-clustering them */ \
         _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                           \
             _Pragma("unroll") for (int tt = 0; tt < TT; ++tt)                                      \
-                he[q & 1][tt] = ffn_mma<0>(w[q], xf[q >> 1][tt], q < 2 ? ffn_f32x4_t{0.f, 0.f, 0.f, 0.f} : he[q & 1][tt]); \
+                he[q & 1][tt] = ffn_mma<0>(w[q], xf[q >> 1][tt], q < 2 ? f32x4_t{0.f, 0.f, 0.f, 0.f} : he[q & 1][tt]); \
             if (WITH_B) w[q] = F2_W2F((C) - 1, q);                                                 \
             else if (WITH_NEXT) w[q] = F2_W1F((C) + 1, q);                                         \
             if ((q & 3) == 3 && (DMA1)) F2_PIECE1((C) + 3, q >> 2)                                 \
@@ -646,7 +616,7 @@ __global__ __launch_bounds__(256, 1) void ffn2_bf16_kernel(
             const float4 ba = *reinterpret_cast<const float4*>(prm2_ + ch), bc = *reinterpret_cast<const float4*>(prm2_ + ch + 4);
             const float bias[8] = {ba.x, ba.y, ba.z, ba.w, bc.x, bc.y, bc.z, bc.w};
             float xr[8];
-            unpack8(xf[kq][tt], xr);
+            unpack8_h16(xf[kq][tt], xr);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float y = e < 4 ? yacc[2 * kq][tt][e] : yacc[2 * kq + 1][tt][e - 4];
@@ -725,15 +695,15 @@ __global__ __launch_bounds__(256, 2) void proj_ln_bf16_kernel(
     for (int tt = 0; tt < 2; ++tt) {
         const long tok = min(tok0 + tt * 16 + n, (long)M - 1);
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) af[ks][tt] = ffn_load16(A + tok * 256 + ks * 32 + g * 8);
+        for (int ks = 0; ks < 8; ++ks) af[ks][tt] = load16(A + tok * 256 + ks * 32 + g * 8);
         if constexpr (!SPLIT) {
 #pragma unroll
-            for (int kq = 0; kq < 4; ++kq) rr[kq][tt] = ffn_load16(R + tok * 256 + 128 * half + 32 * kq + 8 * g);
+            for (int kq = 0; kq < 4; ++kq) rr[kq][tt] = load16(R + tok * 256 + 128 * half + 32 * kq + 8 * g);
         } else {
 #pragma unroll
             for (int kq = 0; kq < 4; ++kq) rr[kq][tt] = make_uint4(0u, 0u, 0u, 0u);
             if (R && reinterpret_cast<const unsigned char*>(R)[tok] == 0) {        // masked token: features zeroed before the projection
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                DTLR_WAITCNT_VM(0);
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) af[ks][tt] = make_uint4(0u, 0u, 0u, 0u);
             }
@@ -751,14 +721,14 @@ __global__ __launch_bounds__(256, 2) void proj_ln_bf16_kernel(
         }                                                                                          \
     }
     PLN_ISSUE(0)
-    ffn_f32x4_t yacc[8][2];
+    f32x4_t yacc[8][2];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) yacc[i][tt] = ffn_f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < 2; ++tt) yacc[i][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #define PLN_GROUP(J)                                                                               \
     {                                                                                              \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   /* A, R and my pieces of group J landed */ \
+        DTLR_WAITCNT_VM(0);   /* A, R and my pieces of group J landed */ \
         __builtin_amdgcn_sched_barrier(0);                                                         \
         __builtin_amdgcn_s_barrier();                      /* ... everyone's; and everyone is done reading the other stage */ \
         if ((J) + 1 < 4) PLN_ISSUE((J) + 1)                                                        \
@@ -788,7 +758,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln_bf16_kernel(
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             float xr[8];
-            unpack8(rr[kq][tt], xr);
+            unpack8_h16(rr[kq][tt], xr);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float y = e < 4 ? yacc[2 * kq][tt][e] : yacc[2 * kq + 1][tt][e - 4];
@@ -841,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void proj_ln_bf16_kernel(
                 if (tok < M) *reinterpret_cast<uint4*>(Y + tok * 256 + ch) = hi;
             } else {
                 float hf[8], l[8];
-                unpack8(hi, hf);
+                unpack8_h16(hi, hf);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) l[e] = o[e] - hf[e];
                 const uint4 lo = make_uint4(pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3]), pack_bf16x2(l[4], l[5]), pack_bf16x2(l[6], l[7]));

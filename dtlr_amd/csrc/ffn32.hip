@@ -27,13 +27,10 @@
 //     (32 MFMAs against identity fragments), so the epilogue is + b2 and LayerNorm only: per
 //     token tile the lane's 128 values are copied out of the AGPRs once (the X fragments are dead by then), packed fp32 math, one
 //     exchange with lane ^ 32 per statistic; stores pair the two half-lanes of a token to 16 bytes per lane.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t f3_bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f3_f32x16_t;
 
 constexpr int F3_NS = 4;                                    // ring stages
 constexpr int F3_RING = 16384;                              // one W1 (or W2) chunk image: 16 fragments of 1 KB
@@ -44,44 +41,11 @@ constexpr int F3_PRM_OFF = F3_B1_OFF + (F3_MAX_DFF + 32) * 4;      // b2 | gamma
 constexpr int F3_LDS = F3_PRM_OFF + 3 * 256 * 4;
 constexpr int FFN32_PAD = 4;                                // zero chunks behind each packed weight (DMA'd, never multiplied)
 
-// LDS-DMA with a wave-uniform base in SGPRs and a 32-bit per-lane byte offset; completion is counted by hand (vmcnt)
-__device__ __forceinline__ void f3_glds16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// same with an immediate byte offset that applies to BOTH the global address and the LDS destination (the 4 pieces of a chunk image
-// are 1 KB apart in both): one base pair per chunk instead of one per piece
-template <int OFF> __device__ __forceinline__ void f3_glds16so(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ uint4 f3_load16(const void* p) {
-    uint4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ f3_f32x16_t f3_mma(const uint4& a, const uint4& b, f3_f32x16_t c) {
-    return DTLR_MFMA_32x32x16_H16(__builtin_bit_cast(f3_bf16x8_t, a), __builtin_bit_cast(f3_bf16x8_t, b), c, 0, 0, 0);
-}
-
-// Phase-A form: accumulator pinned to ARCHITECTURAL VGPRs.  The kernel needs 256 (Y^T) + 32 (H^T) accumulator registers; left to itself
-// hipcc keeps all of them in the 256 AGPRs and shuttles tiles through v_accvgpr moves (448 per chunk).  As inline asm the MFMA is
-// invisible to the hazard recogniser; the uses are arranged so that no software wait states are owed: the two H^T accumulators
-// alternate (the pattern hipcc itself emits back to back), their operands come from ds_read / long-lived registers (waited for by the
-// compiler through the asm operands), and they are first read by VALU two MFMAs (or an explicit s_nop pad) later.
-// ReLU as ONE instruction (fmaxf canonicalises its operand first: two v_max per value)
-__device__ __forceinline__ float f3_relu(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_huge_valf()); }
-typedef __attribute__((ext_vector_type(4))) unsigned f3_u32x4_t;
-__device__ __forceinline__ void f3_mma_v0(const uint4& a, const uint4& b, f3_f32x16_t& c) {        // c = a b (first k-step of a chunk)
-    const f3_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
-}
-__device__ __forceinline__ void f3_mma_v(const uint4& a, const uint4& b, f3_f32x16_t& c) {
-    const f3_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-}
+// Phase A uses mma32_v0 / mma32_v (accumulator pinned to ARCHITECTURAL VGPRs).  The kernel needs 256 (Y^T) + 32 (H^T) accumulator registers;
+// left to itself hipcc keeps all of them in the 256 AGPRs and shuttles tiles through v_accvgpr moves (448 per chunk).  What gfx950_prims.h
+// note 3 asks of the caller is arranged so that no software wait states are owed: the two H^T accumulators alternate (the pattern hipcc itself
+// emits back to back), their operands come from ds_read / long-lived registers, and they are first read by VALU two MFMAs (or an explicit
+// s_nop pad) later.
 
 // DBG (timing experiments only, env DTLR_FFN32_DBG; results are garbage): 1 = no weight DMA inside the chunk loop, 2 = no per-chunk
 // barrier / DMA wait, 4 = no weight-fragment LDS reads inside the chunk loop, 8 = two chunks only (prologue + epilogue cost).  DBG = 0 is the product kernel.
@@ -104,8 +68,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
     const char* W1b = reinterpret_cast<const char*>(W1p) + wave * 4096;
     const char* W2b = reinterpret_cast<const char*>(W2p) + wave * 4096;
     const unsigned my1 = lds_base + (unsigned)wave * 4096u, my2 = my1 + F3_W2_OFF;
-#define F3_PIECE1(C, U) { if (!(DBG & 1) || (C) < 3) f3_glds16so<(U) * 1024>(W1b + (long)(C) * F3_RING, vlane, my1 + (unsigned)((C) & (F3_NS - 1)) * F3_RING); }
-#define F3_PIECE2(C, U) { if (!(DBG & 1) || (C) < 2) f3_glds16so<(U) * 1024>(W2b + (long)(C) * F3_RING, vlane, my2 + (unsigned)((C) & (F3_NS - 1)) * F3_RING); }
+#define F3_PIECE1(C, U) { if (!(DBG & 1) || (C) < 3) glds16so<(U) * 1024>(W1b + (long)(C) * F3_RING, vlane, my1 + (unsigned)((C) & (F3_NS - 1)) * F3_RING); }
+#define F3_PIECE2(C, U) { if (!(DBG & 1) || (C) < 2) glds16so<(U) * 1024>(W2b + (long)(C) * F3_RING, vlane, my2 + (unsigned)((C) & (F3_NS - 1)) * F3_RING); }
 #define F3_ISSUE1(C) { F3_PIECE1(C, 0) F3_PIECE1(C, 1) F3_PIECE1(C, 2) F3_PIECE1(C, 3) }
 #define F3_ISSUE2(C) { F3_PIECE2(C, 0) F3_PIECE2(C, 1) F3_PIECE2(C, 2) F3_PIECE2(C, 3) }
     // prologue order: W1(0) W1(1) | W2(0) W2(1) W1(2); iteration c then issues W2(c + 2), W1(c + 3)
@@ -123,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
     for (int tt = 0; tt < 2; ++tt) {
         const long tok = min(tok0 + tt * 32 + j, (long)M - 1);
 #pragma unroll
-        for (int s = 0; s < 16; ++s) xf[s][tt] = f3_load16(X + tok * 256 + s * 16 + hh * 8);
+        for (int s = 0; s < 16; ++s) xf[s][tt] = load16(X + tok * 256 + s * 16 + hh * 8);
     }
     {   // b1 table (padded with zeros for the chunk read past the end)
         float* b1s = reinterpret_cast<float*>(f3_smem + F3_B1_OFF);
@@ -142,7 +106,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
     // first weight chunks are in flight; the epilogue then needs no X fragments and no separate residual pass, and the accumulators are
     // born in the AGPRs (seeding them with VALU results made hipcc keep some in VGPRs and shuttle them inside the chunk loop).
     // Identity fragments: lane (i, hh), element e is 1.0 iff i == 8 hh + e (k-step 2 ct) / i == 16 + 8 hh + e (k-step 2 ct + 1).
-    f3_f32x16_t yacc[8][2];
+    f32x16_t yacc[8][2];
     {
         uint32_t ia[4], ib[4];
 #pragma unroll
@@ -152,20 +116,20 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
             ib[e2] = (r1 == 0 ? H16_ONE : 0u) | (r1 == 1 ? (H16_ONE << 16) : 0u);
         }
         const uint4 Ia = make_uint4(ia[0], ia[1], ia[2], ia[3]), Ib = make_uint4(ib[0], ib[1], ib[2], ib[3]);
-        f3_f32x16_t zero;
+        f32x16_t zero;
 #pragma unroll
         for (int r = 0; r < 16; ++r) zero[r] = 0.f;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // X (and, being older, the first weight chunks) landed
+        DTLR_WAITCNT_VM(0);            // X (and, being older, the first weight chunks) landed
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
-                yacc[ct][tt] = f3_mma(Ia, xf[2 * ct][tt], zero);
-                yacc[ct][tt] = f3_mma(Ib, xf[2 * ct + 1][tt], yacc[ct][tt]);
+                yacc[ct][tt] = mma32(Ia, xf[2 * ct][tt], zero);
+                yacc[ct][tt] = mma32(Ib, xf[2 * ct + 1][tt], yacc[ct][tt]);
             }
     }
-    f3_f32x16_t he[2];
+    f32x16_t he[2];
     uint4 hb[2][2], hbn[2];                                  // H^T B-fragments [k-step][token tile] of the chunk phase B multiplies; k-step 1 of the next one
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
@@ -175,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
 #define F3_W1F(C, Q) (*reinterpret_cast<const uint4*>(f3_smem + ((C) & (F3_NS - 1)) * F3_RING + (Q) * 1024 + lane * 16))
 #define F3_W2F(C, Q) (*reinterpret_cast<const uint4*>(f3_smem + F3_W2_OFF + ((C) & (F3_NS - 1)) * F3_RING + (Q) * 1024 + lane * 16))
     // everything the prologue issued has landed (mine)
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int q = 0; q < 4; ++q) w[q] = F3_W1F(0, q);
@@ -188,7 +152,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
 #define F3_HEPI(P, BB)                                                                             \
     {                                                                                              \
         const int tt_ = (P) >> 3, p_ = (P) & 7;                                                    \
-        const uint32_t v_ = pack_bf16x2(f3_relu(he[tt_][2 * p_] + (BB).x), f3_relu(he[tt_][2 * p_ + 1] + (BB).y)); \
+        const uint32_t v_ = pack_bf16x2(relu_med3(he[tt_][2 * p_] + (BB).x), relu_med3(he[tt_][2 * p_ + 1] + (BB).y)); \
         uint4& d_ = (p_ < 4) ? hb[0][tt_] : hbn[tt_];                                              \
         if ((p_ & 3) == 0) d_.x = v_;                                                              \
         else if ((p_ & 3) == 1) d_.y = v_;                                                         \
@@ -205,8 +169,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
 #define F3_STEP(C, WITH_A, WITH_B, FIRST)                                                          \
     {                                                                                              \
         if (!(FIRST) && !((DBG & 2) && (WITH_A))) {                                                \
-            if ((WITH_A) && !(DBG & 1)) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); \
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                       \
+            if ((WITH_A) && !(DBG & 1)) DTLR_WAITCNT(8, 0); \
+            else DTLR_WAITCNT(0, 0);                       \
             __builtin_amdgcn_s_barrier();                                                          \
         }                                                                                          \
         /* b1 of this chunk for this lane's accumulator rows: register 4 q + e <-> hidden 32 C + 8 q + 4 hh + e */ \
@@ -216,8 +180,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
         __builtin_amdgcn_sched_barrier(0);                                                         \
         if (WITH_A) {                                                                              \
             _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                       \
-                if (q == 0) { f3_mma_v0(w[0], xf[0][0], he[0]); f3_mma_v0(w[0], xf[0][1], he[1]); } \
-                else { f3_mma_v(w[q & 3], xf[q][0], he[0]); f3_mma_v(w[q & 3], xf[q][1], he[1]); } \
+                if (q == 0) { mma32_v0(w[0], xf[0][0], he[0]); mma32_v0(w[0], xf[0][1], he[1]); } \
+                else { mma32_v(w[q & 3], xf[q][0], he[0]); mma32_v(w[q & 3], xf[q][1], he[1]); } \
                 if ((DBG & 4) && !(FIRST)) {}                                                      \
                 else if (q < 12) w[q & 3] = F3_W1F((C), q + 4);                                    \
                 else if (WITH_B) w[q & 3] = F3_W2F((C) - 1, q - 12);                               \
@@ -232,8 +196,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(
         }                                                                                          \
         if (WITH_B) {                                                                              \
             _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                       \
-                yacc[q & 7][0] = f3_mma(w[q & 3], hb[q >> 3][0], yacc[q & 7][0]);                  \
-                yacc[q & 7][1] = f3_mma(w[q & 3], hb[q >> 3][1], yacc[q & 7][1]);                  \
+                yacc[q & 7][0] = mma32(w[q & 3], hb[q >> 3][0], yacc[q & 7][0]);                  \
+                yacc[q & 7][1] = mma32(w[q & 3], hb[q >> 3][1], yacc[q & 7][1]);                  \
                 if ((DBG & 4) && (WITH_A)) {}                                                      \
                 else if (q < 12) w[q & 3] = F3_W2F((C) - 1, q + 4);                                \
                 else if (WITH_A) w[q & 3] = F3_W1F((C) + 1, q - 12);                               \

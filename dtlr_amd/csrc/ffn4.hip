@@ -41,17 +41,12 @@
 // would make it pay: the loads one step earlier (the slot's last chunk step without its redundant phase A) and the three passes cut into the
 // other slot's MFMA groups like the H epilogue; both need more step bodies, and every extra body in this kernel has cost a fight with the
 // register allocator (see the notes below).  The slot lag is a kernel argument (2 steps; half a period measured 10 us slower).
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
 
-typedef __attribute__((ext_vector_type(8))) h16_hw_t f4_h16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f4_f32x16_t;
-typedef __attribute__((ext_vector_type(4))) unsigned f4_u32x4_t;
-typedef __attribute__((ext_vector_type(2))) float f4_f32x2_t;
-typedef __attribute__((ext_vector_type(4))) float f4_f32x4_t;
-typedef __attribute__((address_space(3))) const f4_f32x4_t* f4_lds4_t;
-typedef __attribute__((address_space(3))) const f4_f32x2_t* f4_lds2_t;
+typedef __attribute__((address_space(3))) const f32x4_t* f4_lds4_t;
+typedef __attribute__((address_space(3))) const f32x2_hw_t* f4_lds2_t;
 
 constexpr int F4_NS = 4;                                    // ring stages
 constexpr int F4_RING = 16384;                              // one W1 (or W2) chunk image: 16 fragments of 1 KB
@@ -62,12 +57,6 @@ constexpr int F4_PRM_OFF = F4_B1_OFF + (F4_MAX_DFF + 32) * 4;      // b2 | gamma
 constexpr int F4_LDS = F4_PRM_OFF + 3 * 256 * 4;
 constexpr int F4_NW = 2;                                    // weight-fragment registers: refilled F4_NW MFMA groups ahead of use
 
-// LDS-DMA with a wave-uniform base in SGPRs, a 32-bit per-lane byte offset and an immediate that applies to both addresses
-template <int OFF> __device__ __forceinline__ void f4_glds16so(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(OFF) : "memory");
-}
 // Every instruction that writes one of the long-lived register arrays (Y^T accumulators, H^T accumulators, X^T fragments) is inline asm with a
 // TIED read-write operand: each array element is then ONE live range for the whole kernel, which the register allocator places once.  (As
 // builtins / plain assignments the seeding step and the loads DEFINE new values that meet the old ones at the loop header; with every register
@@ -75,44 +64,36 @@ template <int OFF> __device__ __forceinline__ void f4_glds16so(const void* sbase
 // every step.)  The price: the hazard recogniser does not see these MFMAs.  The uses are arranged so that no software wait states are owed:
 // an accumulator is re-used as SrcC no earlier than two MFMAs later (8 in phase B), its first VALU reader comes at least two issued MFMAs (H^T)
 // or a whole step (Y^T) later, and MFMA A / B operands come from ds_read / long-lived registers (waited for by the compiler: asm inputs).
-__device__ __forceinline__ void f4_mma_a(const uint4& a, const uint4& b, f4_f32x16_t& c) {         // c += a b, accumulator in the AGPRs
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+__device__ __forceinline__ void f4_mma_a(const uint4& a, const uint4& b, f32x16_t& c) {         // c += a b, accumulator in the AGPRs
+    const u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
     asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, %0" : "+a"(c) : "v"(av), "v"(bv));
 }
-__device__ __forceinline__ void f4_mma_a0(const uint4& a, const uint4& b, f4_f32x16_t& c) {        // c = a b
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+__device__ __forceinline__ void f4_mma_a0(const uint4& a, const uint4& b, f32x16_t& c) {        // c = a b
+    const u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
     asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, 0" : "+a"(c) : "v"(av), "v"(bv));
 }
 // Elements 4 q .. 4 q + 3 of an accumulator tile, read through asm with an "a" operand: the element extraction then stays an AGPR
 // sub-register.  (Plain C++ element reads put the tile's virtual register into a VALU instruction, i.e. into the VGPR class: hipcc copied
 // all eight 16-register tiles of a slot to VGPRs at once -- 128 registers it does not have -- spilled twelve X^T fragments around every
 // epilogue step and left a vmcnt(0) wait for their reload inside the chunk loop that follows.)
-__device__ __forceinline__ f4_f32x4_t f4_acc_read4(const f4_f32x16_t& c, int q) {
+__device__ __forceinline__ f32x4_t f4_acc_read4(const f32x16_t& c, int q) {
     float x0, x1, x2, x3;
     const float s0 = c[4 * q], s1 = c[4 * q + 1], s2 = c[4 * q + 2], s3 = c[4 * q + 3];
     asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
                  : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(x3) : "a"(s0), "a"(s1), "a"(s2), "a"(s3));
-    return f4_f32x4_t{x0, x1, x2, x3};
+    return f32x4_t{x0, x1, x2, x3};
 }
 // the same two for the seeding step, whose operands (identity fragments built by VALU instructions, X^T fragments the compiler may have just
 // re-assembled with v_mov) can be VALU results: a VALU write of an MFMA source register needs wait states in front of the MFMA, which
 // nobody inserts for asm (first build: `v_or_b32 v167, ...` directly in front of `v_mfma ..., v[164:167], ...` -- the first tile of slot 0
 // came out as garbage)
-__device__ __forceinline__ void f4_mma_a_pad(const uint4& a, const uint4& b, f4_f32x16_t& c) {
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+__device__ __forceinline__ void f4_mma_a_pad(const uint4& a, const uint4& b, f32x16_t& c) {
+    const u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
     asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, %0" : "+a"(c) : "v"(av), "v"(bv));
 }
-__device__ __forceinline__ void f4_mma_a0_pad(const uint4& a, const uint4& b, f4_f32x16_t& c) {
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
+__device__ __forceinline__ void f4_mma_a0_pad(const uint4& a, const uint4& b, f32x16_t& c) {
+    const u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
     asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, 0" : "+a"(c) : "v"(av), "v"(bv));
-}
-__device__ __forceinline__ void f4_mma_v0(const uint4& a, const uint4& b, f4_f32x16_t& c) {        // the same in ARCHITECTURAL VGPRs (H^T: read by the VALU)
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));     // a true definition: H^T is dead between a step's last slice and this
-}
-__device__ __forceinline__ void f4_mma_v(const uint4& a, const uint4& b, f4_f32x16_t& c) {
-    const f4_u32x4_t av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_32x32x16_" DTLR_H16_ASM_SUFFIX " %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
 }
 // LDS byte address of this lane's slice of the parameter tables, made opaque in every epilogue slice: computed outside, hipcc hoists one
 // address register per table row out of the tile loop (~100 registers) and spills them
@@ -121,7 +102,6 @@ __device__ __forceinline__ unsigned f4_prm_addr(unsigned lds_base, int hh) {
     asm volatile("" : "+v"(a));
     return a;
 }
-__device__ __forceinline__ float f4_relu(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_huge_valf()); }
 
 __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
     const uint16_t* __restrict__ X, const uint16_t* __restrict__ W1p, const float* __restrict__ b1,
@@ -149,8 +129,8 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
     const char* W1b = reinterpret_cast<const char*>(W1p) + wave * 4096;
     const char* W2b = reinterpret_cast<const char*>(W2p) + wave * 4096;
     const unsigned my1 = lds_base + (unsigned)wave * 4096u, my2 = my1 + F4_W2_OFF;
-#define F4_PIECE1(CI, ST, U) f4_glds16so<(U) * 1024>(W1b + (long)(CI) * F4_RING, vlane, my1 + (unsigned)(ST) * F4_RING);
-#define F4_PIECE2(CI, ST, U) f4_glds16so<(U) * 1024>(W2b + (long)(CI) * F4_RING, vlane, my2 + (unsigned)(ST) * F4_RING);
+#define F4_PIECE1(CI, ST, U) glds16so<(U) * 1024>(W1b + (long)(CI) * F4_RING, vlane, my1 + (unsigned)(ST) * F4_RING);
+#define F4_PIECE2(CI, ST, U) glds16so<(U) * 1024>(W2b + (long)(CI) * F4_RING, vlane, my2 + (unsigned)(ST) * F4_RING);
 #define F4_ISSUE1(CI, ST) { F4_PIECE1(CI, ST, 0) F4_PIECE1(CI, ST, 1) F4_PIECE1(CI, ST, 2) F4_PIECE1(CI, ST, 3) }
 #define F4_ISSUE2(CI, ST) { F4_PIECE2(CI, ST, 0) F4_PIECE2(CI, ST, 1) F4_PIECE2(CI, ST, 2) F4_PIECE2(CI, ST, 3) }
     // prologue: W1(0) W1(1) | W2(0) W2(1) W1(2); step s then issues W2(s + 2), W1(s + 3)   (indices = stream steps; chunk = step mod nchunk;
@@ -185,14 +165,14 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
         prm[256 + threadIdx.x] = gamma[threadIdx.x];
         prm[512 + threadIdx.x] = beta[threadIdx.x];
     }
-    f4_f32x16_t yacc[8][2];
+    f32x16_t yacc[8][2];
 #pragma unroll
     for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) yacc[ct][tt][i] = 0.f;
-    f4_f32x16_t he[2];
+    f32x16_t he[2];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -206,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
     float mean[2] = {0.f, 0.f}, rstd[2] = {0.f, 0.f};
 #define F4_W1F(ST, Q) (*reinterpret_cast<const uint4*>(f4_smem + (ST) * F4_RING + (Q) * 1024 + lane * 16))
 #define F4_W2F(ST, Q) (*reinterpret_cast<const uint4*>(f4_smem + F4_W2_OFF + (ST) * F4_RING + (Q) * 1024 + lane * 16))
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int q = 0; q < F4_NW; ++q) w[q] = F4_W1F(0, q);
@@ -216,7 +196,7 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
 #define F4_HEPI(P, BB)                                                                             \
     {                                                                                              \
         const int tt_ = (P) >> 3, p_ = (P) & 7;                                                    \
-        const uint32_t v_ = pack_bf16x2(f4_relu(he[tt_][2 * p_] + (BB).x), f4_relu(he[tt_][2 * p_ + 1] + (BB).y)); \
+        const uint32_t v_ = pack_bf16x2(relu_med3(he[tt_][2 * p_] + (BB).x), relu_med3(he[tt_][2 * p_ + 1] + (BB).y)); \
         uint4& d_ = (p_ < 4) ? hb[0][tt_] : hbn[tt_];                                              \
         if ((p_ & 3) == 0) d_.x = v_;                                                              \
         else if ((p_ & 3) == 1) d_.y = v_;                                                         \
@@ -239,8 +219,8 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
         (void)b1c_; (void)bnx_;                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                         \
         _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                           \
-            if (q == 0) { if (C0) f4_mma_v0(w[0], xf[0][0], he[0]); if (C1) f4_mma_v0(w[0], xf[0][1], he[1]); } \
-            else { if (C0) f4_mma_v(w[q % F4_NW], xf[q][0], he[0]); if (C1) f4_mma_v(w[q % F4_NW], xf[q][1], he[1]); } \
+            if (q == 0) { if (C0) mma32_v0(w[0], xf[0][0], he[0]); if (C1) mma32_v0(w[0], xf[0][1], he[1]); } \
+            else { if (C0) mma32_v(w[q % F4_NW], xf[q][0], he[0]); if (C1) mma32_v(w[q % F4_NW], xf[q][1], he[1]); } \
             if (!((C0) && (C1))) asm volatile("s_nop 1");       /* one slot: the same accumulator back to back */ \
             if (q < 16 - F4_NW) w[q % F4_NW] = F4_W1F(st, q + F4_NW); else w[q % F4_NW] = F4_W2F(stp, q - (16 - F4_NW)); \
             if (q == 1) F4_PIECE2(c2, st2, 0) else if (q == 5) F4_PIECE2(c2, st2, 1) else if (q == 9) F4_PIECE2(c2, st2, 2) else if (q == 13) F4_PIECE2(c2, st2, 3) \
@@ -288,26 +268,26 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
             hb[0][TT] = make_uint4(0u, 0u, 0u, 0u); hb[1][TT] = make_uint4(0u, 0u, 0u, 0u); hbn[TT] = make_uint4(0u, 0u, 0u, 0u); \
         } else if ((KIND) == 1) {                                                                  \
             const unsigned pa_ = f4_prm_addr(lds_base, hh);                                        \
-            f4_f32x2_t s2 = {0.f, 0.f};                                                            \
+            f32x2_hw_t s2 = {0.f, 0.f};                                                            \
             _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                                       \
                 _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                    \
-                    const f4_f32x4_t bb = *(f4_lds4_t)(size_t)(pa_ + 4u * (32 * ct + 8 * q));              \
-                    const f4_f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q);          \
-                    s2 += (f4_f32x2_t{y4.x, y4.y} + f4_f32x2_t{bb.x, bb.y}) + (f4_f32x2_t{y4.z, y4.w} + f4_f32x2_t{bb.z, bb.w}); \
+                    const f32x4_t bb = *(f4_lds4_t)(size_t)(pa_ + 4u * (32 * ct + 8 * q));              \
+                    const f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q);          \
+                    s2 += (f32x2_hw_t{y4.x, y4.y} + f32x2_hw_t{bb.x, bb.y}) + (f32x2_hw_t{y4.z, y4.w} + f32x2_hw_t{bb.z, bb.w}); \
                 }                                                                                  \
             float sum = s2[0] + s2[1];                                                             \
             sum += __shfl_xor(sum, 32, 64);                                                        \
             mean[TT] = sum * (1.0f / 256.0f);                                                      \
         } else if ((KIND) == 2) {                                                                  \
             const unsigned pa_ = f4_prm_addr(lds_base, hh);                                        \
-            const f4_f32x2_t m2 = {mean[TT], mean[TT]};                                            \
-            f4_f32x2_t q2 = {0.f, 0.f};                                                            \
+            const f32x2_hw_t m2 = {mean[TT], mean[TT]};                                            \
+            f32x2_hw_t q2 = {0.f, 0.f};                                                            \
             _Pragma("unroll") for (int ct = 0; ct < 8; ++ct)                                       \
                 _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                    \
-                    const f4_f32x4_t bb = *(f4_lds4_t)(size_t)(pa_ + 4u * (32 * ct + 8 * q));              \
-                    const f4_f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q);          \
-                    const f4_f32x2_t d0 = (f4_f32x2_t{y4.x, y4.y} + f4_f32x2_t{bb.x, bb.y}) - m2;  \
-                    const f4_f32x2_t d1 = (f4_f32x2_t{y4.z, y4.w} + f4_f32x2_t{bb.z, bb.w}) - m2;  \
+                    const f32x4_t bb = *(f4_lds4_t)(size_t)(pa_ + 4u * (32 * ct + 8 * q));              \
+                    const f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q);          \
+                    const f32x2_hw_t d0 = (f32x2_hw_t{y4.x, y4.y} + f32x2_hw_t{bb.x, bb.y}) - m2;  \
+                    const f32x2_hw_t d1 = (f32x2_hw_t{y4.z, y4.w} + f32x2_hw_t{bb.z, bb.w}) - m2;  \
                     q2 += d0 * d0 + d1 * d1;                                                       \
                 }                                                                                  \
             float sq = q2[0] + q2[1];                                                              \
@@ -315,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
             rstd[TT] = rsqrtf(sq * (1.0f / 256.0f) + eps);                                         \
         } else if ((KIND) == 3 || (KIND) == 4) {                                                   \
             const unsigned pa_ = f4_prm_addr(lds_base, hh);                                        \
-            const f4_f32x2_t m2 = {mean[TT], mean[TT]}, r2 = {rstd[TT], rstd[TT]};                 \
+            const f32x2_hw_t m2 = {mean[TT], mean[TT]}, r2 = {rstd[TT], rstd[TT]};                 \
             const long tok = F4_TOK(TT, NTILE);                                                    \
             /* a wave whose 32 rows all lie past M (ragged last tile) issues no stores and counts none */ \
             const bool wave_rows = __builtin_amdgcn_readfirstlane((int)(tok - j < (long)M)) != 0;  \
@@ -329,15 +309,15 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
                             uint32_t pk[2][2];                                                     \
                             _Pragma("unroll") for (int qo = 0; qo < 2; ++qo) {                     \
                                 const int q = 2 * qp + qo, ch = 32 * ct + 8 * q;                   \
-                                const f4_f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q); \
+                                const f32x4_t y4 = f4_acc_read4(yacc[ct][TT], q); \
                                 _Pragma("unroll") for (int e = 0; e < 2; ++e) {                    \
                                     /* one channel pair at a time (few live temporaries: every register of the file is in use here) */ \
-                                    const f4_f32x2_t ga = *(f4_lds2_t)(size_t)(pa_ + 4u * (256 + ch + 2 * e)); \
-                                    const f4_f32x2_t be = *(f4_lds2_t)(size_t)(pa_ + 4u * (512 + ch + 2 * e)); \
-                                    const f4_f32x2_t bb = *(f4_lds2_t)(size_t)(pa_ + 4u * (ch + 2 * e));   \
-                                    const f4_f32x2_t g2 = ga * r2;                                 \
-                                    const f4_f32x2_t cc = be + (bb - m2) * g2;                     \
-                                    const f4_f32x2_t o2 = (e ? f4_f32x2_t{y4.z, y4.w} : f4_f32x2_t{y4.x, y4.y}) * g2 + cc; \
+                                    const f32x2_hw_t ga = *(f4_lds2_t)(size_t)(pa_ + 4u * (256 + ch + 2 * e)); \
+                                    const f32x2_hw_t be = *(f4_lds2_t)(size_t)(pa_ + 4u * (512 + ch + 2 * e)); \
+                                    const f32x2_hw_t bb = *(f4_lds2_t)(size_t)(pa_ + 4u * (ch + 2 * e));   \
+                                    const f32x2_hw_t g2 = ga * r2;                                 \
+                                    const f32x2_hw_t cc = be + (bb - m2) * g2;                     \
+                                    const f32x2_hw_t o2 = (e ? f32x2_hw_t{y4.z, y4.w} : f32x2_hw_t{y4.x, y4.y}) * g2 + cc; \
                                     pk[qo][e] = pack_bf16x2(o2[0], o2[1]);                         \
                                     __builtin_amdgcn_sched_barrier(0);                             \
                                 }                                                                  \
@@ -364,9 +344,9 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
     {                                                                                              \
         if (s > 0) {   /* the pieces of step s - 2 have landed (mine); then everybody's */        \
             const int allow = post2 + tot1;                                                        \
-            if (allow <= 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");            \
-            else if (allow <= 24) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory");     \
-            else asm volatile("s_waitcnt vmcnt(40) lgkmcnt(0)" ::: "memory");                      \
+            if (allow <= 8) DTLR_WAITCNT(8, 0);            \
+            else if (allow <= 24) DTLR_WAITCNT(24, 0);     \
+            else DTLR_WAITCNT(40, 0);                      \
             __builtin_amdgcn_s_barrier();                                                          \
         }                                                                                          \
         st = s & 3; stp = (s + 3) & 3; stn = (s + 1) & 3; st2 = (s + 2) & 3;                       \
@@ -395,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
             F4_SPECIAL(TT, 4, I_EPI, stc_)                                                         \
         }                                                                                          \
         /* the rows have landed: only the stores issued after them may stay in flight */          \
-        if (stc_) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+        if (stc_) DTLR_WAITCNT_VM(16); else DTLR_WAITCNT_VM(0); \
         F4_SPECIAL(TT, 0, I_NEXT, stc_)                                                            \
         e_ = 16 + stc_;                                                                            \
         } else e_ = 0;                                                                             \
@@ -462,7 +442,7 @@ __global__ __launch_bounds__(256, 1) void ffn4_bf16_kernel(
         F4_SPECIAL_STEP(1, true, np - 1, np, e)
         (void)e;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    DTLR_WAITCNT_VM(0);
 #undef F4_SPECIAL_STEP
 #undef F4_PRELOAD
 #undef F4_END

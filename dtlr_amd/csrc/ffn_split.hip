@@ -23,13 +23,9 @@
 //     lane ^ 32 each), fp32 stores of 16 bytes per lane.
 // 96 MFMAs of 32 cycles per chunk and wave = 3072 matrix cycles against 64 fragment reads (64 KB per wave, 256 KB per CU: 2048 LDS
 // cycles) and 64 KB of DMA writes: the matrix pipe is the bound, the LDS port follows at ~80%.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 fs_f16x8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 fs_f16x2_t;
-typedef __attribute__((ext_vector_type(16))) float fs_f32x16_t;
 
 // experiment hooks (tools/experiments/ffn_split_bench.py builds this file alone with -DFS_STANDALONE and these): fragment look-ahead in groups,
 // and timing ablations whose results are garbage (1: no weight DMA in the chunk loop, 2: no wait / barrier per chunk, 4: no fragment reads)
@@ -56,28 +52,12 @@ constexpr int FS_PAD = 2;                                    // zero chunks behi
 constexpr int FS_PRM_OFF = FS_B1_OFF + (FS_MAX_DFF + 32 * (FS_PAD + 1)) * 4;       // b2 | gamma | beta (3 x 256 floats)
 constexpr int FS_LDS = FS_PRM_OFF + 3 * 256 * 4;
 
-// LDS-DMA: wave-uniform global base in SGPRs + per-lane byte offset; OFF (< 4096) applies to both the global address and the LDS destination
-template <int OFF> __device__ __forceinline__ void fs_glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(OFF) : "memory");
-}
-// (the immediate must be a compile-time constant: in the unrolled group loops `k` folds to one)
+// one 1 KB piece of a chunk image (glds16so's immediate must be a compile-time constant: in the unrolled group loops `k` folds to one)
 __device__ __forceinline__ void fs_piece(int k, const void* sbase, unsigned voff, unsigned lds_dst) {
-    if (k == 0) fs_glds16<0>(sbase, voff, lds_dst);
-    else if (k == 1) fs_glds16<1024>(sbase, voff, lds_dst);
-    else if (k == 2) fs_glds16<2048>(sbase, voff, lds_dst);
-    else fs_glds16<3072>(sbase, voff, lds_dst);
-}
-__device__ __forceinline__ fs_f32x16_t fs_mma(const uint4& a, const uint4& b, fs_f32x16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(fs_f16x8_t, a), __builtin_bit_cast(fs_f16x8_t, b), c, 0, 0, 0);
-}
-// 2 fp32 -> packed fp16 hi pair and lo pair (lo = fp16(x - hi): the difference is exact, both conversions round to nearest even)
-__device__ __forceinline__ void fs_split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-    const fs_f16x2_t a = __builtin_convertvector(f32x2_hw_t{x0, x1}, fs_f16x2_t);
-    const fs_f16x2_t b = __builtin_convertvector(f32x2_hw_t{x0 - (float)a[0], x1 - (float)a[1]}, fs_f16x2_t);
-    hi = __builtin_bit_cast(uint32_t, a);
-    lo = __builtin_bit_cast(uint32_t, b);
+    if (k == 0) glds16so<0>(sbase, voff, lds_dst);
+    else if (k == 1) glds16so<1024>(sbase, voff, lds_dst);
+    else if (k == 2) glds16so<2048>(sbase, voff, lds_dst);
+    else glds16so<3072>(sbase, voff, lds_dst);
 }
 
 // Schedule.  Iteration c (after the barrier that ends iteration c - 1: W1(c + 1) and W2(c) are visible, he_cur = phase A of chunk c):
@@ -139,8 +119,8 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
             const float4 a = *reinterpret_cast<const float4*>(xr + s * 16), c = *reinterpret_cast<const float4*>(xr + s * 16 + 4);
-            fs_split2(a.x, a.y, xh[s].x, xl[s].x); fs_split2(a.z, a.w, xh[s].y, xl[s].y);
-            fs_split2(c.x, c.y, xh[s].z, xl[s].z); fs_split2(c.z, c.w, xh[s].w, xl[s].w);
+            split2_f16(a.x, a.y, xh[s].x, xl[s].x); split2_f16(a.z, a.w, xh[s].y, xl[s].y);
+            split2_f16(c.x, c.y, xh[s].z, xl[s].z); split2_f16(c.z, c.w, xh[s].w, xl[s].w);
         }
     }
     {   // b1 table (zero behind d_ff: the padding chunks) and the epilogue parameters
@@ -152,7 +132,7 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
         prm[256 + threadIdx.x] = gamma[threadIdx.x];
         prm[512 + threadIdx.x] = beta[threadIdx.x];
     }
-    fs_f32x16_t yacc[8], he0, he1, zero16;
+    f32x16_t yacc[8], he0, he1, zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { zero16[r] = 0.f; he0[r] = 0.f; he1[r] = 0.f; }
 #pragma unroll
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
 #define FS_F1(ST, G, PART) (*reinterpret_cast<const uint4*>(lbase + (ST) * FS_IMG + (PART) * 16384 + (G) * 1024))
 #define FS_F2(ST, F, PART) (*reinterpret_cast<const uint4*>(lbase + FS_W2_OFF + (ST) * FS_IMG + (PART) * 16384 + (F) * 1024))
 
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();
     {   // ---- prologue: phase A of chunk 0 (W1 ring stage 0) ------------------------------------------------------------------------
         constexpr int NB = FS_LA + 1;
@@ -172,9 +152,9 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             if (g + FS_LA < 16) { fh[(g + FS_LA) % NB] = FS_F1(0, g + FS_LA, 0); fl[(g + FS_LA) % NB] = FS_F1(0, g + FS_LA, 1); }
-            he0 = fs_mma(fh[g % NB], xl[g], g == 0 ? zero16 : he0);
-            he0 = fs_mma(fl[g % NB], xh[g], he0);
-            he0 = fs_mma(fh[g % NB], xh[g], he0);
+            he0 = mma32_f16(fh[g % NB], xl[g], g == 0 ? zero16 : he0);
+            he0 = mma32_f16(fl[g % NB], xh[g], he0);
+            he0 = mma32_f16(fh[g % NB], xh[g], he0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -197,16 +177,16 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
             else if (g + FS_LA < 16) { fh[(g + FS_LA) % NB] = FS_F1(st1_, g + FS_LA, 0); fl[(g + FS_LA) % NB] = FS_F1(st1_, g + FS_LA, 1); } \
             else if (g + FS_LA < 32) { fh[(g + FS_LA) % NB] = FS_F2(st2_, g + FS_LA - 16, 0); fl[(g + FS_LA) % NB] = FS_F2(st2_, g + FS_LA - 16, 1); } \
             if (g < 16) {                                                                          \
-                HN = fs_mma(fh[g % NB], xl[g], g == 0 ? zero16 : HN);                              \
-                HN = fs_mma(fl[g % NB], xh[g], HN);                                                \
-                HN = fs_mma(fh[g % NB], xh[g], HN);                                                \
+                HN = mma32_f16(fh[g % NB], xl[g], g == 0 ? zero16 : HN);                              \
+                HN = mma32_f16(fl[g % NB], xh[g], HN);                                                \
+                HN = mma32_f16(fh[g % NB], xh[g], HN);                                                \
                 if (!(FS_DBG & 1)) { if (g < 8) FS_PIECE(0, (C) + 2, st2_, g) else FS_PIECE(1, (C) + 1, st1_, g - 8) } \
                 if (g >= 2 && g < 10 && (g & 1) == 0) {        /* H epilogue slice q: registers 4 q .. 4 q + 3 of HC */ \
                     const int q = (g - 2) >> 1;                                                    \
                     const float v0 = fmaxf(HC[4 * q] + bq_[q].x, 0.f), v1 = fmaxf(HC[4 * q + 1] + bq_[q].y, 0.f); \
                     const float v2 = fmaxf(HC[4 * q + 2] + bq_[q].z, 0.f), v3 = fmaxf(HC[4 * q + 3] + bq_[q].w, 0.f); \
                     uint32_t h0, l0, h1, l1;                                                       \
-                    fs_split2(v0, v1, h0, l0); fs_split2(v2, v3, h1, l1);                          \
+                    split2_f16(v0, v1, h0, l0); split2_f16(v2, v3, h1, l1);                          \
                     if (q == 0) { hsh[0].x = h0; hsh[0].y = h1; hsl[0].x = l0; hsl[0].y = l1; }    \
                     else if (q == 1) { hsh[0].z = h0; hsh[0].w = h1; hsl[0].z = l0; hsl[0].w = l1; } \
                     else if (q == 2) { hsh[1].x = h0; hsh[1].y = h1; hsl[1].x = l0; hsl[1].y = l1; } \
@@ -214,14 +194,14 @@ __global__ __launch_bounds__(256, 1) void ffn_split_kernel(
                 }                                                                                  \
             } else {                                                                               \
                 const int ct = (g - 16) & 7, s = (g - 16) >> 3;                                    \
-                yacc[ct] = fs_mma(fh[g % NB], hsl[s], yacc[ct]);                                   \
-                yacc[ct] = fs_mma(fl[g % NB], hsh[s], yacc[ct]);                                   \
-                yacc[ct] = fs_mma(fh[g % NB], hsh[s], yacc[ct]);                                   \
+                yacc[ct] = mma32_f16(fh[g % NB], hsl[s], yacc[ct]);                                   \
+                yacc[ct] = mma32_f16(fl[g % NB], hsh[s], yacc[ct]);                                   \
+                yacc[ct] = mma32_f16(fh[g % NB], hsh[s], yacc[ct]);                                   \
             }                                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }                                                                                          \
         if (!(FS_DBG & 2)) {                                                                       \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                            \
+            DTLR_WAITCNT(0, 0);                            \
             __builtin_amdgcn_s_barrier();                                                          \
         }                                                                                          \
     }

@@ -24,37 +24,21 @@
 // Fused prologue: A + A2 (query = src + pos, deformable_transformer.py:797-812).
 // Fused epilogue: + bias, ReLU, zero masked rows (value.masked_fill, ms_deform_attn.py:95-96),
 //                 + residual, ReLU-after-residual (ResNet bottleneck tail), output fp32 or bf16.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
 
 namespace dtlr {
 
-typedef __attribute__((ext_vector_type(8))) h16_hw_t bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 constexpr int BM = 128, BN = 128, SLAB = 128, LDS_ROW = 128;      // bytes (rows unpadded; XOR-swizzled 16-byte chunks)
 constexpr int TILE_BYTES = BM * LDS_ROW;                           // one operand tile in LDS
 
-// Staging loads are issued through inline asm so that hipcc does not count them: across the loop
-// back-edge its waitcnt pass is conservative and drains vmcnt to 0 at the first LDS store of the older
-// register set, which collapses the two-slab prefetch distance to one.  The kernel places the counted
-// wait itself (cdna_hip_programming.md section 5.7, form iii): one `s_waitcnt vmcnt(N)` + sched_barrier
-// before the LDS stores of a set, N = number of staging loads issued after that set's loads.  vmcnt
-// also counts the epilogue's stores/loads issued in between; that only makes the wait stricter.
-__device__ __forceinline__ uint4 asm_load16(const char* p) {
-    uint4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
+// Staging loads are load16 (uncounted: gfx950_prims.h note 2): across the loop back-edge hipcc's waitcnt
+// pass is conservative and drains vmcnt to 0 at the first LDS store of the older register set, which
+// collapses the two-slab prefetch distance to one.  The kernel places the counted wait itself: one
+// wait_vm<N> before the LDS stores of a set, N = number of staging loads issued after that set's loads.
+// vmcnt also counts the epilogue's stores/loads issued in between; that only makes the wait stricter.
 
 // Ablation switches for timing experiments (tools/profile_kernels.py --only gemm_ablate): only honoured when
 // the library is built with -DDTLR_GEMM_ABLATION, so the production hot loop carries no extra branches.
@@ -106,7 +90,7 @@ template <> struct GT<uint16_t> {   // bf16
         return make_uint4(o[0], o[1], o[2], o[3]);
     }
     static __device__ __forceinline__ void mma(const uint4& w, const uint4& x, f32x4_t& acc) {
-        acc = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), acc, 0, 0, 0);
+        acc = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(h16x8_t, w), __builtin_bit_cast(h16x8_t, x), acc, 0, 0, 0);
     }
 };
 template <> struct GT<float> {
@@ -156,8 +140,6 @@ template <typename T> __device__ __forceinline__ int lds_swz(int r) {
     if constexpr (kSplit<T>) return (r & 7) ^ ((r & 1) << 2);
     else return r & 7;
 }
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 template <> struct GT<f32s_t> {
     static constexpr int BK = 32;
     static __device__ __forceinline__ uint4 add(uint4 a, uint4 b) { return GT<float>::add(a, b); }
@@ -501,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(
     // would be copied before its data lands.  The A2 and fp32-conv variants keep compiler-counted loads.
     constexpr bool ASM_LOADS = !HAS_A2 && !(CONV && sizeof(T) == 4);
     constexpr int LOADS_PER_SLAB = 8;
-#define LD16(PTR) (ASM_LOADS ? asm_load16(PTR) : *reinterpret_cast<const uint4*>(PTR))
+#define LD16(PTR) (ASM_LOADS ? load16(PTR) : *reinterpret_cast<const uint4*>(PTR))
 #define GLOAD1(S, I, OFF)                                                                          \
     rw##S##I = LD16(Wb + w_off[I] + (OFF));                                                        \
     if (CONV) {                                                                                    \
@@ -547,7 +529,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(
     SET_LOAD_TILE(t_begin)
     int lkt = 0, ltile = t_begin;            // slab whose loads were issued last
     GLOAD(P, 0)
-    if (ASM_LOADS) wait_vmcnt<0>();
+    if (ASM_LOADS) wait_vm<0>();
     LSTORE(P, 0)                             // slab 0 -> stage 0
     if (total > 1) ADVANCE_AND_LOAD(Q)       // slab 1 in flight in set Q
     __syncthreads();
@@ -582,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(
         }                                                                                          \
         if (s + 1 < total && !ABLATE(DBG_NO_LDS)) {                                                \
             /* slab s+1's loads are older than the LOADS_PER_SLAB loads of slab s+2 (if any were issued) */ \
-            if (ASM_LOADS) { if (s + 2 < total) wait_vmcnt<LOADS_PER_SLAB>(); else wait_vmcnt<0>(); } \
+            if (ASM_LOADS) { if (s + 2 < total) wait_vm<LOADS_PER_SLAB>(); else wait_vm<0>(); } \
             LSTORE(SS, 1 - (CUR))                                                                  \
         }                                                                                          \
         __syncthreads();                                                                           \
@@ -681,7 +663,7 @@ __global__ __launch_bounds__(512, HAS_A2 ? 2 : 4) void gemm_ws_kernel(
         uint4 raP0, raP1, raP2, raP3, rwP0, rwP1, rwP2, rwP3, rbP0, rbP1, rbP2, rbP3;
         uint4 raQ0, raQ1, raQ2, raQ3, rwQ0, rwQ1, rwQ2, rwQ3, rbQ0, rbQ1, rbQ2, rbQ3;
         (void)rbP0; (void)rbP1; (void)rbP2; (void)rbP3; (void)rbQ0; (void)rbQ1; (void)rbQ2; (void)rbQ3;
-#define WS_LD16(PTR) (ASM ? asm_load16(PTR) : *reinterpret_cast<const uint4*>(PTR))
+#define WS_LD16(PTR) (ASM ? load16(PTR) : *reinterpret_cast<const uint4*>(PTR))
 #define WS_GLOAD1(S, I, OFF)                                                                       \
         rw##S##I = WS_LD16(Wb + w_off[I] + (OFF));                                                 \
         if (CONV) {                                                                                \
@@ -727,7 +709,7 @@ __global__ __launch_bounds__(512, HAS_A2 ? 2 : 4) void gemm_ws_kernel(
         TL_INIT(1)
         WS_SET_TILE(t_begin)
         WS_GLOAD(P, 0)
-        if (ASM) wait_vmcnt<0>();
+        if (ASM) wait_vm<0>();
         WS_LSTORE(P, 0)                                          // slab 0 -> stage 0
         if (total > 1) WS_ADVANCE_AND_LOAD(Q)                    // slab 1 -> set Q (odd slabs)
         if (total > 2) WS_ADVANCE_AND_LOAD(P)                    // slab 2 -> set P (even slabs)
@@ -737,7 +719,7 @@ __global__ __launch_bounds__(512, HAS_A2 ? 2 : 4) void gemm_ws_kernel(
         while (i < total) {
             if (i + 1 < total) {                                 // i even: slab i+1 is odd -> set Q, stage 1
                 TL_EV(1)
-                if (ASM) { if (i + 2 < total) wait_vmcnt<NLOAD>(); else wait_vmcnt<0>(); }
+                if (ASM) { if (i + 2 < total) wait_vm<NLOAD>(); else wait_vm<0>(); }
                 TL_EV(2)
                 if (!ABLATE(DBG_NO_LDS)) WS_LSTORE(Q, 1)
                 TL_EV(3)
@@ -749,7 +731,7 @@ __global__ __launch_bounds__(512, HAS_A2 ? 2 : 4) void gemm_ws_kernel(
             if (++i >= total) break;
             if (i + 1 < total) {                                 // i odd: slab i+1 is even -> set P, stage 0
                 TL_EV(1)
-                if (ASM) { if (i + 2 < total) wait_vmcnt<NLOAD>(); else wait_vmcnt<0>(); }
+                if (ASM) { if (i + 2 < total) wait_vm<NLOAD>(); else wait_vm<0>(); }
                 TL_EV(2)
                 if (!ABLATE(DBG_NO_LDS)) WS_LSTORE(P, 0)
                 TL_EV(3)
@@ -899,16 +881,16 @@ __global__ __launch_bounds__(TallCfg<TBN>::NT, TBN == 64 ? ((kSplit<T> && CONV) 
             const int kh = CONV ? tap / cp.KW : 0, kw = CONV ? tap % cp.KW : 0;
             const long coff = (long)(kt % slabs_per_tap) * SLAB;
 #pragma unroll
-            for (int i = 0; i < WL; ++i) rw[S][i] = asm_load16(Wb + w_off[i] + off);
+            for (int i = 0; i < WL; ++i) rw[S][i] = load16(Wb + w_off[i] + off);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (CONV) {
                     const int hi = hi0[i] + kh, wi = wi0[i] + kw;
                     const bool ok = hi >= 0 && hi < cp.H && wi >= 0 && wi < cp.W;
                     const long po = ((long)hi * cp.W + wi) * cp.Cin * (long)sizeof(T) + coff;
-                    ra[S][i] = asm_load16(ok ? Ab + a_off[i] + po : zero_line);
+                    ra[S][i] = load16(ok ? Ab + a_off[i] + po : zero_line);
                 } else {
-                    ra[S][i] = asm_load16(Ab + a_off[i] + off);
+                    ra[S][i] = load16(Ab + a_off[i] + off);
                 }
             }
         };
@@ -942,7 +924,7 @@ __global__ __launch_bounds__(TallCfg<TBN>::NT, TBN == 64 ? ((kSplit<T> && CONV) 
         constexpr int NLOAD = 8 + WL;
         set_tile(t_begin);
         gload(P_{}, 0);
-        wait_vmcnt<0>();
+        wait_vm<0>();
         lstore(P_{}, 0);
         if (total > 1) advance_and_load(Q_{});
         if (total > 2) advance_and_load(P_{});
@@ -950,14 +932,14 @@ __global__ __launch_bounds__(TallCfg<TBN>::NT, TBN == 64 ? ((kSplit<T> && CONV) 
         int i = 0;
         while (i < total) {
             if (i + 1 < total) {
-                if (i + 2 < total) wait_vmcnt<NLOAD>(); else wait_vmcnt<0>();
+                if (i + 2 < total) wait_vm<NLOAD>(); else wait_vm<0>();
                 lstore(Q_{}, 1);
                 if (i + 3 < total) advance_and_load(Q_{});
             }
             __syncthreads();
             if (++i >= total) break;
             if (i + 1 < total) {
-                if (i + 2 < total) wait_vmcnt<NLOAD>(); else wait_vmcnt<0>();
+                if (i + 2 < total) wait_vm<NLOAD>(); else wait_vm<0>();
                 lstore(P_{}, 0);
                 if (i + 3 < total) advance_and_load(P_{});
             }

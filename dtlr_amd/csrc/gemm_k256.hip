@@ -20,29 +20,15 @@
 // unpadded batch, see engine.py); rows with row_mask[m] != 0 written as zeros (value.masked_fill, ms_deform_attn.py:95-96);
 // C row stride ldc >= N (column slices of a wider matrix: the six decoder value projections share one [T, 1536] buffer).
 // HBM-bound by construction: per CU and 64-token tile 64..80 KB of traffic against 64..96 MFMAs per wave.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t k2_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float k2_f32x4_t;
 
 constexpr int K2_TOK = 64;                       // tokens per stage
 constexpr int K2_STAGE = K2_TOK * 512;           // 32 KB
 constexpr int K2_NS = 4;                         // ring stages
 constexpr int K2_LDS = K2_NS * K2_STAGE;         // 128 KB: one workgroup per CU
 
-// LDS-DMA, 64 lanes x 16 bytes: destination = wave-uniform LDS byte address + 16 * lane (counted by hand: section 5.7)
-__device__ __forceinline__ void k2_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ uint4 k2_load16(const void* p) {
-    uint4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
 __device__ __forceinline__ uint2 k2_load8(const void* p) {
     uint2 r;
     asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
@@ -63,14 +49,6 @@ __device__ __forceinline__ unsigned k2_load_u8(const void* p) {
     unsigned r;
     asm volatile("global_load_ubyte %0, %1, off" : "=v"(r) : "v"(p) : "memory");
     return r;
-}
-__device__ __forceinline__ k2_f32x4_t k2_mma(const uint4& a, const uint4& b, k2_f32x4_t c) {
-    return DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(k2_bf16x8_t, a), __builtin_bit_cast(k2_bf16x8_t, b), c, 0, 0, 0);
-}
-template <int N> __device__ __forceinline__ void k2_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // NRT = 16-channel row tiles per wave: N = 128 * NRT (2 -> 256, 3 -> 384).  Wp: the weight in fragment order (dtlr_k256_pack:
@@ -112,7 +90,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
         for (int u = 0; u < 4; ++u) {
             const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
             const long tok = min(row0(t) + tt8 * 8 + dr, (long)M - 1);
-            k2_glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * K2_STAGE + j * 1024));
+            glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * K2_STAGE + j * 1024));
         }
     };
     // prologue: up to three tiles in flight, then the resident operand
@@ -123,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) wf[rt][ks] = k2_load16(Wp + ((long)((wave * NRT + rt) * 8 + ks) * 64 + lane) * 8);
+        for (int ks = 0; ks < 8; ++ks) wf[rt][ks] = load16(Wp + ((long)((wave * NRT + rt) * 8 + ks) * 64 + lane) * 8);
     float4 bv[NRT];
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
@@ -171,9 +149,9 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
         }
     };
     if constexpr (RES) load_row_operands(t_begin, rs, msk);
-    k2_wait<0>();
+    wait_vm<0>();
 
-    k2_f32x4_t acc[NRT][4];
+    f32x4_t acc[NRT][4];
     unsigned zero_bits = 0;
     auto seed_accumulators = [&]() {                          // RES: acc <- bias + residual row; padding flags -> bits
 #pragma unroll
@@ -181,7 +159,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
             if (row_mask && msk[tt]) zero_bits |= 1u << tt;
 #pragma unroll
             for (int rt = 0; rt < NRT; ++rt)
-                acc[rt][tt] = k2_f32x4_t{bv[rt].x + h16_lo(rs[rt][tt].x), bv[rt].y + h16_hi(rs[rt][tt].x),
+                acc[rt][tt] = f32x4_t{bv[rt].x + h16_lo(rs[rt][tt].x), bv[rt].y + h16_hi(rs[rt][tt].x),
                                          bv[rt].z + h16_lo(rs[rt][tt].y), bv[rt].w + h16_hi(rs[rt][tt].y)};
         }
     };
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
 #pragma unroll
             for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = k2_f32x4_t{0.f, 0.f, 0.f, 0.f};
+                for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         }
         const unsigned char* sb = k2_smem + slot * K2_STAGE;
 #pragma unroll
@@ -214,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
 #pragma unroll
             for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = k2_mma(wf[rt][ks], bf[tt], acc[rt][tt]);
+                for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = mma16(wf[rt][ks], bf[tt], acc[rt][tt]);
         }
         // ---- epilogue: bias, broadcast residual, padding rows, bf16, paired 16-byte stores ---------------------------------
         if constexpr (RES) {
@@ -224,7 +202,7 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
         } else {
             zero_bits = 0;
             if (row_mask) {
-                if (i + 3 < nt) k2_wait<4>(); else k2_wait<0>();
+                if (i + 3 < nt) wait_vm<4>(); else wait_vm<0>();
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) if (msk[tt]) zero_bits |= 1u << tt;
             }
@@ -259,14 +237,14 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
             // iterations).  Older, hence landed: the next tile's row operands and DMA groups i + 1, i + 2.  A ragged tile (fewer
             // stores than E) is always a workgroup's last, where nothing is waited for.
             zero_bits = 0;
-            if (i + 3 < nt) k2_wait<E + 4>();
-            else if (i + 1 < nt) k2_wait<E>();
+            if (i + 3 < nt) wait_vm<E + 4>();
+            else if (i + 1 < nt) wait_vm<E>();
             if (i + 1 < nt) seed_accumulators();
         } else {
             // tile i + 1 must have landed (mine) before the next barrier: everything but the two newest DMA groups and the
             // stores issued around them may stay in flight
-            if (i + 3 < nt) k2_wait<2 * E + 8 <= 16 ? 16 : 24>();
-            else k2_wait<0>();
+            if (i + 3 < nt) wait_vm<2 * E + 8 <= 16 ? 16 : 24>();
+            else wait_vm<0>();
         }
     }
 }
@@ -306,8 +284,8 @@ __global__ __launch_bounds__(512, 2) void proj_ln_k256_kernel(
         for (int u = 0; u < 4; ++u) {
             const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
             const long tok = min((long)t * K2_TOK + tt8 * 8 + dr, (long)M - 1);
-            k2_glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * PK_STAGE + j * 1024));
-            k2_glds16(R + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * PK_STAGE + K2_STAGE + j * 1024));
+            glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * PK_STAGE + j * 1024));
+            glds16(R + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * PK_STAGE + K2_STAGE + j * 1024));
         }
     };
     issue(t_begin, 0);
@@ -315,12 +293,12 @@ __global__ __launch_bounds__(512, 2) void proj_ln_k256_kernel(
 #pragma unroll
     for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) wf[e][ks] = k2_load16(Wp + ((long)((wave * 2 + e) * 8 + ks) * 64 + lane) * 8);
+        for (int ks = 0; ks < 8; ++ks) wf[e][ks] = load16(Wp + ((long)((wave * 2 + e) * 8 + ks) * 64 + lane) * 8);
     const int ch = 32 * wave + 8 * g;                         // this lane's 8 consecutive channels
     float bs[8], gm[8], bt[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { bs[e] = bias[ch + e]; gm[e] = gamma[ch + e]; bt[e] = beta[ch + e]; }
-    k2_wait<0>();
+    wait_vm<0>();
     const unsigned rd0 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + ((g ^ (n & 7)) * 16));
     const unsigned rd1 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + (((4 + g) ^ (n & 7)) * 16));
     // residual chunk of this lane: 16-byte chunk 4 wave + g of the row -> block kb = wave >> 1, chunk c = 4 (wave & 1) + g
@@ -333,11 +311,11 @@ __global__ __launch_bounds__(512, 2) void proj_ln_k256_kernel(
         const int slot = i & 1;
         __builtin_amdgcn_s_barrier();                         // tile i published; stage (i + 1) & 1 and the LN buffers are free
         if (i + 1 < nt) issue(t + 1, slot ^ 1);
-        k2_f32x4_t acc[2][4];
+        f32x4_t acc[2][4];
 #pragma unroll
         for (int e = 0; e < 2; ++e)
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) acc[e][tt] = k2_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int tt = 0; tt < 4; ++tt) acc[e][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const unsigned char* sb = k2_smem + slot * PK_STAGE;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
@@ -348,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void proj_ln_k256_kernel(
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) acc[e][tt] = k2_mma(wf[e][ks], bf[tt], acc[e][tt]);
+                for (int tt = 0; tt < 4; ++tt) acc[e][tt] = mma16(wf[e][ks], bf[tt], acc[e][tt]);
         }
         // v = acc + bias + residual ; first pass: row sums
         float v[4][8], sm[4];
@@ -394,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void proj_ln_k256_kernel(
                     make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7]));
         }
         // my pieces of tile i + 1 must have landed before the next barrier; this tile's 4 stores may stay in flight
-        if (i + 1 < nt) k2_wait<4>(); else k2_wait<0>();
+        if (i + 1 < nt) wait_vm<4>(); else wait_vm<0>();
     }
 }
 

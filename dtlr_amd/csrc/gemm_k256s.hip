@@ -25,13 +25,9 @@
 //   * MODE 1: the residual is read in the accumulator layout (16 bytes per lane and tile), the row statistics are exchanged between the eight
 //     waves through LDS (two passes: mean, then centred squares -- the fp32 LayerNorm kernels' own arithmetic), one extra barrier pair per tile.
 // HBM-bound by construction: 128 KB (MODE 0) / 192 KB (MODE 1) of traffic per 64-token tile against 192 MFMAs and ~700 VALU per wave.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 ks_f16x8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 ks_f16x2_t;
-typedef __attribute__((ext_vector_type(4))) float ks_f32x4_t;
 
 constexpr int KS_TOK = 64;                        // tokens per tile
 constexpr int KS_STAGE = KS_TOK * 1024;           // 64 KB: 64 fp32 rows of 256 (raw), and the same size for their hi | lo fp16 image
@@ -39,21 +35,6 @@ constexpr int KS_IMG_OFF = KS_STAGE;
 constexpr int KS_STAT_OFF = 2 * KS_STAGE;         // statistics exchange: [64 tokens][8 waves] floats
 constexpr int KS_PAR_OFF = KS_STAT_OFF + KS_TOK * 8 * 4;   // bias | gamma | beta, [3][256] floats (read in the epilogue: no VGPRs across the MFMAs)
 constexpr int KS_LDS = KS_PAR_OFF + 3 * 256 * 4;
-
-__device__ __forceinline__ void ks_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ ks_f32x4_t ks_mma(const uint4& a, const uint4& b, ks_f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ks_f16x8_t, a), __builtin_bit_cast(ks_f16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void ks_split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-    const ks_f16x2_t a = __builtin_convertvector(f32x2_hw_t{x0, x1}, ks_f16x2_t);
-    const ks_f16x2_t b = __builtin_convertvector(f32x2_hw_t{x0 - (float)a[0], x1 - (float)a[1]}, ks_f16x2_t);
-    hi = __builtin_bit_cast(uint32_t, a);
-    lo = __builtin_bit_cast(uint32_t, b);
-}
 
 // Wp: [2 parts (hi, lo)][8 waves][2 row tiles][8 k-steps][64 lanes][8 halves]: lane (m = l & 15, g = l >> 4) <- W[32 wave + 16 rt + m][32 ks + 8 g + e]
 // MASK (compile time): row_mask is read.  (As a run-time `if (row_mask)` around the flag loads and around their pin, hipcc's wait insertion
@@ -80,7 +61,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
         for (int u = 0; u < 8; ++u) {
             const int row = 8 * wave + u;
             const long tok = min((long)t * KS_TOK + row, (long)M - 1);
-            ks_glds16(A + tok * 256 + lane * 4, lds_base + (unsigned)(row * 1024));
+            glds16(A + tok * 256 + lane * 4, lds_base + (unsigned)(row * 1024));
         }
     };
     issue(t_begin);
@@ -118,8 +99,8 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
         // my rows of tile t have landed.  The counter is in order and the only requests younger than that DMA group are the previous tile's
         // 8 stores per lane, which stay in flight: vmcnt(8), not a write acknowledgement per tile (first tile: nothing younger, vmcnt(0)).
         // (A tail tile issues fewer stores, but it is the last of its workgroup: nothing waits after it.)
-        if (t == t_begin) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        else              asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+        if (t == t_begin) DTLR_WAITCNT(0, 0);
+        else              DTLR_WAITCNT(8, 0);
         if constexpr (MASK) {                                            // padded batch: this tile's flags, pinned BEFORE the DMA issue (a
 #pragma unroll                                                           // wait after it would drain the DMA; this one drains the stores)
             for (int tt = 0; tt < 4; ++tt) mk[tt] = row_mask[min((long)t * KS_TOK + 16 * tt + n, (long)M - 1)];
@@ -129,7 +110,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
         float4 raw[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) raw[u] = *reinterpret_cast<const float4*>(ks_smem + (8 * wave + u) * 1024 + lane * 16);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
         if constexpr (MASK) {
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) asm volatile("" : "+v"(mk[tt]));
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
         if (t + 1 < t_end) issue(t + 1);
         uint2 sh[8], sl[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { ks_split2(raw[u].x, raw[u].y, sh[u].x, sl[u].x); ks_split2(raw[u].z, raw[u].w, sh[u].y, sl[u].y); }
+        for (int u = 0; u < 8; ++u) { split2_f16(raw[u].x, raw[u].y, sh[u].x, sl[u].x); split2_f16(raw[u].z, raw[u].w, sh[u].y, sl[u].y); }
         __builtin_amdgcn_s_barrier();                                    // every wave has finished reading the previous image
         // ---- 8 bytes of hi at chunk (L >> 1) ^ (row & 15), half L & 1; lo 512 B further
 #pragma unroll
@@ -147,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
             *reinterpret_cast<uint2*>(dst) = sh[u];
             *reinterpret_cast<uint2*>(dst + 512) = sl[u];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
         __builtin_amdgcn_s_barrier();                                    // the image is complete
         float4 rr[4][2];
         if constexpr (MODE == 1) {                                       // this tile's residual rows, in the accumulator layout: requested here,
@@ -159,11 +140,11 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
             }
         }
         const unsigned char* tile = ks_smem + KS_IMG_OFF;
-        ks_f32x4_t acc[2][4];
+        f32x4_t acc[2][4];
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = ks_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int tt = 0; tt < 4; ++tt) acc[rt][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) {
             const int row = 16 * tt + n;                                 // row & 15 == n
@@ -174,9 +155,9 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
                 const uint4 xl = *reinterpret_cast<const uint4*>(rp + 512 + (((4 * ks + g) ^ n) * 16));
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
-                    acc[rt][tt] = ks_mma(wh[rt][ks], xl, acc[rt][tt]);
-                    acc[rt][tt] = ks_mma(wl[rt][ks], xh, acc[rt][tt]);
-                    acc[rt][tt] = ks_mma(wh[rt][ks], xh, acc[rt][tt]);
+                    acc[rt][tt] = mma16_f16(wh[rt][ks], xl, acc[rt][tt]);
+                    acc[rt][tt] = mma16_f16(wl[rt][ks], xh, acc[rt][tt]);
+                    acc[rt][tt] = mma16_f16(wh[rt][ks], xh, acc[rt][tt]);
                 }
             }
         }
@@ -208,7 +189,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_kernel(
                 for (int rt = 0; rt < 2; ++rt) {
                     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
                     if constexpr (MODE == 1) r = rr[tt][rt];
-                    if constexpr (MODE == 2 && MASK) { if (mk[tt] != 0) acc[rt][tt] = ks_f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+                    if constexpr (MODE == 2 && MASK) { if (mk[tt] != 0) acc[rt][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
                     v[tt][rt][0] = acc[rt][tt][0] + bv[rt].x + r.x; v[tt][rt][1] = acc[rt][tt][1] + bv[rt].y + r.y;
                     v[tt][rt][2] = acc[rt][tt][2] + bv[rt].z + r.z; v[tt][rt][3] = acc[rt][tt][3] + bv[rt].w + r.w;
                     ps[tt] += (v[tt][rt][0] + v[tt][rt][1]) + (v[tt][rt][2] + v[tt][rt][3]);
@@ -298,10 +279,6 @@ constexpr int KP_IMG_OFF = 2 * KP_STAGE;
 constexpr int KP_PAR_OFF = 4 * KP_STAGE;
 constexpr int KP_LDS = KP_PAR_OFF + 256 * 4;
 
-template <int N> __device__ __forceinline__ void kp_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
 template <bool MASK>
 __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* __restrict__ A, KsMulti P, int M, int tiles_per_wg, int res_rows, int n_img)
 {
@@ -335,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
         for (int u = 0; u < 4; ++u) {
             const int row = 4 * wave + u;
             const long tok = min(r0 + row, (long)M - 1);
-            ks_glds16(A + tok * 256 + lane * 4, dst + (unsigned)(row * 1024));
+            glds16(A + tok * 256 + lane * 4, dst + (unsigned)(row * 1024));
         }
     };
     // split my 4 raw rows (registers) into image slot `slot`: 8 bytes of hi at chunk (L >> 1) ^ (row & 15), half L & 1; lo 512 B further
@@ -343,8 +320,8 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             uint2 sh, sl;
-            ks_split2(raw[u].x, raw[u].y, sh.x, sl.x);
-            ks_split2(raw[u].z, raw[u].w, sh.y, sl.y);
+            split2_f16(raw[u].x, raw[u].y, sh.x, sl.x);
+            split2_f16(raw[u].z, raw[u].w, sh.y, sl.y);
             const int row = 4 * wave + u;
             unsigned char* dst = ks_smem + KP_IMG_OFF + slot * KP_STAGE + row * 1024 + (((lane >> 1) ^ (row & 15)) * 16) + (lane & 1) * 8;
             *reinterpret_cast<uint2*>(dst) = sh;
@@ -354,7 +331,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
     auto read_raw = [&](float4 (&raw)[4], int slot) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) raw[u] = *reinterpret_cast<const float4*>(ks_smem + slot * KP_STAGE + (4 * wave + u) * 1024 + lane * 16);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
     };
 
     issue(t_begin);
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
         }
     float* par = reinterpret_cast<float*>(ks_smem + KP_PAR_OFF);
     if (threadIdx.x < 256) par[threadIdx.x] = (S.bias && (int)threadIdx.x < S.n_valid) ? S.bias[threadIdx.x] : 0.f;
-    kp_wait<0>();                                                    // both prologue tiles and the resident operand have landed
+    DTLR_WAITCNT_VM(0);                                                    // both prologue tiles and the resident operand have landed
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
@@ -385,7 +362,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
         read_raw(raw, t_begin & 1);
         if (t_begin + 2 < t_end) issue(t_begin + 2);
         split_store(raw, t_begin & 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
     }
     __builtin_amdgcn_s_barrier();
 
@@ -397,7 +374,7 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
         if constexpr (MASK) {                                        // this tile's flags (compiler-counted loads: pinned before anything I count)
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) mk[tt] = row_mask[min(r0 + 16 * tt + n, (long)M - 1)];
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            DTLR_WAITCNT_VM(0);
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) asm volatile("" : "+v"(mk[tt]));
         }
@@ -408,9 +385,9 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
             // iterations follow the prologue's vmcnt(0) (the DMA they need was covered by it or by iteration 0's own wait below).
             if constexpr (!MASK) {
                 const bool d2 = t + 2 < t_end;
-                if (t - t_begin < 2) { if (t == t_begin) {} else kp_wait<0>(); }
-                else if (has_r) { if (d2) kp_wait<16>(); else kp_wait<12>(); }
-                else            { if (d2) kp_wait<12>(); else kp_wait<8>(); }
+                if (t - t_begin < 2) { if (t == t_begin) {} else DTLR_WAITCNT_VM(0); }
+                else if (has_r) { if (d2) DTLR_WAITCNT_VM(16); else DTLR_WAITCNT_VM(12); }
+                else            { if (d2) DTLR_WAITCNT_VM(12); else DTLR_WAITCNT_VM(8); }
             }
             read_raw(raw, (t + 1) & 1);
         }
@@ -421,20 +398,20 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
             for (int tt = 0; tt < 2; ++tt) {
                 const long rrow = n_img > 0 ? rbase + 16 * tt + n : min(rbase + 16 * tt + n, (long)M - 1);
 #pragma unroll
-                for (int rt = 0; rt < 2; ++rt)
+                for (int rt = 0; rt < 2; ++rt)      // load16 of gfx950_prims.h, open-coded: through the helper's return value this kernel's registers are allocated differently
                     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rr[tt][rt]) : "v"(R + rrow * ldr + wave * 32 + rt * 16 + 4 * g) : "memory");
             }
         }
         if (dma3) issue(t + 3);
         if (nxt) split_store(raw, (t + 1) & 1);
 
-        ks_f32x4_t acc[2][2];                                        // the accumulators, then (bias / residual / ReLU / mask applied in place) the output values
+        f32x4_t acc[2][2];                                        // the accumulators, then (bias / residual / ReLU / mask applied in place) the output values
         if (active) {
             const unsigned char* tile = ks_smem + KP_IMG_OFF + (t & 1) * KP_STAGE;
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = ks_f32x4_t{0.f, 0.f, 0.f, 0.f};
+                for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
                 uint4 xh[2], xl[2];
@@ -447,22 +424,22 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = ks_mma(wh[rt][ks], xl[tt], acc[rt][tt]);
+                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = mma16_f16(wh[rt][ks], xl[tt], acc[rt][tt]);
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = ks_mma(wl[rt][ks], xh[tt], acc[rt][tt]);
+                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = mma16_f16(wl[rt][ks], xh[tt], acc[rt][tt]);
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = ks_mma(wh[rt][ks], xh[tt], acc[rt][tt]);
+                    for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = mma16_f16(wh[rt][ks], xh[tt], acc[rt][tt]);
             }
             float4 bv[2];
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) bv[rt] = *reinterpret_cast<const float4*>(par + wave * 32 + rt * 16 + 4 * g);
             if (has_r) {
                 // the residual rows have landed: the only requests younger than them are tile t + 3's 4 DMA rows (if issued)
-                if (dma3) kp_wait<4>(); else kp_wait<0>();
+                if (dma3) DTLR_WAITCNT_VM(4); else DTLR_WAITCNT_VM(0);
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -473,10 +450,10 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
                 const bool masked = MASK && mk[tt] != 0;
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
-                    ks_f32x4_t v = acc[rt][tt] + ks_f32x4_t{bv[rt].x, bv[rt].y, bv[rt].z, bv[rt].w};
-                    if (has_r) v += ks_f32x4_t{__uint_as_float(rr[tt][rt].x), __uint_as_float(rr[tt][rt].y), __uint_as_float(rr[tt][rt].z), __uint_as_float(rr[tt][rt].w)};
-                    if (relu) v = ks_f32x4_t{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-                    if (masked) v = ks_f32x4_t{0.f, 0.f, 0.f, 0.f};
+                    f32x4_t v = acc[rt][tt] + f32x4_t{bv[rt].x, bv[rt].y, bv[rt].z, bv[rt].w};
+                    if (has_r) v += f32x4_t{__uint_as_float(rr[tt][rt].x), __uint_as_float(rr[tt][rt].y), __uint_as_float(rr[tt][rt].z), __uint_as_float(rr[tt][rt].w)};
+                    if (relu) v = f32x4_t{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                    if (masked) v = f32x4_t{0.f, 0.f, 0.f, 0.f};
                     acc[rt][tt] = v;
                 }
             }
@@ -492,26 +469,26 @@ __global__ __launch_bounds__(512, 1) void gemm_k256s_multi_kernel(const float* _
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt)             // row 16 tt + n, 16-byte chunk (8 wave + 4 rt + g) ^ n: conflict-free for the 16 rows of a group
-                    *reinterpret_cast<ks_f32x4_t*>(stg + (16 * tt + n) * 1024 + (((8 * wave + 4 * rt + g) ^ n) * 16)) = acc[rt][tt];
+                    *reinterpret_cast<f32x4_t*>(stg + (16 * tt + n) * 1024 + (((8 * wave + 4 * rt + g) ^ n) * 16)) = acc[rt][tt];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
         __builtin_amdgcn_s_barrier();
         {
             // 4 store instructions per wave and iteration, every wave (the hand-counted waits rely on it; only the ragged last tile of the whole
             // problem issues fewer, in its workgroup's last iteration)
             const int rw = 4 * wave;
-            const ks_f32x4_t o0 = *reinterpret_cast<const ks_f32x4_t*>(stg + (rw + 0) * 1024 + ((lane ^ ((rw + 0) & 15)) * 16));
-            const ks_f32x4_t o1 = *reinterpret_cast<const ks_f32x4_t*>(stg + (rw + 1) * 1024 + ((lane ^ ((rw + 1) & 15)) * 16));
-            const ks_f32x4_t o2 = *reinterpret_cast<const ks_f32x4_t*>(stg + (rw + 2) * 1024 + ((lane ^ ((rw + 2) & 15)) * 16));
-            const ks_f32x4_t o3 = *reinterpret_cast<const ks_f32x4_t*>(stg + (rw + 3) * 1024 + ((lane ^ ((rw + 3) & 15)) * 16));
+            const f32x4_t o0 = *reinterpret_cast<const f32x4_t*>(stg + (rw + 0) * 1024 + ((lane ^ ((rw + 0) & 15)) * 16));
+            const f32x4_t o1 = *reinterpret_cast<const f32x4_t*>(stg + (rw + 1) * 1024 + ((lane ^ ((rw + 1) & 15)) * 16));
+            const f32x4_t o2 = *reinterpret_cast<const f32x4_t*>(stg + (rw + 2) * 1024 + ((lane ^ ((rw + 2) & 15)) * 16));
+            const f32x4_t o3 = *reinterpret_cast<const f32x4_t*>(stg + (rw + 3) * 1024 + ((lane ^ ((rw + 3) & 15)) * 16));
             const bool colok = 4 * lane < S.n_valid;
             float* crow = C + (r0 + rw) * ldc + 4 * lane;
-            if (colok && r0 + rw + 0 < M) *reinterpret_cast<ks_f32x4_t*>(crow) = o0;
-            if (colok && r0 + rw + 1 < M) *reinterpret_cast<ks_f32x4_t*>(crow + ldc) = o1;
-            if (colok && r0 + rw + 2 < M) *reinterpret_cast<ks_f32x4_t*>(crow + 2L * ldc) = o2;
-            if (colok && r0 + rw + 3 < M) *reinterpret_cast<ks_f32x4_t*>(crow + 3L * ldc) = o3;
+            if (colok && r0 + rw + 0 < M) *reinterpret_cast<f32x4_t*>(crow) = o0;
+            if (colok && r0 + rw + 1 < M) *reinterpret_cast<f32x4_t*>(crow + ldc) = o1;
+            if (colok && r0 + rw + 2 < M) *reinterpret_cast<f32x4_t*>(crow + 2L * ldc) = o2;
+            if (colok && r0 + rw + 3 < M) *reinterpret_cast<f32x4_t*>(crow + 3L * ldc) = o3;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        DTLR_WAITCNT_LGKM(0);
         __builtin_amdgcn_s_barrier();                                // image(t + 1) complete; image(t) and raw(t + 1) no longer read
     }
 }
@@ -526,7 +503,7 @@ __global__ __launch_bounds__(256) void k256s_pack_kernel(const float* __restrict
     const float* src = w + (long)(32 * wave + 16 * rt + m) * 256 + 32 * ks + 8 * g;
     uint32_t h[4], l[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ks_split2(src[2 * e], src[2 * e + 1], h[e], l[e]);
+    for (int e = 0; e < 4; ++e) split2_f16(src[2 * e], src[2 * e + 1], h[e], l[e]);
     *reinterpret_cast<uint4*>(out + (long)i * 8) = make_uint4(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<uint4*>(out + (8192L + i) * 8) = make_uint4(l[0], l[1], l[2], l[3]);
 }

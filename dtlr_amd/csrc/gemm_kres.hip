@@ -15,34 +15,12 @@
 //     one 16-byte store per token and pair, no lane exchange;
 //   * ONE barrier per 64 tokens (publishes the tile, frees the stage the next DMA overwrites); DMA groups and stores share the in-order
 //     vmcnt counter and are counted by hand so that a tile's stores are never waited for.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <stdlib.h>
 
 namespace dtlr {
 
-typedef __attribute__((ext_vector_type(8))) h16_hw_t kr_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float kr_f32x4_t;
-
 constexpr int KR_TOK = 64;
-
-__device__ __forceinline__ void kr_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ uint4 kr_load16(const void* p) {
-    uint4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ kr_f32x4_t kr_mma(const uint4& a, const uint4& b, kr_f32x4_t c) {
-    return DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(kr_bf16x8_t, a), __builtin_bit_cast(kr_bf16x8_t, b), c, 0, 0, 0);
-}
-template <int N> __device__ __forceinline__ void kr_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // KB = K / 64 (128-byte k blocks per token row), NP = row-tile pairs per wave (output columns per launch column = 256 NP), NS = stages.
 // Wp: fragment order, block (((slice * 8 + wave) * NP + p) * 2 + e) * KS + ks (KS = 2 KB k-steps of 32) = 64 lanes x 8 elements.
@@ -118,13 +96,13 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
         for (int kb = 0; kb < KB; ++kb) {
             const uint16_t* src = A + tok * K + kb * 64 + dc * 8;
             if constexpr (CAT) src = kb < KB1 ? A + tok * (64 * KB1) + kb * 64 + dc * 8 : A2 + tok2 * (64 * (KB - KB1)) + (kb - KB1) * 64 + dc * 8;
-            kr_glds16(src, dst + (unsigned)((wave * KB + kb) * 1024));
+            glds16(src, dst + (unsigned)((wave * KB + kb) * 1024));
         }
         if constexpr (HAS_R) {
             const long rrow = n_img > 0 ? (long)(t / n_img) * KR_TOK + wave * 8 + dr : tok;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
-                kr_glds16(R + rrow * (long)(n_img > 0 ? n_valid : ld) + col0 + nb * 64 + dc * 8, dst + (unsigned)(A_BYTES + (wave * NB + nb) * 1024));
+                glds16(R + rrow * (long)(n_img > 0 ? n_valid : ld) + col0 + nb * 64 + dc * 8, dst + (unsigned)(A_BYTES + (wave * NB + nb) * 1024));
         }
     };
     // prologue: NS - 1 tiles in flight, then the resident operand
@@ -138,7 +116,7 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
         for (int e = 0; e < 2; ++e)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                wf[p][e][ks] = kr_load16(Wp + ((long)((((int)blockIdx.y * 8 + wave) * NP + p) * 2 + e) * KS + ks) * 512 + lane * 8);
+                wf[p][e][ks] = load16(Wp + ((long)((((int)blockIdx.y * 8 + wave) * NP + p) * 2 + e) * KS + ks) * 512 + lane * 8);
     float bs[NP][8];
 #pragma unroll
     for (int p = 0; p < NP; ++p)
@@ -154,12 +132,12 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
-                for (int ks = 0; ks < 8; ++ks) w2f[j][e][ks] = kr_load16(Wp2 + ((long)(q2 * 2 + e) * 8 + ks) * 512 + lane * 8);
+                for (int ks = 0; ks < 8; ++ks) w2f[j][e][ks] = load16(Wp2 + ((long)(q2 * 2 + e) * 8 + ks) * 512 + lane * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) bs2[j][e] = bias2 ? bias2[32 * q2 + 8 * g + e] : 0.f;
         }
     }
-    kr_wait<0>();
+    wait_vm<0>();
 
     // B-fragment of token tile tt, k-step ks: row group 2 tt + (n >> 3), block ks >> 1, row n & 7, slot (4 (ks & 1) + g) ^ (n & 7)
     const unsigned rdA = (unsigned)((n >> 3) * KB * 1024 + (n & 7) * 128);
@@ -183,13 +161,13 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
         __builtin_amdgcn_s_barrier();                         // tile i published by every wave; stage (i - 1) % NS no longer read
         if (i + NS - 1 < nt) issue(t + NS - 1, (i + NS - 1) % NS);
 
-        kr_f32x4_t acc[NP][2][4];
+        f32x4_t acc[NP][2][4];
 #pragma unroll
         for (int p = 0; p < NP; ++p)
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
-                for (int tt = 0; tt < 4; ++tt) acc[p][e][tt] = kr_f32x4_t{0.f, 0.f, 0.f, 0.f};
+                for (int tt = 0; tt < 4; ++tt) acc[p][e][tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const unsigned char* sb = kr_smem + slot * STAGE;
         const long trow = row0(t);
 #pragma unroll
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
 #pragma unroll
                 for (int e = 0; e < 2; ++e)
 #pragma unroll
-                    for (int tt = 0; tt < 4; ++tt) acc[p][e][tt] = kr_mma(wf[p][e][ks], bf[tt], acc[p][e][tt]);
+                    for (int tt = 0; tt < 4; ++tt) acc[p][e][tt] = mma16(wf[p][e][ks], bf[tt], acc[p][e][tt]);
             }
         }
         // ---- epilogue: + bias + residual (one 16-byte LDS read), ReLU, one 16-byte store per token and pair ---------------------
@@ -235,19 +213,19 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
         }
         if constexpr (NQ2 > 0) {
             // ---- the next block's 1x1 convolution on the tile: C2[64, N2] = relu(Y[64, 256] W2^T + b2) -------------------------------
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            DTLR_WAITCNT_LGKM(0);
             __builtin_amdgcn_s_barrier();                     // the tile's image is complete (the next tile's is written after the next top barrier)
             asm volatile("" ::: "memory");
-            kr_f32x4_t acc2[NQ2][2];
+            f32x4_t acc2[NQ2][2];
 #pragma unroll
-            for (int j = 0; j < NQ2; ++j) { acc2[j][0] = kr_f32x4_t{0.f, 0.f, 0.f, 0.f}; acc2[j][1] = kr_f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+            for (int j = 0; j < NQ2; ++j) { acc2[j][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc2[j][1] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
                 const uint4 yb = *reinterpret_cast<const uint4*>(kr_smem + yrd + ((ks & 1) ? sw1 : sw0) + (ks >> 1) * 1024);
 #pragma unroll
                 for (int j = 0; j < NQ2; ++j) {
-                    acc2[j][0] = kr_mma(w2f[j][0][ks], yb, acc2[j][0]);
-                    acc2[j][1] = kr_mma(w2f[j][1][ks], yb, acc2[j][1]);
+                    acc2[j][0] = mma16(w2f[j][0][ks], yb, acc2[j][0]);
+                    acc2[j][1] = mma16(w2f[j][1][ks], yb, acc2[j][1]);
                 }
             }
             const long tok2 = trow + (wave & 3) * 16 + n;
@@ -265,9 +243,9 @@ __global__ __launch_bounds__(512, NQ2 > 0 ? 1 : 2) void gemm_kres_kernel(
         // and a tile's stores in each of the NS - 2 iterations after it (a ragged tile -- fewer stores -- is always a workgroup's last)
         // (zero-padded column: a wave with fewer valid pairs issues fewer stores than E and waits with vmcnt(0): stricter, never wrong)
         if (i + NS - 1 < nt) {
-            if (col0 + 32 * (wave * NP + NP) > n_valid) kr_wait<0>();
-            else kr_wait<E + (NS - 2) * (G + E)>();
-        } else kr_wait<0>();
+            if (col0 + 32 * (wave * NP + NP) > n_valid) wait_vm<0>();
+            else wait_vm<E + (NS - 2) * (G + E)>();
+        } else wait_vm<0>();
     }
 }
 

@@ -24,12 +24,9 @@
 // 48 MFMAs of 32 cycles per chunk and wave, two waves per SIMD: 3072 matrix cycles per chunk against 64 KB of fragment reads per SIMD pair.
 // Arithmetic: fp32 accumulation; per class the k order is (W_hi b, W_lo a, W_hi a) per 16-k step, k ascending -- the same three terms the
 // tiled GEMM sums as [hi | lo | hi] . [W_hi | W_hi | W_lo], in another order: results agree to fp32 rounding, not bit for bit.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t ht_h16x8_t;
-typedef __attribute__((ext_vector_type(16))) float ht_f32x16_t;
 
 constexpr int HT_CHUNK = 32768;                              // W_hi | W_lo of one 32-class chunk: 2 x 16 fragments of 1 KB
 constexpr int HT_PART = 16384;
@@ -38,15 +35,6 @@ constexpr int HT_LA = 2;                                     // fragment look-ah
 constexpr int HT_TOK = 256;                                  // tokens per workgroup of the 8-wave form (the 4-wave form: 128)
 constexpr int HT_YP = 36;                                    // row pitch (floats) of the per-wave output scratch of mode 1
 constexpr float HT_NEG = -3.0e38f;                           // bias of a padded class: never the maximum, never stored
-
-template <int OFF> __device__ __forceinline__ void ht_glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ ht_f32x16_t ht_mma(const uint4& a, const uint4& b, ht_f32x16_t c) {
-    return DTLR_MFMA_32x32x16_H16(__builtin_bit_cast(ht_h16x8_t, a), __builtin_bit_cast(ht_h16x8_t, b), c, 0, 0, 0);
-}
 
 // MODE 0: out = rowmax [M] fp32.  MODE 1: out = Y [M, N] fp32 (N % 4 == 0).  NPROD 2 | 3.  NW = 8 waves (256 tokens per workgroup) or 4
 // (128 tokens: for M too small to give every CU an 8-wave workgroup -- the decoder's 28,800 rows are 113 of those on 256 CUs, 225 of these).
@@ -73,10 +61,10 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
     {                                                                                              \
         const unsigned char* s_ = Wb + (long)(C) * HT_CHUNK;                                       \
         const unsigned d_ = mine + (unsigned)(ST) * HT_CHUNK;                                      \
-        ht_glds16<0>(s_, vlane, d_); ht_glds16<1024>(s_, vlane, d_); ht_glds16<2048>(s_, vlane, d_); ht_glds16<3072>(s_, vlane, d_); \
+        glds16so<0>(s_, vlane, d_); glds16so<1024>(s_, vlane, d_); glds16so<2048>(s_, vlane, d_); glds16so<3072>(s_, vlane, d_); \
         if constexpr (NW == 4) {                                                                   \
-            ht_glds16<0>(s_ + 4096, vlane, d_ + 4096u); ht_glds16<1024>(s_ + 4096, vlane, d_ + 4096u);                           \
-            ht_glds16<2048>(s_ + 4096, vlane, d_ + 4096u); ht_glds16<3072>(s_ + 4096, vlane, d_ + 4096u);                        \
+            glds16so<0>(s_ + 4096, vlane, d_ + 4096u); glds16so<1024>(s_ + 4096, vlane, d_ + 4096u);                           \
+            glds16so<2048>(s_ + 4096, vlane, d_ + 4096u); glds16so<3072>(s_ + 4096, vlane, d_ + 4096u);                        \
         }                                                                                          \
     }
     HT_IMAGE(0, 0)
@@ -101,14 +89,14 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
         asm volatile("" : "+v"(xa[s].x), "+v"(xa[s].y), "+v"(xa[s].z), "+v"(xa[s].w));
         if constexpr (NPROD == 3) asm volatile("" : "+v"(xb[s].x), "+v"(xb[s].y), "+v"(xb[s].z), "+v"(xb[s].w));
     }
-    ht_f32x16_t zero16;
+    f32x16_t zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
     float rmax = HT_NEG;
     const unsigned char* lbase = ht_smem + lane * 16;
 #define HT_F(ST, G, PART) (*reinterpret_cast<const uint4*>(lbase + (ST) * HT_CHUNK + (PART) * HT_PART + (G) * 1024))
 
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    DTLR_WAITCNT(0, 0);
     __builtin_amdgcn_s_barrier();                              // chunk 0 and the bias table are visible
 
     for (int c = 0; c < nchunk; ++c) {
@@ -123,13 +111,13 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
         float4 bq[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(bc + 8 * q);
-        ht_f32x16_t acc = zero16;
+        f32x16_t acc = zero16;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             if (g + HT_LA < 16) { fh[(g + HT_LA) % NB] = HT_F(st, g + HT_LA, 0); fl[(g + HT_LA) % NB] = HT_F(st, g + HT_LA, 1); }
-            if constexpr (NPROD == 3) acc = ht_mma(fh[g % NB], xb[g], acc);      // W_hi . b
-            acc = ht_mma(fl[g % NB], xa[g], acc);                      // W_lo . a
-            acc = ht_mma(fh[g % NB], xa[g], acc);                      // W_hi . a
+            if constexpr (NPROD == 3) acc = mma32(fh[g % NB], xb[g], acc);      // W_hi . b
+            acc = mma32(fl[g % NB], xa[g], acc);                      // W_lo . a
+            acc = mma32(fh[g % NB], xa[g], acc);                      // W_hi . a
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- chunk epilogue.  Lane (j, hh), register r: class 32 c + 8 (r >> 2) + 4 hh + (r & 3) of token j -------------------------
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
             for (int q = 0; q < 4; ++q) {
                 rmax = fmaxf(rmax, fmaxf(fmaxf(acc[4 * q] + bq[q].x, acc[4 * q + 1] + bq[q].y), fmaxf(acc[4 * q + 2] + bq[q].z, acc[4 * q + 3] + bq[q].w)));
             }
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // my pieces of chunk c + 1 have landed
+            DTLR_WAITCNT(0, 0);          // my pieces of chunk c + 1 have landed
         } else {
             // The accumulator layout gives a lane 4 x 16 bytes of one token's 128-byte class row, interleaved with its partner lane's: stored
             // directly, an instruction wrote 32-byte runs 29 KB apart (1.7 TB/s on the 848 MB logit matrix of the Chinese model).  The
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
             }
             __builtin_amdgcn_wave_barrier();
             // the DMA pieces of chunk c + 1 are OLDER than this chunk's four stores: the in-order counter at <= 4 means they have landed
-            asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+            DTLR_WAITCNT(4, 0);
         }
         __builtin_amdgcn_s_barrier();                          // chunk c + 1 visible to everyone; everyone has left stage st
     }
@@ -170,7 +158,7 @@ __global__ __launch_bounds__(64 * NW, 1) void head_ts_kernel(
         rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
         if (hh == 0 && tok0 + j < M) out[tok0 + j] = rmax;
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the last look-ahead DMA must have landed before the workgroup gives its LDS back
+        DTLR_WAITCNT_VM(0);       // the last look-ahead DMA must have landed before the workgroup gives its LDS back
     }
 }
 

@@ -13,7 +13,7 @@
 // 4-corner gather re-reads value ~18x (Lq*M*L*P*4*D elements); that traffic is served by L2 (the
 // per-image value map is 5.6 MB fp32 / 2.8 MB bf16, blocks of one image are launched adjacently),
 // so HBM traffic stays near compulsory -- see DESIGN.md for the measured FETCH_SIZE.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
 
@@ -388,21 +388,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 3) void msda_fused_l4p4_k
 // every lane gets the other levels' 32 values by quad-broadcast DPP.  Each corner is then ONE 16-byte load per lane and
 // the four lanes of a quad read the 64 contiguous bytes of a pixel row (coalesced -- a first attempt that gave each lane a
 // whole level of its own made every load touch a private cache line and was 30% slower than the original).
-template <int CTRL> __device__ __forceinline__ float quad_bcast_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL> __device__ __forceinline__ int quad_bcast_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-__device__ __forceinline__ void unpack8_bf16(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = h16_lo(w[i]); v[2 * i + 1] = h16_hi(w[i]); }
-}
 template <typename OT> __device__ __forceinline__ void load8f(const OT* p, float (&v)[8]);
 template <> __device__ __forceinline__ void load8f<float>(const float* p, float (&v)[8]) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
-template <> __device__ __forceinline__ void load8f<uint16_t>(const uint16_t* p, float (&v)[8]) { unpack8_bf16(*reinterpret_cast<const uint4*>(p), v); }
+template <> __device__ __forceinline__ void load8f<uint16_t>(const uint16_t* p, float (&v)[8]) { unpack8_h16(*reinterpret_cast<const uint4*>(p), v); }
 template <typename OT> __device__ __forceinline__ void load4f(const OT* p, float (&v)[4]);
 template <> __device__ __forceinline__ void load4f<float>(const float* p, float (&v)[4]) {
     const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
@@ -422,14 +413,14 @@ __device__ __forceinline__ void quad_level(const uint16_t* __restrict__ lbase, c
         float k[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const int o = quad_bcast_i<CTRL>(og[pt][c]);
-            k[c] = quad_bcast_f<CTRL>(kg[pt][c]);
+            const int o = dpp_i<CTRL, false>(og[pt][c]);
+            k[c] = dpp_f<CTRL, false>(kg[pt][c]);
             d[c] = *reinterpret_cast<const uint4*>(lbase + o);
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float v[8];
-            unpack8_bf16(d[c], v);
+            unpack8_h16(d[c], v);
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] += k[c] * v[i];
         }
@@ -461,13 +452,13 @@ __global__ __launch_bounds__(128, 2) void msda_fused_quad_bf16_kernel(
     else { const float4 t = *reinterpret_cast<const float4*>(ref + bq * 16 + 4 * p); rf[0] = t.x; rf[1] = t.y; rf[2] = t.z; rf[3] = t.w; }
     // softmax over the quad's 16 logits (ms_deform_attn.py:99-100)
     float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-    mx = fmaxf(mx, quad_bcast_f<0xB1>(mx));
-    mx = fmaxf(mx, quad_bcast_f<0x4E>(mx));
+    mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+    mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-    sum += quad_bcast_f<0xB1>(sum);
-    sum += quad_bcast_f<0x4E>(sum);
+    sum += dpp_f<0xB1, false>(sum);
+    sum += dpp_f<0x4E, false>(sum);
     const float inv = 1.0f / sum;
     // geometry of level p: element offsets of the 4 corners relative to the level base, weights = bilinear x attention
     int og[4][4];

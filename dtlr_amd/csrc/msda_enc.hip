@@ -16,7 +16,7 @@
 // arithmetic) -- correctness never depends on the offsets being small; only speed does.
 // Front end fused as in msda_fused_l4p4: softmax(16) + location arithmetic from the raw projection row.
 // Arithmetic order = the reference's (cuh:33-84,237-299): fp32 results agree to rounding.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 #include <cstdlib>
 
 namespace dtlr {
@@ -127,9 +127,6 @@ __device__ __forceinline__ float fma_mix_hi(float w, uint32_t data, float acc) {
 // 24 DPP adds.  LDS reads of a pixel row (64 B = 4 x 16-byte pieces) are issued in the rotated piece order
 // (jj + level) & 3 so that the lanes of a quad hit different 16-byte slots (same bank behaviour as the old
 // layout); the rotation cancels in the quad reduce-scatter: lane i ends up owning piece i.
-template <int CTRL> __device__ __forceinline__ float quad_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
 template <typename OT> __device__ __forceinline__ void ld8f(const OT* p, float (&v)[8]);
 template <> __device__ __forceinline__ void ld8f<float>(const float* p, float (&v)[8]) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
@@ -194,13 +191,13 @@ __device__ __forceinline__ void enc_queries_bf16(
         const float2 rf = *reinterpret_cast<const float2*>(ref + bq * 8 + 2 * p);
         // softmax over the quad's 16 logits
         float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-        mx = fmaxf(mx, quad_dpp<0xB1>(mx));
-        mx = fmaxf(mx, quad_dpp<0x4E>(mx));
+        mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+        mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-        sum += quad_dpp<0xB1>(sum);
-        sum += quad_dpp<0x4E>(sum);
+        sum += dpp_f<0xB1, false>(sum);
+        sum += dpp_f<0x4E, false>(sum);
         const float inv = 1.0f / sum;
 
         float acc[4][8];
@@ -271,7 +268,7 @@ __device__ __forceinline__ void enc_queries_bf16(
         float res[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            res[i] = (acc[0][i] + quad_dpp<0x39>(acc[3][i])) + (quad_dpp<0x4E>(acc[2][i]) + quad_dpp<0x93>(acc[1][i]));
+            res[i] = (acc[0][i] + dpp_f<0x39, false>(acc[3][i])) + (dpp_f<0x4E, false>(acc[2][i]) + dpp_f<0x93, false>(acc[1][i]));
         *reinterpret_cast<uint4*>(out + bq * MD + m * 32 + p * 8) = ET<uint16_t>::pack(res);
     }
 }
@@ -295,9 +292,6 @@ __device__ __forceinline__ uint32_t pk_fma_h2(uint32_t w2, uint32_t d, uint32_t 
 __device__ __forceinline__ uint32_t h2_splat(float k) {
     const enc_f2_t f = {k, k};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, enc_h2_t));
-}
-template <int CTRL> __device__ __forceinline__ uint32_t quad_dpp_u(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
 }
 template <typename OT> struct RowRaw;                    // the lane's slice of the projection row, as loaded (conversion deferred)
 template <> struct RowRaw<uint16_t> {
@@ -370,13 +364,13 @@ __device__ __forceinline__ void enc_queries_bf16_h(
         float off[8], lg[4];
         cur.get(off, lg);
         float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-        mx = fmaxf(mx, quad_dpp<0xB1>(mx));
-        mx = fmaxf(mx, quad_dpp<0x4E>(mx));
+        mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+        mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-        sum += quad_dpp<0xB1>(sum);
-        sum += quad_dpp<0x4E>(sum);
+        sum += dpp_f<0xB1, false>(sum);
+        sum += dpp_f<0x4E, false>(sum);
         const float inv = 1.0f / sum;
 
         uint32_t acc[4][4];
@@ -454,7 +448,7 @@ __device__ __forceinline__ void enc_queries_bf16_h(
         float res[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t t3 = quad_dpp_u<0x39>(acc[3][i]), t2 = quad_dpp_u<0x4E>(acc[2][i]), t1 = quad_dpp_u<0x93>(acc[1][i]);
+            const uint32_t t3 = dpp_u<0x39, false>(acc[3][i]), t2 = dpp_u<0x4E, false>(acc[2][i]), t1 = dpp_u<0x93, false>(acc[1][i]);
             res[2 * i] = fma_mix_lo(1.f, t1, fma_mix_lo(1.f, t2, fma_mix_lo(1.f, t3, fma_mix_lo(1.f, acc[0][i], 0.f))));
             res[2 * i + 1] = fma_mix_hi(1.f, t1, fma_mix_hi(1.f, t2, fma_mix_hi(1.f, t3, fma_mix_hi(1.f, acc[0][i], 0.f))));
         }
@@ -533,13 +527,13 @@ __device__ __forceinline__ void enc_queries_bf16_h3(
         float off[8], lg[4];
         cur.get(off, lg);
         float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-        mx = fmaxf(mx, quad_dpp<0xB1>(mx));
-        mx = fmaxf(mx, quad_dpp<0x4E>(mx));
+        mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+        mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-        sum += quad_dpp<0xB1>(sum);
-        sum += quad_dpp<0x4E>(sum);
+        sum += dpp_f<0xB1, false>(sum);
+        sum += dpp_f<0x4E, false>(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
 
         uint32_t acc[4][4];
@@ -612,7 +606,7 @@ __device__ __forceinline__ void enc_queries_bf16_h3(
         float res[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t t3 = quad_dpp_u<0x39>(acc[3][i]), t2 = quad_dpp_u<0x4E>(acc[2][i]), t1 = quad_dpp_u<0x93>(acc[1][i]);
+            const uint32_t t3 = dpp_u<0x39, false>(acc[3][i]), t2 = dpp_u<0x4E, false>(acc[2][i]), t1 = dpp_u<0x93, false>(acc[1][i]);
             res[2 * i] = fma_mix_lo(1.f, t1, fma_mix_lo(1.f, t2, fma_mix_lo(1.f, t3, fma_mix_lo(1.f, acc[0][i], 0.f))));
             res[2 * i + 1] = fma_mix_hi(1.f, t1, fma_mix_hi(1.f, t2, fma_mix_hi(1.f, t3, fma_mix_hi(1.f, acc[0][i], 0.f))));
         }
@@ -674,13 +668,13 @@ __device__ __forceinline__ void enc_queries_bf16_h4(
         float off[8], lg[4];
         cur.get(off, lg);
         float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-        mx = fmaxf(mx, quad_dpp<0xB1>(mx));
-        mx = fmaxf(mx, quad_dpp<0x4E>(mx));
+        mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+        mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-        sum += quad_dpp<0xB1>(sum);
-        sum += quad_dpp<0x4E>(sum);
+        sum += dpp_f<0xB1, false>(sum);
+        sum += dpp_f<0x4E, false>(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
 
         // geometry of the four points: packed corner weights (real ones: the global path uses them), window byte offsets of the four corners
@@ -772,7 +766,7 @@ __device__ __forceinline__ void enc_queries_bf16_h4(
         float res[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint32_t t3 = quad_dpp_u<0x39>(acc[3][i]), t2 = quad_dpp_u<0x4E>(acc[2][i]), t1 = quad_dpp_u<0x93>(acc[1][i]);
+            const uint32_t t3 = dpp_u<0x39, false>(acc[3][i]), t2 = dpp_u<0x4E, false>(acc[2][i]), t1 = dpp_u<0x93, false>(acc[1][i]);
             res[2 * i] = fma_mix_lo(1.f, t1, fma_mix_lo(1.f, t2, fma_mix_lo(1.f, t3, fma_mix_lo(1.f, acc[0][i], 0.f))));
             res[2 * i + 1] = fma_mix_hi(1.f, t1, fma_mix_hi(1.f, t2, fma_mix_hi(1.f, t3, fma_mix_hi(1.f, acc[0][i], 0.f))));
         }
@@ -837,13 +831,13 @@ __device__ __forceinline__ void enc_queries_f32_lvl(
         float off[8], lg[4];
         cur.get(off, lg);
         float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-        mx = fmaxf(mx, quad_dpp<0xB1>(mx));
-        mx = fmaxf(mx, quad_dpp<0x4E>(mx));
+        mx = fmaxf(mx, dpp_f<0xB1, false>(mx));
+        mx = fmaxf(mx, dpp_f<0x4E, false>(mx));
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { lg[i] = __expf(lg[i] - mx); sum += lg[i]; }
-        sum += quad_dpp<0xB1>(sum);
-        sum += quad_dpp<0x4E>(sum);
+        sum += dpp_f<0xB1, false>(sum);
+        sum += dpp_f<0x4E, false>(sum);
         const float inv = 1.0f / sum;
 
         encf2_t acc[8][2];
@@ -933,7 +927,7 @@ __device__ __forceinline__ void enc_queries_f32_lvl(
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
-                    res[4 * e + 2 * h + c] = (acc[e][h][c] + quad_dpp<0x39>(acc[6 + e][h][c])) + (quad_dpp<0x4E>(acc[4 + e][h][c]) + quad_dpp<0x93>(acc[2 + e][h][c]));
+                    res[4 * e + 2 * h + c] = (acc[e][h][c] + dpp_f<0x39, false>(acc[6 + e][h][c])) + (dpp_f<0x4E, false>(acc[4 + e][h][c]) + dpp_f<0x93, false>(acc[2 + e][h][c]));
         float* dst = out + bq * MD + m * 32;                        // res[0..3] = piece (2 i + slot) & 7, res[4..7] = the next one
         *reinterpret_cast<float4*>(dst + ((2 * p + qs) & 7) * 4) = make_float4(res[0], res[1], res[2], res[3]);
         *reinterpret_cast<float4*>(dst + ((2 * p + 1 + qs) & 7) * 4) = make_float4(res[4], res[5], res[6], res[7]);

@@ -17,12 +17,9 @@
 //     window, no shifts, no unaligned LDS access.  2 ds_read_b128 feed 16 MFMAs.
 //   * All 24 weight fragments (24 KB) live in registers (96 VGPRs) for the whole kernel.
 // Workgroup = 4 output rows x 256 output columns of one image; wave = (row, 64-column strip) units.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t stem_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float stem_f32x4_t;
 
 constexpr int STEM_ROWS = 4, STEM_COLS = 256;               // conv outputs per workgroup
 constexpr int STEM_IN_ROWS = 2 * STEM_ROWS + 5;             // 13 input rows per channel
@@ -30,9 +27,8 @@ constexpr int STEM_IN_COLS = 2 * STEM_COLS + 8;             // 520 staged input 
 constexpr int STEM_PITCH = 640;                             // elements per LDS row: 1280 B = 5 x 256 B (rows bank-aligned)
 constexpr int STEM_LDS = 3 * STEM_IN_ROWS * STEM_PITCH * 2; // 49920 B
 
-__device__ __forceinline__ stem_f32x4_t stem_mma(const uint4& a, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, stem_f32x4_t c) {
-    const uint4 b = make_uint4(b0, b1, b2, b3);
-    return DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(stem_bf16x8_t, a), __builtin_bit_cast(stem_bf16x8_t, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4_t stem_mma(const uint4& a, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, f32x4_t c) {
+    return mma16(a, make_uint4(b0, b1, b2, b3), c);
 }
 
 // x [B,3,H,W] fp32 ; wfrag [4][6][64][8] bf16 (fragment-major, see dtlr_stem_pack_weights) ; y [B,Ho,Wo,64] bf16
@@ -93,11 +89,11 @@ __global__ __launch_bounds__(512, 2) void stem_conv7x7_kernel(const float* __res
         const int ro = u >> 2, s = u & 3;
         const int oh = oh0 + ro;
         if (oh >= Ho) continue;                                 // wave-uniform
-        stem_f32x4_t acc[4][4];
+        f32x4_t acc[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[i][t] = stem_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 4; ++t) acc[i][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const uint16_t* base = img + 2 * ro * STEM_PITCH + (16 * s + n) * 8;
 #pragma unroll
         for (int ks = 0; ks < 6; ++ks) {
@@ -140,14 +136,11 @@ __global__ __launch_bounds__(512, 2) void stem_conv7x7_kernel(const float* __res
 //     acc += W_hi . x_lo + W_lo . x_hi + W_hi . x_hi          per (k-step, channel tile, pixel tile): 3 MFMAs, 288 per (row, 64-column strip) unit.
 // LDS: 2 x 49,920 (planes) + 2 x 24,576 (weights) = 148,992 bytes: one workgroup per CU.  Output fp32 NHWC (the folded-BN shift, ReLU and
 // max-pool follow in maxpool3x3s2, as for the exact engine).
-typedef __attribute__((ext_vector_type(8))) _Float16 stem_f16x8_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 stem_f16x2_t;
 constexpr int STEMS_PLANE = 3 * STEM_IN_ROWS * STEM_PITCH * 2;      // 49,920 B
 constexpr int STEMS_WOFF = 2 * STEMS_PLANE;
 constexpr int STEMS_LDS = STEMS_WOFF + 2 * 24576;
-__device__ __forceinline__ stem_f32x4_t stems_mma(const uint4& a, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, stem_f32x4_t c) {
-    const uint4 b = make_uint4(b0, b1, b2, b3);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(stem_f16x8_t, a), __builtin_bit_cast(stem_f16x8_t, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4_t stems_mma(const uint4& a, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, f32x4_t c) {
+    return mma16_f16(a, make_uint4(b0, b1, b2, b3), c);
 }
 
 // x [B,3,H,W] fp32 ; wfrag_hi / wfrag_lo [4][6][64][8] fp16 (dtlr_stem_pack_weights of the fp16 build applied to fp16(w) and to w - fp16(w)) ; y [B,Ho,Wo,64] fp32
@@ -184,8 +177,8 @@ __global__ __launch_bounds__(512, 1) void stem_conv7x7_f32s_kernel(const float* 
         const int p = (int)threadIdx.x + 512 * it;
         if (p < NP) {
             const int row = p / (STEM_IN_COLS / 2), cc = (p % (STEM_IN_COLS / 2)) * 2;
-            const stem_f16x2_t hi = __builtin_convertvector(f32x2_hw_t{v0[it], v1[it]}, stem_f16x2_t);
-            const stem_f16x2_t lo = __builtin_convertvector(f32x2_hw_t{v0[it] - (float)hi[0], v1[it] - (float)hi[1]}, stem_f16x2_t);
+            const f16x2_t hi = __builtin_convertvector(f32x2_hw_t{v0[it], v1[it]}, f16x2_t);
+            const f16x2_t lo = __builtin_convertvector(f32x2_hw_t{v0[it] - (float)hi[0], v1[it] - (float)hi[1]}, f16x2_t);
             *reinterpret_cast<uint32_t*>(img_hi + row * STEM_PITCH + cc) = __builtin_bit_cast(uint32_t, hi);
             *reinterpret_cast<uint32_t*>(img_lo + row * STEM_PITCH + cc) = __builtin_bit_cast(uint32_t, lo);
         }
@@ -215,11 +208,11 @@ __global__ __launch_bounds__(512, 1) void stem_conv7x7_f32s_kernel(const float* 
         const int ro = u >> 2, s = u & 3;
         const int oh = oh0 + ro;
         if (oh >= Ho) continue;                                 // wave-uniform
-        stem_f32x4_t acc[4][4];
+        f32x4_t acc[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[i][t] = stem_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 4; ++t) acc[i][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const int boff = 2 * ro * STEM_PITCH + (16 * s + n) * 8;
 #pragma unroll
         for (int ks = 0; ks < 6; ++ks) {
@@ -282,10 +275,6 @@ constexpr int SP_CP = 144;                                  // bytes per pooled 
                                                             // (address 2 n SP_CP + 8 g) cover all banks: with 128 the 16 lanes of a group collide
 constexpr int SP_HB = SP_CROWS * SP_PCOLS * SP_CP;          // 86400 B row-pooled conv outputs
 constexpr int SP_LDS = SP_IMG + SP_HB;
-
-template <int CTRL> __device__ __forceinline__ float sp_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
 
 __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const float* __restrict__ x, const uint16_t* __restrict__ wfrag,
                                                            const float* __restrict__ bias, uint16_t* __restrict__ y,
@@ -352,11 +341,11 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const float* __restri
             }
             continue;
         }
-        stem_f32x4_t acc[4][4];
+        f32x4_t acc[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[i][t] = stem_f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < 4; ++t) acc[i][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const uint16_t* base = img + 2 * ro * STEM_PITCH + (60 * s + 4 * n) * 2;
 #pragma unroll
         for (int ks = 0; ks < 6; ++ks) {
@@ -385,7 +374,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const float* __restri
             float m0[4], m1[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float nx = sp_dpp<0x101>(e[0][r]);          // row_shl:1 -- lane n receives lane n + 1's first column
+                const float nx = dpp_f<0x101, false>(e[0][r]);          // row_shl:1 -- lane n receives lane n + 1's first column
                 m0[r] = fmaxf(fmaxf(e[0][r], e[1][r]), e[2][r]);
                 m1[r] = fmaxf(fmaxf(e[2][r], e[3][r]), nx);
             }

@@ -14,12 +14,9 @@
 // extent array of extent.hip -- while addressing keeps the canvas pitch: a position outside the line's extent is a padding position
 // whatever the tensor holds there, and every output position outside the extent is written as zero.
 // The MLP's GELU is an epilogue of the GEMM (EPI_GELU), LayerNorm of arbitrary C the generic row kernel of norm.hip.
-#include "dtlr_common.h"
+#include "gfx950_prims.h"
 
 namespace dtlr {
-
-typedef __attribute__((ext_vector_type(8))) h16_hw_t sw_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float sw_f32x4_t;
 
 // ------------------------------------------------------------------------------------------------------------- patch embed
 // x [B,3,H,W] fp32 ; w [48][E] fp32 (k = (c*4 + dy)*4 + dx, k-major) ; b, gamma, beta [E] ; out [B,Hp,Wp,E], Hp = ceil(H/4).
@@ -301,12 +298,12 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
 #pragma unroll
         for (int kt = 0; kt < 12; ++kt) {
             if (kt < KT) {
-                sw_f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+                f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
                 if constexpr (BF) {
                     const int km = 16 * kt + n;                   // A-operand row = key (lane index n plays m)
                     const uint4 kf = *reinterpret_cast<const uint4*>(Ks + km * 64 + ((g ^ ((km >> 2) & 3)) * 16));
                     const uint4 qf = *reinterpret_cast<const uint4*>(Qs + qi * 64 + ((g ^ ((qi >> 2) & 3)) * 16));
-                    acc = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(sw_bf16x8_t, kf), __builtin_bit_cast(sw_bf16x8_t, qf), acc, 0, 0, 0);
+                    acc = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(h16x8_t, kf), __builtin_bit_cast(h16x8_t, qf), acc, 0, 0, 0);
                 } else {
                     const float* kr = reinterpret_cast<const float*>(Ks) + (16 * kt + n) * 33;
                     const float* qr = reinterpret_cast<const float*>(Qs) + qi * 33;
@@ -338,7 +335,7 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.0f / sum;
-        sw_f32x4_t o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        f32x4_t o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         if constexpr (BF) {
             const uint16_t* vt = reinterpret_cast<const uint16_t*>(Vs);
             const int stride = NK + SwinLds<uint16_t>::VT_PAD;
@@ -352,7 +349,7 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
                         const uint16_t* vr = vt + (16 * dt + n) * stride + 32 * kb + 4 * g;          // V^T row d = 16 dt + n
                         const uint2 lo = *reinterpret_cast<const uint2*>(vr), hi = *reinterpret_cast<const uint2*>(vr + 16);
                         const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                        o[dt] = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(sw_bf16x8_t, vf), __builtin_bit_cast(sw_bf16x8_t, pf), o[dt], 0, 0, 0);
+                        o[dt] = DTLR_MFMA_16x16x32_H16(__builtin_bit_cast(h16x8_t, vf), __builtin_bit_cast(h16x8_t, pf), o[dt], 0, 0, 0);
                     }
                 }
             }

@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Which kernels of a .hip file changed between a git revision and the working tree -- at the instruction level (no GPU).
     python tools/isa_diff.py dtlr_amd/csrc/msda_enc.hip [--rev HEAD] [--defs=-DDTLR_HALF_IS_F16]
+    python tools/isa_diff.py --all [--rev HEAD] [--defs=...] [-j N]        every csrc/*.hip: one line per kernel plus a total
 Compiles both versions for gfx950 with --save-temps and compares every kernel's instruction stream (basic-block label numbers
-normalised).  Use: adding a variant / template instantiation next to a verified kernel must leave the verified kernel SAME."""
+normalised).  The old side is compiled inside a copy of the REVISION's dtlr_amd/csrc and include (git archive), so a header that
+changed between the two does not leak into it.  Use: adding a variant / template instantiation next to a verified kernel, or moving
+inline helpers between files, must leave the verified kernels SAME."""
 import argparse
+import concurrent.futures
+import glob
 import os
 import re
 import subprocess
@@ -11,54 +16,80 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = "dtlr_amd/csrc"
 
 
-def kernels(src_text, name, defs):
+def kernels(tree, name, defs):
+    """{kernel symbol: [instructions]} of tree/dtlr_amd/csrc/<name>, compiled against that tree's own headers."""
     with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, name), "w").write(src_text)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/dtlr_amd/csrc",
-                               "--save-temps", "-c", name, "-o", "x.o"] + defs, cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{tree}/include", f"-I{tree}/{CSRC}",
+                               "--save-temps", "-c", f"{tree}/{CSRC}/{name}", "-o", "x.o"] + defs, cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         asm = [f for f in os.listdir(d) if f.endswith(".s") and "amdgcn" in f][0]
         lines = open(os.path.join(d, asm)).read().split("\n")
     out, i = {}, 0
     while i < len(lines):
         m = re.match(r"^(_Z\w+|[A-Za-z_]\w*):\s*(;.*)?$", lines[i])
         if m and i + 1 < len(lines) and not lines[i].startswith("."):
-            j = i
-            while j < len(lines) and not lines[j].strip().startswith("s_endpgm"):
-                if j > i and re.match(r"^(_Z\w+):", lines[j]):
-                    break
+            j = i + 1                                    # the whole body (a kernel with an early exit has several s_endpgm): up to the kernel
+            while j < len(lines) and not re.match(r"^(\.Lfunc_end|\s+\.section\b|_Z\w+:)", lines[j]):      # descriptor's section / .Lfunc_end
                 j += 1
-            if j < len(lines) and lines[j].strip().startswith("s_endpgm"):
-                out[m.group(1)] = [re.sub(r"\.LBB\d+_", ".LBB_", x.split(";")[0].rstrip()) for x in lines[i + 1:j + 1] if x.split(";")[0].strip()]
+            body = [re.sub(r"\.LBB\d+_", ".LBB_", x.split(";")[0].rstrip()) for x in lines[i + 1:j] if x.split(";")[0].strip()]
+            if j < len(lines) and not lines[j].startswith("_Z") and any(x.strip().startswith("s_endpgm") for x in body):
+                out[m.group(1)] = body
                 i = j
         i += 1
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("source")
-    ap.add_argument("--rev", default="HEAD")
-    ap.add_argument("--defs", default="")
-    args = ap.parse_args()
-    rel = os.path.relpath(os.path.abspath(args.source), ROOT)
-    old = subprocess.check_output(["git", "show", f"{args.rev}:{rel}"], cwd=ROOT, text=True)
-    new = open(os.path.join(ROOT, rel)).read()
-    a, b = kernels(old, os.path.basename(rel), args.defs.split()), kernels(new, os.path.basename(rel), args.defs.split())
-    changed = 0
+def diff_file(old_tree, name, defs):
+    """(report lines, kernels compared, kernels that differ) for one file; a file the revision does not have is all NEW."""
+    a = kernels(old_tree, name, defs) if os.path.exists(f"{old_tree}/{CSRC}/{name}") else {}
+    b = kernels(ROOT, name, defs)
+    rep, changed = [], 0
     for k in sorted(set(a) | set(b)):
         if k not in a:
-            print(f"NEW      {k}  ({len(b[k])} instructions)")
+            rep.append(f"NEW      {k}  ({len(b[k])} instructions)")
         elif k not in b:
-            print(f"REMOVED  {k}")
+            rep.append(f"REMOVED  {k}")
             changed += 1
         elif a[k] == b[k]:
-            print(f"SAME     {k}  ({len(a[k])})")
+            rep.append(f"SAME     {k}  ({len(a[k])})")
         else:
-            print(f"CHANGED  {k}  ({len(a[k])} -> {len(b[k])})")
+            rep.append(f"CHANGED  {k}  ({len(a[k])} -> {len(b[k])})")
             changed += 1
-    sys.exit(1 if changed else 0)
+    return rep, len(set(a) | set(b)), changed
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("source", nargs="?")
+    ap.add_argument("--all", action="store_true", help="every dtlr_amd/csrc/*.hip of the working tree and of the revision")
+    ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("--defs", default="")
+    ap.add_argument("-j", type=int, default=8, help="files compiled at a time with --all")
+    args = ap.parse_args()
+    if bool(args.source) == args.all:
+        ap.error("give one source file or --all")
+    defs = args.defs.split()
+    with tempfile.TemporaryDirectory() as old_tree:
+        ar = subprocess.Popen(["git", "archive", args.rev, CSRC, "include"], cwd=ROOT, stdout=subprocess.PIPE)
+        subprocess.check_call(["tar", "-x", "-C", old_tree], stdin=ar.stdout)
+        if ar.wait():
+            sys.exit(f"git archive {args.rev} failed")
+        if not args.all:
+            rel = os.path.relpath(os.path.abspath(args.source), ROOT)
+            rep, _, changed = diff_file(old_tree, os.path.basename(rel), defs)
+            print("\n".join(rep))
+            sys.exit(1 if changed else 0)
+        names = sorted({os.path.basename(p) for t in (ROOT, old_tree) for p in glob.glob(f"{t}/{CSRC}/*.hip")})
+        total = changed = new = 0
+        with concurrent.futures.ThreadPoolExecutor(args.j) as pool:
+            for name, (rep, n, c) in zip(names, pool.map(lambda f: diff_file(old_tree, f, defs), names)):
+                for line in rep:
+                    print(f"{name:16s} {line}")
+                total, changed, new = total + n, changed + c, new + sum(x.startswith("NEW") for x in rep)
+        print(f"TOTAL    {len(names)} files, {total} kernels: {total - changed - new} SAME, {new} NEW, {changed} CHANGED or REMOVED  (rev {args.rev}, defs '{args.defs}')")
+        sys.exit(1 if changed else 0)
 
 
 if __name__ == "__main__":
