@@ -83,6 +83,10 @@ class DTLREngine:
         self.use_dec_query_stage = True   # 16-bit: a decoder layer's query stage (sine, ref_point_head, q | k, v) in one launch
         self.use_l1_chain = True          # 16-bit: layer1's 1x1 convolutions chained (shortcut conv as extra K columns; tail + next conv1 in one launch)
         self.use_l1_chain_out = True      #         ... including the last tail -> layer2.0.conv1
+        self.use_l1_block = 1             # 16-bit: each layer1 bottleneck as ONE launch (dtlr_l1_bottleneck), the 64-channel maps kept on chip ...
+        self.l1_block_min_wgs = 256       #         ... for whole batches whose (image, 64-column segment) workgroups fill every round of 256 (one per CU) at
+                                          #         least this far.  Measured: 256 workgroups (32 lines of 128 x 2048) 8.63 -> 8.48 ms per step; 64 (8 lines)
+                                          #         3.45 -> 3.63 ms: the chain stays.  Fills between those, and counts above 256, are NOT measured.
         self.use_l2_cat = True            # 16-bit: layer2.0's strided shortcut convolution as extra K columns of its tail GEMM
         self.head_ts_min_classes = 1024   # 16-bit engines: class heads with at least this many classes run on the token-stationary kernel (dtlr_head_ts)
         self.head_ts_scores = True        # ... and the two-stage selection scores (row maximum: no logits leave the chip) for EVERY charset: 142 -> 74 us at 166 classes
@@ -525,6 +529,25 @@ class DTLREngine:
                 outs.append(x)
         return outs
 
+    def _l1_block_takes(self, x0, nblocks, ext):
+        """Whether layer1 runs as one ops.l1_bottleneck launch per block: the flag, a whole-batch (not per-line) 16-bit map, ResNet-50's
+        layer1 widths with layer2.0.conv1 behind it, and enough (image, 64-column segment) workgroups to fill the chip."""
+        if not getattr(self, "use_l1_block", 0) or ext is not None or x0.dtype not in ops.H16 or x0.dim() != 4 or nblocks < 2:
+            return False
+        w = self.w
+        for bi in range(nblocks):
+            q = f"l1.{bi}."
+            if tuple(w[q + "c1.w"].shape) != (64, 64 if bi == 0 else 256) or tuple(w[q + "c2.w"].shape) != (64, 3, 3, 64) \
+                    or tuple(w[q + "c3.w"].shape) != (256, 64):
+                return False
+        if self.use_l1_chain_out and ("l2.0.c1.w" not in w or tuple(w["l2.0.c1.w"].shape) != (128, 256)):
+            return False
+        # one workgroup fits per CU (145 KB of LDS), so the workgroups run in rounds of 256: the last round must be as full as the threshold
+        # asks too (320 workgroups = a full round and a quarter-full one, each as long as the other)
+        B, _, W, _ = x0.shape
+        wgs, need = B * -(-W // ops.L1_BLOCK_SEG), getattr(self, "l1_block_min_wgs", 1 << 30)
+        return wgs >= need and (wgs % ops.L1_BLOCK_ROUND == 0 or wgs % ops.L1_BLOCK_ROUND >= need)
+
     def _layer1_chain(self, x0, nblocks, ext=None):
         """layer1 (64-channel bottlenecks on the full-resolution pooled map: the HBM-heaviest part of the backbone) with the 1x1
         convolutions chained (ops.gemm_kres_chain): the first block's `downsample` shortcut is K columns 64..127 of its conv3 GEMM
@@ -540,6 +563,17 @@ class DTLREngine:
         if "l1.0.cat.wk" not in w:
             w["l1.0.cat.wk"] = ops.kres_pack(torch.cat([w["l1.0.c3.w"], w["l1.0.ds.w"]], 1).contiguous())
             w["l1.0.cat.b"] = (w["l1.0.c3.b"].float() + w["l1.0.ds.b"].float()).contiguous()
+        if self._l1_block_takes(x0, nblocks, ext):
+            # every bottleneck as ONE launch (ops.l1_bottleneck: conv1 -> conv2 -> conv3 + shortcut with the 64-channel maps kept on chip),
+            # the last one also emitting layer2.0.conv1; bit-identical to the chain below
+            x, o = x0, None
+            for bi in range(nblocks):
+                q = f"l1.{bi}."
+                last = bi == nblocks - 1 and self.use_l1_chain_out
+                x, o = ops.l1_bottleneck(x, wk(q + "c1"), w[q + "c1.b"], w[q + "c2.w"], w[q + "c2.b"],
+                                         w["l1.0.cat.wk"] if bi == 0 else wk(q + "c3"), w["l1.0.cat.b"] if bi == 0 else w[q + "c3.b"],
+                                         wnp=wk("l2.0.c1") if last else None, bn=w["l2.0.c1.b"] if last else None, n2=128 if last else 0)
+            return x, o
         nxt = [f"l1.{bi + 1}.c1" for bi in range(nblocks - 1)] + (["l2.0.c1"] if self.use_l1_chain_out else [None])
         n2 = [64] * (nblocks - 1) + [128]
         o = self._conv("l1.0.c1", x0, 1, 0, relu=True)

@@ -325,6 +325,48 @@ def gemm_kres_chain(x, wp, b=None, x2=None, residual=None, relu: bool = True, wp
     return y, t
 
 
+L1_BLOCK_SEG = 64          # columns per workgroup of dtlr_l1_bottleneck (== LB_S of csrc/l1_block.hip)
+L1_BLOCK_ROUND = 256       # its workgroups that run at once: one per CU of an MI355X (145 KB of LDS each)
+
+
+def l1_bottleneck(x, w1p, b1, w2, b2, w3p, b3, wnp=None, bn=None, n2: int = 0, out=None, next_out=None):
+    """One whole layer1 bottleneck in one launch (dtlr_l1_bottleneck), the 64-channel intermediates kept on chip:
+        t1 = relu(x @ W1.T + b1); t2 = relu(conv3x3(t1, W2, pad 1) + b2)           (both rounded to 16 bit)
+        y  = relu(t2 @ W3.T + b3 + x)                  x [B, H, W, 256]: identity shortcut, w3p = kres_pack(W3 [256, 64])
+        y  = relu([t2 | x] @ [W3 | Wd].T + b3)         x [B, H, W, 64]: the first bottleneck, w3p = kres_pack([W3 | Wd] [256, 128]), b3 = b3 + bd
+        t  = relu(y @ Wn.T + bn)                       the next bottleneck's first 1x1 convolution, n2 = 64 / 128 (identity form only)
+    w1p = kres_pack(W1 [64, Cin]), w2 [64, 3, 3, 64] (OHWI), wnp = kres_pack(Wn [n2, 256]).  out / next_out: optional contiguous
+    [B, H, W, 256] / [B, H, W, n2] destinations.  Returns (y, t or None); bit-identical to the separate launches."""
+    require_cuda(x, "x")
+    assert x.dtype in H16 and x.dim() == 4 and x.shape[-1] in (64, 256)
+    B, H, W, cin = x.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    assert w1p.dtype == x.dtype and w1p.numel() == 256 * cin and w3p.dtype == x.dtype and w3p.numel() == 256 * (128 if cin == 64 else 64)
+    assert w2.dtype == x.dtype and tuple(w2.shape) == (64, 3, 3, 64) and w2.is_contiguous()
+    assert n2 in (0, 64, 128) and (n2 == 0 or cin == 256) and (n2 == 0) == (wnp is None)
+    b1, b2, b3 = (t if t.dtype == torch.float32 else t.float() for t in (b1, b2, b3))
+    assert b1.numel() == 64 and b2.numel() == 64 and b3.numel() == 256 and b1.is_contiguous() and b2.is_contiguous() and b3.is_contiguous()
+    if n2:
+        assert wnp.dtype == x.dtype and wnp.numel() == 256 * 256 and bn is not None and bn.numel() == n2
+        bn = bn if bn.dtype == torch.float32 else bn.float()
+    if out is None:
+        out = torch.empty((B, H, W, 256), dtype=x.dtype, device=x.device)
+    assert out.dtype == x.dtype and tuple(out.shape) == (B, H, W, 256) and out.is_contiguous()
+    if n2 and next_out is None:
+        next_out = torch.empty((B, H, W, n2), dtype=x.dtype, device=x.device)
+    if n2:
+        assert next_out.dtype == x.dtype and tuple(next_out.shape) == (B, H, W, n2) and next_out.is_contiguous()
+    M = B * H * W
+    nbytes = float(M) * (cin + 256 + n2) * 2 + (64.0 * cin + 64 * 576 + 256 * (128 if cin == 64 else 64) + 256 * n2) * 2
+    flops = 2.0 * M * (64 * cin + 64 * 576 + 256 * (128 if cin == 64 else 64) + 256 * n2)
+    with _Timed("gemm_bf16", flops, nbytes, f"l1_block M{M} C{cin}" + (f" ->N{n2}" if n2 else "")):
+        code = _L(x).dtlr_l1_bottleneck(x.data_ptr(), cin, w1p.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3p.data_ptr(), b3.data_ptr(),
+                                        out.data_ptr(), wnp.data_ptr() if n2 else 0, bn.data_ptr() if n2 else 0, next_out.data_ptr() if n2 else 0,
+                                        n2, B, H, W, _lib.current_stream())
+    _lib.check(code, "dtlr_l1_bottleneck")
+    return out, (next_out if n2 else None)
+
+
 def gemm_kres_cat_s2(t, x, wp, b=None, relu: bool = True):
     """layer2's first bottleneck tail with the strided shortcut convolution as extra K columns (dtlr_gemm_kres_cat_s2):
         y[b, i, j] = relu?([t[b, i, j] | x[b, 2 i, 2 j]] @ W.T + b),   W = [W3 | Wd] [512, 384], b = b3 + bd
@@ -1513,7 +1555,7 @@ def _device_scoped(fn):
     return wrapper
 
 
-for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
+for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "l1_bottleneck", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
               "maxpool_nhwc", "groupnorm_tokens", "msda", "msda_fused", "msda_encoder", "mha", "decoder_query_prep", "box_mlp_refine",
               "box_head_refine", "box_refine", "topk_rows", "decode_blank", "preprocess_lines", "ctc_loss_interleaved", "nms_batched",
               "topk_flat", "ctc_loss_interleaved_backward", "head_grad", "grad_norm_scale", "adamw_step", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):

@@ -243,6 +243,16 @@ int dtlr_gemm_kres(const void *A, const void *Wp, const float *bias, const void 
  *   on the stored C; with R, C is bit-identical to dtlr_gemm_kres. */
 int dtlr_gemm_kres_chain(const void *A, const void *A2, const void *Wp, const float *bias, const void *R, void *C, int M, int relu,
                          const void *Wp2, const float *bias2, void *C2, int N2, void *stream);
+/* One whole layer1 bottleneck as ONE launch (csrc/l1_block.hip): the 64-channel intermediates stay in LDS.
+ *     t1 = relu(X W1^T + b1) ; t2 = relu(conv3x3(t1, W2, pad 1) + b2) ; both rounded to 16 bit, zero padding applied to t1
+ *     OUT = relu(t2 W3^T + b3 + X)                       cin = 256: identity shortcut
+ *     OUT = relu([t2 | X] [W3 | Wd]^T + b3)              cin = 64: the first bottleneck (b3 = the sum of both biases)
+ *     NEXT = relu(OUT Wn^T + bn)                         n2 = 64 / 128 (cin = 256 only); n2 = 0: not computed, Wnp / bn / NEXT unused
+ *   X [B, H, W, cin], OUT [B, H, W, 256], NEXT [B, H, W, n2] 16-bit NHWC; W1p / W3p / Wnp: device copies of
+ *   dtlr_gemm_kres_pack_weights(W1 [64, cin]) / (W3 [256, 64] or [W3 | Wd] [256, 128]) / (Wn [n2, 256]); W2 [64, 3, 3, 64]; biases fp32.
+ *   Every output is bit-identical to the separate launches (1x1 GEMM, dtlr_conv2d_nhwc, dtlr_gemm_kres_chain). */
+int dtlr_l1_bottleneck(const void *X, int cin, const void *W1p, const float *b1, const void *W2, const float *b2, const void *W3p,
+                       const float *b3, void *OUT, const void *Wnp, const float *bn, void *NEXT, int n2, int B, int H, int W, void *stream);
 /* layer2's first bottleneck tail (torchvision resnet50 `layer2[0]`, stride on the 3x3: `out = relu(bn3(conv3(t)) + downsample(x))` with
  * downsample = conv1x1 stride 2 + FrozenBN) as ONE GEMM: the strided shortcut convolution is K columns 128..383,
  *     C[(b, i, j), :] = relu?( [A[(b, i, j), :] | X[b, 2 i, 2 j, :]] W^T + bias ),   W = [W3 | Wd] [512, 384], bias = b3 + bd
