@@ -142,6 +142,11 @@ _SIGNATURES = {
                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dtlr_ngram_beam_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
     "dtlr_decode_blank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "dtlr_decode_blank_located_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
+    "dtlr_decode_blank_located": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dtlr_decode_nms_located": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     # per-line batching
     "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_zero_outside_extent_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -166,13 +166,21 @@ __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict
 // Step 1 of the blank decoder, chip-wide: the label of every query (class index, or -1 = blank), 16 lanes per query.
 // logits [B*nq, C] fp32 -> raw [B*nq] int32.  The 16-lane reductions are DPP row operations (xor 1, xor 2, half-mirror, mirror):
 // no LDS traffic, no 64-lane butterflies.
-__global__ __launch_bounds__(256) void query_label_kernel(const float* __restrict__ logits, int* __restrict__ raw, long nrows, int C, float eps)
+// The per-query step itself is query_label_rows: dtlr_decode_blank and dtlr_decode_blank_located both run it, so the labels of the two
+// come from one sequence of float operations.  SCORE: also write the probability of the argmax class after the blank construction --
+// `top` with the class sum carried in fp64 beside the fp32 one.  The fp32 sum takes C / 16 sequential additions per lane (460 at 7356
+// classes; with near-equal addends every one rounds the same way: 2.5e-6 relative) and stays what the branch and the label are decided
+// on, so that dtlr_decode_blank keeps its bits; the score it would give is 19x further from fp64 than a plain fp32 evaluation is.
+template <bool SCORE>
+__device__ __forceinline__ void query_label_rows(const float* __restrict__ logits, int* __restrict__ raw, float* __restrict__ score,
+                                                 long nrows, int C, float eps)
 {
     const int l16 = threadIdx.x & 15;
     const long q = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool live = q < nrows;
     const float* lr = logits + (live ? q : 0) * C;
     float sum = 0.f, best = -1.f, nonfin = 0.f;
+    double dsum = 0.0;                                              // SCORE only
     int arg = 0x7fffffff;
     for (int c0 = 0; c0 < C; c0 += 64) {                            // four classes per lane in flight
         float x[4];
@@ -183,6 +191,7 @@ __global__ __launch_bounds__(256) void query_label_kernel(const float* __restric
             const int c = c0 + 16 * u + l16;
             const float pq = 1.f / (1.f + expf(-x[u]));             // sigmoid(-inf) = 0 for the padding
             sum += pq;
+            if constexpr (SCORE) dsum += (double)pq;
             if (live && c < C) nonfin += x[u] - x[u];               // 0 for a finite logit, NaN for +-inf / NaN (sigmoid(+-inf) is finite: `sum` alone misses it)
             if (c < C && pq > best) { best = pq; arg = c; }         // ascending c: the first maximum of the lane
         }
@@ -207,7 +216,25 @@ __global__ __launch_bounds__(256) void query_label_kernel(const float* __restric
     // garbage labels.  `nonfin` sums x - x over the query's logits (0 for finite x, NaN otherwise; round 5 tested `sum` only, which a
     // +-inf logit leaves finite: sigmoid(+inf) = 1, sigmoid(-inf) = 0).
     const bool bad = !(nonfin == 0.f) || !(sum - sum == 0.f);
-    if (live && l16 == 0) raw[q] = bad ? -2 : ((blank >= top) ? -1 : arg);       // argmax over [blank | classes]: blank wins ties
+    if (live && l16 == 0) {
+        raw[q] = bad ? -2 : ((blank >= top) ? -1 : arg);                         // argmax over [blank | classes]: blank wins ties
+    }
+    if constexpr (SCORE) {
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) dsum += __shfl_xor(dsum, o, 16);        // the same fp32 addends, summed in fp64
+        if (live && l16 == 0) score[q] = (sum < 1.f - eps) ? best : (float)((1.0 - (double)eps) * (double)best / dsum);
+    }
+}
+
+__global__ __launch_bounds__(256) void query_label_kernel(const float* __restrict__ logits, int* __restrict__ raw, long nrows, int C, float eps)
+{
+    query_label_rows<false>(logits, raw, nullptr, nrows, C, eps);
+}
+
+__global__ __launch_bounds__(256) void query_label_score_kernel(const float* __restrict__ logits, int* __restrict__ raw, float* __restrict__ score,
+                                                                long nrows, int C, float eps)
+{
+    query_label_rows<true>(logits, raw, score, nrows, C, eps);
 }
 
 // Step 2, one workgroup per line: sort the queries by box cx, read their labels in that order, drop the blanks.
@@ -254,6 +281,76 @@ __global__ __launch_bounds__(1024) void decode_blank_kernel(const float* __restr
     }
     for (int i = running + threadIdx.x; i < nq; i += blockDim.x) labels[(long)b * nq + i] = -1;
     if (threadIdx.x == 0) lengths[b] = s_bad ? -1 : running;                     // -1: this line's logits were not finite
+}
+
+// ---- located decoders: every decoded character with the query it came from, its score and its box ---------------------------------
+// A query's cxcywh box as PostProcess computes its xyxy box (util/box_ops.py:9-13, then the product with (W, H, W, H),
+// models/dino/dino.py:1016-1024): every product and every difference rounded on its own, so the result equals torch's bit for bit.
+__device__ __forceinline__ float4 located_xyxy(const float* __restrict__ bx)
+{
+    const float hw = __fmul_rn(0.5f, bx[2]), hh = __fmul_rn(0.5f, bx[3]);
+    return make_float4(__fsub_rn(bx[0], hw), __fsub_rn(bx[1], hh), __fadd_rn(bx[0], hw), __fadd_rn(bx[1], hh));
+}
+__device__ __forceinline__ float4 located_scale(float4 v, float W, float H)
+{
+    return make_float4(__fmul_rn(v.x, W), __fmul_rn(v.y, H), __fmul_rn(v.z, W), __fmul_rn(v.w, H));
+}
+
+// decode_blank_kernel with the record of every kept character: raw / top [B,nq] are query_label_score_kernel's per-query label and
+// score (caller workspace).  The sort key's low word is the query index, so the compaction writes label, query, rank (the position in
+// the reading order of ALL queries = the frame of dtlr_blank_emissions), score and box.  A line with a non-finite query is all padding.
+__global__ __launch_bounds__(1024) void decode_blank_located_kernel(const float* __restrict__ boxes, const int* __restrict__ raw,
+                                                                    const float* __restrict__ top, const float* __restrict__ src_hw,
+                                                                    int* __restrict__ labels, int* __restrict__ query, int* __restrict__ rank,
+                                                                    float* __restrict__ score, float* __restrict__ box,
+                                                                    int* __restrict__ lengths, int nq, int npow2)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];      // [npow2] then int lab[npow2]
+    int* lab = reinterpret_cast<int*>(keys + npow2);
+    __shared__ int wave_tot[16];
+    __shared__ int s_bad;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const long row = (long)b * nq;
+    const float H = src_hw ? src_hw[2 * b] : 1.f, W = src_hw ? src_hw[2 * b + 1] : 1.f;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < npow2; i += blockDim.x) {
+        keys[i] = i < nq ? (((unsigned long long)f32_sortable(boxes[(row + i) * 4])) << 32) | (unsigned)i : ~0ull;
+        if (i < nq && raw[row + i] == -2) s_bad = 1;                            // benign race, same value
+    }
+    bitonic_sort_u64(keys, npow2);                                             // ascending cx, ties: lower index first
+    const bool bad = s_bad != 0;
+    for (int p = threadIdx.x; p < nq; p += blockDim.x) lab[p] = bad ? -1 : raw[row + (int)(keys[p] & 0xffffffffull)];
+    __syncthreads();
+    int running = 0;
+    for (int base = 0; base < nq; base += blockDim.x) {                        // decode_blank_kernel's stable compaction
+        const int p = base + threadIdx.x;
+        const int v = p < nq ? lab[p] : -1;
+        const int keep = v >= 0;
+        const unsigned long long m = __ballot(keep);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_tot[wave] = __popcll(m);
+        __syncthreads();
+        int off = running;
+        for (int w = 0; w < wave; ++w) off += wave_tot[w];
+        int tot = 0;
+        for (int w = 0; w < nwave; ++w) tot += wave_tot[w];
+        if (keep) {
+            const int q = (int)(keys[p] & 0xffffffffull);
+            const long o = row + off + before;
+            labels[o] = v; query[o] = q; rank[o] = p; score[o] = top[row + q];
+            *reinterpret_cast<float4*>(box + o * 4) = located_scale(located_xyxy(boxes + (row + q) * 4), W, H);
+        }
+        running += tot;
+        __syncthreads();
+    }
+    for (int i = running + threadIdx.x; i < nq; i += blockDim.x) {
+        const long o = row + i;
+        labels[o] = -1; query[o] = -1; rank[o] = -1; score[o] = 0.f;
+        *reinterpret_cast<float4*>(box + o * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (threadIdx.x == 0) lengths[b] = bad ? -1 : running;
 }
 
 // ---- CTC-style emissions of the n-gram re-scoring path (ngram/prediction_helpers.py:5-46, get_new_pred_logits; with scale = 1 the
@@ -372,6 +469,30 @@ __global__ __launch_bounds__(1024) void ctc_interleaved_kernel(const float* __re
 // index first).  Stable score sort (bitonic, LDS) -> boxes in sorted order -> the upper-triangular suppression bit-matrix
 // (n x n/64 words, LDS, all threads) -> ONE wave walks the rows in order, OR-ing a kept row's word into its lane's "removed"
 // word (lane w owns word w; no barriers) -> kept original indices, in descending score order.  n <= 1024.
+// the upper-triangular suppression bit-matrix of n boxes in sorted order: bit j of mat[i][j / 64] = (j > i and IoU(i, j) > thr).  All threads.
+__device__ __forceinline__ void nms_fill_matrix(unsigned long long* mat, const float4* sb, int n, int W, float thr)
+{
+    for (int t = threadIdx.x; t < n * W; t += blockDim.x) {
+        const int i = t / W, w = t - i * W;
+        unsigned long long bits = 0ull;
+        if (64 * w + 63 > i) {                                                 // only columns j > i
+            const float4 a = sb[i];
+            const float area_a = (a.z - a.x) * (a.w - a.y);
+            for (int jj = 0; jj < 64; ++jj) {
+                const int j = 64 * w + jj;
+                if (j > i && j < n) {
+                    const float4 c = sb[j];
+                    const float iw = fmaxf(fminf(a.z, c.z) - fmaxf(a.x, c.x), 0.f), ih = fmaxf(fminf(a.w, c.w) - fmaxf(a.y, c.y), 0.f);
+                    const float inter = iw * ih;
+                    const float area_c = (c.z - c.x) * (c.w - c.y);
+                    if (inter / (area_a + area_c - inter) > thr) bits |= 1ull << jj;
+                }
+            }
+        }
+        mat[t] = bits;
+    }
+}
+
 __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, float thr,
                                                    long* __restrict__ keep, int* __restrict__ counts, int n, int npow2)
 {
@@ -392,25 +513,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ box
         sb[i] = *reinterpret_cast<const float4*>(bx + (long)o * 4);
     }
     __syncthreads();                                                           // keys are dead from here: the matrix overwrites them
-    for (int t = threadIdx.x; t < n * W; t += blockDim.x) {
-        const int i = t / W, w = t - i * W;
-        unsigned long long bits = 0ull;
-        if (64 * w + 63 > i) {                                                 // only columns j > i
-            const float4 a = sb[i];
-            const float area_a = (a.z - a.x) * (a.w - a.y);
-            for (int jj = 0; jj < 64; ++jj) {
-                const int j = 64 * w + jj;
-                if (j > i && j < n) {
-                    const float4 c = sb[j];
-                    const float iw = fmaxf(fminf(a.z, c.z) - fmaxf(a.x, c.x), 0.f), ih = fmaxf(fminf(a.w, c.w) - fmaxf(a.y, c.y), 0.f);
-                    const float inter = iw * ih;
-                    const float area_c = (c.z - c.x) * (c.w - c.y);
-                    if (inter / (area_a + area_c - inter) > thr) bits |= 1ull << jj;
-                }
-            }
-        }
-        mat[t] = bits;
-    }
+    nms_fill_matrix(mat, sb, n, W, thr);
     __syncthreads();
     if (threadIdx.x < 64) {                                                    // the sequential sweep, one wave, no barriers
         const int lane = threadIdx.x;
@@ -427,6 +530,88 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ box
         for (int i = cnt + lane; i < n; i += 64) keep[(long)b * n + i] = -1;
         if (lane == 0) counts[b] = cnt;
     }
+}
+
+// The NMS decoder (evaluation.py:94-115) of one line per workgroup, on the flat top-k of dtlr_topk_flat: nms_kernel's stable score sort,
+// bit-matrix and sweep on the NORMALISED boxes of the entries' queries (the reference suppresses on a (1, 1) canvas), then the kept
+// entries with score > score_thr are sorted by cx' = (x0 + x1) / 2 (ties: earlier in descending-score order first) and written out as
+// (label, query, score, box scaled to the source image).  The cx' keys reuse the matrix's head once the sweep is done.
+__global__ __launch_bounds__(1024) void decode_nms_located_kernel(const float* __restrict__ values, const long* __restrict__ index,
+                                                                  const float* __restrict__ boxes, const float* __restrict__ src_hw,
+                                                                  float iou_thr, float score_thr,
+                                                                  int* __restrict__ labels, int* __restrict__ query, float* __restrict__ score,
+                                                                  float* __restrict__ box, int* __restrict__ lengths,
+                                                                  int n, int npow2, int nq, int C)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long nms_lds[];   // matrix [n][W] / keys [npow2] | float4 sb[npow2] | int order[npow2] | int kept[npow2]
+    const int W = (n + 63) >> 6;
+    unsigned long long* mat = nms_lds;
+    float4* sb = reinterpret_cast<float4*>(nms_lds + (size_t)max(n * W, npow2));
+    int* order = reinterpret_cast<int*>(sb + npow2);
+    int* kept = order + npow2;
+    __shared__ int s_cnt, s_ns;
+    const int b = blockIdx.x;
+    const long row = (long)b * n;
+    const float H = src_hw ? src_hw[2 * b] : 1.f, Wd = src_hw ? src_hw[2 * b + 1] : 1.f;
+    unsigned long long* keys = nms_lds;
+    for (int i = threadIdx.x; i < npow2; i += blockDim.x)
+        keys[i] = i < n ? (((unsigned long long)(~f32_sortable(values[row + i]))) << 32) | (unsigned)i : ~0ull;
+    bitonic_sort_u64(keys, npow2);                                             // descending score, ties: lower position first
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int o = (int)(keys[i] & 0xffffffffull);
+        order[i] = o;
+        long q = index[row + o] / C;
+        q = q < 0 ? 0 : (q >= nq ? nq - 1 : q);                                // an index outside the row reads a wrong box, never outside the tensor
+        sb[i] = located_xyxy(boxes + ((long)b * nq + q) * 4);
+    }
+    if (threadIdx.x == 0) s_ns = 0;
+    __syncthreads();                                                           // keys are dead from here: the matrix overwrites them
+    nms_fill_matrix(mat, sb, n, W, iou_thr);
+    __syncthreads();
+    if (threadIdx.x < 64) {                                                    // nms_kernel's sweep; the kept sorted positions go to LDS
+        const int lane = threadIdx.x;
+        unsigned long long removed = 0ull;
+        int cnt = 0;
+        for (int i = 0; i < n; ++i) {
+            const unsigned long long r = __shfl(removed, i >> 6, 64);
+            if (!((r >> (i & 63)) & 1ull)) {
+                if (lane == 0) kept[cnt] = i;
+                ++cnt;
+                if (lane < W) removed |= mat[i * W + lane];
+            }
+        }
+        if (lane == 0) s_cnt = cnt;
+    }
+    __syncthreads();                                                           // the matrix is dead from here
+    const int cnt = s_cnt;
+    for (int j = threadIdx.x; j < npow2; j += blockDim.x) {
+        unsigned long long key = ~0ull;
+        if (j < cnt) {
+            const int i = kept[j];
+            if (values[row + order[i]] > score_thr) {
+                const float cx = __fmul_rn(__fadd_rn(sb[i].x, sb[i].z), 0.5f) + 0.f;          // + 0: -0 and +0 are one cx'
+                key = (((unsigned long long)f32_sortable(cx)) << 32) | (unsigned)i;
+                atomicAdd(&s_ns, 1);
+            }
+        }
+        keys[j] = key;
+    }
+    bitonic_sort_u64(keys, npow2);                                             // ascending cx', ties: lower sorted position first
+    const int ns = s_ns;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const long o = row + j;
+        if (j < ns) {
+            const int i = (int)(keys[j] & 0xffffffffull);
+            const int src = order[i];
+            const long id = index[row + src];
+            labels[o] = (int)(id % C); query[o] = (int)(id / C); score[o] = values[row + src];
+            *reinterpret_cast<float4*>(box + o * 4) = located_scale(sb[i], Wd, H);
+        } else {
+            labels[o] = -1; query[o] = -1; score[o] = 0.f;
+            *reinterpret_cast<float4*>(box + o * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if (threadIdx.x == 0) lengths[b] = ns;
 }
 
 static inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
@@ -564,5 +749,52 @@ extern "C" int dtlr_topk_flat(const float* x, float* values, long* idx_out, int 
     const size_t fl = (size_t)next_pow2(k) * 8;
     if (fl > 48 * 1024) { (void)hipFuncSetAttribute((const void*)topk_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl); (void)hipGetLastError(); }
     hipLaunchKernelGGL(topk_flat_kernel, dim3(B), dim3(1024), fl, (hipStream_t)stream, x, values, idx_out, n, k, next_pow2(k), index_bytes, apply_sigmoid);
+    return check_launch();
+}
+
+/* ---- located decoders -------------------------------------------------------------------------------------------------------- */
+extern "C" long dtlr_decode_blank_located_workspace_bytes(int B, int nq) { return (long)B * nq * 8; }
+
+extern "C" int dtlr_decode_blank_located(const float* logits, const float* boxes, float eps, const float* src_hw,
+                                         int* labels, int* query, int* rank, float* score, float* box, int* lengths,
+                                         void* workspace, int B, int nq, int C, void* stream)
+{
+    clear_stale_error();
+    if (!logits || !boxes || !labels || !query || !rank || !score || !box || !lengths || !workspace) return DTLR_EINVAL;
+    if (B <= 0 || nq <= 0 || C <= 0) return DTLR_EINVAL;
+    if (((uintptr_t)box & 15) != 0) return DTLR_EINVAL;        // the boxes are stored four floats at a time
+    const int np = next_pow2(nq);
+    if ((size_t)np * 16 > 150 * 1024) return DTLR_ESHAPE;      // dtlr_decode_blank's limit
+    const size_t lds = (size_t)np * 12;
+    (void)hipGetLastError();
+    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)decode_blank_located_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipGetLastError();
+    const long nrows = (long)B * nq;
+    int* raw = reinterpret_cast<int*>(workspace);              // [B * nq] int32 labels, then [B * nq] fp32 scores
+    float* top = reinterpret_cast<float*>(workspace) + nrows;
+    hipLaunchKernelGGL(query_label_score_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, raw, top, nrows, C, eps);
+    hipLaunchKernelGGL(decode_blank_located_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, raw, top, src_hw,
+                       labels, query, rank, score, box, lengths, nq, np);
+    return check_launch();
+}
+
+extern "C" int dtlr_decode_nms_located(const float* values, const long* index, const float* boxes, const float* src_hw,
+                                       float iou_threshold, float score_threshold,
+                                       int* labels, int* query, float* score, float* box, int* lengths,
+                                       int B, int k, int nq, int C, void* stream)
+{
+    clear_stale_error();
+    if (!values || !index || !boxes || !labels || !query || !score || !box || !lengths) return DTLR_EINVAL;
+    if (B <= 0 || k <= 0 || nq <= 0 || C <= 0) return DTLR_EINVAL;
+    if (((uintptr_t)box & 15) != 0) return DTLR_EINVAL;
+    if (k > 1024) return DTLR_ESHAPE;                          // dtlr_nms's limit: the suppression bit-matrix lives in LDS
+    const int np = next_pow2(k), W = (k + 63) / 64;
+    const size_t words = (size_t)(k * W > np ? k * W : np);
+    const size_t lds = words * 8 + (size_t)np * 16 + (size_t)np * 8;
+    if (lds > 156 * 1024) return DTLR_ESHAPE;
+    (void)hipFuncSetAttribute((const void*)decode_nms_located_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(decode_nms_located_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, values, index, boxes, src_hw,
+                       iou_threshold, score_threshold, labels, query, score, box, lengths, k, np, nq, C);
     return check_launch();
 }

@@ -26,16 +26,21 @@ from .ms_deform_attn import MSDeformAttn
 
 # ------------------------------------------------------------------------------- util/misc.py
 class NestedTensor(object):
-    def __init__(self, tensors, mask: Optional[torch.Tensor], has_padding: bool = True, sizes: Optional[List[Tuple[int, int]]] = None):
+    def __init__(self, tensors, mask: Optional[torch.Tensor], has_padding: bool = True, sizes: Optional[List[Tuple[int, int]]] = None,
+                 orig_sizes: Optional[List[Tuple[int, int]]] = None):
         self.tensors, self.mask = tensors, mask
         # host-side knowledge that mask is all-False lets the engine skip the value masked_fill
         # (ms_deform_attn.py:95-96) without a device sync; True = unknown / padded
         self.has_padding = has_padding
         # host list of every image's (h, w) inside the canvas, when the producer knows it (None = unknown)
         self.sizes = None if sizes is None else [(int(h), int(w)) for h, w in sizes]
+        # host list of every SOURCE image's (h, w) before the resize, when the producer knows it: what the located decoders scale
+        # the normalised boxes by (None = unknown)
+        self.orig_sizes = None if orig_sizes is None else [(int(h), int(w)) for h, w in orig_sizes]
 
     def to(self, device):
-        return NestedTensor(self.tensors.to(device), None if self.mask is None else self.mask.to(device), sizes=self.sizes)
+        return NestedTensor(self.tensors.to(device), None if self.mask is None else self.mask.to(device), sizes=self.sizes,
+                            orig_sizes=self.orig_sizes)
 
     def decompose(self):
         return self.tensors, self.mask

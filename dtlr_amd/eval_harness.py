@@ -179,6 +179,166 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
     return [None if int(rec[i, nq + 1]) == 1 else rec[i, : int(rec[i, nq])].tolist() for i in range(n)]
 
 
+# ------------------------------------------------------------------------------------------ located transcripts
+# One located line as ONE int32 row, floats as their bit patterns:
+#   [n chars | n words | n word labels | labels K | query K | rank K | score K | box 4K]
+#   and, for the n-gram decoder, [words K x 10 = (first char, end char, source, same, score, box x 4, n labels) | word labels 2K]
+# A rank fills the rows of other ranks' lines with ZEROS and the shards are merged with all_reduce(SUM): exactly one rank owns a line
+# and adding zeros is exact for every bit pattern (the -1 fill + MAX merge of predict_labels is not: a negative coordinate, or
+# -0.0, is a large negative int32).  The status column travels apart, with predict_labels's -1 fill and MAX.
+_LOC_HEAD = 3
+_LOC_WORD = 10                 # first char, end char (-1, -1: no characters), source (1 = ngram), same, score, box x 4, n labels
+
+
+def located_row_width(K: int, with_words: bool) -> int:
+    return _LOC_HEAD + 8 * K + ((_LOC_WORD + 2) * K if with_words else 0)
+
+
+def _f2i(values) -> np.ndarray:
+    return np.asarray(values, dtype=np.float32).reshape(-1).view(np.int32)
+
+
+def _i2f(values) -> np.ndarray:
+    return np.ascontiguousarray(values, dtype=np.int32).view(np.float32)
+
+
+def pack_located(line: "E.LocatedLine", K: int, with_words: bool) -> np.ndarray:
+    """LocatedLine -> int32 row of located_row_width(K, with_words).  Without the word table the words are rebuilt from the characters
+    on the other side (unpack_located(space_label=...))."""
+    row = np.zeros(located_row_width(K, with_words), dtype=np.int32)
+    n = len(line.chars)
+    if n > K:
+        raise ValueError(f"pack_located: {n} characters for {K} slots")
+    row[0] = n
+    o = _LOC_HEAD
+    row[o: o + n] = [c.label for c in line.chars]
+    row[o + K: o + K + n] = [c.query for c in line.chars]
+    row[o + 2 * K: o + 2 * K + n] = [-1 if c.rank is None else c.rank for c in line.chars]
+    row[o + 3 * K: o + 3 * K + n] = _f2i([c.score for c in line.chars])
+    row[o + 4 * K: o + 4 * K + 4 * n] = _f2i([c.box for c in line.chars])
+    if with_words:
+        wl = [v for w in line.words for v in w.labels]
+        if len(line.words) > K or len(wl) > 2 * K:
+            raise ValueError(f"pack_located: {len(line.words)} words / {len(wl)} word labels for {K} slots")
+        row[1], row[2] = len(line.words), len(wl)
+        o = _LOC_HEAD + 8 * K
+        for k, w in enumerate(line.words):
+            c0, c1 = w.chars if w.chars is not None else (-1, -1)
+            row[o + _LOC_WORD * k: o + _LOC_WORD * (k + 1)] = np.concatenate(
+                [np.array([c0, c1, int(w.source == "ngram"), int(w.same)], dtype=np.int32), _f2i([w.score]), _f2i(w.box),
+                 np.array([len(w.labels)], dtype=np.int32)])
+        row[o + _LOC_WORD * K: o + _LOC_WORD * K + len(wl)] = wl
+    return row
+
+
+def unpack_located(row, K: int, with_words: bool, decoder: str, space_label: Optional[int] = None) -> "E.LocatedLine":
+    row = np.asarray(row, dtype=np.int32)
+    n, o = int(row[0]), _LOC_HEAD
+    lab, qry, rk = row[o: o + n].tolist(), row[o + K: o + K + n].tolist(), row[o + 2 * K: o + 2 * K + n].tolist()
+    sc = _i2f(row[o + 3 * K: o + 3 * K + n]).tolist()
+    bx = _i2f(row[o + 4 * K: o + 4 * K + 4 * n]).reshape(n, 4).tolist()
+    chars = [E.LocatedChar(lab[i], sc[i], tuple(bx[i]), qry[i], None if rk[i] < 0 else rk[i]) for i in range(n)]
+    if not with_words:
+        return E.LocatedLine(lab, chars, E.located_words(chars, space_label), decoder)
+    nw, o = int(row[1]), _LOC_HEAD + 8 * K
+    words, at = [], o + _LOC_WORD * K
+    for k in range(nw):
+        w = row[o + _LOC_WORD * k: o + _LOC_WORD * (k + 1)]
+        nl = int(w[9])
+        words.append(E.LocatedWord(row[at: at + nl].tolist(), tuple(_i2f(w[5:9]).tolist()), float(_i2f(w[4:5])[0]),
+                                   None if w[0] < 0 else (int(w[0]), int(w[1])), "ngram" if w[2] else "kept", bool(w[3])))
+        at += nl
+    return E.LocatedLine([v for w in words for v in w.labels], chars, words, decoder)
+
+
+def merge_located(rows: torch.Tensor, status: torch.Tensor, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Merge the shards of a torch.distributed job: `rows` [n, width] int32 (zeros in the rows of other ranks' lines) by SUM,
+    `status` [n] int32 (-1 not mine, 0 decoded, 1 skipped) by MAX.  -> host tensors."""
+    import torch.distributed as dist
+    on = device if (device is not None and dist.get_backend() == "nccl") else None
+    r, st = (rows.to(on), status.to(on)) if on is not None else (rows, status)
+    dist.all_reduce(r, op=dist.ReduceOp.SUM)
+    dist.all_reduce(st, op=dist.ReduceOp.MAX)
+    return r.cpu(), st.cpu()
+
+
+@torch.no_grad()
+def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Optional[float] = None, NM: Optional[float] = None,
+                    device="cuda", size: int = EVAL_SIZE, max_size: int = EVAL_MAX_SIZE, rank: int = 0, world: int = 1,
+                    sizes: Optional[Sequence[Tuple[int, int]]] = None, skip_errors: bool = True, per_line: bool = False,
+                    ngram: Optional[Dict] = None, decoder: str = "blank", space_label: Optional[int] = None) -> List[Optional["E.LocatedLine"]]:
+    """predict_labels with every character located: one LocatedLine per image (None for a skipped line), dataset order, boxes in
+    the SOURCE image's pixels.  decoder: "blank" (eps = 0.03 / C), "nms" (TH / NM, default 0.3 / 0.5) or "ngram" (`ngram` = the bundle
+    of ngram_bundle(); words re-scored by the device beam, boxes at word level).  Batching (`exact`, padded, `per_line`), sharding and
+    error handling are predict_labels's.  pred_boxes are normalised to each line's own extent, so the source (w, h) is the whole
+    scale, for padded and ragged batches alike.  space_label: the charset's ' ' index (words are cut there), or None."""
+    if decoder not in ("blank", "nms", "ngram"):
+        raise ValueError(f"predict_located: unknown decoder {decoder!r}")
+    if decoder == "ngram" and ngram is None:
+        raise ValueError("predict_located: decoder 'ngram' needs the `ngram` bundle")
+    lazy = callable(images)
+    if lazy and sizes is None:
+        raise ValueError("predict_located: a loader callable needs `sizes`")
+    sizes = list(sizes) if sizes is not None else [im.shape[:2] for im in images]
+    n = len(sizes)
+    load = images if lazy else (lambda i: images[i])
+    batches = plan_batches(sizes, batch, exact and not per_line, size, max_size)
+    lo, hi = ddist.shard_bounds(len(batches), rank, world)
+    tf = EvalTransform(size, max_size)
+    K, with_words = model.num_queries, decoder == "ngram"
+    rows = torch.zeros((n, located_row_width(K, with_words)), dtype=torch.int32)
+    status = torch.full((n,), -1, dtype=torch.int32)
+
+    def run(idx):
+        samples = tf([load(i) for i in idx], device=device)
+        out = model(samples, per_line=True) if per_line else model(samples)
+        hw = torch.tensor(samples.orig_sizes, dtype=torch.float32)
+        if decoder == "ngram":
+            from . import ngram as NG
+            lines = NG.rescored_located_batch(out, ngram, hw, space_label)
+        elif decoder == "nms":
+            lines = E.decode_nms_located(out, 0.3 if TH is None else TH, 0.5 if NM is None else NM, hw, space_label)
+        else:
+            lines = E.decode_blank_located(out, None, hw, space_label)
+        for i, line in zip(idx, lines):
+            rows[i] = torch.from_numpy(pack_located(line, K, with_words))
+            status[i] = 0
+
+    for b in batches[lo:hi]:
+        try:
+            run(b)
+        except KeyboardInterrupt:
+            raise
+        except Exception:
+            if not skip_errors:
+                raise
+            for i in b:                                          # retry alone: only the offending line is lost
+                try:
+                    run([i])
+                except KeyboardInterrupt:
+                    raise
+                except Exception as e1:
+                    print(f"An error occurred affecting the metrics computation (line {i}: {type(e1).__name__}: {e1})", file=sys.stderr)
+                    rows[i] = 0
+                    status[i] = 1
+    if world > 1:
+        rows, status = merge_located(rows, status, device)
+    rows_np = rows.numpy()
+    return [None if int(status[i]) == 1 else unpack_located(rows_np[i], K, with_words, decoder, space_label) for i in range(n)]
+
+
+def write_layout(path: str, ids: Sequence[str], lines: Sequence[Optional["E.LocatedLine"]], charset: Sequence[str]) -> int:
+    """`--layout-out`: one JSON object per located line image (a skipped line writes none), in dataset order.  -> lines written."""
+    k = 0
+    with open(path, "w", encoding="utf-8") as f:
+        for line_id, line in zip(ids, lines):
+            if line is None:
+                continue
+            f.write(json.dumps(E.located_line_to_json(line, charset, line_id), ensure_ascii=False) + "\n")
+            k += 1
+    return k
+
+
 def evaluate_predictions(pred_labels: Sequence[Sequence[int]], gt_texts: Sequence[str], charset: Sequence, dataset: str = "IAM",
                          metrics: str = "default", unicode_charset: bool = False) -> Dict:
     """The per-sample metric bookkeeping of evaluation.py:495-581 on already decoded predictions."""
@@ -325,6 +485,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--no_uppercase_words", action="store_true")
     ap.add_argument("--no_digits", action="store_true")
     ap.add_argument("--no_dash", action="store_true")
+    ap.add_argument("--layout-out", default=None, metavar="FILE.jsonl",
+                    help="also write every line's located transcript (characters and words with boxes in source-image pixels), one JSON "
+                         "object per line image; needs a single decoder setting")
     return ap
 
 
@@ -371,10 +534,23 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     bundle = ngram_bundle(args, charset, dev)
     extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
+    if args.layout_out and len(list_TH) * len(list_NM) > 1:
+        raise SystemExit("--layout-out needs one decoder setting (--TH and --NMS, or neither), not the --NMS_inference grid")
     for TH in list_TH:
         for NM in list_NM:
-            preds = predict_labels(model, images, args.batch, args.batching == "exact", TH, NM, post, dev, args.size, args.max_size,
-                                   rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", **extra)
+            if args.layout_out:                                # the same decode with its records kept: the labels are the metrics' input
+                cs_str = [chr(c) if args.unicode else str(c) for c in charset]
+                located = predict_located(model, images, args.batch, args.batching == "exact", TH, NM, dev, args.size, args.max_size,
+                                          rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", ngram=bundle,
+                                          decoder="ngram" if bundle is not None else ("nms" if nms_inference else "blank"),
+                                          space_label=E.space_label_of(cs_str))
+                preds = [None if line is None else list(line.labels) for line in located]
+                if rank == 0:
+                    k = write_layout(args.layout_out, [name for name, _ in rows], located, cs_str)
+                    print(f"wrote {k} located lines to {args.layout_out}", file=sys.stderr)
+            else:
+                preds = predict_labels(model, images, args.batch, args.batching == "exact", TH, NM, post, dev, args.size, args.max_size,
+                                       rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", **extra)
             if rank == 0:
                 res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
                 d = write_outputs(res, args.out, args.dataset, TH, NM)

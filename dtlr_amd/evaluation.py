@@ -16,6 +16,7 @@ driver all-gathers (dtlr_amd/dist.py).
 """
 from __future__ import annotations
 
+import dataclasses
 import re
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -160,6 +161,122 @@ def decode_nms(outputs, postprocessor: Optional[PostProcess] = None, TH: float =
         order = torch.sort(boxes[sel][:, 0], descending=False)[1]
         res.append(o["labels"].long()[sel][order])
     return [[int(i) for i in r.cpu().tolist()] for r in res]
+
+
+# ------------------------------------------------------------------------------- located transcripts ("Located transcripts")
+Box = Tuple[float, float, float, float]
+
+
+@dataclasses.dataclass
+class LocatedChar:
+    """One decoded character: its label, the score the decoder gave it, its xyxy box, the query it came from and (blank decoder) its
+    rank = the query's position in the line's reading order = its frame in the n-gram emissions."""
+    label: int
+    score: float
+    box: Box
+    query: int
+    rank: Optional[int] = None
+
+
+@dataclasses.dataclass
+class LocatedWord:
+    """A word of a located line: `labels`, the union `box` and the minimum `score` of its characters, `chars` = (i0, i1), the range
+    of the line's `chars` it covers (None when it covers none), and `source`: "kept" = the detection decoder's own characters,
+    "ngram" = a span the n-gram beam re-scored (its labels are the beam's; `same` tells whether they equal the detections')."""
+    labels: List[int]
+    box: Box
+    score: float
+    chars: Optional[Tuple[int, int]]
+    source: str = "kept"
+    same: bool = True
+
+
+@dataclasses.dataclass
+class LocatedLine:
+    labels: List[int]
+    chars: List[LocatedChar]
+    words: List[LocatedWord]
+    decoder: str = "blank"
+
+    def text(self, charset: Sequence) -> str:
+        return labels_to_string(self.labels, charset)
+
+
+def union_box(boxes: Sequence[Box]) -> Box:
+    return (min(b[0] for b in boxes), min(b[1] for b in boxes), max(b[2] for b in boxes), max(b[3] for b in boxes))
+
+
+def located_words(chars: Sequence[LocatedChar], space_label: Optional[int]) -> List[LocatedWord]:
+    """A word is a maximal run of characters whose label is not `space_label`; its box is the union of theirs, its score their
+    minimum.  space_label None (scripts without a word separator): the line is one word.  An empty line has no words."""
+    words: List[LocatedWord] = []
+    start = None
+    for i in range(len(chars) + 1):
+        sep = i == len(chars) or (space_label is not None and chars[i].label == space_label)
+        if not sep and start is None:
+            start = i
+        if sep and start is not None:
+            run = chars[start:i]
+            words.append(LocatedWord([c.label for c in run], union_box([c.box for c in run]), min(c.score for c in run), (start, i)))
+            start = None
+    return words
+
+
+def space_label_of(charset: Optional[Sequence]) -> Optional[int]:
+    """the charset's ' ' index, or None"""
+    cs = list(charset) if charset is not None else []
+    return cs.index(" ") if " " in cs else None
+
+
+@torch.no_grad()
+def decode_blank_located_records(outputs, eps: Optional[float] = None, src_hw=None) -> Dict[str, torch.Tensor]:
+    """decode_blank_records with every character's record (dtlr_decode_blank_located): device tensors labels, query, rank [B,nq] int32,
+    score [B,nq] fp32, box [B,nq,4] fp32 xyxy, lengths [B] int32.  src_hw: [B,2] (h, w) of the source images -> boxes in their pixels;
+    None: normalised boxes."""
+    from . import ops
+    C = outputs["pred_logits"].shape[-1]
+    return ops.decode_blank_located(outputs["pred_logits"], outputs["pred_boxes"], 0.03 / C if eps is None else eps, src_hw)
+
+
+@torch.no_grad()
+def decode_nms_located_records(outputs, TH: float = 0.3, NM: float = 0.5, src_hw=None) -> Dict[str, torch.Tensor]:
+    """The NMS decoder (evaluation.py:94-115) of the whole batch as one device path (dtlr_topk_flat + dtlr_decode_nms_located, no host
+    round trip): device tensors labels, query [B,k] int32, score [B,k] fp32, box [B,k,4] fp32 xyxy, lengths [B] int32, k = min(900, nq)."""
+    from . import ops
+    return ops.decode_nms_located(outputs["pred_logits"], outputs["pred_boxes"], TH, NM, src_hw)
+
+
+def located_records_to_lines(rec: Dict[str, torch.Tensor], space_label: Optional[int] = None, decoder: str = "blank") -> List[LocatedLine]:
+    """located records (device or host) -> LocatedLine per line: one copy per tensor, then host lists.  A length of -1 raises like
+    records_to_lists."""
+    host = {k: v.cpu() for k, v in rec.items()}
+    ln = host["lengths"].tolist()
+    records_to_lists(host["labels"], host["lengths"])                       # raises on a line with non-finite logits
+    lab, qry, sc, bx = host["labels"].tolist(), host["query"].tolist(), host["score"].tolist(), host["box"].tolist()
+    rk = host["rank"].tolist() if "rank" in host else None
+    lines = []
+    for b, n in enumerate(ln):
+        chars = [LocatedChar(lab[b][i], sc[b][i], tuple(bx[b][i]), qry[b][i], rk[b][i] if rk is not None else None) for i in range(n)]
+        lines.append(LocatedLine(lab[b][:n], chars, located_words(chars, space_label), decoder))
+    return lines
+
+
+def decode_blank_located(outputs, eps: Optional[float] = None, src_hw=None, space_label: Optional[int] = None) -> List[LocatedLine]:
+    return located_records_to_lines(decode_blank_located_records(outputs, eps, src_hw), space_label, "blank")
+
+
+def decode_nms_located(outputs, TH: float = 0.3, NM: float = 0.5, src_hw=None, space_label: Optional[int] = None) -> List[LocatedLine]:
+    return located_records_to_lines(decode_nms_located_records(outputs, TH, NM, src_hw), space_label, "nms")
+
+
+def located_line_to_json(line: LocatedLine, charset: Sequence, line_id: str) -> Dict:
+    """The object `--layout-out` writes for one line image."""
+    cs = list(charset)
+    return {"id": line_id, "decoder": line.decoder, "text": line.text(cs),
+            "chars": [{"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query} for c in line.chars],
+            "words": [{"text": labels_to_string(w.labels, cs), "box": list(w.box), "score": w.score,
+                       "chars": list(w.chars) if w.chars is not None else None, **({"source": w.source} if line.decoder == "ngram" else {})}
+                      for w in line.words]}
 
 
 def labels_to_string(labels: Sequence[int], charset: Sequence[str]) -> str:

@@ -83,41 +83,56 @@ def get_input_split_indices(model_labels: Sequence[int], ngram_charset: Sequence
     return split, clean
 
 
-def _assemble_words(labels: Sequence[int], indices_to_ignore: Sequence[int], decode_span: Callable) -> list:
+def _assemble_words(labels: Sequence[int], indices_to_ignore: Sequence[int], decode_span: Callable, trace: Optional[list] = None) -> list:
     """The assembly of prediction_helpers.py:49-74 on one argmax row: a list of decoder words (str, from decode_span(first, end)) and
-    of separator channels (int, from the argmax)."""
+    of separator channels (int, from the argmax).  trace (the located form): a list that receives, per group of items appended,
+    (first frame, end frame, number of items, went through the decoder)."""
     ignore = set(int(i) for i in indices_to_ignore)
     split = [-1] + [i for i, v in enumerate(labels) if v in ignore] + [len(labels)]
     items: list = []
     for i in range(len(split) - 1):
         if split[i] < split[i + 1] - 1:
-            items += decode_span(split[i] + 1, split[i + 1])
+            got = decode_span(split[i] + 1, split[i + 1])
+            items += got
+            if trace is not None:
+                trace.append((split[i] + 1, split[i + 1], len(got), True))
         if split[i + 1] < len(labels):
             items.append(int(labels[split[i + 1]]))
+            if trace is not None:
+                trace.append((split[i + 1], split[i + 1] + 1, 1, False))
     return items
 
 
 def _assemble_words_2(labels: Sequence[int], indices_to_ignore: Sequence[int], ngram_charset: Sequence[str], no_uppercase_words: bool,
-                      no_digits: bool, no_dash: bool, decode_span: Callable) -> list:
-    """The assembly of prediction_helpers.py:176-224 on one argmax row: decoder words (str) and argmax channels (int)."""
+                      no_digits: bool, no_dash: bool, decode_span: Callable, trace: Optional[list] = None) -> list:
+    """The assembly of prediction_helpers.py:176-224 on one argmax row: decoder words (str) and argmax channels (int).  trace: as in
+    _assemble_words."""
     split, clean = get_input_split_indices(labels, ngram_charset, indices_to_ignore, no_uppercase_words, no_digits, no_dash)
     items: list = []
     max_added = -1
     inner, head = set(split[1:]), set(split[:-1])
     clean_set = set(clean)
+    note = (lambda lo, hi, n, dec: trace.append((lo, hi, n, dec))) if trace is not None else (lambda lo, hi, n, dec: None)
     for i in range(len(split) - 1):
         a, b = split[i], split[i + 1]
         if a in inner and a > max_added:
             items.append(int(labels[a]))
+            note(a, a + 1, 1, False)
             max_added = a
         if a < b and a in clean_set:
-            items += decode_span(a + 1, b)
+            got = decode_span(a + 1, b)
+            items += got
+            note(a + 1, b, len(got), True)
             max_added = max(b - 1, max_added)
         else:
-            items += [int(v) for v in labels[a + 1: b] if v > 0]
+            got = [int(v) for v in labels[a + 1: b] if v > 0]
+            items += got
+            if got:
+                note(a + 1, b, len(got), False)
             max_added = max(b - 1, max_added)
         if b in head and b > max_added:
             items.append(int(labels[b]))
+            note(b, b + 1, 1, False)
             max_added = b
     return items
 
@@ -422,29 +437,36 @@ class DeviceNgramDecoder:
 
 @torch.no_grad()
 def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
-                   multiply_pred_logits_by) -> List[list]:
-    """Per line: the item list of _assemble_words / _assemble_words_2 (decoder words as str, argmax channels as int)."""
+                   multiply_pred_logits_by, traces: Optional[List[list]] = None) -> List[list]:
+    """Per line: the item list of _assemble_words / _assemble_words_2 (decoder words as str, argmax channels as int).  traces: a list
+    that receives every line's trace (see _assemble_words)."""
     if not per_word_ngram:
         raise NotImplementedError("no test support for full sentence n-gram for now")      # as the reference (:108)
     emissions = get_new_pred_logits(outputs, multiply_pred_logits_by)         # [B, T, V] on the device
     rows = emissions.argmax(-1).cpu().tolist()                                # the one copy the host span logic needs
     second = bool(no_uppercase_words or no_digits)
 
-    def assemble(b, decode_span):
+    def assemble(b, decode_span, trace=None):
         if second:
-            return _assemble_words_2(rows[b], indices_to_ignore, ngram_charset, no_uppercase_words, no_digits, no_dash, decode_span)
-        return _assemble_words(rows[b], indices_to_ignore, decode_span)
+            return _assemble_words_2(rows[b], indices_to_ignore, ngram_charset, no_uppercase_words, no_digits, no_dash, decode_span, trace)
+        return _assemble_words(rows[b], indices_to_ignore, decode_span, trace)
+
+    def final(b, decode_span):
+        if traces is None:
+            return assemble(b, decode_span)
+        traces.append([])
+        return assemble(b, decode_span, traces[-1])
 
     if not isinstance(decoder, DeviceNgramDecoder):                           # any callable with torchaudio's interface: one call per span
         host = emissions.cpu()
-        return [assemble(b, lambda lo, hi, b=b: decoder(host[b, lo:hi][None, :, :])[0][0].words) for b in range(len(rows))]
+        return [final(b, lambda lo, hi, b=b: decoder(host[b, lo:hi][None, :, :])[0][0].words) for b in range(len(rows))]
     spans: List[Tuple[int, int, int]] = []
     for b in range(len(rows)):                                                # pass 1: which spans go to the decoder
         assemble(b, lambda lo, hi, b=b: spans.append((b, lo, hi)) or [])
     labels, lengths, _ = decoder.decode_spans(emissions, spans)
     labels, lengths = labels.cpu().tolist(), lengths.cpu().tolist()           # the records, one copy each
     found = {sp: decoder.words(labels[k], lengths[k]) for k, sp in enumerate(spans)}
-    return [assemble(b, lambda lo, hi, b=b: found[(b, lo, hi)]) for b in range(len(rows))]
+    return [final(b, lambda lo, hi, b=b: found[(b, lo, hi)]) for b in range(len(rows))]
 
 
 def get_ngram_predictions_batch(outputs, decoder: Callable, indices_to_ignore, charset, ngram_charset, per_word_ngram: bool = True,
@@ -469,3 +491,55 @@ def rescored_labels_batch(outputs, bundle: Dict) -> List[List[int]]:
     items = _rescore_batch(outputs, dec, bundle["ignore"], bundle["ngram_charset"], True, bundle.get("no_uppercase_words", False),
                            bundle.get("no_digits", False), bundle.get("no_dash", True), bundle.get("multiply_pred_logits_by", 1.0))
     return [[(chan[it] if isinstance(it, str) else it) - 1 for it in line if isinstance(it, str) or it > 0] for line in items]
+
+
+def rescored_located_batch(outputs, bundle: Dict, src_hw=None, space_label: Optional[int] = None) -> List["E.LocatedLine"]:
+    """rescored_labels_batch at word level, with boxes ("Located transcripts"): per line a LocatedLine whose `labels` are
+    rescored_labels_batch's, whose `chars` are the blank decoder's located characters at the emissions' eps (0.003: a character's
+    `rank` is its frame) and whose `words` are, in order, the spans the assembly emitted: source "ngram" = a span the beam
+    re-scored, "kept" = frames copied from the argmax (a separator, or a span the flags keep away from the beam).  A word's box is the
+    union of the located characters whose rank lies in its frame range; a span that holds none takes the union over all its queries.
+    `chars` = that range of the line's characters; `same` = the word's labels equal theirs (then they are the word's characters, box by
+    box).  Character boxes of a word the beam rewrote are not produced."""
+    dec = bundle["decoder"]
+    chan = {t: c for c, t in enumerate(dec.tokens)}
+    traces: List[list] = []
+    items = _rescore_batch(outputs, dec, bundle["ignore"], bundle["ngram_charset"], True, bundle.get("no_uppercase_words", False),
+                           bundle.get("no_digits", False), bundle.get("no_dash", True), bundle.get("multiply_pred_logits_by", 1.0), traces)
+    det = E.decode_blank_located(outputs, 0.003, src_hw)
+    from . import ops
+    boxes = outputs["pred_boxes"].float()
+    B = boxes.shape[0]
+    hw = ops._src_hw(src_hw, B, boxes.device)
+    from .dino import box_cxcywh_to_xyxy
+    allbox = box_cxcywh_to_xyxy(boxes)                                        # the fall-back: every query's box, PostProcess's arithmetic
+    if hw is not None:
+        allbox = allbox * torch.stack([hw[:, 1], hw[:, 0], hw[:, 1], hw[:, 0]], dim=1)[:, None, :]
+    allbox, cx = allbox.cpu(), boxes[:, :, 0].cpu()
+    lines = []
+    for b in range(B):
+        labels = [(chan[it] if isinstance(it, str) else it) - 1 for it in items[b]]
+        ranks = [c.rank for c in det[b].chars]
+        order = None
+        words, k = [], 0
+        for lo, hi, n, through in traces[b]:
+            group = labels[k: k + n]
+            k += n
+            group = [v for v in group if v >= 0]                              # rescored_labels_batch drops channel 0
+            i0 = next((i for i, r in enumerate(ranks) if r >= lo), len(ranks))
+            i1 = next((i for i, r in enumerate(ranks) if r >= hi), len(ranks))
+            if not group:
+                continue
+            if i1 > i0:
+                inside = det[b].chars[i0:i1]
+                box, score, span = E.union_box([c.box for c in inside]), min(c.score for c in inside), (i0, i1)
+                same = [c.label for c in inside] == group
+            else:
+                if order is None:                                             # reading order of ALL queries: ascending cx, lower query first
+                    order = sorted(range(cx.shape[1]), key=lambda q: (float(cx[b, q]), q))
+                box = E.union_box([tuple(allbox[b, q].tolist()) for q in order[lo:hi]])
+                score, span, same = 0.0, None, False
+            words.append(E.LocatedWord(group, box, score, span, "ngram" if through else "kept", same))
+        flat = [v for v in labels if v >= 0]
+        lines.append(E.LocatedLine(flat, det[b].chars, words, "ngram"))
+    return lines

@@ -1333,6 +1333,65 @@ def decode_blank(logits, boxes, eps: float):
     return labels, lengths
 
 
+def _src_hw(src_hw, B: int, device):
+    """None, or [B,2] fp32 (h, w) on `device`"""
+    if src_hw is None:
+        return None
+    t = torch.as_tensor(src_hw, dtype=torch.float32).to(device).contiguous()
+    if tuple(t.shape) != (B, 2):
+        raise _lib.DTLRError(f"src_hw must be [{B}, 2] (h, w), got {tuple(t.shape)}")
+    return t
+
+
+def decode_blank_located(logits, boxes, eps: float, src_hw=None):
+    """The blank/argmax decoder with every character's record (dtlr_decode_blank_located): logits [B,nq,C], boxes [B,nq,4] cxcywh,
+    src_hw [B,2] (h, w) or None = normalised boxes -> dict(labels, query, rank [B,nq] int32, score [B,nq] fp32, box [B,nq,4] fp32 xyxy,
+    lengths [B] int32), left-packed in reading order, padded with -1 / 0.  No host synchronisation."""
+    require_cuda(logits, "pred_logits")
+    B, nq, C = logits.shape
+    dev = logits.device
+    logits = logits.float().contiguous()
+    boxes = boxes.float().contiguous()
+    hw = _src_hw(src_hw, B, dev)
+    L_ = _lib.lib()
+    i32 = lambda: torch.empty((B, nq), dtype=torch.int32, device=dev)                      # noqa: E731
+    rec = dict(labels=i32(), query=i32(), rank=i32(), score=torch.empty((B, nq), dtype=torch.float32, device=dev),
+               box=torch.empty((B, nq, 4), dtype=torch.float32, device=dev), lengths=torch.empty((B,), dtype=torch.int32, device=dev))
+    ws = torch.empty(L_.dtlr_decode_blank_located_workspace_bytes(B, nq) // 4, dtype=torch.float32, device=dev)
+    code = L_.dtlr_decode_blank_located(logits.data_ptr(), boxes.data_ptr(), float(eps), hw.data_ptr() if hw is not None else None,
+                                        rec["labels"].data_ptr(), rec["query"].data_ptr(), rec["rank"].data_ptr(), rec["score"].data_ptr(),
+                                        rec["box"].data_ptr(), rec["lengths"].data_ptr(), ws.data_ptr(), B, nq, C, _lib.current_stream())
+    _lib.check(code, "dtlr_decode_blank_located")
+    return rec
+
+
+def decode_nms_located(logits, boxes, score_threshold: float, iou_threshold: float, src_hw=None):
+    """The NMS decoder of every line on the device (dtlr_topk_flat with the sigmoid folded in, then dtlr_decode_nms_located: two
+    launches, no host synchronisation): logits [B,nq,C], boxes [B,nq,4] cxcywh -> dict(labels, query [B,k] int32, score [B,k] fp32,
+    box [B,k,4] fp32 xyxy, lengths [B] int32), k = min(900, nq), ordered by the kept boxes' centre, padded with -1 / 0."""
+    require_cuda(logits, "pred_logits")
+    B, nq, C = logits.shape
+    dev = logits.device
+    logits = logits.float().contiguous()
+    boxes = boxes.float().contiguous()
+    hw = _src_hw(src_hw, B, dev)
+    k = min(900, nq)
+    L_ = _lib.lib()
+    values = torch.empty((B, k), dtype=torch.float32, device=dev)
+    index = torch.empty((B, k), dtype=torch.int64, device=dev)
+    code = L_.dtlr_topk_flat(logits.data_ptr(), values.data_ptr(), index.data_ptr(), B, nq * C, k, 1, _lib.current_stream())
+    _lib.check(code, "dtlr_topk_flat")
+    i32 = lambda: torch.empty((B, k), dtype=torch.int32, device=dev)                       # noqa: E731
+    rec = dict(labels=i32(), query=i32(), score=torch.empty((B, k), dtype=torch.float32, device=dev),
+               box=torch.empty((B, k, 4), dtype=torch.float32, device=dev), lengths=torch.empty((B,), dtype=torch.int32, device=dev))
+    code = L_.dtlr_decode_nms_located(values.data_ptr(), index.data_ptr(), boxes.data_ptr(), hw.data_ptr() if hw is not None else None,
+                                      float(iou_threshold), float(score_threshold), rec["labels"].data_ptr(), rec["query"].data_ptr(),
+                                      rec["score"].data_ptr(), rec["box"].data_ptr(), rec["lengths"].data_ptr(), B, k, nq, C,
+                                      _lib.current_stream())
+    _lib.check(code, "dtlr_decode_nms_located")
+    return rec
+
+
 def blank_emissions(logits, boxes, eps: float, scale: float = 1.0):
     """[B, nq, C+1] CTC-style emissions, blank channel first, queries in reading order (dtlr_blank_emissions: per-query sigmoid sums
     chip-wide, the decoders' cx sort per line, one wave per output row) -- get_new_pred_logits (ngram/prediction_helpers.py:5-46) /
@@ -1558,7 +1617,8 @@ def _device_scoped(fn):
 for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "l1_bottleneck", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
               "maxpool_nhwc", "groupnorm_tokens", "msda", "msda_fused", "msda_encoder", "mha", "decoder_query_prep", "box_mlp_refine",
               "box_head_refine", "box_refine", "topk_rows", "decode_blank", "preprocess_lines", "ctc_loss_interleaved", "nms_batched",
-              "topk_flat", "ctc_loss_interleaved_backward", "head_grad", "grad_norm_scale", "adamw_step", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s"):
+              "topk_flat", "ctc_loss_interleaved_backward", "head_grad", "grad_norm_scale", "adamw_step", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s",
+              "decode_blank_located", "decode_nms_located"):
     globals()[_name] = _device_scoped(globals()[_name])
 del _name
 

@@ -90,7 +90,7 @@ def preprocess_lines(images: Sequence, size: int = EVAL_SIZE, max_size: Optional
     Hc = max(d[2] for d in dims)
     Wc = max(d[3] for d in dims)
     canvas, mask = ops.preprocess_lines(flat, offs_t, dims_t, Hc, Wc, ratio, mean, std)
-    return NestedTensor(canvas, mask, sizes=[(d[2], d[3]) for d in dims])
+    return NestedTensor(canvas, mask, sizes=[(d[2], d[3]) for d in dims], orig_sizes=[(d[0], d[1]) for d in dims])
 
 
 class EvalTransform:

@@ -723,6 +723,40 @@ long dtlr_ngram_beam_workspace_bytes(int n, int Tmax, int K);
  *   n <= 1024 (DTLR_ESHAPE otherwise: the suppression bit-matrix lives in LDS). */
 int dtlr_nms(const float *boxes, const float *scores, float iou_threshold, long *keep, int *counts, int B, int n, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Located decoders ("Located transcripts"): every decoded character with the query it came from, its score and its box.
+ *
+ * dtlr_decode_blank_located: dtlr_decode_blank with the record of every kept character.  One workgroup per line.
+ *   logits [B,nq,C] fp32 ; boxes [B,nq,4] fp32 cxcywh ; src_hw [B,2] fp32 (h, w) of every line's source image, or NULL = (1, 1),
+ *   i.e. normalised boxes.  Outputs, left-packed in reading order (ascending cx, equal cx: lower query first), padded with -1 (ints)
+ *   or 0 (floats), every element written on every call:
+ *     labels [B,nq] int32 ; query [B,nq] int32 (the query's index) ; rank [B,nq] int32 (the character's position among ALL nq queries
+ *     in reading order == the frame of dtlr_blank_emissions) ; score [B,nq] fp32 (the probability of the argmax class after the blank
+ *     construction, the (1 - eps) p / s branch included; the branch is the decoder's, s is summed in fp64) ; box [B,nq,4] fp32 xyxy, 16-byte aligned ; lengths [B] int32.
+ *   box = (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h) * (W, H, W, H) with every product, sum and difference rounded on its own:
+ *   PostProcess's box for that query bit for bit (models/dino/dino.py:1016-1024).
+ *   labels / lengths are dtlr_decode_blank's bits on every line whose length is >= 0 (the per-query step is the same code); a line
+ *   with a non-finite logit has length -1 and ALL its rows padded (dtlr_decode_blank leaves that line's labels undefined).
+ *   workspace: dtlr_decode_blank_located_workspace_bytes(B, nq) bytes.  Shape limit: dtlr_decode_blank's (DTLR_ESHAPE beyond).
+ *
+ * dtlr_decode_nms_located: the NMS decoder (evaluation.py:94-115; scripts: --NMS 0.5 --TH 0.3) of every line, one workgroup per line,
+ *   no host round trip.
+ *   values [B,k] fp32, index [B,k] int64: the flat top-k of dtlr_topk_flat(apply_sigmoid = 1) over [B, nq C] ; boxes [B,nq,4] cxcywh.
+ *   Entry i: query = index / C, label = index % C, box = the query's normalised xyxy box (rounded as above).  Greedy NMS with
+ *   dtlr_nms's semantics on the normalised boxes (descending score, equal scores: lower position first, dropped when IoU with a kept
+ *   entry > iou_threshold) ; keep score > score_threshold ; order by cx' = (x0 + x1) / 2 ascending, equal cx': the entry earlier in
+ *   descending-score order first ; box out = the normalised box * (W, H, W, H).
+ *   labels, query [B,k] int32, score [B,k] fp32, box [B,k,4] fp32 (16-byte aligned), lengths [B] int32, padded as above.
+ *   k <= 1024 (DTLR_ESHAPE beyond).  An index outside [0, nq C) reads a wrong box, never outside `boxes`. */
+long dtlr_decode_blank_located_workspace_bytes(int B, int nq);
+int dtlr_decode_blank_located(const float *logits, const float *boxes, float eps, const float *src_hw,
+                              int *labels, int *query, int *rank, float *score, float *box, int *lengths,
+                              void *workspace, int B, int nq, int C, void *stream);
+int dtlr_decode_nms_located(const float *values, const long *index, const float *boxes, const float *src_hw,
+                            float iou_threshold, float score_threshold,
+                            int *labels, int *query, float *score, float *box, int *lengths,
+                            int B, int k, int nq, int C, void *stream);
+
 /* k largest of each row of a [B, n] fp32 matrix that is too long for LDS, descending, equal values: lower index first.
  * Replaces: `torch.topk(prob.view(B, -1), num_select, dim=1)` of PostProcess (models/dino/dino.py:1000-1006), with the sigmoid
  *           folded in (apply_sigmoid: the selection runs on the logits, values are returned as sigmoid(logit)).
