@@ -26,6 +26,7 @@ def _assert(cond: bool, msg: str) -> None:
         raise RuntimeError(msg)
 
 
+@_lib.op
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
     if not value.is_cuda:
         raise RuntimeError("Not implemented on the CPU")            # ms_deform_attn.h:38
@@ -48,12 +49,8 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     lt = torch.float32 if value.dtype in (torch.bfloat16, torch.float16) else value.dtype
     _assert(sampling_loc.dtype == lt and attn_weight.dtype == lt, "sampling_loc / attn_weight dtype mismatch")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-    with torch.cuda.device(value.device):
-        code = _lib.lib(value.dtype).dtlr_msda_forward(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                            sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                                            N, S, M, D, L, Lq, P, _DT[value.dtype], out.data_ptr(),
-                                            _lib.current_stream())
-    _lib.check(code, "dtlr_msda_forward")
+    _lib.launch(_lib.lib(value.dtype), "dtlr_msda_forward", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, _DT[value.dtype], out.data_ptr())
     return out
 
 

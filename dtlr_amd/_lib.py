@@ -3,8 +3,14 @@ object is missing or a symbol is absent, importing/using the product path raises
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from ctypes import c_char_p, c_int, c_int64, c_void_p, c_float, POINTER
+
+# torch must own the process's HIP runtime: libdtlr_hip.so NEEDs libamdhip64.so.7 and, loaded first, would pull a second runtime
+# from /opt/rocm beside torch's bundled one (kernels then launch on a runtime that has no device initialised: hipErrorNoDevice).
+# Importing torch before any CDLL() makes the loader resolve our dependency to the copy torch already mapped.
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # DTLR_HIP_LIB: profiling tools point this at the instrumented build (dtlr_amd/build.py --instr)
@@ -168,11 +174,6 @@ def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise DTLRError(f"{path} not built: run `python -m dtlr_amd.build` (needs hipcc); "
                         "the DTLR HIP path has no CPU/PyTorch fallback")
-    # torch must own the process's HIP runtime: libdtlr_hip.so NEEDs libamdhip64.so.7 and, loaded
-    # first, would pull a second runtime from /opt/rocm beside torch's bundled one (kernels then
-    # launch on a runtime that has no device initialised: hipErrorNoDevice).  Importing torch
-    # first makes the loader resolve our dependency to the copy torch already mapped.
-    import torch  # noqa: F401
     L = ctypes.CDLL(path)                  # RTLD_LOCAL: the two builds export the same symbol names and never see each other
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(L, name)          # AttributeError if the .so is stale -> loud
@@ -183,12 +184,10 @@ def _load(path: str) -> ctypes.CDLL:
 def lib(dtype=None) -> ctypes.CDLL:
     """libdtlr_hip.so (fp32 / fp64 / bf16 operands), or -- lib(torch.float16) -- libdtlr_hip_f16.so (fp16 operands)."""
     global _lib, _lib_f16
-    if dtype is not None:
-        import torch
-        if dtype == torch.float16:
-            if _lib_f16 is None:
-                _lib_f16 = _load(LIB_PATH_F16)
-            return _lib_f16
+    if dtype is not None and dtype == torch.float16:
+        if _lib_f16 is None:
+            _lib_f16 = _load(LIB_PATH_F16)
+        return _lib_f16
     if _lib is None:
         _lib = _load(LIB_PATH)
     return _lib
@@ -198,9 +197,11 @@ def declared_symbols():
     return list(_SIGNATURES)
 
 
-def check(code: int, what: str) -> None:
+def check(code: int, what: str, L=None) -> None:
+    """DTLRError for a non-zero code.  L: the library that returned it (the two builds keep separate last-HIP-error slots); default the
+    bf16 build."""
     if code != 0:
-        L = lib()
+        L = L or lib()
         msg = L.dtlr_strerror(code).decode()
         raise DTLRError(f"{what}: {msg} (code {code}, hip error {L.dtlr_last_hip_error()})")
 
@@ -210,5 +211,47 @@ def ptr(t) -> int:
 
 
 def current_stream() -> int:
-    import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+# ---------------------------------------------------------------------------------------------
+# The launch seam.  A binding names its symbol once, as the string handed to one of these three; which of them it uses states
+# whether the entry point takes a stream (include/dtlr_hip.h: `void *stream` is then its last parameter).
+def launch(L, name: str, *args) -> None:
+    """L.<name>(*args, current stream): an entry point that enqueues work.  DTLRError, in L's words, on a non-zero code.  Every
+    launch of the forward passes here (a single line is ~200 dependent launches, dispatch-bound), hence current_stream() written out
+    and one tuple built."""
+    code = getattr(L, name)(*(args + (torch.cuda.current_stream().cuda_stream,)))
+    if code:
+        check(code, name, L)
+
+
+def call(L, name: str, *args) -> None:
+    """L.<name>(*args): an entry point that returns a code and takes no stream (the host packers)."""
+    code = getattr(L, name)(*args)
+    if code:
+        check(code, name, L)
+
+
+def query(L, name: str, *args):
+    """L.<name>(*args) -> its value, unchecked: sizes, pad counts, `*_supported`, plan checks (no stream, nothing enqueued)."""
+    return getattr(L, name)(*args)
+
+
+def op(fn):
+    """Decorator of every binding that reaches the library with tensors: it runs with the device of its FIRST tensor argument
+    current (not whatever device happens to be), so that `launch` picks up that device's current stream -- a model moved to cuda:1
+    while cuda:0 is current would otherwise enqueue device-1 pointers on a device-0 stream.  One integer compare per call when the
+    devices already agree."""
+    Tensor, current_device, device = torch.Tensor, torch.cuda.current_device, torch.cuda.device
+
+    @functools.wraps(fn)
+    def wrapper(*args, **kwargs):
+        for t in args:
+            if isinstance(t, Tensor):
+                if t.is_cuda and t.device.index != current_device():
+                    with device(t.device):
+                        return fn(*args, **kwargs)
+                break
+        return fn(*args, **kwargs)
+    return wrapper

@@ -5,6 +5,11 @@ Each operator is the seam behind which a hand-written gfx950 kernel sits (libdtl
 dtlr_amd._lib).  Operators that do not have their HIP kernel yet are listed in `LIBRARY_BACKED`
 and call the ROCm libraries through torch (rocBLAS/hipBLASLt GEMM, MIOpen conv) -- still GPU-only:
 nothing here runs on the CPU and nothing imports the oracle.
+
+The seam itself is three rules (dtlr_amd/_lib.py): a binding that enqueues work carries `@_lib.op`, which makes the
+device of its first tensor argument current for the call; it reaches the library through `_lib.launch` (appends that device's current
+stream), `_lib.call` (host packers: no stream) or `_lib.query` (sizes, pad counts, plan checks: a value, not a code); and the symbol is
+named once, as the string handed to that helper, which is also the name an error reports -- in the words of the library that was called.
 """
 from __future__ import annotations
 
@@ -36,6 +41,7 @@ class SplitWeight(torch.Tensor):
     row slices of an image are images of the same rows (the default __torch_function__ keeps the subclass); its VALUES mean nothing to torch."""
 
 
+@_lib.op
 def split_pack(w):
     """fp32 weight [N, K] (nn.Linear) or [Cout, KH, KW, Cin] (NHWC convolution), K (resp. KH*KW*Cin) a multiple of 32, on the GPU ->
     SplitWeight of the same shape (dtlr_split_pack_weights)."""
@@ -46,8 +52,7 @@ def split_pack(w):
     if K % 32:
         raise _lib.DTLRError(f"ops.split_pack: K = {K} is not a multiple of 32")
     out = torch.empty_like(w)
-    code = _lib.lib().dtlr_split_pack_weights(w.data_ptr(), out.data_ptr(), rows, K, _lib.current_stream())
-    _lib.check(code, "dtlr_split_pack_weights")
+    _lib.launch(_lib.lib(), "dtlr_split_pack_weights", w.data_ptr(), out.data_ptr(), rows, K)
     return out.as_subclass(SplitWeight)
 
 
@@ -83,16 +88,17 @@ def require_cuda(t: torch.Tensor, what: str = "input") -> None:
     _lib.lib()      # raises if libdtlr_hip.so is missing
 
 
+@_lib.op
 def workspace_reserve(dtype, nbytes: int = 128 << 20) -> None:
     """Pre-size the current stream's scratch workspace of the library serving `dtype` (split-K partial tiles, hidden-split FFN parts:
     include/dtlr_hip.h, dtlr_workspace_reserve) -- outside stream capture, so that a later captured forward allocates nothing and takes the
     same kernels as an eager one.  128 MiB covers every shape of a 32-line batch (the largest user: 8 parts x 12288 rows x 1 KB)."""
-    _lib.check(_L(dtype).dtlr_workspace_reserve(int(nbytes), _lib.current_stream()), "dtlr_workspace_reserve")
+    _lib.launch(_L(dtype), "dtlr_workspace_reserve", int(nbytes))
 
 
 def workspace_retired_bytes(dtype=None) -> int:
     """bytes of replaced workspace buffers the library keeps allocated (a captured graph may still hold their addresses)"""
-    return int(_L(dtype if dtype is not None else torch.float32).dtlr_workspace_retired_bytes())
+    return int(_lib.query(_L(dtype if dtype is not None else torch.float32), "dtlr_workspace_retired_bytes"))
 
 
 # --------------------------------------------------------------------------------------------
@@ -127,6 +133,7 @@ class _Timed:
         return False
 
 
+@_lib.op
 def linear(x, w, b=None, relu=False, residual=None, a2=None, row_mask=None, out_dtype=None):
     """y = epilogue((x [+ a2]) @ w.T): + b -> ReLU (relu=True/1) or exact GELU (relu=3) -> zero rows where row_mask -> + residual
     -> ReLU (relu=2, the ResNet bottleneck tail).
@@ -152,9 +159,8 @@ def linear(x, w, b=None, relu=False, residual=None, a2=None, row_mask=None, out_
         es = x.element_size()
         with _Timed(_gkind(x, w), 2.0 * M * N * K,
                     float(M) * K * es + float(R2) * K * es + float(N) * K * es + float(M) * N * es, f"linear M{M} N{N} K{K}+a2bcast{R2}"):
-            code = _L(x).dtlr_gemm_nt_a2bcast(x.data_ptr(), a2.data_ptr(), R2, w.data_ptr(), 0 if b is None else b.data_ptr(), y.data_ptr(),
-                                                   M, N, K, _in_dt(x, w), _lib.current_stream())
-        _lib.check(code, "dtlr_gemm_nt_a2bcast")
+            _lib.launch(_L(x), "dtlr_gemm_nt_a2bcast", x.data_ptr(), a2.data_ptr(), R2, w.data_ptr(), 0 if b is None else b.data_ptr(), y.data_ptr(),
+                        M, N, K, _in_dt(x, w))
         return y
     if x.dtype in H16 + (torch.float32,) and w.dtype == x.dtype and K % slab == 0 \
             and (x.dtype in H16 or out_dtype == torch.float32):
@@ -172,16 +178,15 @@ def linear(x, w, b=None, relu=False, residual=None, a2=None, row_mask=None, out_
         nbytes = float(M) * K * es * (2 if a2 is not None else 1) + float(N) * K * es + float(M) * N * eo * (2 if residual is not None else 1)
         tag = f"linear M{M} N{N} K{K}" + ("+a2" if a2 is not None else "") + ("+res" if residual is not None else "") + ("" if out_dtype == x.dtype else "->f32")
         with _Timed(_gkind(x, w), 2.0 * M * N * K, nbytes, tag):
-            code = _L(x).dtlr_gemm_nt(x.data_ptr(), 0 if a2 is None else a2.data_ptr(), w.data_ptr(),
-                                           0 if b is None else b.data_ptr(), 0 if residual is None else residual.data_ptr(),
-                                           0 if row_mask is None else row_mask.data_ptr(), y.data_ptr(),
-                                           M, N, K, int(relu), _in_dt(x, w), _DT[out_dtype], _lib.current_stream())
-        _lib.check(code, "dtlr_gemm_nt")
+            _lib.launch(_L(x), "dtlr_gemm_nt", x.data_ptr(), 0 if a2 is None else a2.data_ptr(), w.data_ptr(), 0 if b is None else b.data_ptr(),
+                        0 if residual is None else residual.data_ptr(), 0 if row_mask is None else row_mask.data_ptr(), y.data_ptr(), M, N, K,
+                        int(relu), _in_dt(x, w), _DT[out_dtype])
         return y
     raise _lib.DTLRError(f"ops.linear: no HIP kernel for x {tuple(x.shape)} {x.dtype} @ w {tuple(w.shape)} {w.dtype} -> {out_dtype} "
                          f"(K must be a multiple of {slab} elements; fp32 operands give fp32 results); there is no library fallback")
 
 
+@_lib.op
 def linear_resbcast(x, w, resid, b=None):
     """x @ w.T [+ b] + resid[row % R]: `linear` with a row-BROADCAST residual (dtlr_gemm_nt_resbcast).  x [..., K] (M rows in all), w [N, K]
     (same dtype, or a SplitWeight for fp32 x), resid [R, N] in the output dtype with M % R == 0.  The encoder's [offsets | logits] projection of
@@ -197,9 +202,8 @@ def linear_resbcast(x, w, resid, b=None):
     y = torch.empty(x.shape[:-1] + (N,), dtype=x.dtype, device=x.device)
     es = x.element_size()
     with _Timed(_gkind(x, w), 2.0 * M * N * K, float(M) * K * es + float(N) * K * es + float(M) * N * es + float(R) * N * es, f"linear M{M} N{N} K{K}+resb{R}"):
-        code = _L(x).dtlr_gemm_nt_resbcast(x.data_ptr(), w.data_ptr(), 0 if b is None else b.data_ptr(), resid.data_ptr(), R, y.data_ptr(),
-                                           M, N, K, _in_dt(x, w), _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_nt_resbcast")
+        _lib.launch(_L(x), "dtlr_gemm_nt_resbcast", x.data_ptr(), w.data_ptr(), 0 if b is None else b.data_ptr(), resid.data_ptr(), R, y.data_ptr(),
+                    M, N, K, _in_dt(x, w))
     return y
 
 
@@ -213,6 +217,7 @@ def k256_pack(w):
     return w.detach().to(_hdt(w)).view(8, nrt, 16, 8, 4, 8).permute(0, 1, 3, 4, 2, 5).contiguous().view(-1)
 
 
+@_lib.op
 def gemm_k256(x, wp, n_out: int, b=None, resid=None, row_mask=None, out=None):
     """Weight-resident streaming projection (dtlr_gemm_k256): y = x @ W.T + b [+ resid[m % rows]] with padded rows zeroed.
     x [..., 256] bf16 contiguous; wp = k256_pack(W); resid [rows, n_out] bf16; row_mask [...] bool/uint8;
@@ -237,10 +242,8 @@ def gemm_k256(x, wp, n_out: int, b=None, resid=None, row_mask=None, out=None):
         assert row_mask.numel() == M and row_mask.is_contiguous() and row_mask.dtype in (torch.bool, torch.uint8)
     nbytes = float(M) * 256 * 2 + float(n_out) * 256 * 2 + float(M) * n_out * 2
     with _Timed("gemm_bf16", 2.0 * M * n_out * 256, nbytes, f"k256 M{M} N{n_out} K256" + ("+resb" if resid is not None else "")):
-        code = _L(x).dtlr_gemm_k256(x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
-                                         0 if resid is None else resid.data_ptr(), 0 if resid is None else resid.numel() // n_out,
-                                         0 if row_mask is None else row_mask.data_ptr(), out.data_ptr(), ldc, M, n_out, _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_k256")
+        _lib.launch(_L(x), "dtlr_gemm_k256", x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(), 0 if resid is None else resid.data_ptr(),
+                    0 if resid is None else resid.numel() // n_out, 0 if row_mask is None else row_mask.data_ptr(), out.data_ptr(), ldc, M, n_out)
     return out
 
 
@@ -264,6 +267,7 @@ def kres_pack(w, np_pairs=None):
     return v.permute(0, 1, 2, 4, 6, 7, 3, 5, 8).contiguous().view(-1)             # sl, wave, p, e, ks, [g, mh, ml] = lane, x
 
 
+@_lib.op
 def gemm_kres(x, wp, n_out: int, b=None, residual=None, relu: bool = False):
     """relu?(x @ W.T + b + residual) with the weight resident in registers and the rows of x / residual streamed through LDS
     (dtlr_gemm_kres); wp = kres_pack(W).  x [..., K] bf16, residual [..., n_out] bf16 or None."""
@@ -280,13 +284,12 @@ def gemm_kres(x, wp, n_out: int, b=None, residual=None, relu: bool = False):
     out = torch.empty(x.shape[:-1] + (n_out,), dtype=x.dtype, device=x.device)
     nbytes = float(M) * K * 2 + float(n_out) * K * 2 + float(M) * n_out * 2 * (2 if residual is not None else 1)
     with _Timed("gemm_bf16", 2.0 * M * n_out * K, nbytes, f"kres M{M} N{n_out} K{K}" + ("+res" if residual is not None else "")):
-        code = _L(x).dtlr_gemm_kres(x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
-                                         0 if residual is None else residual.data_ptr(), out.data_ptr(), M, n_out, K, 1 if relu else 0,
-                                         _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_kres")
+        _lib.launch(_L(x), "dtlr_gemm_kres", x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
+                    0 if residual is None else residual.data_ptr(), out.data_ptr(), M, n_out, K, 1 if relu else 0)
     return out
 
 
+@_lib.op
 def gemm_kres_chain(x, wp, b=None, x2=None, residual=None, relu: bool = True, wp2=None, b2=None, n2: int = 0):
     """A layer1 bottleneck tail chained with its neighbours (dtlr_gemm_kres_chain):
         y  = relu?([x | x2] @ W.T + b (+ residual))     x [..., 64]; exactly one of x2 [..., 64] (first bottleneck: the 1x1 shortcut
@@ -317,11 +320,9 @@ def gemm_kres_chain(x, wp, b=None, x2=None, residual=None, relu: bool = True, wp
     nbytes = float(M) * K * 2 + 256.0 * K * 2 + float(M) * 256 * 2 * (2 if residual is not None else 1) + (float(M) * n2 * 2 + 512.0 * n2 if t is not None else 0.0)
     flops = 2.0 * M * 256 * K + (2.0 * M * n2 * 256 if t is not None else 0.0)
     with _Timed("gemm_bf16", flops, nbytes, f"kres_chain M{M} K{K}" + ("+res" if residual is not None else "+cat") + (f" ->N{n2}" if t is not None else "")):
-        code = _L(x).dtlr_gemm_kres_chain(x.data_ptr(), 0 if x2 is None else x2.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
-                                          0 if residual is None else residual.data_ptr(), y.data_ptr(), M, 1 if relu else 0,
-                                          0 if wp2 is None else wp2.data_ptr(), 0 if b2 is None else b2.data_ptr(),
-                                          0 if t is None else t.data_ptr(), n2, _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_kres_chain")
+        _lib.launch(_L(x), "dtlr_gemm_kres_chain", x.data_ptr(), 0 if x2 is None else x2.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
+                    0 if residual is None else residual.data_ptr(), y.data_ptr(), M, 1 if relu else 0, 0 if wp2 is None else wp2.data_ptr(),
+                    0 if b2 is None else b2.data_ptr(), 0 if t is None else t.data_ptr(), n2)
     return y, t
 
 
@@ -329,6 +330,7 @@ L1_BLOCK_SEG = 64          # columns per workgroup of dtlr_l1_bottleneck (== LB_
 L1_BLOCK_ROUND = 256       # its workgroups that run at once: one per CU of an MI355X (145 KB of LDS each)
 
 
+@_lib.op
 def l1_bottleneck(x, w1p, b1, w2, b2, w3p, b3, wnp=None, bn=None, n2: int = 0, out=None, next_out=None):
     """One whole layer1 bottleneck in one launch (dtlr_l1_bottleneck), the 64-channel intermediates kept on chip:
         t1 = relu(x @ W1.T + b1); t2 = relu(conv3x3(t1, W2, pad 1) + b2)           (both rounded to 16 bit)
@@ -360,13 +362,13 @@ def l1_bottleneck(x, w1p, b1, w2, b2, w3p, b3, wnp=None, bn=None, n2: int = 0, o
     nbytes = float(M) * (cin + 256 + n2) * 2 + (64.0 * cin + 64 * 576 + 256 * (128 if cin == 64 else 64) + 256 * n2) * 2
     flops = 2.0 * M * (64 * cin + 64 * 576 + 256 * (128 if cin == 64 else 64) + 256 * n2)
     with _Timed("gemm_bf16", flops, nbytes, f"l1_block M{M} C{cin}" + (f" ->N{n2}" if n2 else "")):
-        code = _L(x).dtlr_l1_bottleneck(x.data_ptr(), cin, w1p.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3p.data_ptr(), b3.data_ptr(),
-                                        out.data_ptr(), wnp.data_ptr() if n2 else 0, bn.data_ptr() if n2 else 0, next_out.data_ptr() if n2 else 0,
-                                        n2, B, H, W, _lib.current_stream())
-    _lib.check(code, "dtlr_l1_bottleneck")
+        _lib.launch(_L(x), "dtlr_l1_bottleneck", x.data_ptr(), cin, w1p.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3p.data_ptr(),
+                    b3.data_ptr(), out.data_ptr(), wnp.data_ptr() if n2 else 0, bn.data_ptr() if n2 else 0, next_out.data_ptr() if n2 else 0, n2, B,
+                    H, W)
     return out, (next_out if n2 else None)
 
 
+@_lib.op
 def gemm_kres_cat_s2(t, x, wp, b=None, relu: bool = True):
     """layer2's first bottleneck tail with the strided shortcut convolution as extra K columns (dtlr_gemm_kres_cat_s2):
         y[b, i, j] = relu?([t[b, i, j] | x[b, 2 i, 2 j]] @ W.T + b),   W = [W3 | Wd] [512, 384], b = b3 + bd
@@ -382,9 +384,8 @@ def gemm_kres_cat_s2(t, x, wp, b=None, relu: bool = True):
     y = torch.empty((B, Hout, Wout, 512), dtype=t.dtype, device=t.device)
     M = B * Hout * Wout
     with _Timed("gemm_bf16", 2.0 * M * 512 * 384, float(M) * (128 + 256 + 512) * 2 + 512.0 * 384 * 2, f"kres_cat_s2 M{M} N512 K128+256s2"):
-        code = _L(t).dtlr_gemm_kres_cat_s2(t.data_ptr(), x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(), y.data_ptr(),
-                                           B, Hin, Win, 1 if relu else 0, _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_kres_cat_s2")
+        _lib.launch(_L(t), "dtlr_gemm_kres_cat_s2", t.data_ptr(), x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(), y.data_ptr(), B, Hin,
+                    Win, 1 if relu else 0)
     return y
 
 
@@ -395,6 +396,7 @@ def kres_pack_bcast384(w):
     return kres_pack(wpad, np_pairs=2)
 
 
+@_lib.op
 def gemm_kres_bcast384(x, wp, resid):
     """x @ W.T + resid[m % rows] for W [384, 256]: the weight-resident streaming kernel with the row-broadcast residual DMA'd through LDS
     (dtlr_gemm_kres_bcast384); wp = kres_pack_bcast384(W); resid [rows, 384] bf16, rows % 64 == 0, M % rows == 0."""
@@ -407,11 +409,11 @@ def gemm_kres_bcast384(x, wp, resid):
     out = torch.empty(x.shape[:-1] + (384,), dtype=x.dtype, device=x.device)
     nbytes = float(M) * 256 * 2 + 384.0 * 256 * 2 + float(M) * 384 * 2
     with _Timed("gemm_bf16", 2.0 * M * 384 * 256, nbytes, f"kres M{M} N384 K256+resb"):
-        code = _L(x).dtlr_gemm_kres_bcast384(x.data_ptr(), wp.data_ptr(), resid.data_ptr(), rows, out.data_ptr(), M, _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_kres_bcast384")
+        _lib.launch(_L(x), "dtlr_gemm_kres_bcast384", x.data_ptr(), wp.data_ptr(), resid.data_ptr(), rows, out.data_ptr(), M)
     return out
 
 
+@_lib.op
 def linear_rowmax(x, w, b=None):
     """max over the output channels of (x @ w.T + b), without materialising the product (dtlr_gemm_nt_rowmax: the GEMM's
     row-max epilogue): x [..., K], w [N, K] (same dtype, 16-bit or fp32), b [N] fp32 -> [...] fp32.  The two-stage selection
@@ -434,12 +436,12 @@ def linear_rowmax(x, w, b=None):
     es = x.element_size()
     with _Timed(_gkind(x, w), 2.0 * M * N * K, float(M) * K * es + float(N) * K * es + 4.0 * M,
                 f"rowmax M{M} N{N} K{K}"):
-        code = _L(x).dtlr_gemm_nt_rowmax_lda(x.data_ptr(), lda, w.data_ptr(), 0 if b is None else b.data_ptr(), out.data_ptr(),
-                                             M, N, K, _in_dt(x, w), _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_nt_rowmax_lda")
+        _lib.launch(_L(x), "dtlr_gemm_nt_rowmax_lda", x.data_ptr(), lda, w.data_ptr(), 0 if b is None else b.data_ptr(), out.data_ptr(), M, N, K,
+                    _in_dt(x, w))
     return out
 
 
+@_lib.op
 def two_stage_gather(om, proposals, idx):
     """The gathers after the two-stage top-k in one launch (dtlr_two_stage_gather).  om [B,S,768] bf16 ([hi|lo|hi]) or [B,S,256]
     fp32; proposals [B,S,4] fp32; idx [B,k] int64 -> (sel_raw like om with S -> k, sel_x [B,k,256] bf16 = bf16(hi+lo) or None,
@@ -455,13 +457,12 @@ def two_stage_gather(om, proposals, idx):
     sel_x = torch.empty((B, k, 256), dtype=om.dtype, device=om.device) if split else None
     prop_sel = torch.empty((B, k, 4), dtype=torch.float32, device=om.device)
     init_box = torch.empty((B, k, 4), dtype=torch.float32, device=om.device)
-    code = _L(om).dtlr_two_stage_gather(om.data_ptr(), proposals.data_ptr(), idx.data_ptr(), sel_raw.data_ptr(),
-                                            None if sel_x is None else sel_x.data_ptr(), prop_sel.data_ptr(), init_box.data_ptr(),
-                                            B, S, k, _DT[om.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_two_stage_gather")
+    _lib.launch(_L(om), "dtlr_two_stage_gather", om.data_ptr(), proposals.data_ptr(), idx.data_ptr(), sel_raw.data_ptr(),
+                None if sel_x is None else sel_x.data_ptr(), prop_sel.data_ptr(), init_box.data_ptr(), B, S, k, _DT[om.dtype])
     return sel_raw, sel_x, prop_sel, init_box
 
 
+@_lib.op
 def layernorm(x, w, b, eps: float = 1e-5, residual=None):
     """LayerNorm(x [+ residual]) over the last dim (HIP kernel: one wavefront per row, fp32 stats).
     x/residual [..., C] fp32 or bf16, contiguous; w, b [C] fp32."""
@@ -472,23 +473,23 @@ def layernorm(x, w, b, eps: float = 1e-5, residual=None):
         residual = residual.contiguous()
     y = torch.empty_like(x)
     rows = x.numel() // C
-    code = _L(x).dtlr_layernorm(x.data_ptr(), 0 if residual is None else residual.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                     y.data_ptr(), rows, C, eps, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_layernorm")
+    _lib.launch(_L(x), "dtlr_layernorm", x.data_ptr(), 0 if residual is None else residual.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), rows,
+                C, eps, _DT[x.dtype])
     return y
 
 
+@_lib.op
 def proj_pack_w(w):
     """[256,256] projection weight (bf16, any device) -> the fragment-major image dtlr_proj_ln_bf16 streams (bf16, same device)."""
     import numpy as np
     assert tuple(w.shape) == (256, 256)
     src = np.ascontiguousarray(w.detach().to(_hdt(w)).cpu().view(torch.int16).numpy()).view(np.uint16)
     out = np.empty(256 * 256, dtype=np.uint16)
-    code = _L(w).dtlr_proj_pack_weights(src.ctypes.data, out.ctypes.data)
-    _lib.check(code, "dtlr_proj_pack_weights")
+    _lib.call(_L(w), "dtlr_proj_pack_weights", src.ctypes.data, out.ctypes.data)
     return torch.from_numpy(out.view(np.int16)).view(_hdt(w)).to(w.device)
 
 
+@_lib.op
 def proj_ln(a, wp, b, residual, ln_w, ln_b, eps: float = 1e-5):
     """LayerNorm(residual + a W^T + b) in ONE kernel (dtlr_proj_ln_bf16): the attention block's output projection with its
     post-norm; a, residual [..., 256] bf16, wp = proj_pack_w(W) (bf16, 65536 elements), b / LN params fp32."""
@@ -500,9 +501,8 @@ def proj_ln(a, wp, b, residual, ln_w, ln_b, eps: float = 1e-5):
     y = torch.empty_like(residual)
     M = a.numel() // 256
     with _Timed("proj_ln_bf16", 2.0 * M * 256 * 256, 3.0 * M * 256 * 2 + 256 * 256 * 2):
-        code = _L(a).dtlr_proj_ln_bf16(a.data_ptr(), wp.data_ptr(), b.data_ptr(), residual.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-                                            eps, y.data_ptr(), M, 256, _lib.current_stream())
-    _lib.check(code, "dtlr_proj_ln_bf16")
+        _lib.launch(_L(a), "dtlr_proj_ln_bf16", a.data_ptr(), wp.data_ptr(), b.data_ptr(), residual.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), eps,
+                    y.data_ptr(), M, 256)
     return y
 
 
@@ -513,6 +513,7 @@ def proj_ln_k256_pack(w):
     return w.detach().to(_hdt(w)).view(8, 4, 2, 4, 8, 4, 8).permute(0, 2, 4, 5, 1, 3, 6).contiguous().view(-1)
 
 
+@_lib.op
 def proj_ln_k256(a, wp, b, residual, ln_w, ln_b, eps: float = 1e-5):
     """LayerNorm(residual + a W^T + b) for many rows (dtlr_proj_ln_k256: weights resident in registers, the a / residual tiles DMA'd
     through an LDS ring); wp = proj_ln_k256_pack(W).  Same result as proj_ln up to fp32 summation order in the statistics."""
@@ -523,12 +524,12 @@ def proj_ln_k256(a, wp, b, residual, ln_w, ln_b, eps: float = 1e-5):
     y = torch.empty_like(residual)
     M = a.numel() // 256
     with _Timed("proj_ln_bf16", 2.0 * M * 256 * 256, 3.0 * M * 256 * 2 + 256 * 256 * 2):
-        code = _L(a).dtlr_proj_ln_k256(a.data_ptr(), wp.data_ptr(), b.data_ptr(), residual.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-                                            eps, y.data_ptr(), M, _lib.current_stream())
-    _lib.check(code, "dtlr_proj_ln_k256")
+        _lib.launch(_L(a), "dtlr_proj_ln_k256", a.data_ptr(), wp.data_ptr(), b.data_ptr(), residual.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), eps,
+                    y.data_ptr(), M)
     return y
 
 
+@_lib.op
 def proj_ln_split(a, wp, b, keep, ln_w, ln_b, eps: float = 1e-5):
     """LayerNorm(Linear(a with rows where keep == 0 zeroed)) written as [hi | lo | hi] bf16 (dtlr_proj_ln_split_bf16): a [..., 256]
     bf16, wp = proj_pack_w(W), keep [...] uint8/bool or None -> [..., 768] bf16.  hi + lo reproduces the fp32 LayerNorm output to
@@ -543,9 +544,8 @@ def proj_ln_split(a, wp, b, keep, ln_w, ln_b, eps: float = 1e-5):
         assert keep.numel() == M and keep.is_cuda
     y = torch.empty(a.shape[:-1] + (768,), dtype=a.dtype, device=a.device)
     with _Timed("proj_ln_bf16", 2.0 * M * 256 * 256, 4.0 * M * 256 * 2 + 256 * 256 * 2):
-        code = _L(a).dtlr_proj_ln_split_bf16(a.data_ptr(), wp.data_ptr(), b.data_ptr(), keep.data_ptr() if keep is not None else None,
-                                                  ln_w.data_ptr(), ln_b.data_ptr(), eps, y.data_ptr(), M, 256, _lib.current_stream())
-    _lib.check(code, "dtlr_proj_ln_split_bf16")
+        _lib.launch(_L(a), "dtlr_proj_ln_split_bf16", a.data_ptr(), wp.data_ptr(), b.data_ptr(), keep.data_ptr() if keep is not None else None,
+                    ln_w.data_ptr(), ln_b.data_ptr(), eps, y.data_ptr(), M, 256)
     return y
 
 
@@ -575,7 +575,7 @@ def head_ts_pack(w, b, dtype=torch.bfloat16):
     N = w.shape[0]
     assert w.dim() == 2 and w.shape[1] == 256 and dtype in H16
     nc = -(-N // 32)
-    pad = int(_lib.lib().dtlr_head_ts_pad_chunks())
+    pad = int(_lib.query(_lib.lib(), "dtlr_head_ts_pad_chunks"))
     wf = torch.zeros((nc * 32, 256), dtype=torch.float32, device=w.device)
     wf[:N] = w.float()
     hi = wf.to(dtype)
@@ -594,6 +594,7 @@ def head_ts_supported(N: int, mode: str) -> bool:
     return N <= (15360 if mode == "logits" else 24576) and (mode != "logits" or N % 4 == 0)
 
 
+@_lib.op
 def head_ts(x, img, bias, N: int, mode: str, a_off: int = 0, b_off=None):
     """Token-stationary class head (dtlr_head_ts): x [..., ldx] 16-bit rows; the 256-wide operand A = x[..., a_off:a_off+256] and, when b_off is
     given, B = x[..., b_off:b_off+256] (three products A.Whi + B.Whi + A.Wlo: x = proj_ln_split's [hi | lo | hi] image with a_off 0, b_off 256)
@@ -604,13 +605,12 @@ def head_ts(x, img, bias, N: int, mode: str, a_off: int = 0, b_off=None):
     M = x.numel() // ldx
     nprod = 3 if b_off is not None else 2
     nc = -(-N // 32)
-    assert bias.numel() == nc * 32 and img.numel() == (nc + int(_lib.lib().dtlr_head_ts_pad_chunks())) * 16384, "(img, bias) is not head_ts_pack of this N"
+    assert bias.numel() == nc * 32 and img.numel() == (nc + int(_lib.query(_lib.lib(), "dtlr_head_ts_pad_chunks"))) * 16384, "(img, bias) is not head_ts_pack of this N"
     out = torch.empty(x.shape[:-1] + ((N,) if mode == "logits" else ()), dtype=torch.float32, device=x.device)
     with _Timed(_gkind(x, img), 2.0 * M * N * 256 * nprod, float(M) * 256 * 2 * (nprod - 1) + float(N) * 512 * 2 + 4.0 * M * (N if mode == "logits" else 1),
                 f"head_ts {mode} M{M} N{N} x{nprod}"):
-        code = _L(x).dtlr_head_ts(x.data_ptr(), ldx, a_off, 0 if b_off is None else b_off, img.data_ptr(), bias.data_ptr(), N, nprod,
-                                  1 if mode == "logits" else 0, out.data_ptr(), M, _lib.current_stream())
-    _lib.check(code, "dtlr_head_ts")
+        _lib.launch(_L(x), "dtlr_head_ts", x.data_ptr(), ldx, a_off, 0 if b_off is None else b_off, img.data_ptr(), bias.data_ptr(), N, nprod,
+                    1 if mode == "logits" else 0, out.data_ptr(), M)
     return out
 
 
@@ -641,6 +641,7 @@ def ffn32_pack(w1, w2):
     return torch.cat([a, pad]).contiguous().view(-1), torch.cat([b, pad]).contiguous().view(-1)
 
 
+@_lib.op
 def ffn32(x, w1p, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     """LayerNorm(x + relu(x W1^T + b1) W2^T + b2) for many rows (dtlr_ffn32_bf16: 32x32x16 MFMAs, one wave per SIMD, 256 rows per
     workgroup); (w1p, w2p) = ffn32_pack(W1, W2).  Same result as ffn_fused up to fp32 summation order."""
@@ -653,12 +654,12 @@ def ffn32(x, w1p, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     assert y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
     M = x.numel() // 256
     with _Timed("ffn_fused_bf16", 4.0 * M * 256 * d_ff, 2.0 * M * 256 * 2 + 2.0 * 256 * d_ff * 2, symbol="ffn3_bf16_kernel<0>"):
-        code = _L(x).dtlr_ffn32_bf16(x.data_ptr(), w1p.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(),
-                                          ln_w.data_ptr(), ln_b.data_ptr(), eps, y.data_ptr(), M, d_ff, _lib.current_stream())
-    _lib.check(code, "dtlr_ffn32_bf16")
+        _lib.launch(_L(x), "dtlr_ffn32_bf16", x.data_ptr(), w1p.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), ln_w.data_ptr(),
+                    ln_b.data_ptr(), eps, y.data_ptr(), M, d_ff)
     return y
 
 
+@_lib.op
 def ffn4(x, w1p, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     """LayerNorm(x + relu(x W1^T + b1) W2^T + b2) for any number of rows as ONE persistent launch (dtlr_ffn4_bf16, round 6: two 128-row tiles
     per workgroup half a period apart over a cyclic weight stream; epilogues and loads under the other tile's MFMAs); (w1p, w2p) =
@@ -672,12 +673,12 @@ def ffn4(x, w1p, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     assert y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
     M = x.numel() // 256
     with _Timed("ffn_fused_bf16", 4.0 * M * 256 * d_ff, 2.0 * M * 256 * 2 + 2.0 * 256 * d_ff * 2, symbol="ffn4_bf16_kernel"):
-        code = _L(x).dtlr_ffn4_bf16(x.data_ptr(), w1p.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(),
-                                    ln_w.data_ptr(), ln_b.data_ptr(), eps, y.data_ptr(), M, d_ff, _lib.current_stream())
-    _lib.check(code, "dtlr_ffn4_bf16")
+        _lib.launch(_L(x), "dtlr_ffn4_bf16", x.data_ptr(), w1p.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), ln_w.data_ptr(),
+                    ln_b.data_ptr(), eps, y.data_ptr(), M, d_ff)
     return y
 
 
+@_lib.op
 def ffn_fused(x, w1, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     """LayerNorm(x + relu(x W1^T + b1) W2^T + b2) in ONE kernel (dtlr_ffn_fused_bf16): the [M, d_ff]
     intermediate never reaches HBM.  x [..., 256] bf16; W1 [d_ff,256] bf16; w2p = ffn_pack_w2(W2) ([d_ff/32,256,32] bf16);
@@ -696,10 +697,8 @@ def ffn_fused(x, w1, b1, w2p, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     hidden_split = (M + 127) // 128 <= 96 and w1.shape[0] >= 512 and min(8, 256 // ((M + 127) // 128), (w1.shape[0] // 32) // 8) >= 2
     sym = "ffn2_bf16_kernel<3>" if 32768 < M <= 49152 else ("ffn_fused_bf16_kernel<0, false, false>" if (M <= 32768 and not hidden_split) else None)
     with _Timed("ffn_fused_bf16", 4.0 * M * x.shape[-1] * w1.shape[0], 2.0 * M * 256 * 2 + 2.0 * w1.numel() * 2, symbol=sym):
-        code = _L(x).dtlr_ffn_fused_bf16(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(),
-                                              ln_w.data_ptr(), ln_b.data_ptr(), eps, y.data_ptr(), M, x.shape[-1], w1.shape[0],
-                                              _lib.current_stream())
-    _lib.check(code, "dtlr_ffn_fused_bf16")
+        _lib.launch(_L(x), "dtlr_ffn_fused_bf16", x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), ln_w.data_ptr(),
+                    ln_b.data_ptr(), eps, y.data_ptr(), M, x.shape[-1], w1.shape[0])
     return y
 
 
@@ -712,7 +711,7 @@ def ffn_split_pack(w1, w2):
     d_ff = w1.shape[0]
     assert tuple(w1.shape) == (d_ff, 256) and tuple(w2.shape) == (256, d_ff) and d_ff % 32 == 0 and 32 <= d_ff <= 2048
     nc = d_ff // 32
-    total = ((nc + 1) & ~1) + int(_lib.lib().dtlr_ffn_split_pad_chunks())
+    total = ((nc + 1) & ~1) + int(_lib.query(_lib.lib(), "dtlr_ffn_split_pad_chunks"))
     w1f, w2f = w1.detach().float(), w2.detach().float()
     parts = []
     for wf, kind in ((w1f, 1), (w2f, 2)):
@@ -728,6 +727,7 @@ def ffn_split_pack(w1, w2):
     return out.view(torch.uint8).reshape(-1)
 
 
+@_lib.op
 def ffn_split(x, wp, b1, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     """LayerNorm(x + relu(x W1^T + b1) W2^T + b2) for fp32 rows in ONE kernel, every product as three fp16 MFMAs on hi + lo halves
     (dtlr_ffn_split: the split-fp32 engine's FFN block; the [M, d_ff] intermediate never reaches HBM).  x [..., 256] fp32;
@@ -735,7 +735,7 @@ def ffn_split(x, wp, b1, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     require_cuda(x, "x")
     d_ff = b1.numel()
     assert x.dtype == torch.float32 and x.shape[-1] == 256 and wp.dtype == torch.uint8 and d_ff % 32 == 0
-    assert wp.numel() == ((((d_ff // 32) + 1) & ~1) + int(_lib.lib().dtlr_ffn_split_pad_chunks())) * 65536, "wp is not ffn_split_pack(W1, W2) of this d_ff"
+    assert wp.numel() == ((((d_ff // 32) + 1) & ~1) + int(_lib.query(_lib.lib(), "dtlr_ffn_split_pad_chunks"))) * 65536, "wp is not ffn_split_pack(W1, W2) of this d_ff"
     x = x if x.is_contiguous() else x.contiguous()
     y = torch.empty_like(x) if out is None else out
     assert y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
@@ -747,12 +747,12 @@ def ffn_split(x, wp, b1, b2, ln_w, ln_b, eps: float = 1e-5, out=None):
     nc2 = ((d_ff // 32) + 1) & ~1
     ns = min(4, 256 // rem, nc2 // 8) if (rem > 0 and full > 0) else 1
     with _Timed("ffn_fused_f32s", 4.0 * M * 256 * d_ff, 2.0 * M * 256 * 4 + 2.0 * 256 * d_ff * 4, symbol="ffn_split_kernel<false>" if ns < 2 else None):
-        code = _lib.lib().dtlr_ffn_split(x.data_ptr(), wp.data_ptr(), b1.data_ptr(), b2.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-                                         eps, y.data_ptr(), M, d_ff, _lib.current_stream())
-    _lib.check(code, "dtlr_ffn_split")
+        _lib.launch(_lib.lib(), "dtlr_ffn_split", x.data_ptr(), wp.data_ptr(), b1.data_ptr(), b2.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), eps,
+                    y.data_ptr(), M, d_ff)
     return y
 
 
+@_lib.op
 def k256s_pack(w):
     """fp32 [256, 256] weight on the GPU -> the resident-operand image of dtlr_gemm_k256s (int16 [2 x 65536]: hi then lo fp16 halves in MFMA
     fragment order; dtlr_k256s_pack_weights)."""
@@ -760,10 +760,11 @@ def k256s_pack(w):
     assert tuple(w.shape) == (256, 256)
     w = w.detach().float().contiguous()
     out = torch.empty(2 * 65536, dtype=torch.int16, device=w.device)
-    _lib.check(_lib.lib().dtlr_k256s_pack_weights(w.data_ptr(), out.data_ptr(), _lib.current_stream()), "dtlr_k256s_pack_weights")
+    _lib.launch(_lib.lib(), "dtlr_k256s_pack_weights", w.data_ptr(), out.data_ptr())
     return out
 
 
+@_lib.op
 def gemm_k256s(x, wp, b, residual=None, row_mask=None, ln_w=None, ln_b=None, eps: float = 1e-5):
     """The split-fp32 engine's weight-resident streaming K = N = 256 projection (dtlr_gemm_k256s).  x [..., 256] fp32, wp = k256s_pack(W).
     no LN params:  x W^T + b with the rows flagged in row_mask (bool [M], optional) written as zeros (value_proj + masked_fill);
@@ -784,13 +785,13 @@ def gemm_k256s(x, wp, b, residual=None, row_mask=None, ln_w=None, ln_b=None, eps
     nbytes = float(M) * 256 * 4 * (3 if residual is not None else 2) + 2.0 * 65536 * 2
     tag = f"k256s M{M}" + ("+res+ln" if residual is not None else "+ln" if ln_w is not None else "")
     with _Timed("gemm_f32s", 2.0 * M * 256 * 256, nbytes, tag):
-        code = _lib.lib().dtlr_gemm_k256s(x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(), 0 if residual is None else residual.data_ptr(),
-                                          0 if row_mask is None else row_mask.data_ptr(), 0 if ln_w is None else ln_w.data_ptr(),
-                                          0 if ln_b is None else ln_b.data_ptr(), eps, y.data_ptr(), M, _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_k256s")
+        _lib.launch(_lib.lib(), "dtlr_gemm_k256s", x.data_ptr(), wp.data_ptr(), 0 if b is None else b.data_ptr(),
+                    0 if residual is None else residual.data_ptr(), 0 if row_mask is None else row_mask.data_ptr(),
+                    0 if ln_w is None else ln_w.data_ptr(), 0 if ln_b is None else ln_b.data_ptr(), eps, y.data_ptr(), M)
     return y
 
 
+@_lib.op
 def gemm_k256s_multi(x, slices, row_mask=None, res_rows: int = 0):
     """ONE pass over x [..., 256] fp32 for several projections of it (dtlr_gemm_k256s_multi; split-fp32 engine).  slices: list of dicts
     {wp: k256s_pack image of the slice's weight zero-padded to [256, 256], out: fp32 view [..., n] (last dim contiguous, any row stride),
@@ -825,11 +826,11 @@ def gemm_k256s_multi(x, slices, row_mask=None, res_rows: int = 0):
     if row_mask is not None:
         assert row_mask.numel() == M and row_mask.dtype in (torch.bool, torch.uint8) and row_mask.is_contiguous()
     with _Timed("gemm_f32s", 2.0 * M * 256 * ncols, nbytes, f"k256s_multi M{M} N{ncols}x{len(slices)}"):
-        code = _lib.lib().dtlr_gemm_k256s_multi(x.data_ptr(), M, ctypes.addressof(arr), len(slices), 0 if row_mask is None else row_mask.data_ptr(),
-                                                int(res_rows), _lib.current_stream())
-    _lib.check(code, "dtlr_gemm_k256s_multi")
+        _lib.launch(_lib.lib(), "dtlr_gemm_k256s_multi", x.data_ptr(), M, ctypes.addressof(arr), len(slices),
+                    0 if row_mask is None else row_mask.data_ptr(), int(res_rows))
 
 
+@_lib.op
 def conv2d_nhwc(x, w, bias, stride: int, padding: int, relu=False, residual=None):
     """NHWC convolution + folded-BN bias [+ residual] [+ ReLU].  x [B,H,W,Cin] contiguous.
     w: [Cout,KH,KW,Cin] contiguous ("OHWI") -> the implicit-GEMM HIP kernel (dtlr_conv2d_nhwc), which
@@ -847,17 +848,16 @@ def conv2d_nhwc(x, w, bias, stride: int, padding: int, relu=False, residual=None
         nbytes = (float(x.numel()) / (stride * stride if KH == 1 else 1) + float(w.numel()) + float(B) * Ho * Wo * Cout * (2 if residual is not None else 1)) * es
         tag = f"conv{KH}x{KW}s{stride} M{B * Ho * Wo} N{Cout} K{KH * KW * Cin}" + ("+res" if residual is not None else "")
         with _Timed(_gkind(x, w), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin, nbytes, tag):
-            code = _L(x).dtlr_conv2d_nhwc(x.data_ptr(), w.data_ptr(), 0 if bias is None else bias.data_ptr(),
-                                               0 if residual is None else residual.data_ptr(), y.data_ptr(),
-                                               B, H, W, Cin, Cout, KH, KW, stride, padding, 2 if relu else 0,
-                                               _in_dt(x, w), _lib.current_stream())
-        _lib.check(code, "dtlr_conv2d_nhwc")
+            _lib.launch(_L(x), "dtlr_conv2d_nhwc", x.data_ptr(), w.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                        0 if residual is None else residual.data_ptr(), y.data_ptr(), B, H, W, Cin, Cout, KH, KW, stride, padding, 2 if relu else 0,
+                        _in_dt(x, w))
         return y
     raise _lib.DTLRError(f"ops.conv2d_nhwc: no HIP kernel for x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)} (weights must be "
                          "[Cout,KH,KW,Cin] contiguous with Cin * element size a multiple of 128 bytes; the 3-channel stem has its "
                          "own kernels: stem_conv7x7 / stem_conv7x7_f32); there is no library fallback")
 
 
+@_lib.op
 def stem_pack_weights(w_oihw, dtype=torch.bfloat16):
     """conv1.weight with the FrozenBN scale folded, [64,3,7,7] (any float dtype, any device) -> the 24 KB fragment-major
     bf16 weight image dtlr_stem_conv7x7 keeps in registers (uint16 tensor on the CPU; move it to the device once)."""
@@ -865,8 +865,7 @@ def stem_pack_weights(w_oihw, dtype=torch.bfloat16):
     w = np.ascontiguousarray(w_oihw.detach().float().cpu().numpy())
     assert w.shape == (64, 3, 7, 7)
     out = np.zeros(4 * 6 * 64 * 8, dtype=np.uint16)
-    code = _L(dtype).dtlr_stem_pack_weights(w.ctypes.data, out.ctypes.data)
-    _lib.check(code, "dtlr_stem_pack_weights")
+    _lib.call(_L(dtype), "dtlr_stem_pack_weights", w.ctypes.data, out.ctypes.data)
     return torch.from_numpy(out.view(np.int16)).clone()
 
 
@@ -877,6 +876,7 @@ def stem_pack_weights_f32(w_oihw):
     return w_oihw.detach().float().reshape(64, 147).t().contiguous()
 
 
+@_lib.op
 def stem_conv7x7_f32(x_nchw, wk):
     """ResNet stem 7x7/s2/p3 convolution 3 -> 64 in exact fp32 (the parity engine; HIP kernel dtlr_stem_conv7x7_f32, direct
     convolution on the vector ALUs with the patch and the weights in LDS): x [B,3,H,W] fp32 NCHW -> [B,Ho,Wo,64] fp32 NHWC, no
@@ -886,8 +886,7 @@ def stem_conv7x7_f32(x_nchw, wk):
     x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
     B, _, H, W = x.shape
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), dtype=torch.float32, device=x.device)
-    code = _L(x_nchw).dtlr_stem_conv7x7_f32(x.data_ptr(), wk.data_ptr(), y.data_ptr(), B, H, W, _lib.current_stream())
-    _lib.check(code, "dtlr_stem_conv7x7_f32")
+    _lib.launch(_L(x_nchw), "dtlr_stem_conv7x7_f32", x.data_ptr(), wk.data_ptr(), y.data_ptr(), B, H, W)
     return y
 
 
@@ -899,6 +898,7 @@ def stem_pack_weights_split(w_oihw):
     return stem_pack_weights(hi, torch.float16), stem_pack_weights(wf - hi, torch.float16)
 
 
+@_lib.op
 def stem_conv7x7_f32s(x_nchw, wfrag_hi, wfrag_lo):
     """ResNet stem 7x7/s2/p3 convolution 3 -> 64 for the split-fp32 engine (dtlr_stem_conv7x7_f32s: the MFMA formulation of stem_conv7x7
     with the image and the weights as fp16 hi + lo halves, three MFMAs per product): x [B,3,H,W] fp32 NCHW -> [B,Ho,Wo,64] fp32 NHWC, no bias."""
@@ -908,11 +908,11 @@ def stem_conv7x7_f32s(x_nchw, wfrag_hi, wfrag_lo):
     x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
     B, _, H, W = x.shape
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), dtype=torch.float32, device=x.device)
-    code = _lib.lib().dtlr_stem_conv7x7_f32s(x.data_ptr(), wfrag_hi.data_ptr(), wfrag_lo.data_ptr(), y.data_ptr(), B, H, W, _lib.current_stream())
-    _lib.check(code, "dtlr_stem_conv7x7_f32s")
+    _lib.launch(_lib.lib(), "dtlr_stem_conv7x7_f32s", x.data_ptr(), wfrag_hi.data_ptr(), wfrag_lo.data_ptr(), y.data_ptr(), B, H, W)
     return y
 
 
+@_lib.op
 def stem_conv7x7(x_nchw, wfrag, out_dtype=torch.bfloat16):
     """ResNet stem 7x7/s2/p3 convolution 3 -> 64 on the bf16 MFMA (HIP kernel): x [B,3,H,W] fp32 NCHW -> [B,Ho,Wo,64] bf16
     NHWC, no bias (the max-pool pass applies the folded-BN shift + ReLU)."""
@@ -921,11 +921,11 @@ def stem_conv7x7(x_nchw, wfrag, out_dtype=torch.bfloat16):
     x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
     B, _, H, W = x.shape
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), dtype=out_dtype, device=x.device)
-    code = _L(out_dtype).dtlr_stem_conv7x7(x.data_ptr(), wfrag.data_ptr(), y.data_ptr(), B, H, W, _DT[out_dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_stem_conv7x7")
+    _lib.launch(_L(out_dtype), "dtlr_stem_conv7x7", x.data_ptr(), wfrag.data_ptr(), y.data_ptr(), B, H, W, _DT[out_dtype])
     return y
 
 
+@_lib.op
 def stem_conv7x7_pool(x_nchw, wfrag, bias, out_dtype=torch.bfloat16):
     """conv1 (7x7/s2/p3, folded-BN scale in the weights) + shift + ReLU + 3x3/s2/p1 max-pool in ONE kernel (dtlr_stem_conv7x7_pool, 16-bit
     engines): x [B,3,H,W] fp32 NCHW -> [B,Hp,Wp,64] NHWC.  The full-resolution 64-channel map never reaches HBM."""
@@ -935,36 +935,35 @@ def stem_conv7x7_pool(x_nchw, wfrag, bias, out_dtype=torch.bfloat16):
     B, _, H, W = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((B, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1, 64), dtype=out_dtype, device=x.device)
-    code = _L(out_dtype).dtlr_stem_conv7x7_pool(x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W, _DT[out_dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_stem_conv7x7_pool")
+    _lib.launch(_L(out_dtype), "dtlr_stem_conv7x7_pool", x.data_ptr(), wfrag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W, _DT[out_dtype])
     return y
 
 
+@_lib.op
 def maxpool_nhwc(x, k: int = 3, stride: int = 2, padding: int = 1, bias=None, relu: bool = False):
     """3x3/s2/p1 max pooling on NHWC (HIP kernel); with bias/relu: maxpool(relu(x + bias)) in the same pass."""
     assert (k, stride, padding) == (3, 2, 1)
     B, H, W, C = x.shape
     x = x if x.is_contiguous() else x.contiguous()
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
-    code = _L(x).dtlr_maxpool3x3s2_nhwc(x.data_ptr(), y.data_ptr(), 0 if bias is None else bias.data_ptr(), 1 if relu else 0,
-                                             B, H, W, C, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_maxpool3x3s2_nhwc")
+    _lib.launch(_L(x), "dtlr_maxpool3x3s2_nhwc", x.data_ptr(), y.data_ptr(), 0 if bias is None else bias.data_ptr(), 1 if relu else 0, B, H, W, C,
+                _DT[x.dtype])
     return y
 
 
+@_lib.op
 def groupnorm_tokens(x, groups: int, w, b, eps: float = 1e-5, out=None):
     """GroupNorm(32, 256) over [B, T, C] tokens of one feature level: statistics per (sample,
     group) over (C/groups channels x T positions) -- models/dino/dino.py:121-134 (HIP kernels)."""
     B, T, C = x.shape
     x = x if x.is_contiguous() else x.contiguous()
     L_ = _L(x)
-    ws = torch.empty(L_.dtlr_groupnorm_workspace_bytes(B, T), dtype=torch.uint8, device=x.device)
+    ws = torch.empty(_lib.query(L_, "dtlr_groupnorm_workspace_bytes", B, T), dtype=torch.uint8, device=x.device)
     # out: a [B, T, C] slice (dim 1) of a larger contiguous [B, S, C] token matrix -- the level is normalised straight into place
     y = torch.empty_like(x) if out is None else out
     assert y.shape == x.shape and y.dtype == x.dtype and y.stride(2) == 1 and y.stride(1) == C
-    code = L_.dtlr_groupnorm_tokens_strided(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), ws.data_ptr(),
-                                            B, T, C, groups, eps, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_groupnorm_tokens")
+    _lib.launch(L_, "dtlr_groupnorm_tokens_strided", x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), ws.data_ptr(), B, T, C,
+                groups, eps, _DT[x.dtype])
     return y
 
 
@@ -973,6 +972,7 @@ def groupnorm_tokens(x, groups: int, w, b, eps: float = 1e-5, out=None):
 MSDA_EVENTS = None
 
 
+@_lib.op
 def msda(value, spatial_shapes, level_start_index, loc, attn):
     """value [N,S,M,D]; loc [N,Lq,M,L,P,2] f32; attn [N,Lq,M,L,P] f32 -> [N,Lq,M*D] (HIP kernel)."""
     if MSDA_EVENTS is None:
@@ -986,6 +986,7 @@ def msda(value, spatial_shapes, level_start_index, loc, attn):
     return out
 
 
+@_lib.op
 def msda_fused(value, spatial_shapes, level_start_index, ow, ref):
     """MSDeformAttn front end fused into the sampling kernel (L=4, P=4): value [N,S,M,D] (fp32/bf16),
     ow [N,Lq,M*48] raw [offsets|logits] projection (fp32, or bf16 with bf16 value),
@@ -1004,10 +1005,8 @@ def msda_fused(value, spatial_shapes, level_start_index, ow, ref):
         st = torch.cuda.current_stream()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(st)
-    code = _L(value).dtlr_msda_fused_forward_strided(value.data_ptr(), vs[1], spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                                      ow.data_ptr(), ref.data_ptr(), ref.shape[-1], N, S, M, D, L, Lq, 4,
-                                                      _DT[value.dtype], _DT[ow.dtype], out.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_msda_fused_forward_strided")
+    _lib.launch(_L(value), "dtlr_msda_fused_forward_strided", value.data_ptr(), vs[1], spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                ow.data_ptr(), ref.data_ptr(), ref.shape[-1], N, S, M, D, L, Lq, 4, _DT[value.dtype], _DT[ow.dtype], out.data_ptr())
     if ev is not None:
         b.record(st)
         ev.append((a, b, N, Lq, S))
@@ -1021,6 +1020,7 @@ def _check_ext(ext, B):
     assert ext.is_cuda and ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2) and ext.is_contiguous()
 
 
+@_lib.op
 def swin_patch_embed(x_nchw, w_kE, b, ln_w, ln_b, out_dtype, eps: float = 1e-5, ext=None):
     """PatchEmbed of a Swin backbone (dtlr_swin_patch_embed): x [B,3,H,W] fp32 -> [B, ceil(H/4), ceil(W/4), E] out_dtype
     (4x4/s4 convolution with zero padding + LayerNorm).  w_kE [48, E] fp32 = proj.weight.reshape(E, 48).t().
@@ -1034,16 +1034,15 @@ def swin_patch_embed(x_nchw, w_kE, b, ln_w, ln_b, out_dtype, eps: float = 1e-5, 
     out = torch.empty((B, (H + 3) // 4, (W + 3) // 4, E), dtype=out_dtype, device=x.device)
     if ext is not None:
         _check_ext(ext, B)
-        code = _L(out_dtype).dtlr_swin_patch_embed_ext(x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), out.data_ptr(),
-                                                       ext.data_ptr(), B, H, W, E, eps, _DT[out_dtype], _lib.current_stream())
-        _lib.check(code, "dtlr_swin_patch_embed_ext")
+        _lib.launch(_L(out_dtype), "dtlr_swin_patch_embed_ext", x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+                    out.data_ptr(), ext.data_ptr(), B, H, W, E, eps, _DT[out_dtype])
         return out
-    code = _L(out_dtype).dtlr_swin_patch_embed(x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), out.data_ptr(),
-                                            B, H, W, E, eps, _DT[out_dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_swin_patch_embed")
+    _lib.launch(_L(out_dtype), "dtlr_swin_patch_embed", x.data_ptr(), w_kE.data_ptr(), b.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), out.data_ptr(),
+                B, H, W, E, eps, _DT[out_dtype])
     return out
 
 
+@_lib.op
 def swin_window_attn(qkv, qkv_bias, rpb, n_heads: int, window: int, shift: int, ext=None, s: Optional[int] = None):
     """Attention core of a Swin block (dtlr_swin_window_attn): qkv [B,H,W,3C] -> [B,H,W,C]; rpb = swin_dense_bias(table, window).
     ext, s (per-line batches: dtlr_swin_window_attn_ext): padding, roll, mask regions and crop of every line at its own stride-2^s
@@ -1055,13 +1054,11 @@ def swin_window_attn(qkv, qkv_bias, rpb, n_heads: int, window: int, shift: int, 
     out = torch.empty((B, H, W, C), dtype=qkv.dtype, device=qkv.device)
     if ext is not None:
         _check_ext(ext, B)
-        code = _L(qkv).dtlr_swin_window_attn_ext(qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), ext.data_ptr(), int(s),
-                                                 B, H, W, C, n_heads, window, shift, _DT[qkv.dtype], _lib.current_stream())
-        _lib.check(code, "dtlr_swin_window_attn_ext")
+        _lib.launch(_L(qkv), "dtlr_swin_window_attn_ext", qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), ext.data_ptr(), int(s),
+                    B, H, W, C, n_heads, window, shift, _DT[qkv.dtype])
         return out
-    code = _L(qkv).dtlr_swin_window_attn(qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), B, H, W, C, n_heads, window, shift,
-                                            _DT[qkv.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_swin_window_attn")
+    _lib.launch(_L(qkv), "dtlr_swin_window_attn", qkv.data_ptr(), qkv_bias.data_ptr(), rpb.data_ptr(), out.data_ptr(), B, H, W, C, n_heads, window,
+                shift, _DT[qkv.dtype])
     return out
 
 
@@ -1081,6 +1078,7 @@ def swin_dense_bias(table, window: int):
     return out.contiguous()
 
 
+@_lib.op
 def swin_patch_merge(x, ln_w, ln_b, eps: float = 1e-5, ext=None, s: Optional[int] = None):
     """PatchMerging up to its LayerNorm (dtlr_swin_patch_merge): x [B,H,W,C] -> [B, ceil(H/2), ceil(W/2), 4C].
     ext, s (per-line batches: dtlr_swin_patch_merge_ext; s = the stride exponent of x): zeros for every input position outside a
@@ -1091,18 +1089,17 @@ def swin_patch_merge(x, ln_w, ln_b, eps: float = 1e-5, ext=None, s: Optional[int
     y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, 4 * C), dtype=x.dtype, device=x.device)
     if ext is not None:
         _check_ext(ext, B)
-        code = _L(x).dtlr_swin_patch_merge_ext(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), ext.data_ptr(), int(s),
-                                               B, H, W, C, eps, _DT[x.dtype], _lib.current_stream())
-        _lib.check(code, "dtlr_swin_patch_merge_ext")
+        _lib.launch(_L(x), "dtlr_swin_patch_merge_ext", x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), ext.data_ptr(), int(s), B, H, W,
+                    C, eps, _DT[x.dtype])
         return y
-    code = _L(x).dtlr_swin_patch_merge(x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), B, H, W, C, eps, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_swin_patch_merge")
+    _lib.launch(_L(x), "dtlr_swin_patch_merge", x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), B, H, W, C, eps, _DT[x.dtype])
     return y
 
 
 _POS_TABLES = {}
 
 
+@_lib.op
 def geometry(mask, level_hw, level_embed, temperature_h: float, temperature_w: float, pos_dtype):
     """Everything that depends only on the padding mask, in one launch (dtlr_geometry): per-level masks, valid ratios,
     sine position embedding + level embedding, encoder reference points, proposals and their validity.
@@ -1127,10 +1124,9 @@ def geometry(mask, level_hw, level_embed, temperature_h: float, temperature_w: f
     vr = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
     enc_ref = torch.empty((B, S, 4, 2), dtype=torch.float32, device=dev)
     prop = torch.empty((B, S, 4), dtype=torch.float32, device=dev)
-    code = _L(pos_dtype).dtlr_geometry(mask.data_ptr(), B, H, W, ctypes.cast(hw, ctypes.c_void_p), level_embed.data_ptr(),
-                                    dim_ty.data_ptr(), dim_tx.data_ptr(), _DT[pos_dtype], mask_flat.data_ptr(), keep.data_ptr(),
-                                    pos.data_ptr(), vr.data_ptr(), enc_ref.data_ptr(), prop.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_geometry")
+    _lib.launch(_L(pos_dtype), "dtlr_geometry", mask.data_ptr(), B, H, W, ctypes.cast(hw, ctypes.c_void_p), level_embed.data_ptr(), dim_ty.data_ptr(),
+                dim_tx.data_ptr(), _DT[pos_dtype], mask_flat.data_ptr(), keep.data_ptr(), pos.data_ptr(), vr.data_ptr(), enc_ref.data_ptr(),
+                prop.data_ptr())
     return dict(mask_flat=mask_flat, keep=keep, pos=pos, valid_ratios=vr, enc_ref=enc_ref, proposals=prop)
 
 
@@ -1138,12 +1134,14 @@ def msda_encoder_fits(level_hw, dtype, halo: Optional[int] = None) -> bool:
     """Whether the LDS-window encoder kernel's plan fits these level shapes (it stages full-height column windows: canvases
     taller than ~270 px in fp32 / ~550 px in bf16 do not fit, and the caller uses msda_fused, the gather kernel, instead)."""
     hw = (ctypes.c_int * 8)(*[int(v) for pair in level_hw for v in pair])
-    rc = _L(dtype).dtlr_msda_encoder_plan_ok(ctypes.cast(hw, ctypes.c_void_p), _DT[dtype], MSDA_HALO if halo is None else int(halo))
+    L_ = _L(dtype)
+    rc = _lib.query(L_, "dtlr_msda_encoder_plan_ok", ctypes.cast(hw, ctypes.c_void_p), _DT[dtype], MSDA_HALO if halo is None else int(halo))
     if rc < 0:
-        _lib.check(rc, "dtlr_msda_encoder_plan_ok")
+        _lib.check(rc, "dtlr_msda_encoder_plan_ok", L_)
     return rc == 1
 
 
+@_lib.op
 def msda_encoder(value, level_hw, ow, ref, halo: Optional[int] = None):
     """Encoder MSDA (Lq == S, queries are the level pixels) with LDS-staged value windows.
     value [N,S,M,32] fp32/bf16; level_hw: HOST list of (H_l, W_l); ow [N,S,M*48]; ref [N,S,4,2] fp32."""
@@ -1158,15 +1156,15 @@ def msda_encoder(value, level_hw, ow, ref, halo: Optional[int] = None):
         st = torch.cuda.current_stream()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(st)
-    code = _L(value).dtlr_msda_encoder_forward(value.data_ptr(), ow.data_ptr(), ref.data_ptr(), hw, N, M, D, 4, 4, MSDA_HALO if halo is None else int(halo),
-                                                _DT[value.dtype], _DT[ow.dtype], out.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_msda_encoder_forward")
+    _lib.launch(_L(value), "dtlr_msda_encoder_forward", value.data_ptr(), ow.data_ptr(), ref.data_ptr(), hw, N, M, D, 4, 4,
+                MSDA_HALO if halo is None else int(halo), _DT[value.dtype], _DT[ow.dtype], out.data_ptr())
     if ev is not None:
         b.record(st)
         ev.append((a, b, N, S, S))
     return out
 
 
+@_lib.op
 def msda_encoder_far_fraction(value_dtype, level_hw, ow, ref, n_heads: int = 8, halo: Optional[int] = None):
     """Fraction of the in-map sampling points of an encoder MSDA call that msda_encoder would fetch through its global path (outside the
     staged column window of the query's tile; dtlr_msda_encoder_far_samples).  Synchronises (reads two counters back): a probe."""
@@ -1175,13 +1173,13 @@ def msda_encoder_far_fraction(value_dtype, level_hw, ow, ref, n_heads: int = 8, 
     import ctypes
     hw = (ctypes.c_int * 8)(*[int(v) for pair in level_hw for v in pair])
     counts = torch.zeros(2, dtype=torch.int64, device=ow.device)
-    code = _L(value_dtype).dtlr_msda_encoder_far_samples(ow.data_ptr(), ref.data_ptr(), hw, ow.shape[0], n_heads, MSDA_HALO if halo is None else int(halo), _DT[value_dtype],
-                                                    _DT[ow.dtype], counts.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_msda_encoder_far_samples")
+    _lib.launch(_L(value_dtype), "dtlr_msda_encoder_far_samples", ow.data_ptr(), ref.data_ptr(), hw, ow.shape[0], n_heads,
+                MSDA_HALO if halo is None else int(halo), _DT[value_dtype], _DT[ow.dtype], counts.data_ptr())
     far, inside = counts.tolist()
     return far / max(inside, 1)
 
 
+@_lib.op
 def mha(qk, v, n_heads: int, split: bool = False):
     """Self-attention core.  qk [B, L, 2C] (projected q | k), v [B, L, C] -> [B, L, C].  Fused flash-style HIP
     kernel on the matrix cores, scores never leave the chip: bf16 / fp16 (mfma 16x16x32), exact fp32 (mfma 16x16x4), or -- fp32 tensors
@@ -1193,19 +1191,19 @@ def mha(qk, v, n_heads: int, split: bool = False):
         raise RuntimeError(f"dtlr_amd.ops.mha: unsupported dtype/head_dim {qk.dtype}/{hd}")
     qk, v = qk.contiguous(), v.contiguous()
     L_ = _L(qk)
-    ws = torch.empty(L_.dtlr_mha_workspace_bytes(B, L, n_heads, hd), dtype=torch.uint8, device=qk.device)
+    ws = torch.empty(_lib.query(L_, "dtlr_mha_workspace_bytes", B, L, n_heads, hd), dtype=torch.uint8, device=qk.device)
     out = torch.empty((B, L, C), dtype=qk.dtype, device=qk.device)
     if split and qk.dtype != torch.float32:
         raise RuntimeError("dtlr_amd.ops.mha: split=True takes fp32 tensors")
-    code = L_.dtlr_mha_forward(qk.data_ptr(), v.data_ptr(), ws.data_ptr(), out.data_ptr(), B, L, n_heads, hd,
-                               _lib.DTLR_F32S if split else _DT[qk.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_mha_forward")
+    _lib.launch(L_, "dtlr_mha_forward", qk.data_ptr(), v.data_ptr(), ws.data_ptr(), out.data_ptr(), B, L, n_heads, hd,
+                _lib.DTLR_F32S if split else _DT[qk.dtype])
     return out
 
 
 _DIM_T = {}
 
 
+@_lib.op
 def decoder_query_prep(ref, valid_ratios, out_dtype, per_line: bool = False):
     """ref [B,nq,4] fp32, valid_ratios [B,L,2] fp32 -> (ref_in [B,nq,L,4] fp32, sine [B,nq,512] out_dtype).
     per_line: the sine embedding of the unscaled reference (dtlr_decoder_query_prep_per_line); ref_in is still scaled."""
@@ -1219,10 +1217,8 @@ def decoder_query_prep(ref, valid_ratios, out_dtype, per_line: bool = False):
     valid_ratios = valid_ratios.contiguous()
     ref_in = torch.empty((B, nq, L, 4), dtype=torch.float32, device=ref.device)
     sine = torch.empty((B, nq, 512), dtype=out_dtype, device=ref.device)
-    fn = _L(out_dtype).dtlr_decoder_query_prep_per_line if per_line else _L(out_dtype).dtlr_decoder_query_prep
-    code = fn(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), ref_in.data_ptr(),
-                                              sine.data_ptr(), B, nq, L, _DT[out_dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_decoder_query_prep")
+    _lib.launch(_L(out_dtype), "dtlr_decoder_query_prep_per_line" if per_line else "dtlr_decoder_query_prep", ref.data_ptr(), valid_ratios.data_ptr(),
+                _DIM_T[key].data_ptr(), ref_in.data_ptr(), sine.data_ptr(), B, nq, L, _DT[out_dtype])
     return ref_in, sine
 
 
@@ -1235,6 +1231,7 @@ def dq_pack(w):
     return v.permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)                   # u, ks, t, [g, m] = lane, e
 
 
+@_lib.op
 def dec_query_stage(ref, valid_ratios, tgt, w0, b0, w1, b1, wqk, bqk, wv, bv, per_line: bool = False):
     """The query stage of a decoder layer in ONE launch (dtlr_dec_query_stage, 16-bit engines): reference boxes per level, sine
     embedding, ref_point_head MLP, and the q | k (on tgt + query_pos) and v (on tgt) input projections of the self-attention.
@@ -1260,15 +1257,14 @@ def dec_query_stage(ref, valid_ratios, tgt, w0, b0, w1, b1, wqk, bqk, wv, bv, pe
     M = B * nq
     with _Timed("gemm_bf16", 2.0 * M * (512 * 256 + 256 * 256 + 256 * 512 + 256 * 256), float(M) * (256 + 256 + 512 + 256) * 2 + 393216.0 * 2,
                 f"dec_query_stage M{M}"):
-        fn = _L(tgt).dtlr_dec_query_stage_per_line if per_line else _L(tgt).dtlr_dec_query_stage
-        code = fn(ref.data_ptr(), valid_ratios.data_ptr(), _DIM_T[key].data_ptr(), tgt.data_ptr(),
-                                            w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), wqk.data_ptr(), bqk.data_ptr(),
-                                            wv.data_ptr(), bv.data_ptr(), ref_in.data_ptr(), qpos.data_ptr(), qk.data_ptr(), v.data_ptr(),
-                                            B, nq, L, _DT[tgt.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_dec_query_stage")
+        _lib.launch(_L(tgt), "dtlr_dec_query_stage_per_line" if per_line else "dtlr_dec_query_stage", ref.data_ptr(), valid_ratios.data_ptr(),
+                    _DIM_T[key].data_ptr(), tgt.data_ptr(), w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), wqk.data_ptr(),
+                    bqk.data_ptr(), wv.data_ptr(), bv.data_ptr(), ref_in.data_ptr(), qpos.data_ptr(), qk.data_ptr(), v.data_ptr(), B, nq, L,
+                    _DT[tgt.dtype])
     return ref_in, qpos, qk, v
 
 
+@_lib.op
 def box_mlp_refine(x, w1, b1, w2p, b2, w3, b3, ref, mode: int = 0):
     """3-layer box MLP + refinement in ONE launch (dtlr_box_mlp_refine_bf16): x [..,256] bf16, W1 [256,256] bf16,
     w2p = ffn_pack_w2(W2) bf16, W3 [4,256] / biases fp32, ref [..,4] fp32 -> [..,4] fp32.
@@ -1278,12 +1274,12 @@ def box_mlp_refine(x, w1, b1, w2p, b2, w3, b3, ref, mode: int = 0):
     x = x if x.is_contiguous() else x.contiguous()
     ref = ref if ref.is_contiguous() else ref.contiguous()
     out = torch.empty_like(ref)
-    code = _L(x).dtlr_box_mlp_refine_bf16(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), w3.data_ptr(),
-                                               b3.data_ptr(), ref.data_ptr(), out.data_ptr(), x.numel() // 256, mode, _lib.current_stream())
-    _lib.check(code, "dtlr_box_mlp_refine_bf16")
+    _lib.launch(_L(x), "dtlr_box_mlp_refine_bf16", x.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), w3.data_ptr(),
+                b3.data_ptr(), ref.data_ptr(), out.data_ptr(), x.numel() // 256, mode)
     return out
 
 
+@_lib.op
 def box_head_refine(h, w, b, ref, mode: int = 0):
     """Last layer of the box MLP (256 -> 4) fused with its consumer (HIP kernel, one wavefront per row):
     mode 0: sigmoid(h W^T + b + inverse_sigmoid(ref)) ; mode 1: h W^T + b + ref.  h [..,256] fp32, ref [..,4] fp32."""
@@ -1292,32 +1288,31 @@ def box_head_refine(h, w, b, ref, mode: int = 0):
     h = h if h.is_contiguous() else h.contiguous()
     ref = ref if ref.is_contiguous() else ref.contiguous()
     out = torch.empty_like(ref)
-    code = _L(h).dtlr_box_head_refine(h.data_ptr(), w.data_ptr(), b.data_ptr(), ref.data_ptr(), out.data_ptr(),
-                                           h.numel() // 256, 256, mode, _lib.current_stream())
-    _lib.check(code, "dtlr_box_head_refine")
+    _lib.launch(_L(h), "dtlr_box_head_refine", h.data_ptr(), w.data_ptr(), b.data_ptr(), ref.data_ptr(), out.data_ptr(), h.numel() // 256, 256, mode)
     return out
 
 
+@_lib.op
 def box_refine(delta, ref):
     """sigmoid(delta + inverse_sigmoid(ref)) (fp32)."""
     delta, ref = delta.contiguous(), ref.contiguous()
     out = torch.empty_like(ref)
-    code = _L(delta).dtlr_box_refine(delta.data_ptr(), ref.data_ptr(), out.data_ptr(), ref.numel(), _lib.current_stream())
-    _lib.check(code, "dtlr_box_refine")
+    _lib.launch(_L(delta), "dtlr_box_refine", delta.data_ptr(), ref.data_ptr(), out.data_ptr(), ref.numel())
     return out
 
 
+@_lib.op
 def topk_rows(scores, k: int):
     """Indices [B,k] int64 of the k largest per row, descending, ties -> lower index (two-stage selection,
     deformable_transformer.py:345).  Scores are always fp32.  HIP kernel: per-row bitonic sort in LDS."""
     B, S = scores.shape
     scores = scores.float().contiguous()
     idx = torch.empty((B, k), dtype=torch.int64, device=scores.device)
-    code = _L(scores).dtlr_topk_rows(scores.data_ptr(), idx.data_ptr(), B, S, k, _lib.current_stream())
-    _lib.check(code, "dtlr_topk_rows")
+    _lib.launch(_L(scores), "dtlr_topk_rows", scores.data_ptr(), idx.data_ptr(), B, S, k)
     return idx
 
 
+@_lib.op
 def decode_blank(logits, boxes, eps: float):
     """Blank/argmax decoder (HIP kernel): logits [B,nq,C], boxes [B,nq,4] -> (labels [B,nq] int32 left-packed
     -1 padded, lengths [B] int32)."""
@@ -1327,9 +1322,7 @@ def decode_blank(logits, boxes, eps: float):
     boxes = boxes.float().contiguous()
     labels = torch.empty((B, nq), dtype=torch.int32, device=logits.device)
     lengths = torch.empty((B,), dtype=torch.int32, device=logits.device)
-    code = _L(logits).dtlr_decode_blank(logits.data_ptr(), boxes.data_ptr(), labels.data_ptr(), lengths.data_ptr(), B, nq, C,
-                                        float(eps), _lib.current_stream())
-    _lib.check(code, "dtlr_decode_blank")
+    _lib.launch(_L(logits), "dtlr_decode_blank", logits.data_ptr(), boxes.data_ptr(), labels.data_ptr(), lengths.data_ptr(), B, nq, C, float(eps))
     return labels, lengths
 
 
@@ -1343,6 +1336,7 @@ def _src_hw(src_hw, B: int, device):
     return t
 
 
+@_lib.op
 def decode_blank_located(logits, boxes, eps: float, src_hw=None):
     """The blank/argmax decoder with every character's record (dtlr_decode_blank_located): logits [B,nq,C], boxes [B,nq,4] cxcywh,
     src_hw [B,2] (h, w) or None = normalised boxes -> dict(labels, query, rank [B,nq] int32, score [B,nq] fp32, box [B,nq,4] fp32 xyxy,
@@ -1357,14 +1351,14 @@ def decode_blank_located(logits, boxes, eps: float, src_hw=None):
     i32 = lambda: torch.empty((B, nq), dtype=torch.int32, device=dev)                      # noqa: E731
     rec = dict(labels=i32(), query=i32(), rank=i32(), score=torch.empty((B, nq), dtype=torch.float32, device=dev),
                box=torch.empty((B, nq, 4), dtype=torch.float32, device=dev), lengths=torch.empty((B,), dtype=torch.int32, device=dev))
-    ws = torch.empty(L_.dtlr_decode_blank_located_workspace_bytes(B, nq) // 4, dtype=torch.float32, device=dev)
-    code = L_.dtlr_decode_blank_located(logits.data_ptr(), boxes.data_ptr(), float(eps), hw.data_ptr() if hw is not None else None,
-                                        rec["labels"].data_ptr(), rec["query"].data_ptr(), rec["rank"].data_ptr(), rec["score"].data_ptr(),
-                                        rec["box"].data_ptr(), rec["lengths"].data_ptr(), ws.data_ptr(), B, nq, C, _lib.current_stream())
-    _lib.check(code, "dtlr_decode_blank_located")
+    ws = torch.empty(_lib.query(L_, "dtlr_decode_blank_located_workspace_bytes", B, nq) // 4, dtype=torch.float32, device=dev)
+    _lib.launch(L_, "dtlr_decode_blank_located", logits.data_ptr(), boxes.data_ptr(), float(eps), hw.data_ptr() if hw is not None else None,
+                rec["labels"].data_ptr(), rec["query"].data_ptr(), rec["rank"].data_ptr(), rec["score"].data_ptr(), rec["box"].data_ptr(),
+                rec["lengths"].data_ptr(), ws.data_ptr(), B, nq, C)
     return rec
 
 
+@_lib.op
 def decode_nms_located(logits, boxes, score_threshold: float, iou_threshold: float, src_hw=None):
     """The NMS decoder of every line on the device (dtlr_topk_flat with the sigmoid folded in, then dtlr_decode_nms_located: two
     launches, no host synchronisation): logits [B,nq,C], boxes [B,nq,4] cxcywh -> dict(labels, query [B,k] int32, score [B,k] fp32,
@@ -1379,19 +1373,17 @@ def decode_nms_located(logits, boxes, score_threshold: float, iou_threshold: flo
     L_ = _lib.lib()
     values = torch.empty((B, k), dtype=torch.float32, device=dev)
     index = torch.empty((B, k), dtype=torch.int64, device=dev)
-    code = L_.dtlr_topk_flat(logits.data_ptr(), values.data_ptr(), index.data_ptr(), B, nq * C, k, 1, _lib.current_stream())
-    _lib.check(code, "dtlr_topk_flat")
+    _lib.launch(L_, "dtlr_topk_flat", logits.data_ptr(), values.data_ptr(), index.data_ptr(), B, nq * C, k, 1)
     i32 = lambda: torch.empty((B, k), dtype=torch.int32, device=dev)                       # noqa: E731
     rec = dict(labels=i32(), query=i32(), score=torch.empty((B, k), dtype=torch.float32, device=dev),
                box=torch.empty((B, k, 4), dtype=torch.float32, device=dev), lengths=torch.empty((B,), dtype=torch.int32, device=dev))
-    code = L_.dtlr_decode_nms_located(values.data_ptr(), index.data_ptr(), boxes.data_ptr(), hw.data_ptr() if hw is not None else None,
-                                      float(iou_threshold), float(score_threshold), rec["labels"].data_ptr(), rec["query"].data_ptr(),
-                                      rec["score"].data_ptr(), rec["box"].data_ptr(), rec["lengths"].data_ptr(), B, k, nq, C,
-                                      _lib.current_stream())
-    _lib.check(code, "dtlr_decode_nms_located")
+    _lib.launch(L_, "dtlr_decode_nms_located", values.data_ptr(), index.data_ptr(), boxes.data_ptr(), hw.data_ptr() if hw is not None else None,
+                float(iou_threshold), float(score_threshold), rec["labels"].data_ptr(), rec["query"].data_ptr(), rec["score"].data_ptr(),
+                rec["box"].data_ptr(), rec["lengths"].data_ptr(), B, k, nq, C)
     return rec
 
 
+@_lib.op
 def blank_emissions(logits, boxes, eps: float, scale: float = 1.0):
     """[B, nq, C+1] CTC-style emissions, blank channel first, queries in reading order (dtlr_blank_emissions: per-query sigmoid sums
     chip-wide, the decoders' cx sort per line, one wave per output row) -- get_new_pred_logits (ngram/prediction_helpers.py:5-46) /
@@ -1401,17 +1393,16 @@ def blank_emissions(logits, boxes, eps: float, scale: float = 1.0):
     boxes = boxes.float().contiguous()
     B, nq, C = logits.shape
     L_ = _lib.lib()
-    ws = torch.empty(L_.dtlr_blank_emissions_workspace_bytes(B, nq) // 4, dtype=torch.float32, device=logits.device)
+    ws = torch.empty(_lib.query(L_, "dtlr_blank_emissions_workspace_bytes", B, nq) // 4, dtype=torch.float32, device=logits.device)
     out = torch.empty((B, nq, C + 1), dtype=torch.float32, device=logits.device)
-    code = L_.dtlr_blank_emissions(logits.data_ptr(), boxes.data_ptr(), out.data_ptr(), ws.data_ptr(), B, nq, C, float(scale), float(eps),
-                                   _lib.current_stream())
-    _lib.check(code, "dtlr_blank_emissions")
+    _lib.launch(L_, "dtlr_blank_emissions", logits.data_ptr(), boxes.data_ptr(), out.data_ptr(), ws.data_ptr(), B, nq, C, float(scale), float(eps))
     return out
 
 
 _NGRAM_LM_FIELDS = ("tok", "child_lo", "child_hi", "suffix", "ctx", "logp", "bo")
 
 
+@_lib.op
 def ngram_beam(emissions, spans, lm=None, lm_weight: float = 0.0, beam_size: int = 50, beam_size_token: int = 0,
                bos: bool = True, eos: bool = True):
     """Character n-gram CTC prefix beam search over every span in ONE launch (dtlr_ngram_beam; semantics: DESIGN.md section 10).
@@ -1448,15 +1439,16 @@ def ngram_beam(emissions, spans, lm=None, lm_weight: float = 0.0, beam_size: int
                 raise _lib.DTLRError(f"ngram_beam: lm['{k}'] must be a contiguous {want} tensor on {dev}")
         st = _lib.NgramLM(*[lm[k].data_ptr() for k in _NGRAM_LM_FIELDS], int(lm["tok"].numel()), int(lm["order"]),
                           int(lm["bos_state"]), int(lm["eos_tok"]), float(lm["unk"]))
-    ws = torch.empty(L_.dtlr_ngram_beam_workspace_bytes(n, Tmax, int(beam_size)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.query(L_, "dtlr_ngram_beam_workspace_bytes", n, Tmax, int(beam_size)), dtype=torch.uint8, device=dev)
     spans_dev = sp.to(torch.int32).to(dev)
-    code = L_.dtlr_ngram_beam(emissions.data_ptr(), B, T, V, spans_dev.data_ptr(), n, Tmax, ctypes.cast(ctypes.pointer(st), ctypes.c_void_p) if st is not None else None,
-                              float(lm_weight), int(beam_size), int(beam_size_token or 0), int(bool(bos)), int(bool(eos)),
-                              labels.data_ptr(), Lmax, lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_ngram_beam")
+    _lib.launch(L_, "dtlr_ngram_beam", emissions.data_ptr(), B, T, V, spans_dev.data_ptr(), n, Tmax,
+                ctypes.cast(ctypes.pointer(st), ctypes.c_void_p) if st is not None else None, float(lm_weight), int(beam_size),
+                int(beam_size_token or 0), int(bool(bos)), int(bool(eos)), labels.data_ptr(), Lmax, lengths.data_ptr(), scores.data_ptr(),
+                ws.data_ptr())
     return labels, lengths, scores
 
 
+@_lib.op
 def preprocess_lines(src_u8, offsets, dims, Hc: int, Wc: int, max_downscale: float, mean, std):
     """Resize + ToTensor + Normalize + pad of a batch of uint8 RGB images in ONE launch (dtlr_preprocess_lines).
     src_u8: flat uint8 CUDA tensor (images back to back, HWC); offsets [B] int64 CUDA; dims [B,4] int32 CUDA = (h, w, oh, ow).
@@ -1468,13 +1460,12 @@ def preprocess_lines(src_u8, offsets, dims, Hc: int, Wc: int, max_downscale: flo
     mask = torch.empty((B, Hc, Wc), dtype=torch.bool, device=src_u8.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    code = _L(src_u8).dtlr_preprocess_lines(src_u8.data_ptr(), offsets.data_ptr(), dims.data_ptr(), B, Hc, Wc, float(max_downscale),
-                                            ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
-                                            canvas.data_ptr(), mask.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_preprocess_lines")
+    _lib.launch(_L(src_u8), "dtlr_preprocess_lines", src_u8.data_ptr(), offsets.data_ptr(), dims.data_ptr(), B, Hc, Wc, float(max_downscale),
+                ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), canvas.data_ptr(), mask.data_ptr())
     return canvas, mask
 
 
+@_lib.op
 def ctc_loss_interleaved(logits, boxes, targets, target_lengths, max_target_length: int, eps: float = 0.003, filler: float = 1e-5):
     """Per-line CTC negative log-likelihood of the reference's evaluation loss (dtlr_ctc_loss_interleaved): logits [B,nq,C],
     boxes [B,nq,4], targets [B,Lmax] int32 (label + 1), target_lengths [B] int32 (CUDA) -> nll [B] fp32 (inf -> 0)."""
@@ -1487,13 +1478,12 @@ def ctc_loss_interleaved(logits, boxes, targets, target_lengths, max_target_leng
     Lmax = targets.shape[1]
     nll = torch.empty((B,), dtype=torch.float32, device=logits.device)
     ws = torch.empty((B * nq,), dtype=torch.float32, device=logits.device)
-    code = _L(logits).dtlr_ctc_loss_interleaved(logits.data_ptr(), boxes.data_ptr(), targets.data_ptr() if Lmax > 0 else None,
-                                                target_lengths.data_ptr(), nll.data_ptr(), ws.data_ptr(), B, nq, C, Lmax,
-                                                int(max_target_length), float(eps), float(filler), _lib.current_stream())
-    _lib.check(code, "dtlr_ctc_loss_interleaved")
+    _lib.launch(_L(logits), "dtlr_ctc_loss_interleaved", logits.data_ptr(), boxes.data_ptr(), targets.data_ptr() if Lmax > 0 else None,
+                target_lengths.data_ptr(), nll.data_ptr(), ws.data_ptr(), B, nq, C, Lmax, int(max_target_length), float(eps), float(filler))
     return nll
 
 
+@_lib.op
 def ctc_loss_interleaved_backward(logits, boxes, targets, target_lengths, max_target_length: int, eps: float = 0.003, filler: float = 1e-5):
     """dtlr_ctc_loss_interleaved_backward: ctc_loss_interleaved's arguments -> (nll [B] fp32, bit-identical to ctc_loss_interleaved;
     dlogits [B,nq,C] fp32 = the gradient of mean_b(nll_b / max(L_b, 1)) with respect to the logits; 0 for a line without a feasible
@@ -1508,14 +1498,14 @@ def ctc_loss_interleaved_backward(logits, boxes, targets, target_lengths, max_ta
     L = _L(logits)
     nll = torch.empty((B,), dtype=torch.float32, device=logits.device)
     dlogits = torch.empty((B, nq, C), dtype=torch.float32, device=logits.device)
-    ws = torch.empty((L.dtlr_ctc_loss_interleaved_backward_workspace_bytes(B, nq, Lmax) // 4,), dtype=torch.float32, device=logits.device)
-    code = L.dtlr_ctc_loss_interleaved_backward(logits.data_ptr(), boxes.data_ptr(), targets.data_ptr() if Lmax > 0 else None,
-                                                target_lengths.data_ptr(), nll.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), B, nq, C, Lmax,
-                                                int(max_target_length), float(eps), float(filler), _lib.current_stream())
-    _lib.check(code, "dtlr_ctc_loss_interleaved_backward")
+    ws = torch.empty((_lib.query(L, "dtlr_ctc_loss_interleaved_backward_workspace_bytes", B, nq, Lmax) // 4,), dtype=torch.float32, device=logits.device)
+    _lib.launch(L, "dtlr_ctc_loss_interleaved_backward", logits.data_ptr(), boxes.data_ptr(), targets.data_ptr() if Lmax > 0 else None,
+                target_lengths.data_ptr(), nll.data_ptr(), dlogits.data_ptr(), ws.data_ptr(), B, nq, C, Lmax, int(max_target_length), float(eps),
+                float(filler))
     return nll, dlogits
 
 
+@_lib.op
 def head_grad(g, x, out=None):
     """dtlr_head_grad: g [M,C] fp32 (dlogits), x [M,D] fp32 (decoder states), D % 64 == 0 -> the flat gradient [C*D + C] fp32 of a
     Linear(D -> C): dW = g^T x row-major, then db = g.sum(0).  Exact fp32 products; reproducible run to run.  out: a buffer to fill."""
@@ -1529,15 +1519,15 @@ def head_grad(g, x, out=None):
     if out is None:
         out = torch.empty((C * D + C,), dtype=torch.float32, device=g.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == C * D + C
-    nbytes = L.dtlr_head_grad_workspace_bytes(M, C, D)
+    nbytes = _lib.query(L, "dtlr_head_grad_workspace_bytes", M, C, D)
     if M and nbytes <= 0:
         raise _lib.DTLRError(f"dtlr_head_grad: unsupported shape M={M} C={C} D={D} (D must be a multiple of 64)")
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=g.device)
-    code = L.dtlr_head_grad(g.data_ptr(), x.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * C * D, ws.data_ptr(), M, C, D, _lib.current_stream())
-    _lib.check(code, "dtlr_head_grad")
+    _lib.launch(L, "dtlr_head_grad", g.data_ptr(), x.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * C * D, ws.data_ptr(), M, C, D)
     return out
 
 
+@_lib.op
 def grad_norm_scale(grad, max_norm: float, out=None):
     """dtlr_grad_norm_scale: flat fp32 grad -> device tensor [2] = (clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)), norm);
     max_norm <= 0: the coefficient is 1.  No host synchronisation."""
@@ -1546,12 +1536,12 @@ def grad_norm_scale(grad, max_norm: float, out=None):
     L = _L(grad)
     if out is None:
         out = torch.empty((2,), dtype=torch.float32, device=grad.device)
-    ws = torch.empty((L.dtlr_grad_norm_scale_workspace_bytes() // 8,), dtype=torch.float64, device=grad.device)
-    code = L.dtlr_grad_norm_scale(grad.data_ptr(), grad.numel(), float(max_norm), out.data_ptr(), ws.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_grad_norm_scale")
+    ws = torch.empty((_lib.query(L, "dtlr_grad_norm_scale_workspace_bytes") // 8,), dtype=torch.float64, device=grad.device)
+    _lib.launch(L, "dtlr_grad_norm_scale", grad.data_ptr(), grad.numel(), float(max_norm), out.data_ptr(), ws.data_ptr())
     return out
 
 
+@_lib.op
 def adamw_step(param, exp_avg, exp_avg_sq, grad, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                grad_scale=None):
     """dtlr_adamw_step: torch.optim.AdamW's update, in place, over flat fp32 buffers; `step` >= 1 is this step's number; grad_scale: a
@@ -1559,13 +1549,13 @@ def adamw_step(param, exp_avg, exp_avg_sq, grad, step: int, lr: float, betas=(0.
     require_cuda(param, "param")
     for t in (param, exp_avg, exp_avg_sq, grad):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == param.numel() and t.device == param.device
-    code = _L(param).dtlr_adamw_step(param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(),
-                                     grad_scale.data_ptr() if grad_scale is not None else None, param.numel(), float(lr), float(betas[0]),
-                                     float(betas[1]), float(eps), float(weight_decay), int(step), _lib.current_stream())
-    _lib.check(code, "dtlr_adamw_step")
+    _lib.launch(_L(param), "dtlr_adamw_step", param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(),
+                grad_scale.data_ptr() if grad_scale is not None else None, param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                float(weight_decay), int(step))
     return param
 
 
+@_lib.op
 def nms_batched(boxes, scores, iou_threshold: float):
     """Greedy NMS per image on the device (dtlr_nms): boxes [B,n,4] xyxy fp32, scores [B,n] fp32 -> (keep [B,n] int64: kept
     original indices in descending score order, -1 padded; counts [B] int32).  n <= 1024."""
@@ -1575,12 +1565,11 @@ def nms_batched(boxes, scores, iou_threshold: float):
     scores = scores.float().contiguous()
     keep = torch.empty((B, n), dtype=torch.int64, device=boxes.device)
     counts = torch.empty((B,), dtype=torch.int32, device=boxes.device)
-    code = _L(boxes).dtlr_nms(boxes.data_ptr(), scores.data_ptr(), float(iou_threshold), keep.data_ptr(), counts.data_ptr(), B, n,
-                               _lib.current_stream())
-    _lib.check(code, "dtlr_nms")
+    _lib.launch(_L(boxes), "dtlr_nms", boxes.data_ptr(), scores.data_ptr(), float(iou_threshold), keep.data_ptr(), counts.data_ptr(), B, n)
     return keep, counts
 
 
+@_lib.op
 def topk_flat(x, k: int, apply_sigmoid: bool = False):
     """Per-row top-k of a long [B, n] fp32 matrix (dtlr_topk_flat: exact radix select over the row in global memory + a 1024-key sort):
     -> (values [B,k] fp32 descending, indices [B,k] int64; equal values: lower index first).  k <= 8192."""
@@ -1590,43 +1579,15 @@ def topk_flat(x, k: int, apply_sigmoid: bool = False):
     B, n = x.shape
     values = torch.empty((B, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((B, k), dtype=torch.int64, device=x.device)
-    code = _L(x).dtlr_topk_flat(x.data_ptr(), values.data_ptr(), idx.data_ptr(), B, n, int(k), int(bool(apply_sigmoid)), _lib.current_stream())
-    _lib.check(code, "dtlr_topk_flat")
+    _lib.launch(_L(x), "dtlr_topk_flat", x.data_ptr(), values.data_ptr(), idx.data_ptr(), B, n, int(k), int(bool(apply_sigmoid)))
     return values, idx
-
-
-# --------------------------------------------------------------------------------------------
-# Every operator launches on the current stream of the device its FIRST tensor argument lives on (not of whatever device
-# happens to be current): a model moved to cuda:1 while cuda:0 is current would otherwise launch on device 0 with device-1
-# pointers.  The check costs one integer compare per call when the devices already agree.
-def _device_scoped(fn):
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(*args, **kwargs):
-        for t in args:
-            if isinstance(t, torch.Tensor):
-                if t.is_cuda and t.device.index != torch.cuda.current_device():
-                    with torch.cuda.device(t.device):
-                        return fn(*args, **kwargs)
-                break
-        return fn(*args, **kwargs)
-    return wrapper
-
-
-for _name in ("msda_encoder_far_fraction", "gemm_kres", "gemm_kres_chain", "l1_bottleneck", "gemm_kres_cat_s2", "gemm_kres_bcast384", "ffn32", "ffn4", "proj_ln_k256", "swin_patch_embed", "swin_window_attn", "swin_patch_merge", "geometry", "linear", "gemm_k256", "linear_rowmax", "two_stage_gather", "layernorm", "proj_ln", "proj_ln_split", "ffn_fused", "conv2d_nhwc", "stem_conv7x7", "stem_conv7x7_f32",
-              "maxpool_nhwc", "groupnorm_tokens", "msda", "msda_fused", "msda_encoder", "mha", "decoder_query_prep", "box_mlp_refine",
-              "box_head_refine", "box_refine", "topk_rows", "decode_blank", "preprocess_lines", "ctc_loss_interleaved", "nms_batched",
-              "topk_flat", "ctc_loss_interleaved_backward", "head_grad", "grad_norm_scale", "adamw_step", "stem_conv7x7_pool", "dec_query_stage", "blank_emissions", "ngram_beam", "split_pack", "linear_resbcast", "ffn_split", "stem_conv7x7_f32s", "k256s_pack", "gemm_k256s",
-              "decode_blank_located", "decode_nms_located"):
-    globals()[_name] = _device_scoped(globals()[_name])
-del _name
 
 
 # ------------------------------------------------------------------------------ per-line batching (csrc/extent.hip and the extent forms)
 # A line's extent (h, w) is its unpadded top-left rectangle in the input mask; at stride 2^s it is (ceil(h / 2^s), ceil(w / 2^s)).
 # The extents stay on the device ([B, 2] int32): none of these wrappers reads anything back.
 
+@_lib.op
 def line_extents(mask):
     """mask [B,H,W] bool (True = padding) -> [B,2] int32 (h, w): unmasked rows of column 0, unmasked columns of row 0."""
     require_cuda(mask, "mask")
@@ -1634,33 +1595,33 @@ def line_extents(mask):
     mask = mask if mask.is_contiguous() else mask.contiguous()
     B, H, W = mask.shape
     ext = torch.empty((B, 2), dtype=torch.int32, device=mask.device)
-    code = _lib.lib().dtlr_line_extents(mask.data_ptr(), ext.data_ptr(), B, H, W, _lib.current_stream())
-    _lib.check(code, "dtlr_line_extents")
+    _lib.launch(_lib.lib(), "dtlr_line_extents", mask.data_ptr(), ext.data_ptr(), B, H, W)
     return ext
 
 
+@_lib.op
 def zero_outside_extent(x, ext, s: int):
     """In place: zero the positions of the NHWC map x [B,H,W,C] outside each line's stride-2^s extent.  Returns x."""
     require_cuda(x, "x")
     assert x.dim() == 4 and x.is_contiguous() and ext.dtype == torch.int32 and tuple(ext.shape) == (x.shape[0], 2)
     B, H, W, C = x.shape
-    code = _L(x).dtlr_zero_outside_extent_nhwc(x.data_ptr(), ext.data_ptr(), int(s), B, H, W, C, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_zero_outside_extent_nhwc")
+    _lib.launch(_L(x), "dtlr_zero_outside_extent_nhwc", x.data_ptr(), ext.data_ptr(), int(s), B, H, W, C, _DT[x.dtype])
     return x
 
 
+@_lib.op
 def maxpool_nhwc_ext(x, ext, s_in: int, bias=None, relu: bool = False):
     """maxpool_nhwc whose window skips taps outside the input's stride-2^s_in extent; 0 outside the output's extent."""
     B, H, W, C = x.shape
     x = x if x.is_contiguous() else x.contiguous()
     assert ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2)
     y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
-    code = _L(x).dtlr_maxpool3x3s2_nhwc_ext(x.data_ptr(), y.data_ptr(), 0 if bias is None else bias.data_ptr(), 1 if relu else 0,
-                                            ext.data_ptr(), int(s_in), B, H, W, C, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_maxpool3x3s2_nhwc_ext")
+    _lib.launch(_L(x), "dtlr_maxpool3x3s2_nhwc_ext", x.data_ptr(), y.data_ptr(), 0 if bias is None else bias.data_ptr(), 1 if relu else 0,
+                ext.data_ptr(), int(s_in), B, H, W, C, _DT[x.dtype])
     return y
 
 
+@_lib.op
 def groupnorm_tokens_ext(x, hw, ext, s: int, groups: int, w, b, eps: float = 1e-5, out=None):
     """groupnorm_tokens over a level of hw = (Hl, Wl) tokens, statistics over each line's stride-2^s extent only, 0 written outside it."""
     B, T, C = x.shape
@@ -1668,15 +1629,15 @@ def groupnorm_tokens_ext(x, hw, ext, s: int, groups: int, w, b, eps: float = 1e-
     assert T == Hl * Wl and ext.dtype == torch.int32 and tuple(ext.shape) == (B, 2)
     x = x if x.is_contiguous() else x.contiguous()
     L_ = _L(x)
-    ws = torch.empty(L_.dtlr_groupnorm_workspace_bytes(B, T), dtype=torch.uint8, device=x.device)
+    ws = torch.empty(_lib.query(L_, "dtlr_groupnorm_workspace_bytes", B, T), dtype=torch.uint8, device=x.device)
     y = torch.empty_like(x) if out is None else out
     assert y.shape == x.shape and y.dtype == x.dtype and y.stride(2) == 1 and y.stride(1) == C
-    code = L_.dtlr_groupnorm_tokens_ext(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), ws.data_ptr(), ext.data_ptr(),
-                                        int(s), Hl, Wl, B, C, groups, eps, _DT[x.dtype], _lib.current_stream())
-    _lib.check(code, "dtlr_groupnorm_tokens_ext")
+    _lib.launch(L_, "dtlr_groupnorm_tokens_ext", x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), y.stride(0), ws.data_ptr(), ext.data_ptr(),
+                int(s), Hl, Wl, B, C, groups, eps, _DT[x.dtype])
     return y
 
 
+@_lib.op
 def geometry_ext(ext, s0: int, level_hw, level_embed, temperature_h: float, temperature_w: float, pos_dtype):
     """geometry() with the level masks taken from the line extents (level q: stride 2^(s0 + q)) instead of the interpolated mask."""
     require_cuda(ext, "ext")
@@ -1698,13 +1659,13 @@ def geometry_ext(ext, s0: int, level_hw, level_embed, temperature_h: float, temp
     vr = torch.empty((B, 4, 2), dtype=torch.float32, device=dev)
     enc_ref = torch.empty((B, S, 4, 2), dtype=torch.float32, device=dev)
     prop = torch.empty((B, S, 4), dtype=torch.float32, device=dev)
-    code = _L(pos_dtype).dtlr_geometry_ext(ext.data_ptr(), int(s0), B, ctypes.cast(hw, ctypes.c_void_p), level_embed.data_ptr(),
-                                           dim_ty.data_ptr(), dim_tx.data_ptr(), _DT[pos_dtype], mask_flat.data_ptr(), keep.data_ptr(),
-                                           pos.data_ptr(), vr.data_ptr(), enc_ref.data_ptr(), prop.data_ptr(), _lib.current_stream())
-    _lib.check(code, "dtlr_geometry_ext")
+    _lib.launch(_L(pos_dtype), "dtlr_geometry_ext", ext.data_ptr(), int(s0), B, ctypes.cast(hw, ctypes.c_void_p), level_embed.data_ptr(),
+                dim_ty.data_ptr(), dim_tx.data_ptr(), _DT[pos_dtype], mask_flat.data_ptr(), keep.data_ptr(), pos.data_ptr(), vr.data_ptr(),
+                enc_ref.data_ptr(), prop.data_ptr())
     return dict(mask_flat=mask_flat, keep=keep, pos=pos, valid_ratios=vr, enc_ref=enc_ref, proposals=prop)
 
 
+@_lib.op
 def topk_rows_masked(scores, excl, k: int):
     """topk_rows that never returns an element with excl[b, i] True (as long as k elements of the row are not excluded)."""
     B, S = scores.shape
@@ -1712,6 +1673,5 @@ def topk_rows_masked(scores, excl, k: int):
     scores = scores.float().contiguous()
     excl = excl.contiguous()
     idx = torch.empty((B, k), dtype=torch.int64, device=scores.device)
-    code = _L(scores).dtlr_topk_rows_masked(scores.data_ptr(), excl.data_ptr(), idx.data_ptr(), B, S, k, _lib.current_stream())
-    _lib.check(code, "dtlr_topk_rows_masked")
+    _lib.launch(_L(scores), "dtlr_topk_rows_masked", scores.data_ptr(), excl.data_ptr(), idx.data_ptr(), B, S, k)
     return idx
