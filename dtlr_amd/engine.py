@@ -35,6 +35,68 @@ def _fold_bn(sd, conv_key: str, bn_prefix: str):
     return w * scale.view(-1, 1, 1, 1), bias
 
 
+# ------------------------------------------------------------------------------ packed weight images
+# kind -> builder(engine, name) of the image derived from the base weight(s) `name` (`name.w` / `name.b` in DTLREngine.w).  DTLREngine._image
+# builds it on first use and keeps it in DTLREngine.w under the tuple (kind, name): no base name, and no key that two kinds could share.
+# A new operator adds its image as ONE entry here; a replaced base weight drops its images by name (DTLREngine._drop_images).
+def _k256s_slices(e, n):
+    wf, = e._f32("k256s_slices", n)
+    blocks = [wf[r0:r0 + 256] for r0 in range(0, wf.shape[0], 256)]             # the last one is zero-padded to 256 rows
+    return [(ops.k256s_pack(torch.cat([b, b.new_zeros((256 - b.shape[0], 256))], 0).contiguous()), 256 * j, b.shape[0]) for j, b in enumerate(blocks)]
+
+
+def _head_hi_lo(e, n):
+    wf = e.w[n + ".w"].float()
+    hi = wf.to(e.dtype)
+    return torch.cat([hi, (wf - hi.float()).to(e.dtype)], 1).contiguous()
+
+
+_IMAGES = {
+    # ops.kres_pack: a 1x1 convolution's weight resident in registers (dtlr_gemm_kres, dtlr_gemm_kres_chain, dtlr_l1_bottleneck)
+    "kres": lambda e, n: ops.kres_pack(e.w[n + ".w"]),
+    # ops.kres_pack of [W3 | Wd] + the summed fp32 bias of bottleneck `n`, its shortcut conv as extra K columns (l1.0: chain / l1_bottleneck; l2.0: cat_s2)
+    "kres_cat": lambda e, n: (ops.kres_pack(torch.cat([e.w[n + ".c3.w"], e.w[n + ".ds.w"]], 1).contiguous()),
+                              (e.w[n + ".c3.b"].float() + e.w[n + ".ds.b"].float()).contiguous()),
+    # ops.kres_pack_bcast384: the encoder's [offsets | logits] projection with a row-broadcast residual (dtlr_gemm_kres_bcast384)
+    "bcast384": lambda e, n: ops.kres_pack_bcast384(e.w[n + ".w"]),
+    # ops.k256_pack: a [256 | 384, 256] projection over all tokens (dtlr_gemm_k256)
+    "k256": lambda e, n: ops.k256_pack(e.w[n + ".w"]),
+    # ops.k256_pack of every 384 rows of a taller weight, as a list (dtlr_gemm_k256 into column slices: dec.value_all)
+    "k256_slices": lambda e, n: [ops.k256_pack(e.w[n + ".w"][r0:r0 + 384]) for r0 in range(0, e.w[n + ".w"].shape[0], 384)],
+    # ops.proj_ln_k256_pack: output projection + residual + LayerNorm over many rows (dtlr_proj_ln_k256)
+    "pln_k256": lambda e, n: ops.proj_ln_k256_pack(e.w[n + ".w"]),
+    # ops.proj_pack_w: the same over few rows, and the two-stage enc_output (dtlr_proj_ln_bf16, dtlr_proj_ln_split_bf16)
+    "proj": lambda e, n: ops.proj_pack_w(e.w[n + ".w"]),
+    # ops.ffn_pack_w2: chunk-major second layer of an FFN, or of a box MLP from its 16-bit copy `n.wh` (dtlr_ffn_fused_bf16, ops.box_mlp_refine)
+    "ffn_w2": lambda e, n: ops.ffn_pack_w2(e.w[n + ".wh"] if n + ".wh" in e.w else e.w[n + ".w"]),
+    # ops.ffn32_pack of (n1.w, n2.w) -> (W1 image, W2 image) (dtlr_ffn32_bf16)
+    "ffn32": lambda e, n: ops.ffn32_pack(e.w[n + "1.w"], e.w[n + "2.w"]),
+    # ops.ffn_split_pack of the fp32 n1, n2 (dtlr_ffn_split)
+    "ffn_split": lambda e, n: ops.ffn_split_pack(*e._f32("ffn_split", n + "1", n + "2")),
+    # ops.k256s_pack of the fp32 [256, 256] weight (dtlr_gemm_k256s)
+    "k256s": lambda e, n: ops.k256s_pack(*e._f32("k256s", n)),
+    # ops.k256s_pack of every 256 rows of the fp32 [N, 256] weight -> [(image, first row, rows)] (dtlr_gemm_k256s_multi)
+    "k256s_slices": _k256s_slices,
+    # ops.head_ts_pack -> (image, padded bias): the token-stationary class head (dtlr_head_ts)
+    "head_ts": lambda e, n: ops.head_ts_pack(e.w[n + ".w"], e.w[n + ".b"], e.dtype),
+    # no packer: [W_hi | W_lo] in the engine dtype, the class head as a two-term product on [hs | hs] (ops.linear, the tiled GEMM)
+    "head_hi_lo": _head_hi_lo,
+    # ops.split_head_weight -> ([W_hi | W_hi | W_lo], bias padded with -inf): the two-stage head on a [hi | lo | hi] activation (ops.linear_rowmax)
+    "head_split3": lambda e, n: ops.split_head_weight(e.w[n + ".w"], e.w[n + ".b"], dtype=e.dtype),
+    # ops.dq_pack: the four projections of the decoder's query stage (dtlr_dec_query_stage)
+    "dq": lambda e, n: ops.dq_pack(e.w[n + ".w"]),
+}
+
+# Split engine: the kinds packed from the fp32 weight itself.  kind -> (the weights image `n` is packed from, the weights _put_linear keeps for it
+# under ("f32", name)).  A kept weight is released when its image is built, so it has ONE consumer: no two rules may keep the same name.
+_F32_SOURCES = {
+    "ffn_split": (lambda n: (n + "1", n + "2"), lambda name, shape: name.endswith((".ff1", ".ff2"))),
+    "k256s": (lambda n: (n,), lambda name, shape: shape == (256, 256) and (
+        name.endswith((".attn.out", ".sa.out")) or (name.startswith("enc") and name.endswith(".attn.value")) or name == "enc_output")),
+    "k256s_slices": (lambda n: (n,), lambda name, shape: (name.startswith("enc") and name.endswith(".attn.ow")) or name == "dec.value_all"),
+}
+
+
 class DTLREngine:
     def __init__(self, cfg: DTLRConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0",
                  dtype: torch.dtype = torch.float32, split: bool = False):
@@ -55,9 +117,7 @@ class DTLREngine:
         if self.device.type != "cuda":
             raise RuntimeError("DTLREngine runs on the GPU only (no CPU path)")
         ops.require_cuda(torch.empty(0, device=self.device))
-        self.w: Dict[str, torch.Tensor] = {}
-        self._ffn_f32: Dict[str, torch.Tensor] = {}
-        self._k256s_ok = set()                      # split engine: the [256, 256] encoder projections that run through dtlr_gemm_k256s
+        self.w: dict = {}                  # base weights by name (str); packed images by (kind, name), see _IMAGES
         self._pack(state_dict)
         self._shape_cache: Dict[tuple, dict] = {}
         self._level_cache: Dict[tuple, tuple] = {}
@@ -138,12 +198,8 @@ class DTLREngine:
         self.w[name + ".b"] = b.to(device=self.device, dtype=torch.float32).contiguous()
 
     def _put_linear(self, name, w, b):
-        if self.split and (name.endswith((".ff1", ".ff2", ".attn.out", ".sa.out")) or (name.startswith("enc") and name.endswith((".attn.value", ".attn.ow")))
-                           or name in ("enc_output", "dec.value_all")):
-            # the fused split FFN and the weight-resident K = 256 projections pack their own images from the fp32 weights
-            self._ffn_f32[name] = w.to(device=self.device, dtype=torch.float32).contiguous()
-            if not name.endswith((".ff1", ".ff2")) and tuple(w.shape) == (256, 256):
-                self._k256s_ok.add(name)
+        if self.split and any(keeps(name, tuple(w.shape)) for _, keeps in _F32_SOURCES.values()):
+            self.w["f32", name] = w.to(device=self.device, dtype=torch.float32).contiguous()      # until its image is built (_f32)
         self.w[name + ".w"] = self._gw(w)
         self._put(name + ".b", b, torch.float32)          # biases enter the GEMM epilogue in fp32
 
@@ -322,8 +378,8 @@ class DTLREngine:
                 self._put(f"bbox{i}.wh", sd[f"bbox_embed.0.layers.{i}.weight"])
                 self._put(f"enc_bbox{i}.wh", sd[f"{t}enc_out_bbox_embed.layers.{i}.weight"])
                 if i == 1:                             # second layer also chunk-major for the one-launch MLP kernel
-                    self.w["bbox1.wp"] = ops.ffn_pack_w2(self.w["bbox1.wh"])
-                    self.w["enc_bbox1.wp"] = ops.ffn_pack_w2(self.w["enc_bbox1.wh"])
+                    self._image("ffn_w2", "bbox1")
+                    self._image("ffn_w2", "enc_bbox1")
         self._put("enc_class.w", sd[t + "enc_out_class_embed.weight"], f32)
         self._put("enc_class.b", sd[t + "enc_out_class_embed.bias"], f32)
         self._put("class.w", sd["class_embed.0.weight"], f32)
@@ -332,6 +388,31 @@ class DTLREngine:
             self.w["enc_class.w"] = ops.split_pack(self.w["enc_class.w"])
             self.w["class.w"] = ops.split_pack(self.w["class.w"])
         self.num_classes = int(sd["class_embed.0.weight"].shape[0])
+
+    def _image(self, kind, name):
+        """the packed image of `kind` derived from the base weight(s) `name`, built on first use by _IMAGES[kind] and kept as w[kind, name]"""
+        if (kind, name) not in self.w:
+            self.w[kind, name] = _IMAGES[kind](self, name)
+        return self.w[kind, name]
+
+    def _has_image(self, kind, name) -> bool:
+        """whether _image(kind, name) can be served: built, or its fp32 sources still held (base weights are never released: always True)"""
+        return (kind, name) in self.w or kind not in _F32_SOURCES or all(torch.is_tensor(self.w.get(("f32", s))) for s in _F32_SOURCES[kind][0](name))
+
+    def _f32(self, kind, *names):
+        """split engine: the kept fp32 weights `names`, handed to the builder of `kind` and released (the entry then names that kind)"""
+        held = [self.w.get(("f32", s)) for s in names]
+        for s, t in zip(names, held):
+            if not torch.is_tensor(t):
+                raise RuntimeError(f"image kind {kind!r}: " + (f"no fp32 weight {s!r} is held (a split engine keeps those that _F32_SOURCES names)" if t is None else
+                                   f"the fp32 weight {s!r} was released when its {t!r} image was built -- two kinds cannot be packed from one weight"))
+        self.w.update({("f32", s): kind for s in names})
+        return held
+
+    def _drop_images(self, name) -> None:
+        """forget every image derived from the base weight(s) `name` (they were replaced): the next use rebuilds them"""
+        for key in [k for k in self.w if isinstance(k, tuple) and k[1] == name]:
+            del self.w[key]
 
     # ------------------------------------------------------------------------------ stages
     def _conv(self, name, x, stride, padding, relu=False, residual=None):
@@ -343,9 +424,7 @@ class DTLREngine:
             M = x.numel() // x.shape[-1]
             if self.use_kres and ops.kres_supported(M, w.shape[0], w.shape[1], x.dtype) and (residual is None or w.shape[0] >= 256) \
                     and (w.shape[0] >= 256 or (self.use_kres_narrow and w.shape[1] == 256)):     # narrow outputs: the 256 -> 64 / 128 reductions only
-                if name + ".wk" not in self.w:                # weight-resident streaming form (bottleneck tail / layer1 downsample)
-                    self.w[name + ".wk"] = ops.kres_pack(w)
-                return ops.gemm_kres(x, self.w[name + ".wk"], w.shape[0], self.w[name + ".b"], residual, relu=bool(relu))
+                return ops.gemm_kres(x, self._image("kres", name), w.shape[0], self.w[name + ".b"], residual, relu=bool(relu))
             return ops.linear(x, w, self.w[name + ".b"], relu=(2 if relu else 0), residual=residual)
         return ops.conv2d_nhwc(x, w, self.w[name + ".b"], stride, padding, relu, residual)
 
@@ -353,7 +432,7 @@ class DTLREngine:
         w = self.w[name + ".w"]
         if self.use_k256_small and x.dtype in ops.H16 and not relu and residual is None and a2 is None and out_dtype in (None, x.dtype) \
                 and w.shape[1] == 256 and w.shape[0] in (256, 384) and x.numel() // 256 >= 16384 and x.is_contiguous():
-            return ops.gemm_k256(x, self._k256w(name), w.shape[0], self.w[name + ".b"], row_mask=row_mask)     # plain K = 256 projections
+            return ops.gemm_k256(x, self._image("k256", name), w.shape[0], self.w[name + ".b"], row_mask=row_mask)     # plain K = 256 projections
         return ops.linear(x, w, self.w[name + ".b"], relu, residual, a2, row_mask, out_dtype)
 
     def _ln(self, name, x, residual=None):
@@ -362,24 +441,13 @@ class DTLREngine:
     def _proj_ln(self, proj, norm, a, residual):
         """output projection of an attention block + residual + post-norm (deformable_transformer.py:810-815, 847-870)."""
         w = self.w
-        if self.split and self.use_k256s and proj in self._k256s_ok and a.shape[-1] == 256 and a.numel() // 256 >= self.pln_k256_min_rows:
-            return ops.gemm_k256s(a, self._k256sw(proj), w[proj + ".b"], residual=residual, ln_w=w[norm + ".w"], ln_b=w[norm + ".b"])
+        if self.split and self.use_k256s and self._has_image("k256s", proj) and a.shape[-1] == 256 and a.numel() // 256 >= self.pln_k256_min_rows:
+            return ops.gemm_k256s(a, self._image("k256s", proj), w[proj + ".b"], residual=residual, ln_w=w[norm + ".w"], ln_b=w[norm + ".b"])
         if self.use_pln_k256 and a.dtype in ops.H16 and a.shape[-1] == 256 and a.numel() // 256 >= self.pln_k256_min_rows:
-            if proj + ".wk" not in w:                          # large M (the encoder): weight-resident streaming form
-                w[proj + ".wk"] = ops.proj_ln_k256_pack(w[proj + ".w"])
-            return ops.proj_ln_k256(a, w[proj + ".wk"], w[proj + ".b"], residual, w[norm + ".w"], w[norm + ".b"])
+            return ops.proj_ln_k256(a, self._image("pln_k256", proj), w[proj + ".b"], residual, w[norm + ".w"], w[norm + ".b"])
         if self.use_fused_ffn and a.dtype in ops.H16 and a.shape[-1] == 256:
-            if proj + ".wp" not in w:                          # fragment-major copy of the projection weight, packed once
-                w[proj + ".wp"] = ops.proj_pack_w(w[proj + ".w"])
-            return ops.proj_ln(a, w[proj + ".wp"], w[proj + ".b"], residual, w[norm + ".w"], w[norm + ".b"])
+            return ops.proj_ln(a, self._image("proj", proj), w[proj + ".b"], residual, w[norm + ".w"], w[norm + ".b"])
         return self._ln(norm, self._lin(proj, a), residual=residual)
-
-    def _head_ts(self, name):
-        """(image, padded bias) of class head `name` for the token-stationary kernel, packed once (ops.head_ts_pack)"""
-        key = name + ".ts"
-        if key not in self.w:
-            self.w[key] = ops.head_ts_pack(self.w[name + ".w"], self.w[name + ".b"], self.dtype)
-        return self.w[key]
 
     @torch.no_grad()
     def set_class_head(self, weight, bias) -> None:
@@ -394,8 +462,7 @@ class DTLREngine:
         self._put("class.b", bias.detach().clone(), torch.float32)
         if self.split:
             self.w["class.w"] = ops.split_pack(self.w["class.w"])
-        self.w.pop("class.w2", None)
-        self.w.pop("class.ts", None)
+        self._drop_images("class")
         self.num_classes = int(weight.shape[0])
 
     def _class_head(self, hs):
@@ -408,13 +475,8 @@ class DTLREngine:
             if C >= self.head_ts_min_classes and ops.head_ts_supported(C, "logits") and hs.shape[-1] == 256:
                 # large charsets (Chinese: 7356 classes): tokens stationary in registers, the weight streamed once per 256 tokens --
                 # the same two terms hs . W_hi + hs . W_lo (dtlr_head_ts; the tiled GEMM ran this head at 0.2 of the MFMA peak)
-                img, bias = self._head_ts("class")
-                return ops.head_ts(hs.contiguous(), img, bias, C, "logits")
-            if "class.w2" not in w:
-                wf = w["class.w"].float()
-                hi = wf.to(hs.dtype)
-                w["class.w2"] = torch.cat([hi, (wf - hi.float()).to(hs.dtype)], 1).contiguous()
-            return ops.linear(torch.cat([hs, hs], -1), w["class.w2"], w["class.b"], out_dtype=torch.float32)
+                return ops.head_ts(hs.contiguous(), *self._image("head_ts", "class"), C, "logits")
+            return ops.linear(torch.cat([hs, hs], -1), self._image("head_hi_lo", "class"), w["class.b"], out_dtype=torch.float32)
         return ops.linear(hs.float(), w["class.w"], w["class.b"])
 
     def _ffn(self, q, norm, x):
@@ -423,32 +485,24 @@ class DTLREngine:
         w = self.w
         if self.use_fused_ffn and self.use_ffn32 and x.dtype in ops.H16 and x.numel() // 256 >= 65536 and w[q + "ff1.w"].shape[0] % 32 == 0 \
                 and 64 <= w[q + "ff1.w"].shape[0] <= 2048:
-            if q + "ff.p32" not in w:                           # both weights in the 32x32 fragment order, packed once
-                w[q + "ff.p32"] = ops.ffn32_pack(w[q + "ff1.w"], w[q + "ff2.w"])
-            w1p, w2p = w[q + "ff.p32"]
+            w1p, w2p = self._image("ffn32", q + "ff")
             # whole rounds of 256 workgroups x 256 rows on the 32x32 kernel; a last partial round that fits 256 workgroups of the 16x16
             # kernel (192 or 128 rows each: a shorter round than a third full-length one) goes to that kernel
             M = x.numel() // 256
             rem = M % 65536
             if self.ffn32_tail and 0 < rem <= 49152 and ops.ffn_fused_supported(x, w[q + "ff1.w"]):
-                if q + "ff2.wp" not in w:
-                    w[q + "ff2.wp"] = ops.ffn_pack_w2(w[q + "ff2.w"])
                 x2 = x.reshape(M, 256)
                 y = torch.empty_like(x2)
                 ops.ffn32(x2[:M - rem], w1p, w[q + "ff1.b"], w2p, w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"], out=y[:M - rem])
-                ops.ffn_fused(x2[M - rem:], w[q + "ff1.w"], w[q + "ff1.b"], w[q + "ff2.wp"], w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"],
+                ops.ffn_fused(x2[M - rem:], w[q + "ff1.w"], w[q + "ff1.b"], self._image("ffn_w2", q + "ff2"), w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"],
                               out=y[M - rem:])
                 return y.view(x.shape)
             return ops.ffn32(x, w1p, w[q + "ff1.b"], w2p, w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"])
         if self.split and self.use_fused_ffn and x.shape[-1] == 256 and w[q + "ff1.b"].numel() % 32 == 0 and 32 <= w[q + "ff1.b"].numel() <= 2048:
             # split-fp32 engine: linear1 + ReLU + linear2 + residual + LayerNorm in one kernel on split operands (ffn_split.hip)
-            if q + "ff.sp" not in w:
-                w[q + "ff.sp"] = ops.ffn_split_pack(self._ffn_f32.pop(q + "ff1"), self._ffn_f32.pop(q + "ff2"))
-            return ops.ffn_split(x, w[q + "ff.sp"], w[q + "ff1.b"], w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"])
+            return ops.ffn_split(x, self._image("ffn_split", q + "ff"), w[q + "ff1.b"], w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"])
         if self.use_fused_ffn and ops.ffn_fused_supported(x, w[q + "ff1.w"]):
-            if q + "ff2.wp" not in w:                           # chunk-major copy of linear2.weight, packed once
-                w[q + "ff2.wp"] = ops.ffn_pack_w2(w[q + "ff2.w"])
-            return ops.ffn_fused(x, w[q + "ff1.w"], w[q + "ff1.b"], w[q + "ff2.wp"], w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"])
+            return ops.ffn_fused(x, w[q + "ff1.w"], w[q + "ff1.b"], self._image("ffn_w2", q + "ff2"), w[q + "ff2.b"], w[q + norm + ".w"], w[q + norm + ".b"])
         h = self._lin(q + "ff1", x, relu=True)
         return self._ln(q + norm, self._lin(q + "ff2", h), residual=x)
 
@@ -518,10 +572,7 @@ class DTLREngine:
                 if join is not None:
                     cur.wait_stream(join)
                 if cat:       # the strided shortcut convolution as K columns 128..383 of the tail GEMM: no shortcut map, no gather launch
-                    if q + "cat.wk" not in self.w:
-                        self.w[q + "cat.wk"] = ops.kres_pack(torch.cat([self.w[q + "c3.w"], self.w[q + "ds.w"]], 1).contiguous())
-                        self.w[q + "cat.b"] = (self.w[q + "c3.b"].float() + self.w[q + "ds.b"].float()).contiguous()
-                    x = ops.gemm_kres_cat_s2(o, x, self.w[q + "cat.wk"], self.w[q + "cat.b"], relu=True)
+                    x = ops.gemm_kres_cat_s2(o, x, *self._image("kres_cat", q[:-1]), relu=True)
                 else:
                     x = self._conv(q + "c3", o, 1, 0, relu=True, residual=idt)
                 s += stride - 1
@@ -555,14 +606,8 @@ class DTLREngine:
         produces the NEXT bottleneck's conv1 output from the tile it has on chip (the 256-channel map is written once and not re-read
         by conv1; the last tail feeds layer2.0.conv1).  torchvision Bottleneck.forward: out = relu(bn3(conv3(.)) + identity)."""
         w = self.w
-
-        def wk(name):
-            if name + ".wk" not in w:
-                w[name + ".wk"] = ops.kres_pack(w[name + ".w"])
-            return w[name + ".wk"]
-        if "l1.0.cat.wk" not in w:
-            w["l1.0.cat.wk"] = ops.kres_pack(torch.cat([w["l1.0.c3.w"], w["l1.0.ds.w"]], 1).contiguous())
-            w["l1.0.cat.b"] = (w["l1.0.c3.b"].float() + w["l1.0.ds.b"].float()).contiguous()
+        wk = lambda name: self._image("kres", name)
+        cat_w, cat_b = self._image("kres_cat", "l1.0")
         if self._l1_block_takes(x0, nblocks, ext):
             # every bottleneck as ONE launch (ops.l1_bottleneck: conv1 -> conv2 -> conv3 + shortcut with the 64-channel maps kept on chip),
             # the last one also emitting layer2.0.conv1; bit-identical to the chain below
@@ -571,7 +616,7 @@ class DTLREngine:
                 q = f"l1.{bi}."
                 last = bi == nblocks - 1 and self.use_l1_chain_out
                 x, o = ops.l1_bottleneck(x, wk(q + "c1"), w[q + "c1.b"], w[q + "c2.w"], w[q + "c2.b"],
-                                         w["l1.0.cat.wk"] if bi == 0 else wk(q + "c3"), w["l1.0.cat.b"] if bi == 0 else w[q + "c3.b"],
+                                         cat_w if bi == 0 else wk(q + "c3"), cat_b if bi == 0 else w[q + "c3.b"],
                                          wnp=wk("l2.0.c1") if last else None, bn=w["l2.0.c1.b"] if last else None, n2=128 if last else 0)
             return x, o
         nxt = [f"l1.{bi + 1}.c1" for bi in range(nblocks - 1)] + (["l2.0.c1"] if self.use_l1_chain_out else [None])
@@ -589,7 +634,7 @@ class DTLREngine:
                 nm = None                       # a next conv1 the chain kernel has no form for (other widths; a one-block layer1): separate launch
             kw = dict(wp2=wk(nm), b2=w[nm + ".b"], n2=n2[bi]) if nm is not None else {}
             if bi == 0:
-                x, o = ops.gemm_kres_chain(o, w["l1.0.cat.wk"], w["l1.0.cat.b"], x2=x0, relu=True, **kw)
+                x, o = ops.gemm_kres_chain(o, cat_w, cat_b, x2=x0, relu=True, **kw)
             elif nm is not None:
                 x, o = ops.gemm_kres_chain(o, wk(f"l1.{bi}.c3"), w[f"l1.{bi}.c3.b"], residual=x, relu=True, **kw)
             else:
@@ -615,37 +660,6 @@ class DTLREngine:
         shapes, lsi, fits = self._level_cache[key]
         g.update(shapes=shapes, lsi=lsi, has_padding=has_padding, level_hw=level_hw, lds_msda_fits=fits)
         return g
-
-    def _k256sw(self, name):
-        """split engine: the resident-operand image of a [256, 256] projection for dtlr_gemm_k256s, packed once from the fp32 weight."""
-        key = name + ".k256s"
-        if key not in self.w:
-            self.w[key] = ops.k256s_pack(self._ffn_f32.pop(name))
-        return self.w[key]
-
-    def _k256s_slices(self, name):
-        """split engine: the weight [N, 256] of projection `name` (N a multiple of 128) as ceil(N / 256) resident-operand images of
-        dtlr_gemm_k256s_multi, the last one zero-padded to 256 rows; packed once from the fp32 weight.  Returns [(image, first row, rows)]."""
-        key = name + ".k256sm"
-        if key not in self.w:
-            wf = self._ffn_f32.pop(name)
-            N = wf.shape[0]
-            imgs = []
-            for r0 in range(0, N, 256):
-                n = min(256, N - r0)
-                blk = wf[r0:r0 + n]
-                if n < 256:
-                    blk = torch.cat([blk, blk.new_zeros((256 - n, 256))], 0)
-                imgs.append((ops.k256s_pack(blk.contiguous()), r0, n))
-            self.w[key] = imgs
-        return self.w[key]
-
-    def _k256w(self, name):
-        """fragment-order image of a [N, 256] projection weight for the weight-resident kernel, packed once."""
-        key = name + ".k256"
-        if key not in self.w:
-            self.w[key] = ops.k256_pack(self.w[name + ".w"])
-        return self.w[key]
 
     def _msda_mode(self, name, value_dtype, level_hw, ow, ref, n_heads):
         """'lds' or 'gather' for this encoder layer.  The LDS-window kernel fetches sampling points outside its staged columns through a
@@ -710,27 +724,25 @@ class DTLREngine:
         S = value_src.shape[1]
         M, L, P = cfg.nheads, cfg.num_feature_levels, n_points
         k256 = self.use_k256 and query.dtype in ops.H16 and C == 256 and Lq == S
-        k256s = self.split and self.use_k256s and C == 256 and Lq == S and (name + ".value") in self._k256s_ok
+        k256s = self.split and self.use_k256s and C == 256 and Lq == S and self._has_image("k256s", name + ".value")
         ow = None
         if (k256s and self.use_k256s_multi_enc and value is None and ow_res is not None and not g["has_padding"] and value_src is query
-                and query.is_contiguous() and ((name + ".ow") in self._ffn_f32 or (name + ".ow.k256sm") in self.w)
+                and query.is_contiguous() and self._has_image("k256s_slices", name + ".ow")
                 and tuple(self.w[name + ".ow.w"].shape) == (384, 256) and ow_res.shape[-2] == S and S % 32 == 0):
             # split engine, unpadded batch: value_proj(src) and [offsets | logits](src + pos) = src W^T + (pos W^T + b) in ONE pass over src
             # (three slices: 256 | 256 | 128 channels; the position term is the row-broadcast residual of the last two)
-            vimg = self._k256sw(name + ".value")
-            oimgs = self._k256s_slices(name + ".ow")
             value = torch.empty((B, S, 256), dtype=torch.float32, device=query.device)
             ow = torch.empty((B, S, 384), dtype=torch.float32, device=query.device)
-            sl = [dict(wp=vimg, out=value, bias=self.w[name + ".value.b"])]
-            for img, r0, nr in oimgs:
+            sl = [dict(wp=self._image("k256s", name + ".value"), out=value, bias=self.w[name + ".value.b"])]
+            for img, r0, nr in self._image("k256s_slices", name + ".ow"):
                 sl.append(dict(wp=img, out=ow[..., r0:r0 + nr], residual=ow_res[..., r0:r0 + nr]))
             ops.gemm_k256s_multi(query, sl, res_rows=S)
         if value is None:
             if k256s:
-                value = ops.gemm_k256s(value_src, self._k256sw(name + ".value"), self.w[name + ".value.b"],
+                value = ops.gemm_k256s(value_src, self._image("k256s", name + ".value"), self.w[name + ".value.b"],
                                        row_mask=g["mask_flat"] if g["has_padding"] else None)
             elif k256:
-                value = ops.gemm_k256(value_src, self._k256w(name + ".value"), 256, self.w[name + ".value.b"],
+                value = ops.gemm_k256(value_src, self._image("k256", name + ".value"), 256, self.w[name + ".value.b"],
                                       row_mask=g["mask_flat"] if g["has_padding"] else None)
             else:
                 value = self._lin(name + ".value", value_src, row_mask=g["mask_flat"] if g["has_padding"] else None)
@@ -743,11 +755,9 @@ class DTLREngine:
             # image (L2-resident): the projection streams src alone and adds the row-broadcast term in its epilogue
             rows = ow_res.numel() // 384
             if self.use_kres and rows % 64 == 0 and (query.numel() // 256) % rows == 0 and self.w[name + ".ow.w"].shape[0] == 384:
-                if name + ".ow.kb" not in self.w:               # residual tile DMA'd through LDS with the token tile (dtlr_gemm_kres_bcast384)
-                    self.w[name + ".ow.kb"] = ops.kres_pack_bcast384(self.w[name + ".ow.w"])
-                ow = ops.gemm_kres_bcast384(query, self.w[name + ".ow.kb"], ow_res)
+                ow = ops.gemm_kres_bcast384(query, self._image("bcast384", name + ".ow"), ow_res)     # residual tile DMA'd through LDS with the token tile
             else:
-                ow = ops.gemm_k256(query, self._k256w(name + ".ow"), 384, None, resid=ow_res)
+                ow = ops.gemm_k256(query, self._image("k256", name + ".ow"), 384, None, resid=ow_res)
         elif ow_res is not None:
             # fp32 / split engines, unpadded batch: the same identity through the tiled GEMM's row-broadcast residual epilogue (the A + A2
             # prologue variant keeps compiler-counted loads and half the occupancy: 212 us against the plain projection's ~140 at B = 32)
@@ -798,10 +808,7 @@ class DTLREngine:
             # head then runs on the bf16 matrix cores against [W_hi | W_hi | W_lo] (three-term split product, ~2^-16 relative:
             # selection scores as good as the fp32 MFMA path at a third of its time), and output_memory of the 900 selected rows
             # is rebuilt as hi + lo.
-            if "enc_output.wp" not in w:
-                w["enc_output.wp"] = ops.proj_pack_w(w["enc_output.w"])
-                w["enc_class.w3"], w["enc_class.b3"] = ops.split_head_weight(w["enc_class.w"], w["enc_class.b"], dtype=memory.dtype)
-            om = ops.proj_ln_split(memory, w["enc_output.wp"], w["enc_output.b"], g["keep"], w["enc_output_norm.w"], w["enc_output_norm.b"])
+            om = ops.proj_ln_split(memory, self._image("proj", "enc_output"), w["enc_output.b"], g["keep"], w["enc_output_norm.w"], w["enc_output_norm.b"])
             # only max_c of the class head feeds the top-k: the GEMM's row-max epilogue (no [T, C] matrix, no reduction pass)
             # (Round 3 measured a two-pass form for the 7356-class head -- hi-only product over all tokens, exact three-term product over
             # the 1536 best candidates per line: 18.22 -> 17.56 ms per cfg5 step only, because the K = 256 pass is epilogue-bound (one
@@ -812,16 +819,15 @@ class DTLREngine:
             if (self.head_ts_scores or C_enc >= self.head_ts_min_classes) and ops.head_ts_supported(C_enc, "rowmax"):
                 # round 5: for a large charset the tiled GEMM re-reads its token rows once per 128-channel tile (58 times for 7356 classes:
                 # 4.9 of the Chinese step's 17 ms at 0.2 of the MFMA peak); the token-stationary kernel streams the weight instead
-                img, bias = self._head_ts("enc_class")
-                scores = ops.head_ts(om, img, bias, C_enc, "rowmax", 0, 256)
+                scores = ops.head_ts(om, *self._image("head_ts", "enc_class"), C_enc, "rowmax", 0, 256)
             else:
-                scores = ops.linear_rowmax(om, w["enc_class.w3"], w["enc_class.b3"])
+                scores = ops.linear_rowmax(om, *self._image("head_split3", "enc_class"))
         else:
-            if self.split and self.use_k256s and "enc_output" in self._k256s_ok and memory.shape[-1] == 256:
+            if self.split and self.use_k256s and self._has_image("k256s", "enc_output") and memory.shape[-1] == 256:
                 # split engine: masking, projection and LayerNorm in one streaming pass (dtlr_gemm_k256s, LN form with a row mask)
                 if "drop_rows" not in g:
                     g["drop_rows"] = (~g["keep"].bool()).contiguous()
-                om = ops.gemm_k256s(memory, self._k256sw("enc_output"), w["enc_output.b"], row_mask=g["drop_rows"],
+                om = ops.gemm_k256s(memory, self._image("k256s", "enc_output"), w["enc_output.b"], row_mask=g["drop_rows"],
                                     ln_w=w["enc_output_norm.w"], ln_b=w["enc_output_norm.b"])
             else:
                 om = memory * g["keep"].unsqueeze(-1).to(memory.dtype)
@@ -870,8 +876,8 @@ class DTLREngine:
     def _box_mlp(self, name, x, ref, mode):
         """3-layer box MLP + consumer: mode 0 sigmoid(mlp(x) + inverse_sigmoid(ref)), mode 1 mlp(x) + ref."""
         w = self.w
-        if name + "1.wp" in w:                         # bf16 engine: one launch
-            return ops.box_mlp_refine(x.to(self.dtype), w[name + "0.wh"], w[name + "0.b"], w[name + "1.wp"], w[name + "1.b"],
+        if name + "1.wh" in w:                         # bf16 engine: one launch
+            return ops.box_mlp_refine(x.to(self.dtype), w[name + "0.wh"], w[name + "0.b"], self._image("ffn_w2", name + "1"), w[name + "1.b"],
                                       w[name + "2.w"], w[name + "2.b"], ref, mode)
         return ops.box_head_refine(self._box_mlp_hidden(name, x), w[name + "2.w"], w[name + "2.b"], ref, mode=mode)
 
@@ -897,18 +903,15 @@ class DTLREngine:
         Nall = self.w["dec.value_all.w"].shape[0]
         if self.use_k256 and memory.dtype in ops.H16 and C == 256 and Nall % 384 == 0:
             # weight-resident streaming kernel, 384 output channels per launch, written as column slices of one [B, S, N] buffer
-            for j in range(Nall // 384):
-                key = f"dec.value_all.k256.{j}"
-                if key not in self.w:
-                    self.w[key] = ops.k256_pack(self.w["dec.value_all.w"][384 * j:384 * (j + 1)])
-                ops.gemm_k256(memory, self.w[key], 384, self.w["dec.value_all.b"][384 * j:384 * (j + 1)], row_mask=rmask,
+            for j, img in enumerate(self._image("k256_slices", "dec.value_all")):
+                ops.gemm_k256(memory, img, 384, self.w["dec.value_all.b"][384 * j:384 * (j + 1)], row_mask=rmask,
                               out=vall[..., 384 * j:384 * (j + 1)])
             return True
         if (self.split and self.use_k256s_multi and C == 256 and Nall % 256 == 0 and Nall // 256 <= 8 and memory.is_contiguous()
-                and ("dec.value_all" in self._ffn_f32 or "dec.value_all.k256sm" in self.w)):
+                and self._has_image("k256s_slices", "dec.value_all")):
             # split engine: the six value projections as six slices of ONE pass over memory (dtlr_gemm_k256s_multi)
             bias = self.w["dec.value_all.b"]
-            ops.gemm_k256s_multi(memory, [dict(wp=img, out=vall[..., r0:r0 + nr], bias=bias[r0:r0 + nr]) for img, r0, nr in self._k256s_slices("dec.value_all")],
+            ops.gemm_k256s_multi(memory, [dict(wp=img, out=vall[..., r0:r0 + nr], bias=bias[r0:r0 + nr]) for img, r0, nr in self._image("k256s_slices", "dec.value_all")],
                                  row_mask=rmask)
             return True
         return False
@@ -937,12 +940,9 @@ class DTLREngine:
             q = f"dec{n}."
             w = self.w
             if self.use_dec_query_stage and tgt.dtype in ops.H16 and C == 256 and w["dec.rph0.w"].shape == (256, 512):
-                for nm in ("dec.rph0", "dec.rph1", q + "sa.qk", q + "sa.v"):
-                    if nm + ".dq" not in w:                    # fragment-order images, packed once
-                        w[nm + ".dq"] = ops.dq_pack(w[nm + ".w"])
-                ref_in, qpos, qk, v = ops.dec_query_stage(ref, g["valid_ratios"], tgt, w["dec.rph0.dq"], w["dec.rph0.b"], w["dec.rph1.dq"],
-                                                          w["dec.rph1.b"], w[q + "sa.qk.dq"], w[q + "sa.qk.b"], w[q + "sa.v.dq"], w[q + "sa.v.b"],
-                                                          per_line=per_line)
+                dq = [self._image("dq", nm) for nm in ("dec.rph0", "dec.rph1", q + "sa.qk", q + "sa.v")]
+                ref_in, qpos, qk, v = ops.dec_query_stage(ref, g["valid_ratios"], tgt, dq[0], w["dec.rph0.b"], dq[1], w["dec.rph1.b"],
+                                                          dq[2], w[q + "sa.qk.b"], dq[3], w[q + "sa.v.b"], per_line=per_line)
             else:
                 ref_in, sine = ops.decoder_query_prep(ref, g["valid_ratios"], self.dtype, per_line)      # [B,nq,L,4], [B,nq,512]
                 qpos = self._lin("dec.rph1", self._lin("dec.rph0", sine, relu=True))
@@ -1063,10 +1063,9 @@ class DTLREngine:
         if "hs_enc3" in ts:                                        # bf16 engine: the two-stage head on its split images
             C = int(self.w["enc_class.w"].shape[0])     # the two-stage head's OWN class count (--fix_enc_out_class keeps the old one)
             if C >= self.head_ts_min_classes and ops.head_ts_supported(C, "logits"):
-                img, bias = self._head_ts("enc_class")
-                interm_class = ops.head_ts(ts["hs_enc3"].contiguous(), img, bias, C, "logits", 0, 256)
+                interm_class = ops.head_ts(ts["hs_enc3"].contiguous(), *self._image("head_ts", "enc_class"), C, "logits", 0, 256)
             else:
-                interm_class = ops.linear(ts["hs_enc3"], self.w["enc_class.w3"][:C], self.w["enc_class.b3"][:C], out_dtype=torch.float32)
+                interm_class = ops.linear(ts["hs_enc3"], *(t[:C] for t in self._image("head_split3", "enc_class")), out_dtype=torch.float32)
         else:
             interm_class = ops.linear(ts["hs_enc"], self.w["enc_class.w"], self.w["enc_class.b"])
         out["interm_outputs"] = {"pred_logits": interm_class, "pred_boxes": ts["ref_unsig"].sigmoid()}
