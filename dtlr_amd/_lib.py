@@ -153,6 +153,11 @@ _SIGNATURES = {
                                           c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_decode_nms_located": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # forced alignment (csrc/ctc_align.hip)
+    "dtlr_ctc_align": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtlr_ctc_align_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int, c_int]),
+    "dtlr_reading_order": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     # per-line batching
     "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_zero_outside_extent_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -186,12 +186,21 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
 # A rank fills the rows of other ranks' lines with ZEROS and the shards are merged with all_reduce(SUM): exactly one rank owns a line
 # and adding zeros is exact for every bit pattern (the -1 fill + MAX merge of predict_labels is not: a negative coordinate, or
 # -0.0, is a large negative int32).  The status column travels apart, with predict_labels's -1 fill and MAX.
+#   and, with aligned words (align_rewritten), [per word: 0 = none, else 1 + its aligned characters, K | aligned characters 2K x 10 =
+#   (label, query, rank, first, last, score, box x 4)]
+# A line of the forced alignment (decoder "align") is the first form plus [first K | last K | logp as the two halves of its fp64 |
+# feasible]; its transcript is the caller's and does not travel.
 _LOC_HEAD = 3
 _LOC_WORD = 10                 # first char, end char (-1, -1: no characters), source (1 = ngram), same, score, box x 4, n labels
+_LOC_ALIGNED = 10              # label, query, rank, first, last, score, box x 4
 
 
-def located_row_width(K: int, with_words: bool) -> int:
-    return _LOC_HEAD + 8 * K + ((_LOC_WORD + 2) * K if with_words else 0)
+def located_row_width(K: int, with_words: bool, with_aligned: bool = False) -> int:
+    return _LOC_HEAD + 8 * K + ((_LOC_WORD + 2) * K if with_words else 0) + ((1 + 2 * _LOC_ALIGNED) * K if with_aligned else 0)
+
+
+def aligned_row_width(K: int) -> int:
+    return located_row_width(K, False) + 2 * K + 3
 
 
 def _f2i(values) -> np.ndarray:
@@ -202,10 +211,21 @@ def _i2f(values) -> np.ndarray:
     return np.ascontiguousarray(values, dtype=np.int32).view(np.float32)
 
 
-def pack_located(line: "E.LocatedLine", K: int, with_words: bool) -> np.ndarray:
-    """LocatedLine -> int32 row of located_row_width(K, with_words).  Without the word table the words are rebuilt from the characters
-    on the other side (unpack_located(space_label=...))."""
-    row = np.zeros(located_row_width(K, with_words), dtype=np.int32)
+def _pack_aligned_char(c: "E.LocatedChar") -> np.ndarray:
+    ints = np.array([c.label, c.query, -1 if c.rank is None else c.rank, -1 if c.first is None else c.first,
+                     -1 if c.last is None else c.last], dtype=np.int32)
+    return np.concatenate([ints, _f2i([c.score]), _f2i(c.box)])
+
+
+def _unpack_aligned_char(v) -> "E.LocatedChar":
+    opt = lambda x: None if x < 0 else int(x)                              # noqa: E731
+    return E.LocatedChar(int(v[0]), float(_i2f(v[5:6])[0]), tuple(_i2f(v[6:10]).tolist()), int(v[1]), opt(v[2]), opt(v[3]), opt(v[4]))
+
+
+def pack_located(line: "E.LocatedLine", K: int, with_words: bool, with_aligned: bool = False) -> np.ndarray:
+    """LocatedLine -> int32 row of located_row_width(K, with_words, with_aligned).  Without the word table the words are rebuilt from
+    the characters on the other side (unpack_located(space_label=...))."""
+    row = np.zeros(located_row_width(K, with_words, with_aligned), dtype=np.int32)
     n = len(line.chars)
     if n > K:
         raise ValueError(f"pack_located: {n} characters for {K} slots")
@@ -228,10 +248,47 @@ def pack_located(line: "E.LocatedLine", K: int, with_words: bool) -> np.ndarray:
                 [np.array([c0, c1, int(w.source == "ngram"), int(w.same)], dtype=np.int32), _f2i([w.score]), _f2i(w.box),
                  np.array([len(w.labels)], dtype=np.int32)])
         row[o + _LOC_WORD * K: o + _LOC_WORD * K + len(wl)] = wl
+        if with_aligned:
+            o = located_row_width(K, True)
+            at = o + K
+            if sum(len(w.aligned or ()) for w in line.words) > 2 * K:
+                raise ValueError(f"pack_located: more than {2 * K} aligned characters")
+            for k, w in enumerate(line.words):
+                if w.aligned is not None:
+                    row[o + k] = 1 + len(w.aligned)
+                    for c in w.aligned:
+                        row[at: at + _LOC_ALIGNED] = _pack_aligned_char(c)
+                        at += _LOC_ALIGNED
     return row
 
 
-def unpack_located(row, K: int, with_words: bool, decoder: str, space_label: Optional[int] = None) -> "E.LocatedLine":
+def pack_aligned(line: "E.LocatedLine", K: int) -> np.ndarray:
+    """A line of the forced alignment -> int32 row of aligned_row_width(K)"""
+    row = np.zeros(aligned_row_width(K), dtype=np.int32)
+    o = located_row_width(K, False)
+    row[:o] = pack_located(line, K, False)
+    n = len(line.chars)
+    row[o: o + n] = [c.first for c in line.chars]
+    row[o + K: o + K + n] = [c.last for c in line.chars]
+    feasible = line.logp is not None and line.logp > float("-inf")
+    row[o + 2 * K: o + 2 * K + 2] = np.array([line.logp if feasible else 0.0], dtype=np.float64).view(np.int32)
+    row[o + 2 * K + 2] = int(feasible)
+    return row
+
+
+def unpack_aligned(row, K: int, labels: Sequence[int], space_label: Optional[int] = None) -> "E.LocatedLine":
+    """pack_aligned's row and the line's transcript -> the LocatedLine of E.align_ctc"""
+    row = np.asarray(row, dtype=np.int32)
+    o = located_row_width(K, False)
+    base = unpack_located(row[:o], K, False, "align", space_label)
+    for i, c in enumerate(base.chars):
+        c.first, c.last = int(row[o + i]), int(row[o + K + i])
+    logp = float(np.ascontiguousarray(row[o + 2 * K: o + 2 * K + 2]).view(np.float64)[0]) if row[o + 2 * K + 2] else float("-inf")
+    return E.LocatedLine([int(v) for v in labels], base.chars, E.located_words(base.chars, space_label), "align", logp)
+
+
+def unpack_located(row, K: int, with_words: bool, decoder: str, space_label: Optional[int] = None,
+                   with_aligned: bool = False) -> "E.LocatedLine":
     row = np.asarray(row, dtype=np.int32)
     n, o = int(row[0]), _LOC_HEAD
     lab, qry, rk = row[o: o + n].tolist(), row[o + K: o + K + n].tolist(), row[o + 2 * K: o + 2 * K + n].tolist()
@@ -248,6 +305,13 @@ def unpack_located(row, K: int, with_words: bool, decoder: str, space_label: Opt
         words.append(E.LocatedWord(row[at: at + nl].tolist(), tuple(_i2f(w[5:9]).tolist()), float(_i2f(w[4:5])[0]),
                                    None if w[0] < 0 else (int(w[0]), int(w[1])), "ngram" if w[2] else "kept", bool(w[3])))
         at += nl
+    if with_aligned:
+        o = located_row_width(K, True)
+        at = o + K
+        for k, w in enumerate(words):
+            if row[o + k]:
+                w.aligned = [_unpack_aligned_char(row[at + _LOC_ALIGNED * i: at + _LOC_ALIGNED * (i + 1)]) for i in range(int(row[o + k]) - 1)]
+                at += _LOC_ALIGNED * len(w.aligned)
     return E.LocatedLine([v for w in words for v in w.labels], chars, words, decoder)
 
 
@@ -266,16 +330,23 @@ def merge_located(rows: torch.Tensor, status: torch.Tensor, device=None) -> Tupl
 def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Optional[float] = None, NM: Optional[float] = None,
                     device="cuda", size: int = EVAL_SIZE, max_size: int = EVAL_MAX_SIZE, rank: int = 0, world: int = 1,
                     sizes: Optional[Sequence[Tuple[int, int]]] = None, skip_errors: bool = True, per_line: bool = False,
-                    ngram: Optional[Dict] = None, decoder: str = "blank", space_label: Optional[int] = None) -> List[Optional["E.LocatedLine"]]:
+                    ngram: Optional[Dict] = None, decoder: str = "blank", space_label: Optional[int] = None,
+                    targets: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                    align_rewritten: bool = False) -> List[Optional["E.LocatedLine"]]:
     """predict_labels with every character located: one LocatedLine per image (None for a skipped line), dataset order, boxes in
     the SOURCE image's pixels.  decoder: "blank" (eps = 0.03 / C), "nms" (TH / NM, default 0.3 / 0.5) or "ngram" (`ngram` = the bundle
     of ngram_bundle(); words re-scored by the device beam, boxes at word level).  Batching (`exact`, padded, `per_line`), sharding and
     error handling are predict_labels's.  pred_boxes are normalised to each line's own extent, so the source (w, h) is the whole
-    scale, for padded and ragged batches alike.  space_label: the charset's ' ' index (words are cut there), or None."""
-    if decoder not in ("blank", "nms", "ngram"):
+    scale, for padded and ragged batches alike.  space_label: the charset's ' ' index (words are cut there), or None.
+    decoder "align": the forced alignment of `targets` (per image its transcript as label indices; None: the line is skipped) against
+    the model's output (E.align_ctc, eps = 0.003, loss_CTC's lattice).  align_rewritten (decoder "ngram"): words the beam rewrote
+    carry their aligned characters."""
+    if decoder not in ("blank", "nms", "ngram", "align"):
         raise ValueError(f"predict_located: unknown decoder {decoder!r}")
     if decoder == "ngram" and ngram is None:
         raise ValueError("predict_located: decoder 'ngram' needs the `ngram` bundle")
+    if decoder == "align" and targets is None:
+        raise ValueError("predict_located: decoder 'align' needs `targets`")
     lazy = callable(images)
     if lazy and sizes is None:
         raise ValueError("predict_located: a loader callable needs `sizes`")
@@ -286,22 +357,31 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
     lo, hi = ddist.shard_bounds(len(batches), rank, world)
     tf = EvalTransform(size, max_size)
     K, with_words = model.num_queries, decoder == "ngram"
-    rows = torch.zeros((n, located_row_width(K, with_words)), dtype=torch.int32)
+    with_aligned = with_words and align_rewritten
+    if decoder == "align":
+        if len(targets) != n:
+            raise ValueError(f"predict_located: {len(targets)} transcripts for {n} images")
+        K = max([1] + [len(t) for t in targets if t is not None])
+    rows = torch.zeros((n, aligned_row_width(K) if decoder == "align" else located_row_width(K, with_words, with_aligned)), dtype=torch.int32)
     status = torch.full((n,), -1, dtype=torch.int32)
 
     def run(idx):
         samples = tf([load(i) for i in idx], device=device)
         out = model(samples, per_line=True) if per_line else model(samples)
         hw = torch.tensor(samples.orig_sizes, dtype=torch.float32)
-        if decoder == "ngram":
+        if decoder == "align":
+            if any(targets[i] is None for i in idx):
+                raise ValueError("a transcript holds a character outside the charset")
+            lines = E.align_ctc(out, [targets[i] for i in idx], 0.003, hw, True, space_label)
+        elif decoder == "ngram":
             from . import ngram as NG
-            lines = NG.rescored_located_batch(out, ngram, hw, space_label)
+            lines = NG.rescored_located_batch(out, ngram, hw, space_label, align_rewritten)
         elif decoder == "nms":
             lines = E.decode_nms_located(out, 0.3 if TH is None else TH, 0.5 if NM is None else NM, hw, space_label)
         else:
             lines = E.decode_blank_located(out, None, hw, space_label)
         for i, line in zip(idx, lines):
-            rows[i] = torch.from_numpy(pack_located(line, K, with_words))
+            rows[i] = torch.from_numpy(pack_aligned(line, K) if decoder == "align" else pack_located(line, K, with_words, with_aligned))
             status[i] = 0
 
     for b in batches[lo:hi]:
@@ -324,7 +404,9 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
     if world > 1:
         rows, status = merge_located(rows, status, device)
     rows_np = rows.numpy()
-    return [None if int(status[i]) == 1 else unpack_located(rows_np[i], K, with_words, decoder, space_label) for i in range(n)]
+    if decoder == "align":
+        return [None if int(status[i]) == 1 else unpack_aligned(rows_np[i], K, targets[i], space_label) for i in range(n)]
+    return [None if int(status[i]) == 1 else unpack_located(rows_np[i], K, with_words, decoder, space_label, with_aligned) for i in range(n)]
 
 
 def write_layout(path: str, ids: Sequence[str], lines: Sequence[Optional["E.LocatedLine"]], charset: Sequence[str]) -> int:
@@ -337,6 +419,24 @@ def write_layout(path: str, ids: Sequence[str], lines: Sequence[Optional["E.Loca
             f.write(json.dumps(E.located_line_to_json(line, charset, line_id), ensure_ascii=False) + "\n")
             k += 1
     return k
+
+
+def write_aligned(path: str, ids: Sequence[str], lines: Sequence[Optional["E.LocatedLine"]], charset: Sequence[str]) -> int:
+    """`--align-out`: one JSON object per aligned line image (a skipped line writes none), in dataset order.  -> lines written."""
+    k = 0
+    with open(path, "w", encoding="utf-8") as f:
+        for line_id, line in zip(ids, lines):
+            if line is None:
+                continue
+            f.write(json.dumps(E.aligned_line_to_json(line, charset, line_id), ensure_ascii=False) + "\n")
+            k += 1
+    return k
+
+
+def transcript_labels(texts: Sequence[str], charset: Sequence[str]) -> List[Optional[List[int]]]:
+    """per transcript its label indices, or None when it holds a character the charset lacks"""
+    index = {c: i for i, c in enumerate(charset)}
+    return [[index[ch] for ch in t] if all(ch in index for ch in t) else None for t in texts]
 
 
 def evaluate_predictions(pred_labels: Sequence[Sequence[int]], gt_texts: Sequence[str], charset: Sequence, dataset: str = "IAM",
@@ -488,6 +588,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--layout-out", default=None, metavar="FILE.jsonl",
                     help="also write every line's located transcript (characters and words with boxes in source-image pixels), one JSON "
                          "object per line image; needs a single decoder setting")
+    ap.add_argument("--layout-align", action="store_true",
+                    help="with --layout-out and an n-gram: a word the beam rewrote also gets \"aligned\", its characters placed by the "
+                         "forced alignment of its labels over its own frames")
+    ap.add_argument("--align-out", default=None, metavar="FILE.jsonl",
+                    help="also write the forced alignment of every line's transcript (--labels) against the model's output: the located "
+                         "JSON with \"decoder\": \"align\", each character where the best CTC path puts it, plus \"logp\" and \"feasible\"")
     return ap
 
 
@@ -536,6 +642,14 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     last = {}
     if args.layout_out and len(list_TH) * len(list_NM) > 1:
         raise SystemExit("--layout-out needs one decoder setting (--TH and --NMS, or neither), not the --NMS_inference grid")
+    if args.align_out:                                         # the transcripts against the model's output; apart from the decoders
+        cs_str = [chr(c) if args.unicode else str(c) for c in charset]
+        aligned = predict_located(model, images, args.batch, args.batching == "exact", None, None, dev, args.size, args.max_size,
+                                  rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", decoder="align",
+                                  space_label=E.space_label_of(cs_str), targets=transcript_labels(texts, cs_str))
+        if rank == 0:
+            k = write_aligned(args.align_out, [name for name, _ in rows], aligned, cs_str)
+            print(f"wrote {k} aligned lines to {args.align_out}", file=sys.stderr)
     for TH in list_TH:
         for NM in list_NM:
             if args.layout_out:                                # the same decode with its records kept: the labels are the metrics' input
@@ -543,7 +657,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                 located = predict_located(model, images, args.batch, args.batching == "exact", TH, NM, dev, args.size, args.max_size,
                                           rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", ngram=bundle,
                                           decoder="ngram" if bundle is not None else ("nms" if nms_inference else "blank"),
-                                          space_label=E.space_label_of(cs_str))
+                                          space_label=E.space_label_of(cs_str), align_rewritten=args.layout_align and bundle is not None)
                 preds = [None if line is None else list(line.labels) for line in located]
                 if rank == 0:
                     k = write_layout(args.layout_out, [name for name, _ in rows], located, cs_str)

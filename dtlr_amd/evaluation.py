@@ -170,25 +170,31 @@ Box = Tuple[float, float, float, float]
 @dataclasses.dataclass
 class LocatedChar:
     """One decoded character: its label, the score the decoder gave it, its xyxy box, the query it came from and (blank decoder) its
-    rank = the query's position in the line's reading order = its frame in the n-gram emissions."""
+    rank = the query's position in the line's reading order = its frame in the n-gram emissions.  A character placed by the forced
+    alignment also carries `first` / `last`, the frames of the first and the last lattice frame its state holds (rank = the peak)."""
     label: int
     score: float
     box: Box
     query: int
     rank: Optional[int] = None
+    first: Optional[int] = None
+    last: Optional[int] = None
 
 
 @dataclasses.dataclass
 class LocatedWord:
     """A word of a located line: `labels`, the union `box` and the minimum `score` of its characters, `chars` = (i0, i1), the range
     of the line's `chars` it covers (None when it covers none), and `source`: "kept" = the detection decoder's own characters,
-    "ngram" = a span the n-gram beam re-scored (its labels are the beam's; `same` tells whether they equal the detections')."""
+    "ngram" = a span the n-gram beam re-scored (its labels are the beam's; `same` tells whether they equal the detections').
+    `aligned`: the characters of a word the beam rewrote, placed by the forced alignment of its labels over its own frames
+    (ngram.rescored_located_batch(align_rewritten=True)); None otherwise, [] when the labels do not fit the frames."""
     labels: List[int]
     box: Box
     score: float
     chars: Optional[Tuple[int, int]]
     source: str = "kept"
     same: bool = True
+    aligned: Optional[List[LocatedChar]] = None
 
 
 @dataclasses.dataclass
@@ -197,6 +203,7 @@ class LocatedLine:
     chars: List[LocatedChar]
     words: List[LocatedWord]
     decoder: str = "blank"
+    logp: Optional[float] = None        # decoder "align": ln p of the best path of `labels`; -inf: they do not fit the line
 
     def text(self, charset: Sequence) -> str:
         return labels_to_string(self.labels, charset)
@@ -270,13 +277,112 @@ def decode_nms_located(outputs, TH: float = 0.3, NM: float = 0.5, src_hw=None, s
 
 
 def located_line_to_json(line: LocatedLine, charset: Sequence, line_id: str) -> Dict:
-    """The object `--layout-out` writes for one line image."""
+    """The object `--layout-out` writes for one line image.  A word that carries aligned characters adds them as "aligned"."""
     cs = list(charset)
+    char = lambda c: {"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query}     # noqa: E731
     return {"id": line_id, "decoder": line.decoder, "text": line.text(cs),
-            "chars": [{"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query} for c in line.chars],
+            "chars": [char(c) for c in line.chars],
             "words": [{"text": labels_to_string(w.labels, cs), "box": list(w.box), "score": w.score,
-                       "chars": list(w.chars) if w.chars is not None else None, **({"source": w.source} if line.decoder == "ngram" else {})}
+                       "chars": list(w.chars) if w.chars is not None else None, **({"source": w.source} if line.decoder == "ngram" else {}),
+                       **({"aligned": [dict(char(c), rank=c.rank, first=c.first, last=c.last) for c in w.aligned]}
+                          if w.aligned is not None else {})}
                       for w in line.words]}
+
+
+def aligned_line_to_json(line: LocatedLine, charset: Sequence, line_id: str) -> Dict:
+    """The object `--align-out` writes for one line image: the located JSON of the transcript's characters (each with the frames it
+    holds), plus the best path's "logp" (null when there is none) and "feasible"."""
+    obj = located_line_to_json(line, charset, line_id)
+    for d, c in zip(obj["chars"], line.chars):
+        d.update(rank=c.rank, first=c.first, last=c.last)
+    feasible = line.logp is not None and line.logp > float("-inf")
+    obj.update(logp=line.logp if feasible else None, feasible=feasible)
+    return obj
+
+
+# ------------------------------------------------------------------------------- forced alignment (DESIGN.md section 13)
+ALIGN_EMISSION_BYTES = 256 << 20        # the emissions of one chunk of lines stay under this (C = 7356: 900 x 7357 x 4 = 26 MB a line)
+
+
+def query_boxes_xyxy(boxes: torch.Tensor, src_hw=None) -> torch.Tensor:
+    """[B,nq,4] xyxy boxes of every query with PostProcess's arithmetic (box_cxcywh_to_xyxy, then the (W, H, W, H) scale as an
+    element-wise product of its own): the bits of the located decoders' boxes."""
+    from . import ops
+    from .dino import box_cxcywh_to_xyxy
+    boxes = boxes.float()
+    out = box_cxcywh_to_xyxy(boxes)
+    hw = ops._src_hw(src_hw, boxes.shape[0], boxes.device)
+    if hw is not None:
+        out = out * torch.stack([hw[:, 1], hw[:, 0], hw[:, 1], hw[:, 0]], dim=1)[:, None, :]
+    return out
+
+
+def gather_aligned(peak: torch.Tensor, order: torch.Tensor, allbox: torch.Tensor, line: Optional[torch.Tensor] = None):
+    """peak [n,L] int32 frames (-1 padded) of spans on lines `line` [n] (None: span k is line k) -> (query [n,L] int32, -1 padded;
+    box [n,L,4] fp32, 0 padded): query = order[line, peak], box = allbox[line, query]."""
+    n, L = peak.shape
+    valid = peak >= 0
+    idx = peak.clamp(min=0).long()
+    rows = (torch.arange(n, device=peak.device) if line is None else line.long().to(peak.device))[:, None].expand(n, L)
+    query = order[rows, idx]
+    box = torch.where(valid[:, :, None], allbox[rows, query.long()], allbox.new_zeros(()))
+    return torch.where(valid, query, torch.full_like(query, -1)), box
+
+
+@torch.no_grad()
+def align_ctc_records(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.003, src_hw=None,
+                      interleaved: bool = True) -> Dict[str, torch.Tensor]:
+    """CTC forced alignment of every line against its KNOWN transcript (dtlr_ctc_align over the emissions of dtlr_blank_emissions, each
+    line one span): where each character of target_labels[b] (label indices, no blank shift) sits.  Device tensors, left-packed, padded
+    with -1 / 0: labels, query, rank (the peak frame), first, last [B,Lmax] int32, score [B,Lmax] fp32 (the emission at the peak),
+    box [B,Lmax,4] fp32 xyxy (that query's box, bit for bit the located decoders'), lengths [B] int32 (-1: the transcript does not fit
+    the line; all its rows are padding), logp [B] fp64 (ln p of the best path, -inf then).  interleaved: loss_CTC's lattice (a filler
+    frame after every query) or the plain frames.  A label outside 0..C-1 raises ValueError."""
+    from . import ops
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    B, nq, C = logits.shape
+    if len(target_labels) != B:
+        raise ValueError(f"align_ctc_records: {len(target_labels)} label sequences for a batch of {B}")
+    lens = [len(t) for t in target_labels]
+    Lmax = max(lens) if lens else 0
+    tt = torch.zeros((B, Lmax), dtype=torch.int64)
+    for i, t in enumerate(target_labels):
+        if len(t):
+            tt[i, : len(t)] = torch.as_tensor([int(v) for v in t], dtype=torch.int64) + 1
+    dev = logits.device
+    chunk = max(1, ALIGN_EMISSION_BYTES // (nq * (C + 1) * 4))
+    parts = []
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        em = ops.blank_emissions(logits[b0:b1], boxes[b0:b1], eps)
+        parts.append(ops.ctc_align(em, [(i, 0, nq) for i in range(b1 - b0)], tt[b0:b1], lens[b0:b1], interleaved))
+        del em
+    rec = {k: torch.cat([p[k] for p in parts]) for k in parts[0]} if parts else ops.ctc_align(logits.new_zeros((1, 1, 2)), [], [], [])
+    order = ops.reading_order(boxes)
+    query, box = gather_aligned(rec["peak"], order, query_boxes_xyxy(boxes, src_hw))
+    labels = torch.where(rec["peak"] >= 0, (tt - 1).to(torch.int32).to(dev), torch.full((B, Lmax), -1, dtype=torch.int32, device=dev))
+    return dict(labels=labels, query=query, rank=rec["peak"], first=rec["first"], last=rec["last"], score=rec["prob"], box=box,
+                lengths=rec["length"], logp=rec["score"])
+
+
+def aligned_chars(labels, query, rank, first, last, score, box, n: int) -> List[LocatedChar]:
+    """host rows of an alignment record -> its first n characters"""
+    return [LocatedChar(int(labels[i]), float(score[i]), tuple(box[i]), int(query[i]), int(rank[i]), int(first[i]), int(last[i]))
+            for i in range(n)]
+
+
+def align_ctc(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.003, src_hw=None, interleaved: bool = True,
+              space_label: Optional[int] = None) -> List[LocatedLine]:
+    """align_ctc_records as LocatedLines with decoder "align": `labels` are the transcript's, `chars` its characters where the best
+    path puts them, words cut by located_words, `logp` the path's log-probability.  A transcript that does not fit its line gives a
+    line without chars or words and logp = -inf."""
+    host = {k: v.cpu().tolist() for k, v in align_ctc_records(outputs, target_labels, eps, src_hw, interleaved).items()}
+    lines = []
+    for b, n in enumerate(host["lengths"]):
+        chars = aligned_chars(*(host[k][b] for k in ("labels", "query", "rank", "first", "last", "score", "box")), max(n, 0))
+        lines.append(LocatedLine([int(v) for v in target_labels[b]], chars, located_words(chars, space_label), "align",
+                                 float(host["logp"][b]) if n >= 0 else float("-inf")))
+    return lines
 
 
 def labels_to_string(labels: Sequence[int], charset: Sequence[str]) -> str:

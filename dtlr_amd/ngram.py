@@ -437,12 +437,14 @@ class DeviceNgramDecoder:
 
 @torch.no_grad()
 def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
-                   multiply_pred_logits_by, traces: Optional[List[list]] = None) -> List[list]:
+                   multiply_pred_logits_by, traces: Optional[List[list]] = None, keep: Optional[Dict] = None) -> List[list]:
     """Per line: the item list of _assemble_words / _assemble_words_2 (decoder words as str, argmax channels as int).  traces: a list
-    that receives every line's trace (see _assemble_words)."""
+    that receives every line's trace (see _assemble_words).  keep: a dict that receives the device "emissions"."""
     if not per_word_ngram:
         raise NotImplementedError("no test support for full sentence n-gram for now")      # as the reference (:108)
     emissions = get_new_pred_logits(outputs, multiply_pred_logits_by)         # [B, T, V] on the device
+    if keep is not None:
+        keep["emissions"] = emissions
     rows = emissions.argmax(-1).cpu().tolist()                                # the one copy the host span logic needs
     second = bool(no_uppercase_words or no_digits)
 
@@ -493,19 +495,25 @@ def rescored_labels_batch(outputs, bundle: Dict) -> List[List[int]]:
     return [[(chan[it] if isinstance(it, str) else it) - 1 for it in line if isinstance(it, str) or it > 0] for line in items]
 
 
-def rescored_located_batch(outputs, bundle: Dict, src_hw=None, space_label: Optional[int] = None) -> List["E.LocatedLine"]:
+def rescored_located_batch(outputs, bundle: Dict, src_hw=None, space_label: Optional[int] = None,
+                           align_rewritten: bool = False) -> List["E.LocatedLine"]:
     """rescored_labels_batch at word level, with boxes ("Located transcripts"): per line a LocatedLine whose `labels` are
     rescored_labels_batch's, whose `chars` are the blank decoder's located characters at the emissions' eps (0.003: a character's
     `rank` is its frame) and whose `words` are, in order, the spans the assembly emitted: source "ngram" = a span the beam
     re-scored, "kept" = frames copied from the argmax (a separator, or a span the flags keep away from the beam).  A word's box is the
     union of the located characters whose rank lies in its frame range; a span that holds none takes the union over all its queries.
     `chars` = that range of the line's characters; `same` = the word's labels equal theirs (then they are the word's characters, box by
-    box).  Character boxes of a word the beam rewrote are not produced."""
+    box).  align_rewritten: every word the beam rewrote (source "ngram", `same` False) also gets `aligned`, its characters placed by
+    the forced alignment of its labels over its own frames [lo, hi) on the beam's lattice (dtlr_ctc_align, interleaved = 0; all such
+    words of the batch in one launch): each a LocatedChar with the box of the query at its peak frame.  Off, every object is what it
+    was without the switch."""
     dec = bundle["decoder"]
     chan = {t: c for c, t in enumerate(dec.tokens)}
     traces: List[list] = []
+    keep: Dict = {}
     items = _rescore_batch(outputs, dec, bundle["ignore"], bundle["ngram_charset"], True, bundle.get("no_uppercase_words", False),
-                           bundle.get("no_digits", False), bundle.get("no_dash", True), bundle.get("multiply_pred_logits_by", 1.0), traces)
+                           bundle.get("no_digits", False), bundle.get("no_dash", True), bundle.get("multiply_pred_logits_by", 1.0), traces,
+                           keep if align_rewritten else None)
     det = E.decode_blank_located(outputs, 0.003, src_hw)
     from . import ops
     boxes = outputs["pred_boxes"].float()
@@ -515,8 +523,10 @@ def rescored_located_batch(outputs, bundle: Dict, src_hw=None, space_label: Opti
     allbox = box_cxcywh_to_xyxy(boxes)                                        # the fall-back: every query's box, PostProcess's arithmetic
     if hw is not None:
         allbox = allbox * torch.stack([hw[:, 1], hw[:, 0], hw[:, 1], hw[:, 0]], dim=1)[:, None, :]
+    allbox_dev = allbox
     allbox, cx = allbox.cpu(), boxes[:, :, 0].cpu()
     lines = []
+    rewritten: List[Tuple["E.LocatedWord", int, int, int]] = []             # (word, line, lo, hi)
     for b in range(B):
         labels = [(chan[it] if isinstance(it, str) else it) - 1 for it in items[b]]
         ranks = [c.rank for c in det[b].chars]
@@ -540,6 +550,28 @@ def rescored_located_batch(outputs, bundle: Dict, src_hw=None, space_label: Opti
                 box = E.union_box([tuple(allbox[b, q].tolist()) for q in order[lo:hi]])
                 score, span, same = 0.0, None, False
             words.append(E.LocatedWord(group, box, score, span, "ngram" if through else "kept", same))
+            if align_rewritten and through and not same:
+                rewritten.append((words[-1], b, lo, hi))
         flat = [v for v in labels if v >= 0]
         lines.append(E.LocatedLine(flat, det[b].chars, words, "ngram"))
+    if rewritten:
+        _align_rewritten(rewritten, keep["emissions"], boxes, allbox_dev)
     return lines
+
+
+def _align_rewritten(rewritten, emissions, boxes, allbox) -> None:
+    """word.aligned for every (word, line, lo, hi): one dtlr_ctc_align launch over all of them, one copy of each record back"""
+    from . import ops
+    Lmax = max(len(w.labels) for w, _, _, _ in rewritten)
+    tg = torch.zeros((len(rewritten), Lmax), dtype=torch.int64)
+    for k, (w, _, _, _) in enumerate(rewritten):
+        tg[k, : len(w.labels)] = torch.as_tensor(w.labels, dtype=torch.int64) + 1
+    line = torch.tensor([b for _, b, _, _ in rewritten], dtype=torch.int64)
+    rec = ops.ctc_align(emissions, [(b, lo, hi) for _, b, lo, hi in rewritten], tg, [len(w.labels) for w, _, _, _ in rewritten],
+                        interleaved=False)
+    query, box = E.gather_aligned(rec["peak"], ops.reading_order(boxes), allbox, line)
+    host = {k: v.cpu().tolist() for k, v in dict(rec, query=query, box=box).items()}
+    for k, (w, _, _, _) in enumerate(rewritten):
+        n = max(host["length"][k], 0)
+        w.aligned = E.aligned_chars(w.labels, host["query"][k], host["peak"][k], host["first"][k], host["last"][k], host["prob"][k],
+                                    host["box"][k], n)

@@ -1448,6 +1448,75 @@ def ngram_beam(emissions, spans, lm=None, lm_weight: float = 0.0, beam_size: int
     return labels, lengths, scores
 
 
+def ctc_align_tables(spans, targets, target_lengths, B: int, T: int, V: int):
+    """The host check of ctc_align's tables (the kernel only clamps): -> (spans [n,3], targets [n,Lmax], lengths [n]) int64 CPU tensors.
+    ValueError for a span outside [0, B) x [0, T], a length outside 0..Lmax, a used label outside 1..V-1 or a target longer than the
+    one-thread-per-state limit (2 L + 1 <= 1024)."""
+    sp = torch.as_tensor(spans, dtype=torch.int64).cpu().reshape(-1, 3)
+    n = int(sp.shape[0])
+    tl = torch.as_tensor(target_lengths, dtype=torch.int64).cpu().reshape(-1)
+    tg = torch.as_tensor(targets, dtype=torch.int64).cpu()
+    tg = tg.reshape(n, -1) if tg.numel() else tg.new_zeros((n, 0))
+    if int(tl.numel()) != n:
+        raise ValueError(f"ctc_align: {n} spans but {int(tl.numel())} target lengths")
+    if n == 0:
+        return sp, tg, tl
+    if int(sp[:, 0].min()) < 0 or int(sp[:, 0].max()) >= B or int(sp[:, 1].min()) < 0 or int(sp[:, 2].max()) > T \
+            or bool((sp[:, 1] > sp[:, 2]).any()):
+        raise ValueError(f"ctc_align: span table outside emissions [{B}, {T}, {V}]")
+    Lmax = int(tg.shape[1])
+    if int(tl.min()) < 0 or int(tl.max()) > Lmax:
+        raise ValueError(f"ctc_align: target length outside 0..{Lmax}")
+    if 2 * int(tl.max()) + 1 > 1024:
+        raise ValueError(f"ctc_align: a target of {int(tl.max())} characters needs {2 * int(tl.max()) + 1} states, the limit is 1024")
+    if Lmax:
+        used = torch.arange(Lmax).unsqueeze(0) < tl.unsqueeze(1)
+        if bool((used & ((tg < 1) | (tg > V - 1))).any()):
+            raise ValueError(f"ctc_align: target label outside 1..{V - 1}")
+    return sp, tg, tl
+
+
+@_lib.op
+def ctc_align(emissions, spans, targets, target_lengths, interleaved: bool = True, filler: float = 1e-5):
+    """CTC forced alignment of every span against its target in ONE launch (dtlr_ctc_align; semantics: DESIGN.md section 13).
+    emissions [B,T,V] fp32 CUDA probabilities (channel 0 = blank); spans [n,3] (line, first frame, one past the last), targets [n,Lmax]
+    (emission channels 1..V-1, rows padded arbitrarily) and target_lengths [n]: integers, checked on the host before the upload
+    (ValueError).  -> dict(score [n] fp64, first / last / peak [n,Lmax] int32, prob [n,Lmax] fp32, length [n] int32) on the device,
+    padded with -1 / 0; length -1 and score -inf: no alignment exists."""
+    require_cuda(emissions, "emissions")
+    if emissions.dim() != 3:
+        raise ValueError("ctc_align: emissions must be [B, T, V]")
+    emissions = emissions.float().contiguous()
+    B, T, V = emissions.shape
+    sp, tg, tl = ctc_align_tables(spans, targets, target_lengths, B, T, V)
+    n, Lmax, dev = int(sp.shape[0]), int(tg.shape[1]), emissions.device
+    i32 = lambda: torch.empty((n, Lmax), dtype=torch.int32, device=dev)                    # noqa: E731
+    out = dict(score=torch.empty((n,), dtype=torch.float64, device=dev), first=i32(), last=i32(), peak=i32(),
+               prob=torch.empty((n, Lmax), dtype=torch.float32, device=dev), length=torch.empty((n,), dtype=torch.int32, device=dev))
+    if n == 0:
+        return out
+    Tmax, Lcap, inter = int((sp[:, 2] - sp[:, 1]).max()), int(tl.max()), int(bool(interleaved))
+    L_ = _lib.lib()
+    ws = torch.empty(max(_lib.query(L_, "dtlr_ctc_align_workspace_bytes", n, Tmax, Lcap, inter), 8) // 8, dtype=torch.int64, device=dev)
+    sp_d, tg_d, tl_d = sp.to(torch.int32).to(dev), tg.to(torch.int32).contiguous().to(dev), tl.to(torch.int32).to(dev)
+    _lib.launch(L_, "dtlr_ctc_align", emissions.data_ptr(), B, T, V, sp_d.data_ptr(), tg_d.data_ptr() if Lmax else None, tl_d.data_ptr(),
+                n, Lmax, Lcap, Tmax, inter, float(filler), out["score"].data_ptr(), out["first"].data_ptr(), out["last"].data_ptr(),
+                out["peak"].data_ptr(), out["prob"].data_ptr(), out["length"].data_ptr(), ws.data_ptr())
+    return out
+
+
+@_lib.op
+def reading_order(boxes):
+    """order [B,nq] int32: order[b, r] = the query at rank r of line b (dtlr_reading_order: ascending cx, equal cx -> the lower query
+    first -- the decoders' key, the row order of blank_emissions)."""
+    require_cuda(boxes, "pred_boxes")
+    boxes = boxes.float().contiguous()
+    B, nq = boxes.shape[:2]
+    order = torch.empty((B, nq), dtype=torch.int32, device=boxes.device)
+    _lib.launch(_lib.lib(), "dtlr_reading_order", boxes.data_ptr(), order.data_ptr(), B, nq)
+    return order
+
+
 @_lib.op
 def preprocess_lines(src_u8, offsets, dims, Hc: int, Wc: int, max_downscale: float, mean, std):
     """Resize + ToTensor + Normalize + pad of a batch of uint8 RGB images in ONE launch (dtlr_preprocess_lines).

@@ -757,6 +757,41 @@ int dtlr_decode_nms_located(const float *values, const long *index, const float 
                             int *labels, int *query, float *score, float *box, int *lengths,
                             int B, int k, int nq, int C, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CTC forced alignment (csrc/ctc_align.hip; semantics: DESIGN.md section 13): the best path of a KNOWN transcript through a span of
+ * emissions, every span of a table in one launch, one workgroup per span, one thread per state.
+ *   emissions [B,T,V] fp32 probabilities, channel 0 = the CTC blank, row r = the r-th query in reading order (what
+ *     dtlr_blank_emissions writes and dtlr_ngram_beam reads) ;
+ *   spans [n,3] int32 on the DEVICE: (line, first frame, one past the last frame) ; targets [n,Lmax] int32 on the DEVICE: emission
+ *     channels 1..V-1, rows padded arbitrarily ; target_lengths [n] int32 on the DEVICE.  The kernel clamps every line to [0, B), every
+ *     frame to [0, T], every span to its first Tmax frames, every length to [0, max_target_length] and every channel to [0, V): a bad
+ *     table gives a wrong or infeasible record, never a fault ;
+ *   max_target_length <= Lmax: the longest target as the HOST knows it (sizes the workgroup: 2 L + 1 <= 1024, else DTLR_ESHAPE) ;
+ *   Tmax >= 0: the longest span, as the caller states it ;
+ *   interleaved = 0: the lattice frames are the span's real frames (the beam's lattice).  interleaved = 1: real frame i is lattice frame
+ *     2 i, followed by a constant frame 2 i + 1 with p(blank) = 1 and p(c) = filler (SetCriterion.loss_CTC's padded sequence; the
+ *     lattice of dtlr_ctc_loss_interleaved).  Lattice frame j belongs to real frame t0 + j / 2, or t0 + j ;
+ *   lp = ln(max((double) p, 1e-30)), all scores fp64.  States s = 0..2L (even: blank, odd: targets[(s-1)/2]); a path starts in state 0
+ *     or 1 and ends in 2L-1 or 2L (2L-1 on equal scores; L = 0: state 0); d_j(s) = max(d_{j-1}(s), d_{j-1}(s-1), d_{j-1}(s-2) when s is
+ *     odd, s >= 3 and the label differs from the previous one) + lp_j(s), equal candidates taking the smallest shift.
+ * Outputs, every element written on every call, ints padded with -1 and floats with 0:
+ *   score [n] fp64: ln p of the best path; -inf when there is none, or when the span is empty and L > 0 (empty span, L = 0: 0.0) ;
+ *   first, last [n,Lmax] int32: the real frames of the first and the last lattice frame spent in character i's state ;
+ *   peak [n,Lmax] int32: the real frame of the lattice frame of that run with the largest lp of the character, the earliest on equality ;
+ *   prob [n,Lmax] fp32: the emission at the peak, copied: the emissions' own value, or `filler` when the peak is a filler frame ;
+ *   length [n] int32: L, or -1 when infeasible (all rows of that span are then padding).
+ * workspace: dtlr_ctc_align_workspace_bytes(n, Tmax, max_target_length, interleaved) bytes, 8-byte aligned: the 2-bit back-pointers
+ *   of spans whose frames x states do not fit LDS; 0 when they do (NULL is then accepted).  Asynchronous on `stream`; never synchronises. */
+int dtlr_ctc_align(const float *emissions, int B, int T, int V, const int *spans, const int *targets, const int *target_lengths,
+                   int n, int Lmax, int max_target_length, int Tmax, int interleaved, float filler,
+                   double *score, int *first, int *last, int *peak, float *prob, int *length, void *workspace, void *stream);
+long dtlr_ctc_align_workspace_bytes(int n, int Tmax, int max_target_length, int interleaved);
+
+/* order [B,nq] int32: order[b, r] = the query at rank r of line b in reading order, by the decoders' own 64-bit key (ascending cx of
+ * boxes [B,nq,4] cxcywh, equal cx: the lower query first): the row order of dtlr_blank_emissions, the `rank` of
+ * dtlr_decode_blank_located.  One workgroup per line, sorted in LDS (nq <= 16384, else DTLR_ESHAPE). */
+int dtlr_reading_order(const float *boxes, int *order, int B, int nq, void *stream);
+
 /* k largest of each row of a [B, n] fp32 matrix that is too long for LDS, descending, equal values: lower index first.
  * Replaces: `torch.topk(prob.view(B, -1), num_select, dim=1)` of PostProcess (models/dino/dino.py:1000-1006), with the sigmoid
  *           folded in (apply_sigmoid: the selection runs on the logits, values are returned as sigmoid(logit)).
