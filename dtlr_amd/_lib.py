@@ -158,6 +158,10 @@ _SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dtlr_ctc_align_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int, c_int]),
     "dtlr_reading_order": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    # keyword spotting (csrc/ctc_spot.hip)
+    "dtlr_ctc_spot": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dtlr_ctc_spot_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
     # per-line batching
     "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dtlr_zero_outside_extent_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -119,7 +119,8 @@ def image_size(path: str) -> Tuple[int, int]:
 def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optional[float] = None,
                    NM: Optional[float] = None, postprocessor=None, device="cuda", size: int = EVAL_SIZE,
                    max_size: int = EVAL_MAX_SIZE, rank: int = 0, world: int = 1, sizes: Optional[Sequence[Tuple[int, int]]] = None,
-                   skip_errors: bool = True, per_line: bool = False, ngram: Optional[Dict] = None) -> List[Optional[List[int]]]:
+                   skip_errors: bool = True, per_line: bool = False, ngram: Optional[Dict] = None,
+                   spot: Optional[Dict] = None) -> List[Optional[List[int]]]:
     """convert_output_to_pred (evaluation.py:94-158) for a list of RGB uint8 images -> one label list per image, dataset
     order.  TH / NM given: the NMS decoder; otherwise the blank/argmax decoder with eps = 0.03 / C.
     `images`: a sequence of [h, w, 3] uint8 arrays, or (with `sizes` = the (h, w) of every line) a callable i -> array that is
@@ -128,7 +129,8 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
     per_line (`--batching ragged`): mixed sizes share a padded batch as with exact=False, and the forward runs per line
     (DINO.forward(per_line=True)): every line gets the result it gets alone.
     ngram (`--ngram-arpa`): the bundle of ngram_bundle(); the batch's lines are then re-scored by the device n-gram beam decoder
-    (ngram.rescored_labels_batch: one launch over every word span of the batch) instead of decoded by the blank / NMS decoder."""
+    (ngram.rescored_labels_batch: one launch over every word span of the batch) instead of decoded by the blank / NMS decoder.
+    spot (`--spot-words`): the bundle of spot_bundle(); every batch's output is also searched for its keywords (spot_batch)."""
     lazy = callable(images)
     if lazy and sizes is None:
         raise ValueError("predict_labels: a loader callable needs `sizes`")
@@ -144,6 +146,8 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
     def run(idx):
         samples = tf([load(i) for i in idx], device=device)
         out = model(samples, per_line=True) if per_line else model(samples)
+        if spot is not None:
+            spot_batch(spot, out, samples, idx)
         if ngram is not None:
             from . import ngram as NG
             preds = NG.rescored_labels_batch(out, ngram)
@@ -170,6 +174,8 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
                     print(f"An error occurred affecting the metrics computation (line {i}: {type(e1).__name__}: {e1})", file=sys.stderr)
                     rec[i, :nq] = -1
                     rec[i, nq], rec[i, nq + 1] = 0, 1
+                    if spot is not None:
+                        spot["hits"].pop(i, None)
             del e
     if world > 1:                               # every line is owned by exactly one rank: element-wise max merges the shards
         import torch.distributed as dist
@@ -332,7 +338,7 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
                     sizes: Optional[Sequence[Tuple[int, int]]] = None, skip_errors: bool = True, per_line: bool = False,
                     ngram: Optional[Dict] = None, decoder: str = "blank", space_label: Optional[int] = None,
                     targets: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                    align_rewritten: bool = False) -> List[Optional["E.LocatedLine"]]:
+                    align_rewritten: bool = False, spot: Optional[Dict] = None) -> List[Optional["E.LocatedLine"]]:
     """predict_labels with every character located: one LocatedLine per image (None for a skipped line), dataset order, boxes in
     the SOURCE image's pixels.  decoder: "blank" (eps = 0.03 / C), "nms" (TH / NM, default 0.3 / 0.5) or "ngram" (`ngram` = the bundle
     of ngram_bundle(); words re-scored by the device beam, boxes at word level).  Batching (`exact`, padded, `per_line`), sharding and
@@ -340,7 +346,7 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
     scale, for padded and ragged batches alike.  space_label: the charset's ' ' index (words are cut there), or None.
     decoder "align": the forced alignment of `targets` (per image its transcript as label indices; None: the line is skipped) against
     the model's output (E.align_ctc, eps = 0.003, loss_CTC's lattice).  align_rewritten (decoder "ngram"): words the beam rewrote
-    carry their aligned characters."""
+    carry their aligned characters.  spot: as in predict_labels (single process only)."""
     if decoder not in ("blank", "nms", "ngram", "align"):
         raise ValueError(f"predict_located: unknown decoder {decoder!r}")
     if decoder == "ngram" and ngram is None:
@@ -369,6 +375,8 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
         samples = tf([load(i) for i in idx], device=device)
         out = model(samples, per_line=True) if per_line else model(samples)
         hw = torch.tensor(samples.orig_sizes, dtype=torch.float32)
+        if spot is not None:
+            spot_batch(spot, out, samples, idx)
         if decoder == "align":
             if any(targets[i] is None for i in idx):
                 raise ValueError("a transcript holds a character outside the charset")
@@ -401,6 +409,8 @@ def predict_located(model, images, batch: int = 32, exact: bool = True, TH: Opti
                     print(f"An error occurred affecting the metrics computation (line {i}: {type(e1).__name__}: {e1})", file=sys.stderr)
                     rows[i] = 0
                     status[i] = 1
+                    if spot is not None:
+                        spot["hits"].pop(i, None)
     if world > 1:
         rows, status = merge_located(rows, status, device)
     rows_np = rows.numpy()
@@ -430,6 +440,54 @@ def write_aligned(path: str, ids: Sequence[str], lines: Sequence[Optional["E.Loc
                 continue
             f.write(json.dumps(E.aligned_line_to_json(line, charset, line_id), ensure_ascii=False) + "\n")
             k += 1
+    return k
+
+
+def spot_bundle(words: Sequence[str], charset: Sequence[str], min_conf: float = 0.5, max_hits: int = 4) -> Dict:
+    """What predict_labels / predict_located take as `spot`: the words that can be searched (1..32 characters, all in the charset) as
+    label lists, and `hits`: image index -> its KeywordHits, filled batch by batch.  A word that cannot be searched is named on stderr
+    and skipped."""
+    if not 1 <= int(max_hits) <= 16:
+        raise ValueError(f"--spot-max-hits {max_hits} outside 1..16")
+    if not 0.0 <= float(min_conf) <= 1.0:
+        raise ValueError(f"--spot-min-conf {min_conf} outside 0..1")
+    kept, keywords = [], []
+    for w, z in zip(words, transcript_labels(words, charset)):
+        if z is None:
+            print(f"--spot-words: {w!r} holds a character outside the charset: skipped", file=sys.stderr)
+        elif not 1 <= len(z) <= 32:
+            print(f"--spot-words: {w!r} has {len(z)} characters, the limits are 1..32: skipped", file=sys.stderr)
+        else:
+            kept.append(w)
+            keywords.append(z)
+    return dict(words=kept, keywords=keywords, min_conf=float(min_conf), max_hits=int(max_hits), hits={})
+
+
+def load_spot_words(path: str) -> List[str]:
+    """`--spot-words`: one word per line, UTF-8; empty lines are dropped, a repeated word is searched once"""
+    with open(path, encoding="utf-8") as f:
+        words = [ln.rstrip("\r\n") for ln in f]
+    return list(dict.fromkeys(w for w in words if w))
+
+
+@torch.no_grad()
+def spot_batch(spot: Dict, out, samples, idx: Sequence[int]) -> None:
+    """search the batch's output for the bundle's keywords (E.spot_keywords, eps = 0.003, boxes in the source images' pixels)"""
+    if not spot["keywords"]:
+        return
+    hw = torch.tensor(samples.orig_sizes, dtype=torch.float32)
+    for i, hits in zip(idx, E.spot_keywords(out, spot["keywords"], spot["min_conf"], spot["max_hits"], 0.003, hw)):
+        spot["hits"][i] = hits
+
+
+def write_spotted(path: str, ids: Sequence[str], spot: Dict, charset: Sequence[str]) -> int:
+    """`--spot-out`: one JSON object per hit, in dataset order, then the word list's, then best first.  -> hits written."""
+    k = 0
+    with open(path, "w", encoding="utf-8") as f:
+        for i, line_id in enumerate(ids):
+            for hit in spot["hits"].get(i, ()):
+                f.write(json.dumps(E.keyword_hit_to_json(hit, charset, line_id), ensure_ascii=False) + "\n")
+                k += 1
     return k
 
 
@@ -594,6 +652,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--align-out", default=None, metavar="FILE.jsonl",
                     help="also write the forced alignment of every line's transcript (--labels) against the model's output: the located "
                          "JSON with \"decoder\": \"align\", each character where the best CTC path puts it, plus \"logp\" and \"feasible\"")
+    ap.add_argument("--spot-words", default=None, metavar="FILE",
+                    help="keyword spotting: the words to look for in every line, one per line (UTF-8); needs --spot-out; single process only")
+    ap.add_argument("--spot-out", default=None, metavar="FILE.jsonl",
+                    help="one JSON object per hit: the line's id, the word, conf, ratio, the ranks it covers, its box in the source image's "
+                         "pixels and its characters")
+    ap.add_argument("--spot-min-conf", type=float, default=0.5, help="a hit needs exp(ratio / length) >= this (0: the best hit of every word)")
+    ap.add_argument("--spot-max-hits", type=int, default=4, help="hits per (line, word), 1..16")
     return ap
 
 
@@ -601,6 +666,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     args = build_parser().parse_args(argv)
     from .dino import DINO, PostProcess
     rank, local, world = ddist.init_from_env()
+    if bool(args.spot_words) != bool(args.spot_out):
+        raise SystemExit("--spot-words and --spot-out go together")
+    if args.spot_words and world > 1:
+        raise SystemExit(f"--spot-words runs in a single process (this job has {world} ranks): hits are not merged across ranks")
     if not torch.cuda.is_available():
         raise SystemExit("dtlr_amd.evaluation needs an MI355X (no CPU path)")
     torch.cuda.set_device(local)
@@ -640,6 +709,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     bundle = ngram_bundle(args, charset, dev)
     extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
+    spot = None
+    if args.spot_words:
+        cs_str = [chr(c) if args.unicode else str(c) for c in charset]
+        spot = spot_bundle(load_spot_words(args.spot_words), cs_str, args.spot_min_conf, args.spot_max_hits)
     if args.layout_out and len(list_TH) * len(list_NM) > 1:
         raise SystemExit("--layout-out needs one decoder setting (--TH and --NMS, or neither), not the --NMS_inference grid")
     if args.align_out:                                         # the transcripts against the model's output; apart from the decoders
@@ -657,14 +730,19 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                 located = predict_located(model, images, args.batch, args.batching == "exact", TH, NM, dev, args.size, args.max_size,
                                           rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", ngram=bundle,
                                           decoder="ngram" if bundle is not None else ("nms" if nms_inference else "blank"),
-                                          space_label=E.space_label_of(cs_str), align_rewritten=args.layout_align and bundle is not None)
+                                          space_label=E.space_label_of(cs_str), align_rewritten=args.layout_align and bundle is not None,
+                                          spot=spot)
                 preds = [None if line is None else list(line.labels) for line in located]
                 if rank == 0:
                     k = write_layout(args.layout_out, [name for name, _ in rows], located, cs_str)
                     print(f"wrote {k} located lines to {args.layout_out}", file=sys.stderr)
             else:
                 preds = predict_labels(model, images, args.batch, args.batching == "exact", TH, NM, post, dev, args.size, args.max_size,
-                                       rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", **extra)
+                                       rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", spot=spot, **extra)
+            if spot is not None:                               # the first pass over the images carries the search
+                k = write_spotted(args.spot_out, [name for name, _ in rows], spot, cs_str)
+                print(f"wrote {k} hits of {len(spot['words'])} words to {args.spot_out}", file=sys.stderr)
+                spot = None
             if rank == 0:
                 res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
                 d = write_outputs(res, args.out, args.dataset, TH, NM)

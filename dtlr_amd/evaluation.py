@@ -385,6 +385,125 @@ def align_ctc(outputs, target_labels: Sequence[Sequence[int]], eps: float = 0.00
     return lines
 
 
+# ------------------------------------------------------------------------------- keyword spotting
+@dataclasses.dataclass
+class KeywordHit:
+    """One occurrence of a keyword in a line: `keyword` = its index in the list that was searched, `line` = the line's index in the
+    batch, `start` / `end` = the first and the last frame (rank in reading order) of the hit, `ratio` = the log-likelihood ratio of its
+    best path against the frame-wise argmax path over the same frames (<= 0), `conf` = exp(ratio / L), the geometric mean per character
+    in (0, 1], `box` = the union of its characters' boxes, `chars` = its characters where the forced alignment of the hit's frames puts
+    them."""
+    keyword: int
+    line: int
+    start: int
+    end: int
+    ratio: float
+    conf: float
+    box: Box
+    chars: List[LocatedChar]
+
+
+def _spot_tables(keywords: Sequence[Sequence[int]], C: int, min_conf: float):
+    """keywords as label indices -> (emission channels = label + 1, min_ratio [Q] fp64 = L ln(min_conf))"""
+    import math
+    if not 0.0 <= float(min_conf) <= 1.0:
+        raise ValueError(f"spot: min_conf {min_conf} outside 0..1")
+    chans = []
+    for i, z in enumerate(keywords):
+        z = [int(v) for v in z]
+        if any(not 0 <= v < C for v in z):
+            raise ValueError(f"spot: keyword {i} has a label outside 0..{C - 1}")
+        chans.append([v + 1 for v in z])
+    ln = math.log(min_conf) if min_conf > 0 else float("-inf")
+    return chans, torch.tensor([len(z) * ln if len(z) else ln for z in chans], dtype=torch.float64)
+
+
+@torch.no_grad()
+def spot_records(outputs, keywords: Sequence[Sequence[int]], min_conf: float = 0.5, max_hits: int = 4, eps: float = 0.003, src_hw=None,
+                 with_chars: bool = False) -> Dict[str, torch.Tensor]:
+    """Query-by-string keyword spotting of every keyword (label indices, no blank shift) in every line of the batch (dtlr_ctc_spot over
+    the emissions of dtlr_blank_emissions, chunked under ALIGN_EMISSION_BYTES).  Device tensors: count [B,Q] int32, start / end [B,Q,H]
+    int32 (frames = ranks in reading order, -1 padded), ratio [B,Q,H] fp64 and conf [B,Q,H] fp64 = exp(ratio / L) (0 padded), hits best
+    first; a hit needs conf >= min_conf (min_conf 0: every keyword's best hit is returned wherever the keyword fits the line).
+    with_chars: every hit of the batch is aligned by dtlr_ctc_align over its own frames [start, end + 1) of the plain lattice, and the
+    record gains hit [n,3] int64 (line, keyword, h), query / rank / first / last [n,Lmax] int32, score [n,Lmax] fp32, box [n,Lmax,4]
+    fp32 xyxy and logp [n] fp64 (the alignment's score), rows in (line, keyword, h) order: one host round trip for the span table.
+    ValueError for a label outside 0..C-1, an empty or too long keyword, max_hits outside 1..16."""
+    from . import ops
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    B, nq, C = logits.shape
+    chans, min_ratio = _spot_tables(keywords, C, min_conf)
+    kw, kl = ops.ctc_spot_tables(chans, C + 1, max_hits)
+    Q, Lmax, H, dev = len(chans), int(kw.shape[1]), int(max_hits), logits.device
+    chunk = max(1, ALIGN_EMISSION_BYTES // (nq * (C + 1) * 4))
+    parts, hits, aligned = [], [], []
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        em = ops.blank_emissions(logits[b0:b1], boxes[b0:b1], eps)
+        rec = ops.ctc_spot(em, chans, min_ratio, H)
+        parts.append(rec)
+        if with_chars and Q:
+            cnt, st, en = rec["count"].cpu(), rec["start"].cpu(), rec["end"].cpu()
+            idx = [(b, q, h) for b in range(b1 - b0) for q in range(Q) for h in range(int(cnt[b, q]))]
+            if idx:
+                spans = [(b, int(st[b, q, h]), int(en[b, q, h]) + 1) for b, q, h in idx]
+                aligned.append(ops.ctc_align(em, spans, kw[[q for _, q, _ in idx]], kl[[q for _, q, _ in idx]], False))
+                hits += [(b0 + b, q, h) for b, q, h in idx]
+        del em
+    if parts:
+        out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    else:
+        out = dict(count=torch.empty((0, Q), dtype=torch.int32, device=dev), start=torch.empty((0, Q, H), dtype=torch.int32, device=dev),
+                   end=torch.empty((0, Q, H), dtype=torch.int32, device=dev), ratio=torch.empty((0, Q, H), dtype=torch.float64, device=dev))
+    taken = torch.arange(H, device=dev)[None, None, :] < out["count"][:, :, None]
+    lens = kl.to(dev).double().clamp(min=1)[None, :, None]
+    out["conf"] = torch.where(taken, torch.exp(out["ratio"] / lens), torch.zeros((), dtype=torch.float64, device=dev))
+    if with_chars:
+        n = len(hits)
+        hit = torch.tensor(hits, dtype=torch.int64).reshape(n, 3).to(dev)
+        if aligned:
+            al = {k: torch.cat([p[k] for p in aligned]) for k in aligned[0]}
+            order = ops.reading_order(boxes)
+            query, box = gather_aligned(al["peak"], order, query_boxes_xyxy(boxes, src_hw), hit[:, 0])
+        else:
+            i32 = lambda: torch.empty((0, Lmax), dtype=torch.int32, device=dev)                         # noqa: E731
+            al = dict(peak=i32(), first=i32(), last=i32(), prob=torch.empty((0, Lmax), dtype=torch.float32, device=dev),
+                      score=torch.empty((0,), dtype=torch.float64, device=dev))
+            query, box = i32(), torch.empty((0, Lmax, 4), dtype=torch.float32, device=dev)
+        out.update(hit=hit, query=query, rank=al["peak"], first=al["first"], last=al["last"], score=al["prob"], box=box, logp=al["score"])
+    return out
+
+
+def spot_keywords(outputs, keywords: Sequence[Sequence[int]], min_conf: float = 0.5, max_hits: int = 4, eps: float = 0.003,
+                  src_hw=None) -> List[List[KeywordHit]]:
+    """spot_records(with_chars=True) as KeywordHits, one list per line, in (keyword, best hit first) order."""
+    rec = spot_records(outputs, keywords, min_conf, max_hits, eps, src_hw, with_chars=True)
+    host = {k: v.cpu().tolist() for k, v in rec.items()}
+    lines: List[List[KeywordHit]] = [[] for _ in range(outputs["pred_logits"].shape[0])]
+    for k, (b, q, h) in enumerate(host["hit"]):
+        z = [int(v) for v in keywords[q]]
+        chars = aligned_chars(z, *(host[key][k] for key in ("query", "rank", "first", "last", "score", "box")), len(z))
+        lines[b].append(KeywordHit(q, b, host["start"][b][q][h], host["end"][b][q][h], host["ratio"][b][q][h], host["conf"][b][q][h],
+                                   union_box([c.box for c in chars]), chars))
+    return lines
+
+
+def keyword_hit_to_json(hit: KeywordHit, charset: Sequence, line_id: str) -> Dict:
+    """The object `--spot-out` writes for one hit: the line's id, the word, its confidence and ratio, the first and the last rank
+    (frame in reading order) it covers, its box and its characters (each as in `--align-out`)."""
+    cs = list(charset)
+    return {"id": line_id, "word": "".join(str(cs[c.label]) for c in hit.chars), "keyword": hit.keyword, "line": hit.line,
+            "conf": hit.conf, "ratio": hit.ratio, "start": hit.start, "end": hit.end, "box": list(hit.box),
+            "chars": [{"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query, "rank": c.rank,
+                       "first": c.first, "last": c.last} for c in hit.chars]}
+
+
+def keyword_hit_from_json(obj: Dict) -> KeywordHit:
+    """the KeywordHit a `--spot-out` object was written from"""
+    chars = [LocatedChar(c["label"], c["score"], tuple(c["box"]), c["query"], c["rank"], c["first"], c["last"]) for c in obj["chars"]]
+    return KeywordHit(obj["keyword"], obj["line"], obj["start"], obj["end"], obj["ratio"], obj["conf"], tuple(obj["box"]), chars)
+
+
 def labels_to_string(labels: Sequence[int], charset: Sequence[str]) -> str:
     return "".join(charset[int(i)] for i in labels)
 

@@ -1517,6 +1517,58 @@ def reading_order(boxes):
     return order
 
 
+def ctc_spot_tables(keywords, V: int, max_hits: int):
+    """The host check of ctc_spot's tables (the kernel only clamps): keywords = sequences of emission channels -> (keywords [Q,Lmax]
+    int64, zero padded; lengths [Q] int64) CPU tensors.  ValueError for an empty keyword or one longer than 32 (one lane per state), a
+    label outside 1..V-1, or max_hits outside 1..16."""
+    if not 1 <= int(max_hits) <= 16:
+        raise ValueError(f"ctc_spot: max_hits {max_hits} outside 1..16")
+    rows = [[int(v) for v in (k.tolist() if hasattr(k, "tolist") else k)] for k in keywords]
+    for i, z in enumerate(rows):
+        if not 1 <= len(z) <= 32:
+            raise ValueError(f"ctc_spot: keyword {i} has {len(z)} characters, the limits are 1..32")
+        if any(not 1 <= v <= V - 1 for v in z):
+            raise ValueError(f"ctc_spot: keyword {i} has a label outside 1..{V - 1}")
+    Lmax = max([len(z) for z in rows] + [1])
+    kw = torch.zeros((len(rows), Lmax), dtype=torch.int64)
+    for i, z in enumerate(rows):
+        kw[i, : len(z)] = torch.tensor(z, dtype=torch.int64)
+    return kw, torch.tensor([len(z) for z in rows], dtype=torch.int64)
+
+
+@_lib.op
+def ctc_spot(emissions, keywords, min_ratio, max_hits: int = 4):
+    """Keyword spotting of Q keywords in every line in ONE search launch (dtlr_ctc_spot; semantics: DESIGN.md section 14).
+    emissions [B,T,V] fp32 CUDA probabilities (channel 0 = blank); keywords: Q sequences of emission channels 1..V-1, 1..32 long, checked
+    on the host before the upload (ValueError); min_ratio: a float or Q floats (fp64, -inf allowed), the smallest log-likelihood ratio
+    of a hit.  -> dict(count [B,Q] int32, start / end [B,Q,H] int32, ratio [B,Q,H] fp64) on the device, hits in the order taken (best
+    first, never overlapping), padded with -1 / 0."""
+    require_cuda(emissions, "emissions")
+    if emissions.dim() != 3:
+        raise ValueError("ctc_spot: emissions must be [B, T, V]")
+    emissions = emissions.float().contiguous()
+    B, T, V = emissions.shape
+    kw, kl = ctc_spot_tables(keywords, V, max_hits)
+    Q, Lmax, H, dev = int(kw.shape[0]), int(kw.shape[1]), int(max_hits), emissions.device
+    mr = torch.as_tensor(min_ratio, dtype=torch.float64).cpu().reshape(-1)
+    if int(mr.numel()) == 1:
+        mr = mr.expand(Q).contiguous()
+    if int(mr.numel()) != Q:
+        raise ValueError(f"ctc_spot: {Q} keywords but {int(mr.numel())} thresholds")
+    out = dict(count=torch.empty((B, Q), dtype=torch.int32, device=dev), start=torch.empty((B, Q, H), dtype=torch.int32, device=dev),
+               end=torch.empty((B, Q, H), dtype=torch.int32, device=dev), ratio=torch.empty((B, Q, H), dtype=torch.float64, device=dev))
+    if B == 0 or Q == 0:
+        return out
+    if T == 0:
+        raise ValueError("ctc_spot: emissions without frames")
+    L_ = _lib.lib()
+    ws = torch.empty(max(_lib.query(L_, "dtlr_ctc_spot_workspace_bytes", B, T), 8) // 8 + 1, dtype=torch.float64, device=dev)
+    kw_d, kl_d, mr_d = kw.to(torch.int32).to(dev), kl.to(torch.int32).to(dev), mr.to(dev)
+    _lib.launch(L_, "dtlr_ctc_spot", emissions.data_ptr(), B, T, V, kw_d.data_ptr(), kl_d.data_ptr(), mr_d.data_ptr(), Q, Lmax, H,
+                out["count"].data_ptr(), out["start"].data_ptr(), out["end"].data_ptr(), out["ratio"].data_ptr(), ws.data_ptr())
+    return out
+
+
 @_lib.op
 def preprocess_lines(src_u8, offsets, dims, Hc: int, Wc: int, max_downscale: float, mean, std):
     """Resize + ToTensor + Normalize + pad of a batch of uint8 RGB images in ONE launch (dtlr_preprocess_lines).

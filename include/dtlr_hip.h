@@ -792,6 +792,33 @@ long dtlr_ctc_align_workspace_bytes(int n, int Tmax, int max_target_length, int 
  * dtlr_decode_blank_located.  One workgroup per line, sorted in LDS (nq <= 16384, else DTLR_ESHAPE). */
 int dtlr_reading_order(const float *boxes, int *order, int B, int nq, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Keyword spotting (csrc/ctc_spot.hip; semantics: DESIGN.md section 14): where, and how confidently, each of Q GIVEN words occurs in each
+ * of B lines.  Every (line, keyword) pair is searched over all T frames of the plain lattice (no filler frames), one wavefront per pair,
+ * one lane per state, all B x Q pairs in one launch (after a small launch for the per-frame maxima).
+ *   emissions [B,T,V] fp32 probabilities, channel 0 = the CTC blank, rows in reading order (what dtlr_blank_emissions writes) ;
+ *   keywords [Q,Lmax] int32 on the DEVICE: emission channels 1..V-1, rows padded arbitrarily ; keyword_lengths [Q] int32 on the DEVICE ;
+ *     min_ratio [Q] fp64 on the DEVICE (-inf allowed).  The kernel clamps every length to [1, min(32, Lmax)] and every channel to [0, V):
+ *     a bad table gives a wrong record, never a fault ;
+ *   1 <= Lmax <= 32 (one lane per state, 2 L - 1 <= 63) and 1 <= H <= 16, else DTLR_ESHAPE ; T <= 12800 (a wave keeps 12 bytes per frame
+ *     in LDS; one wave per workgroup is the least), else DTLR_ESHAPE.  Up to T = 3200 a workgroup is four waves.
+ *   gain: mx[b,t] = the fp32 maximum of E[b,t,:]; g(t,c) = 0 when E[b,t,c] == mx[b,t], else ln(max((double) E, 1e-30)) -
+ *     ln(max((double) mx, 1e-30)) in fp64: a path's score is its log-likelihood ratio against the frame-wise argmax path, <= 0 ;
+ *   states s = 0..2L-2 (even: keyword[s/2], odd: the blank between two characters; no outer blanks).  Each state carries a score d and an
+ *     entry frame a, d = -inf at first.  Frame t, candidates in this order: state 0: stay (d(0), a(0)), a fresh entry (0, t); state s >= 1:
+ *     stay, s - 1, s - 2 (only for even s >= 2 whose character differs from the previous one).  The largest wins, the earlier on equality;
+ *     d'(s) = best + g(t, channel of s), a'(s) = the winner's entry frame.  r[t] = d'(2L-2), start[t] = a'(2L-2) ;
+ *   hits of a pair: the frames with finite r[t] >= min_ratio[q], taken by descending r (equal r: the smaller t), skipping every frame whose
+ *     [start[t], t] overlaps a hit already taken, H at the most.
+ * Outputs, every element written on every call, in the order taken, ints padded with -1 and ratios with 0:
+ *   count [B,Q] int32 ; start, end [B,Q,H] int32: the first and the last frame of a hit ; ratio [B,Q,H] fp64.
+ * workspace: dtlr_ctc_spot_workspace_bytes(B, T) bytes, 8-byte aligned: ln mx as fp64, then mx.  B == 0 or Q == 0: nothing is done.
+ * Asynchronous on `stream`; never synchronises. */
+int dtlr_ctc_spot(const float *emissions, int B, int T, int V, const int *keywords, const int *keyword_lengths,
+                  const double *min_ratio, int Q, int Lmax, int H, int *count, int *start, int *end, double *ratio,
+                  void *workspace, void *stream);
+long dtlr_ctc_spot_workspace_bytes(int B, int T);
+
 /* k largest of each row of a [B, n] fp32 matrix that is too long for LDS, descending, equal values: lower index first.
  * Replaces: `torch.topk(prob.view(B, -1), num_select, dim=1)` of PostProcess (models/dino/dino.py:1000-1006), with the sigmoid
  *           folded in (apply_sigmoid: the selection runs on the logits, values are returned as sigmoid(logit)).
