@@ -5,7 +5,8 @@ from __future__ import annotations
 import ctypes
 import functools
 import os
-from ctypes import c_char_p, c_int, c_int64, c_void_p, c_float, POINTER
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_void_p
 
 # torch must own the process's HIP runtime: libdtlr_hip.so NEEDs libamdhip64.so.7 and, loaded first, would pull a second runtime
 # from /opt/rocm beside torch's bundled one (kernels then launch on a runtime that has no device initialised: hipErrorNoDevice).
@@ -19,8 +20,6 @@ LIB_PATH = os.environ.get("DTLR_HIP_LIB") or os.path.join(HERE, "libdtlr_hip.so"
 # symbols, accepts DTLR_F16 wherever libdtlr_hip.so accepts DTLR_BF16
 LIB_PATH_F16 = os.environ.get("DTLR_HIP_LIB_F16") or os.path.join(HERE, "libdtlr_hip_f16.so")
 
-DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S = 0, 1, 2, 3, 4
-
 _lib = None
 _lib_f16 = None
 
@@ -29,154 +28,94 @@ class DTLRError(RuntimeError):
     pass
 
 
+# ---------------------------------------------------------------------------------------------
+# The header reader.  include/dtlr_hip.h is the only statement of the ABI; its opening comment states the dialect read here.
+_BY_VALUE = {"int": c_int, "long": c_long, "float": c_float, "double": c_double}
+_RETURNS = {"int": c_int, "long": c_long, "const char *": c_char_p}
+_STATEMENT = re.compile(r'\s*(?:(extern\s*"C"\s*\{)|(\})|typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;|([^;{}]+);)')
+_DECLARATORS = re.compile(r"\s*((?:\w+\s+)*\w+)\b\s*((?:\*\s*)*\w+(?:\s*,\s*(?:\*\s*)*\w+)*)\s*")
+_DEFINE = re.compile(r"\s*#\s*define\s+(\w+)\s*(.*?)\s*")
+
+
+def _declarators(decl: str):
+    """One parameter or one struct line: `const int *a, *b` -> [(c_void_p, "a"), (c_void_p, "b")], `long M` -> [(c_long, "M")].  Every
+    pointer is c_void_p; a by-value type is one of the four or an error (never a guessed int)."""
+    m = _DECLARATORS.fullmatch(decl)
+    if not m:
+        raise DTLRError(f"dtlr_hip.h: cannot read the declaration `{decl.strip()}`")
+    base, out = " ".join(m.group(1).split()), []
+    for d in m.group(2).split(","):
+        if "*" not in d and base not in _BY_VALUE:
+            raise DTLRError(f"dtlr_hip.h: `{decl.strip()}`: by-value type `{base}` is not one of {', '.join(_BY_VALUE)}")
+        out.append((c_void_p if "*" in d else _BY_VALUE[base], d.strip("* \t\n")))
+    return out
+
+
+def read_header(text: str):
+    """The text of include/dtlr_hip.h -> (functions, structs, constants):
+    functions  name -> (restype, [(ctype, parameter name), ...])
+    structs    name -> [(field, ctype), ...] in declaration order
+    constants  NAME -> int, every `#define NAME <integer or (-integer)>`
+    DTLRError, naming the text, for anything but function declarations, `typedef struct`s, `extern "C"` braces and integer defines."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    functions, structs, constants, code = {}, {}, {}, []
+    for line in text.splitlines():
+        if "//" in line:
+            raise DTLRError(f"dtlr_hip.h: `{line.strip()}`: only /* */ comments")
+        m = _DEFINE.fullmatch(line)
+        if m and m.group(2):
+            if not re.fullmatch(r"-?\d+|\(\s*-?\d+\s*\)", m.group(2)):
+                raise DTLRError(f"dtlr_hip.h: `{line.strip()}`: a #define's value must be an integer")
+            constants[m.group(1)] = int(m.group(2).strip("( )"))
+        elif not line.lstrip().startswith("#"):
+            code.append(line)
+    code, pos, depth = "\n".join(code).rstrip(), 0, 0
+    while pos < len(code):
+        m = _STATEMENT.match(code, pos)
+        if not m or (m.group(2) and not depth):                            # a `}` closes nothing but the extern "C" block
+            raise DTLRError(f"dtlr_hip.h: cannot read the statement `{code[pos:].strip()[:80]}`")
+        pos, depth = m.end(), depth + (m.group(1) is not None) - (m.group(2) is not None)
+        if m.group(4):
+            structs[m.group(4)] = [(name, t) for field in m.group(3).split(";") if field.strip() for t, name in _declarators(field)]
+        elif m.group(5):
+            f = re.fullmatch(r"\s*(.*?)\b(\w+)\s*\((.*)\)\s*", m.group(5), re.S)
+            ret = f and " ".join(f.group(1).replace("*", " * ").split())
+            if not f or ret not in _RETURNS:
+                raise DTLRError(f"dtlr_hip.h: `{m.group(5).strip()[:80]}` is not a function declaration returning {' / '.join(_RETURNS)}")
+            params = [] if f.group(3).strip() == "void" else [p for decl in f.group(3).split(",") for p in _declarators(decl)]
+            functions[f.group(2)] = (_RETURNS[ret], params)
+    return functions, structs, constants
+
+
+def _read_header_file():
+    path = os.path.join(HERE, "..", "include", "dtlr_hip.h")                 # where build.py fingerprints it
+    if not os.path.exists(path):
+        raise DTLRError(f"{path} is missing: the binding reads every signature from it (it ships with the sources; there is no second table)")
+    with open(path) as f:
+        return read_header(f.read())
+
+
+# parsed once per process, for both libraries
+_FUNCTIONS, _STRUCTS, CONSTANTS = _read_header_file()
+# name -> (restype, argtypes): every symbol include/dtlr_hip.h declares
+_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _FUNCTIONS.items()}
+globals().update(CONSTANTS)            # DTLR_OK, DTLR_EINVAL .. DTLR_ELAUNCH; the dtype codes DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S
+
+
 class K256sSlice(ctypes.Structure):
     """include/dtlr_hip.h: dtlr_k256s_slice"""
-    _fields_ = [("Wp", c_void_p), ("bias", c_void_p), ("R", c_void_p), ("C", c_void_p),
-                ("ldc", c_int), ("ldr", c_int), ("n_valid", c_int), ("relu", c_int)]
+    _fields_ = _STRUCTS["dtlr_k256s_slice"]
 
 
 class NgramLM(ctypes.Structure):
     """include/dtlr_hip.h: dtlr_ngram_lm"""
-    _fields_ = [("tok", c_void_p), ("child_lo", c_void_p), ("child_hi", c_void_p), ("suffix", c_void_p), ("ctx", c_void_p),
-                ("logp", c_void_p), ("bo", c_void_p), ("n_nodes", c_int), ("order", c_int), ("bos_state", c_int), ("eos_tok", c_int),
-                ("unk", ctypes.c_double)]
+    _fields_ = _STRUCTS["dtlr_ngram_lm"]
 
 
-# name -> (restype, argtypes): every symbol include/dtlr_hip.h declares
-_SIGNATURES = {
-    "dtlr_strerror": (c_char_p, [c_int]),
-    "dtlr_last_hip_error": (c_int, []),
-    "dtlr_abi_version": (c_int, []),
-    "dtlr_workspace_reserve": (c_int, [ctypes.c_long, c_void_p]),
-    "dtlr_workspace_retired_bytes": (ctypes.c_long, []),
-    "dtlr_msda_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "dtlr_msda_fused_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "dtlr_msda_fused_forward_strided": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "dtlr_msda_encoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_int, c_void_p, c_void_p]),
-    "dtlr_msda_encoder_plan_ok": (c_int, [c_void_p, c_int, c_int]),
-    "dtlr_msda_encoder_far_samples": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "dtlr_swin_patch_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_swin_window_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_swin_patch_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_geometry": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_float, c_int, c_void_p]),
-    "dtlr_ffn_fused_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
-                                    c_int, c_int, c_int, c_void_p]),
-    "dtlr_conv3x3_patch_supported": (c_int, [c_int, c_int]),
-    "dtlr_conv3x3_patch_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_conv3x3_patch_f32s_supported": (c_int, [c_int, c_int]),
-    "dtlr_conv3x3_patch_f32s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_kres_pack_weights": (c_int, [c_void_p, c_void_p, c_int, c_int]),
-    "dtlr_gemm_kres_pack_weights_bcast384": (c_int, [c_void_p, c_void_p]),
-    "dtlr_gemm_kres_bcast384": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "dtlr_gemm_kres": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_kres_chain": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "dtlr_l1_bottleneck": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_kres_cat_s2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_ffn32_pack_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
-    "dtlr_ffn32_pad_chunks": (c_int, []),
-    "dtlr_ffn32_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
-                                ctypes.c_long, c_int, c_void_p]),
-    "dtlr_ffn4_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
-                               ctypes.c_long, c_int, c_void_p]),
-    "dtlr_ffn_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_long, c_int, c_void_p]),
-    "dtlr_ffn_split_pad_chunks": (c_int, []),
-    "dtlr_head_ts": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_long, c_void_p]),
-    "dtlr_head_ts_pad_chunks": (c_int, []),
-    "dtlr_k256s_pack_weights": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "dtlr_gemm_k256s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, ctypes.c_long, c_void_p]),
-    "dtlr_gemm_k256s_multi": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "dtlr_proj_pack_weights": (c_int, [c_void_p, c_void_p]),
-    "dtlr_proj_ln_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
-    "dtlr_proj_ln_split_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
-    "dtlr_mha_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_mha_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int, c_int]),
-    "dtlr_gemm_nt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_split_pack_weights": (c_int, [c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p]),
-    "dtlr_k256_pack_weights": (c_int, [c_void_p, c_void_p, c_int]),
-    "dtlr_gemm_k256": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_proj_ln_k256_pack_weights": (c_int, [c_void_p, c_void_p]),
-    "dtlr_proj_ln_k256": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p]),
-    "dtlr_gemm_nt_a2bcast": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_nt_resbcast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_nt_rowmax": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_gemm_nt_rowmax_lda": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_two_stage_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_conv2d_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_dq_pack_weights": (c_int, [c_void_p, c_void_p, c_int, c_int]),
-    "dtlr_dec_query_stage": (c_int, [c_void_p] * 16 + [c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_decoder_query_prep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_box_refine": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p]),
-    "dtlr_groupnorm_tokens_strided": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_groupnorm_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_groupnorm_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
-    "dtlr_box_mlp_refine_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "dtlr_box_head_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_void_p]),
-    "dtlr_stem_pack_weights": (c_int, [c_void_p, c_void_p]),
-    "dtlr_stem_conv7x7": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_stem_conv7x7_pool": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_stem_conv7x7_f32s": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_stem_conv7x7_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_maxpool3x3s2_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_preprocess_lines": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_topk_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_ctc_loss_interleaved": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]),
-    "dtlr_topk_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_long, c_int, c_int, c_void_p]),
-    # class-head adaptation (csrc/ctc_grad.hip, csrc/head_grad.hip)
-    "dtlr_ctc_loss_interleaved_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                                   c_int, c_float, c_float, c_void_p]),
-    "dtlr_ctc_loss_interleaved_backward_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
-    "dtlr_head_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_void_p]),
-    "dtlr_head_grad_workspace_bytes": (ctypes.c_long, [ctypes.c_long, c_int, c_int]),
-    "dtlr_grad_norm_scale": (c_int, [c_void_p, ctypes.c_long, c_float, c_void_p, c_void_p, c_void_p]),
-    "dtlr_grad_norm_scale_workspace_bytes": (ctypes.c_long, []),
-    "dtlr_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_float, c_float, c_float, c_float, c_float,
-                                c_int, c_void_p]),
-    "dtlr_nms": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "dtlr_blank_emissions": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p]),
-    "dtlr_blank_emissions_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
-    "dtlr_ngram_beam": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int, c_int, c_int,
-                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_ngram_beam_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int]),
-    "dtlr_decode_blank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "dtlr_decode_blank_located_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
-    "dtlr_decode_blank_located": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_decode_nms_located": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    # forced alignment (csrc/ctc_align.hip)
-    "dtlr_ctc_align": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_ctc_align_workspace_bytes": (ctypes.c_long, [c_int, c_int, c_int, c_int]),
-    "dtlr_reading_order": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    # keyword spotting (csrc/ctc_spot.hip)
-    "dtlr_ctc_spot": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_ctc_spot_workspace_bytes": (ctypes.c_long, [c_int, c_int]),
-    # per-line batching
-    "dtlr_line_extents": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_zero_outside_extent_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_maxpool3x3s2_nhwc_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_groupnorm_tokens_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_int, c_int,
-                                          c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_geometry_ext": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dtlr_topk_rows_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "dtlr_decoder_query_prep_per_line": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_dec_query_stage_per_line": (c_int, [c_void_p] * 16 + [c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_swin_patch_embed_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "dtlr_swin_window_attn_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "dtlr_swin_patch_merge_ext": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-}
+def takes_stream(name: str) -> bool:
+    """whether the entry point's last parameter is `void *stream` (it is then reached through launch())"""
+    params = _FUNCTIONS[name][1]
+    return bool(params) and params[-1] == (c_void_p, "stream")
 
 
 def _load(path: str) -> ctypes.CDLL:

@@ -8,6 +8,12 @@
  *     models/dino/ops/src/cuda/ms_deform_im2col_cuda.cuh:948-952).
  *
  * Each declaration cites the reference interface it replaces (paths under /root/reference).
+ *
+ * This file is the only statement of the ABI: the Python binding (dtlr_amd/_lib.py) reads every signature, both structs and the
+ * integer #defines from this text when it is imported, and refuses what it cannot read.  So the file stays in a small dialect:
+ * plain C99; comments in the block form only, never the double-slash form; by-value parameters and fields of type int, long,
+ * float or double, everything else a pointer; returns int, long or const char *; structs as `typedef struct tag { ... } name;`;
+ * constants as #define NAME followed by an integer or a parenthesised negative integer.
  */
 #ifndef DTLR_HIP_H
 #define DTLR_HIP_H

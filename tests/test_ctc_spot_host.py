@@ -4,15 +4,11 @@ wrapper's host checks), the JSON of a hit and the CLI's flags."""
 import itertools
 import json
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import ctc_spot_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _tiny_cases():
@@ -141,9 +137,8 @@ def test_the_draw_has_the_keywords_it_promises():
 def test_symbols_are_declared_and_the_wrapper_checks_its_tables():
     import torch
     from dtlr_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, "include", "dtlr_hip.h")).read()
     for name in ("dtlr_ctc_spot", "dtlr_ctc_spot_workspace_bytes"):
-        assert re.search(rf"\b{name}\s*\(", hdr) and name in _lib._SIGNATURES, name
+        assert name in _lib._SIGNATURES, name                         # read from include/dtlr_hip.h
     assert _lib._SIGNATURES["dtlr_ctc_spot"][0] is _lib.c_int and len(_lib._SIGNATURES["dtlr_ctc_spot"][1]) == 16
     assert hasattr(ops.ctc_spot, "__wrapped__")
     kw, kl = ops.ctc_spot_tables([[1, 5, 2], [3], [4] * 32], 6, 4)

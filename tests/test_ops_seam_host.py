@@ -2,7 +2,6 @@
 use in dtlr_amd/ops.py and dtlr_amd/MultiScaleDeformableAttention.py).  Stand-in objects with callable attributes play the libraries."""
 import ast
 import os
-import re
 
 import pytest
 import torch
@@ -175,25 +174,14 @@ def test_no_rebinding_and_no_call_around_the_helpers(rel):
     assert "_device_scoped" not in {getattr(n, "name", None) for n in tree.body}
 
 
-def _header_declarations():
-    """symbol -> whether its last parameter is `void *stream` (include/dtlr_hip.h)"""
-    with open(os.path.join(ROOT, "include", "dtlr_hip.h")) as f:
-        hdr = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    decl = {m.group(1): re.search(r"void\s*\*\s*stream\s*$", m.group(2)) is not None
-            for m in re.finditer(r"\b(dtlr_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;", hdr)}
-    assert len(decl) == len(_lib._SIGNATURES)
-    return decl
-
-
 @pytest.mark.parametrize("rel", BINDINGS)
 def test_every_symbol_is_declared_and_the_helper_matches_its_stream_parameter(rel):
-    takes_stream = _header_declarations()
     seen = set()
     for helper, arg in _helper_calls(_tree(rel)):
         for name in _names(arg):
             seen.add(name)
             assert name in _lib._SIGNATURES, f"{rel}:{arg.lineno}: {name} is not a declared symbol"
-            assert takes_stream[name] == (helper == "launch"), f"{rel}:{arg.lineno}: {name} through _lib.{helper}"
+            assert _lib.takes_stream(name) == (helper == "launch"), f"{rel}:{arg.lineno}: {name} through _lib.{helper}"
             # launch / call raise on a non-zero return: only for entry points that return a code
             assert helper == "query" or _lib._SIGNATURES[name][0] is _lib.c_int
     assert len(seen) >= (75 if rel.endswith("ops.py") else 1)
