@@ -703,21 +703,15 @@ extern "C" int dtlr_mha_forward(const void* qk, const void* v, void* vt_workspac
         const int nkb = Lpad / 32, cap = 19;
         const int nchunks = (nkb + cap - 1) / cap, kc = (nkb + nchunks - 1) / nchunks;
         const size_t lds = (size_t)kc * 8192;
-        static DevOnce attr_s;
-        if (attr_s.first()) { (void)hipFuncSetAttribute((const void*)mha_fwd_f32s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); (void)hipGetLastError(); }
-        hipLaunchKernelGGL(mha_fwd_f32s_kernel, dim3(H, B), dim3(1024), lds, st, (const float*)qk, (const float*)v, (float*)out, L, Lpad, H, kc,
-                           1.4426950408889634f / sqrtf((float)head_dim));
-        return check_launch();
+        return launch<mha_fwd_f32s_kernel>(dim3(H, B), dim3(1024), lds, st, (const float*)qk, (const float*)v, (float*)out, L, Lpad, H, kc,
+                                           1.4426950408889634f / sqrtf((float)head_dim));
     }
     if (dtype == DTLR_F32) {
-        hipLaunchKernelGGL(v_transpose_f32_kernel, dim3(Lpad / 32, B), dim3(256), (size_t)C * 33 * sizeof(float), st,
-                           (const float*)v, (float*)vt_workspace, L, Lpad, H);
-        int rc0 = check_launch();
-        if (rc0) return rc0;
-        hipLaunchKernelGGL(mha_fwd_f32_kernel, dim3((L + 127) / 128, H, B), dim3(256), 0, st,
-                           (const float*)qk, (const float*)vt_workspace, (float*)out, L, Lpad, H,
-                           1.4426950408889634f / sqrtf((float)head_dim));
-        return check_launch();
+        if (int rc = launch<v_transpose_f32_kernel>(dim3(Lpad / 32, B), dim3(256), (size_t)C * 33 * sizeof(float), st,
+                                                    (const float*)v, (float*)vt_workspace, L, Lpad, H)) return rc;
+        return launch<mha_fwd_f32_kernel>(dim3((L + 127) / 128, H, B), dim3(256), 0, st,
+                                          (const float*)qk, (const float*)vt_workspace, (float*)out, L, Lpad, H,
+                                          1.4426950408889634f / sqrtf((float)head_dim));
     }
     const float scale_log2e = 1.4426950408889634f / sqrtf((float)head_dim);
     const size_t lds = (size_t)(Lpad / 32) * 4096;               // K image + V^T image
@@ -726,26 +720,17 @@ extern "C" int dtlr_mha_forward(const void* qk, const void* v, void* vt_workspac
         // the online-softmax form stays reachable in experiment builds only (DTLR_MHA_V=0)
         static const bool two_pass = exp_env_int("DTLR_MHA_V", 1) != 0;
         if (two_pass) {
-            static DevOnce attr2;
-            if (attr2.first()) { (void)hipFuncSetAttribute((const void*)mha_fwd_bf16_lds2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); (void)hipGetLastError(); }
             const int nz = (B * H <= 64 && (L + 31) / 32 > 16) ? 2 : 1;        // few (batch, head) pairs: split the query blocks over two workgroups
-            hipLaunchKernelGGL(mha_fwd_bf16_lds2_kernel, dim3(H, B, nz), dim3(1024), lds, st,
-                               (const uint16_t*)qk, (const uint16_t*)v, (uint16_t*)out, L, Lpad, H, scale_log2e);
-            return check_launch();
+            return launch<mha_fwd_bf16_lds2_kernel>(dim3(H, B, nz), dim3(1024), lds, st,
+                                                    (const uint16_t*)qk, (const uint16_t*)v, (uint16_t*)out, L, Lpad, H, scale_log2e);
         }
-        static DevOnce attr;
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)mha_fwd_bf16_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); (void)hipGetLastError(); }
-        hipLaunchKernelGGL(mha_fwd_bf16_lds_kernel, dim3(H, B), dim3(1024), lds, st,
-                           (const uint16_t*)qk, (const uint16_t*)v, (uint16_t*)out, L, Lpad, H, scale_log2e);
-        return check_launch();
+        return launch<mha_fwd_bf16_lds_kernel>(dim3(H, B), dim3(1024), lds, st,
+                                               (const uint16_t*)qk, (const uint16_t*)v, (uint16_t*)out, L, Lpad, H, scale_log2e);
     }
-    hipLaunchKernelGGL(v_transpose_kernel, dim3(Lpad / 32, B), dim3(256), (size_t)C * 33 * sizeof(uint16_t), st,
-                       (const uint16_t*)v, (uint16_t*)vt_workspace, L, Lpad, H);
-    int rc = check_launch();
-    if (rc) return rc;
-    hipLaunchKernelGGL(mha_fwd_bf16_kernel, dim3((L + 127) / 128, H, B), dim3(256), 0, st,
-                       (const uint16_t*)qk, (const uint16_t*)vt_workspace, (uint16_t*)out, L, Lpad, H, scale_log2e);
-    return check_launch();
+    if (int rc = launch<v_transpose_kernel>(dim3(Lpad / 32, B), dim3(256), (size_t)C * 33 * sizeof(uint16_t), st,
+                                            (const uint16_t*)v, (uint16_t*)vt_workspace, L, Lpad, H)) return rc;
+    return launch<mha_fwd_bf16_kernel>(dim3((L + 127) / 128, H, B), dim3(256), 0, st,
+                                       (const uint16_t*)qk, (const uint16_t*)vt_workspace, (uint16_t*)out, L, Lpad, H, scale_log2e);
 }
 
 extern "C" long dtlr_mha_workspace_bytes(int B, int L, int H, int head_dim)

@@ -297,14 +297,11 @@ extern "C" int dtlr_conv3x3_patch_f32s(const float* X, const void* Wt, const flo
 #define CPS_LAUNCH(CB_, BN_, NW_, NS_)                                                             \
     {                                                                                              \
         constexpr int lds_ = 2 * CB_ * CP_PLANE + NS_ * BN_ * 256;                                 \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)conv3x3_patch_f32s_kernel<CB_, BN_, NW_, NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((conv3x3_patch_f32s_kernel<CB_, BN_, NW_, NS_>), grid, dim3(64 * NW_), lds_, st, X, (const unsigned char*)Wt, bias, Y, H, W, Cout, relu); \
+        return launch<conv3x3_patch_f32s_kernel<CB_, BN_, NW_, NS_>>(grid, dim3(64 * NW_), lds_, st, X, (const unsigned char*)Wt, bias, Y, H, W, Cout, relu); \
     }
     if (Cin == 64) CPS_LAUNCH(1, 64, 4, 2)          // 46 KB of planes + 2 x 16 KB: two workgroups per CU
     else CPS_LAUNCH(2, 128, 8, 2)                   // 92 KB + 2 x 32 KB = 156 KB: one workgroup of eight waves
 #undef CPS_LAUNCH
-    return check_launch();
 }
 
 // 1 when dtlr_conv3x3_patch_bf16 takes this shape
@@ -329,9 +326,7 @@ extern "C" int dtlr_conv3x3_patch_bf16(const void* X, const void* Wt, const floa
 #define CP_LAUNCH(CB_, BN_, NW_)                                                                   \
     {                                                                                              \
         constexpr int lds_ = CB_ * CP_PLANE + CP_NS * BN_ * 128;                                   \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<CB_, BN_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((conv3x3_patch_kernel<CB_, BN_, NW_>), grid, dim3(64 * NW_), lds_, st, (const uint16_t*)X, (const uint16_t*)Wt, bias, (uint16_t*)Y, H, W, Cout, relu); \
+        return launch<conv3x3_patch_kernel<CB_, BN_, NW_>>(grid, dim3(64 * NW_), lds_, st, (const uint16_t*)X, (const uint16_t*)Wt, bias, (uint16_t*)Y, H, W, Cout, relu); \
     }
     static const int nw8 = exp_env_int("DTLR_CONV_PATCH_NW8", 1);     // experiment builds: =0 four waves everywhere (A/B timing)
     if (BN == 128) {
@@ -342,7 +337,6 @@ extern "C" int dtlr_conv3x3_patch_bf16(const void* X, const void* Wt, const floa
         if (Cin == 64) CP_LAUNCH(1, 64, 4) else if (Cin == 128) CP_LAUNCH(2, 64, 4) else CP_LAUNCH(4, 64, 4)
     }
 #undef CP_LAUNCH
-    return check_launch();
 }
 
 }  // namespace dtlr

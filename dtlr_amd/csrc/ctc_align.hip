@@ -239,12 +239,9 @@ extern "C" int dtlr_ctc_align(const float* emissions, int B, int T, int V, const
     const CtcaPlan p = ctca_plan(Tmax, max_target_length, interleaved != 0);
     if (p.rows < 1) return DTLR_ESHAPE;
     if (p.use_ws && !workspace) return DTLR_EINVAL;
-    if (p.lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)ctc_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ctc_align_kernel, dim3(n), dim3(p.threads), p.lds, (hipStream_t)stream, emissions, spans, targets, target_lengths,
-                       score, first, last, peak, prob, length, reinterpret_cast<unsigned long long*>(workspace), B, T, V, Lmax,
-                       max_target_length, Tmax, interleaved != 0 ? 1 : 0, filler, p.rows, p.use_ws ? 1 : 0, p.ws_span);
-    return check_launch();
+    return launch<ctc_align_kernel>(dim3(n), dim3(p.threads), p.lds, (hipStream_t)stream, emissions, spans, targets, target_lengths,
+                                    score, first, last, peak, prob, length, reinterpret_cast<unsigned long long*>(workspace), B, T, V, Lmax,
+                                    max_target_length, Tmax, interleaved != 0 ? 1 : 0, filler, p.rows, p.use_ws ? 1 : 0, p.ws_span);
 }
 
 extern "C" int dtlr_reading_order(const float* boxes, int* order, int B, int nq, void* stream)
@@ -255,9 +252,6 @@ extern "C" int dtlr_reading_order(const float* boxes, int* order, int B, int nq,
     while (np < nq) np <<= 1;
     if ((size_t)np * 8 > CTCA_LDS_BUDGET) return DTLR_ESHAPE;
     const size_t lds = (size_t)np * 8;
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)ctca_reading_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
     const int threads = np / 2 >= 1024 ? 1024 : (np / 2 <= 64 ? 64 : np / 2);
-    hipLaunchKernelGGL(ctca_reading_order_kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, boxes, order, nq, np);
-    return check_launch();
+    return launch<ctca_reading_order_kernel>(dim3(B), dim3(threads), lds, (hipStream_t)stream, boxes, order, nq, np);
 }

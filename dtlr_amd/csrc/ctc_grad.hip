@@ -268,12 +268,9 @@ extern "C" int dtlr_ctc_loss_interleaved_backward(const float* logits, const flo
     if (nrows > 0x7fffffffl) return DTLR_ESHAPE;
     const int Lc = Lmax > 0 ? Lmax : 1, SW = 2 * Lmax + 1;
     const CtcbWs w = ctcb_ws(workspace, B, nq, Lc);
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)ctc_interleaved_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ctcb_query_sum_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, w.sums, nrows, C);
-    hipLaunchKernelGGL(ctc_interleaved_bwd_kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, logits, boxes, w.sums, targets,
-                       target_lengths, nll, w.order, w.lscale, w.chain, w.occ, B, nq, C, Lmax, max_target_length, Lc, SW, eps, filler, np);
-    hipLaunchKernelGGL(ctc_dlogits_kernel, dim3((unsigned)nrows), dim3(256), (size_t)C * 4, (hipStream_t)stream, logits, w.sums, w.order,
-                       w.lscale, w.chain, w.occ, targets, target_lengths, dlogits, nq, C, Lmax, max_target_length, Lc, SW, eps);
-    return check_launch();
+    if (int rc = launch<ctcb_query_sum_kernel>(dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, w.sums, nrows, C)) return rc;
+    if (int rc = launch<ctc_interleaved_bwd_kernel>(dim3(B), dim3(threads), lds, (hipStream_t)stream, logits, boxes, w.sums, targets,
+                                                    target_lengths, nll, w.order, w.lscale, w.chain, w.occ, B, nq, C, Lmax, max_target_length, Lc, SW, eps, filler, np)) return rc;
+    return launch<ctc_dlogits_kernel>(dim3((unsigned)nrows), dim3(256), (size_t)C * 4, (hipStream_t)stream, logits, w.sums, w.order,
+                                      w.lscale, w.chain, w.occ, targets, target_lengths, dlogits, nq, C, Lmax, max_target_length, Lc, SW, eps);
 }

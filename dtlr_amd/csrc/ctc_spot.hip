@@ -183,12 +183,9 @@ extern "C" int dtlr_ctc_spot(const float* emissions, int B, int T, int V, const 
     if ((rows + 3) / 4 > 0x7fffffffL || (long)B * nqb > 0x7fffffffL || (long)B * Q * H > 0x7fffffffL) return DTLR_ESHAPE;
     double* lnmx = reinterpret_cast<double*>(workspace);
     float* mx = reinterpret_cast<float*>(lnmx + rows);
-    hipLaunchKernelGGL(ctcs_rowmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, emissions, mx, lnmx, rows, V);
+    if (int rc = launch<ctcs_rowmax_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, emissions, mx, lnmx, rows, V)) return rc;
     const int wave_bytes = (int)ctcs_wave_bytes(T);
     const size_t lds = (size_t)nw * wave_bytes;
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)ctc_spot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ctc_spot_kernel, dim3((unsigned)(B * nqb)), dim3(64 * nw), lds, (hipStream_t)stream, emissions, mx, lnmx, keywords,
-                       keyword_lengths, min_ratio, count, start, end, ratio, B, T, V, Q, Lmax, H, (int)nqb, wave_bytes);
-    return check_launch();
+    return launch<ctc_spot_kernel>(dim3((unsigned)(B * nqb)), dim3(64 * nw), lds, (hipStream_t)stream, emissions, mx, lnmx, keywords,
+                                   keyword_lengths, min_ratio, count, start, end, ratio, B, T, V, Q, Lmax, H, (int)nqb, wave_bytes);
 }

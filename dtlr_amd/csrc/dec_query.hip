@@ -295,19 +295,13 @@ static int dec_query_stage_launch(const float* ref, const float* valid_ratios, c
     if (grid <= 64) {
         // small batches (round 5; one line = 900 queries = 8 workgroups of 128): workgroups of 32 queries -- the four dependent GEMM stages,
         // the sine quarters and the 64 KB of output per workgroup shrink four-fold, the per-workgroup weight fetch from L2 does not grow
-        static DevOnce attrs;
-        if (attrs.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<2, UNSCALED_SINE>, hipFuncAttributeMaxDynamicSharedMemorySize, DqCfg<2>::LDS); (void)hipGetLastError(); }
-        hipLaunchKernelGGL((dec_query_stage_kernel<2, UNSCALED_SINE>), dim3((unsigned)((Q + 31) / 32)), dim3(512), DqCfg<2>::LDS, (hipStream_t)stream,
-                           ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
-                           (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
-        return check_launch();
+        return launch<dec_query_stage_kernel<2, UNSCALED_SINE>>(dim3((unsigned)((Q + 31) / 32)), dim3(512), DqCfg<2>::LDS, (hipStream_t)stream,
+                                                                ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
+                                                                (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
     }
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)dec_query_stage_kernel<8, UNSCALED_SINE>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL((dec_query_stage_kernel<8, UNSCALED_SINE>), dim3((unsigned)grid), dim3(512), DQ_LDS, (hipStream_t)stream,
-                       ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
-                       (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
-    return check_launch();
+    return launch<dec_query_stage_kernel<8, UNSCALED_SINE>>(dim3((unsigned)grid), dim3(512), DQ_LDS, (hipStream_t)stream,
+                                                            ref, valid_ratios, dim_t, (const uint16_t*)tgt, (const uint16_t*)W0, b0, (const uint16_t*)W1, b1,
+                                                            (const uint16_t*)Wqk, bqk, (const uint16_t*)Wv, bv, ref_in, (uint16_t*)qpos, (uint16_t*)qk, (uint16_t*)v, Q, nq, L);
 }
 
 extern "C" int dtlr_dec_query_stage(const float* ref, const float* valid_ratios, const float* dim_t, const void* tgt,

@@ -634,16 +634,10 @@ static int topk_rows_launch(const float* scores, const unsigned char* excl, long
         int index_bytes = 1;
         while (index_bytes < 4 && ((long)S - 1) >> (8 * index_bytes)) ++index_bytes;
         const size_t fl = (size_t)kp * 8;
-        if (fl > 48 * 1024) { (void)hipFuncSetAttribute((const void*)topk_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl); (void)hipGetLastError(); }
-        hipLaunchKernelGGL(topk_flat_kernel, dim3(B), dim3(1024), fl, (hipStream_t)stream, scores, (float*)nullptr, idx_out, (long)S, k, kp, index_bytes, 0,
-                           excl);
-        return check_launch();
+        return launch<topk_flat_kernel>(dim3(B), dim3(1024), fl, (hipStream_t)stream, scores, (float*)nullptr, idx_out, (long)S, k, kp, index_bytes, 0,
+                                        excl);
     }
-    (void)hipGetLastError();                                   // do not inherit a stale error from an earlier API call
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)topk_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(topk_rows_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, scores, idx_out, S, k, np, kp, excl);
-    return check_launch();
+    return launch<topk_rows_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, scores, idx_out, S, k, np, kp, excl);
 }
 
 extern "C" int dtlr_topk_rows(const float* scores, long* idx_out, int B, int S, int k, void* stream)
@@ -666,13 +660,9 @@ extern "C" int dtlr_decode_blank(const float* logits, const float* boxes, int* l
     const int np = next_pow2(nq);
     const size_t lds = (size_t)np * 16;
     if (lds > 150 * 1024) return DTLR_ESHAPE;
-    (void)hipGetLastError();
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)decode_blank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
     const long nrows = (long)B * nq;
-    hipLaunchKernelGGL(query_label_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, labels, nrows, C, eps);
-    hipLaunchKernelGGL(decode_blank_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, labels, lengths, nq, np);
-    return check_launch();
+    if (int rc = launch<query_label_kernel>(dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, labels, nrows, C, eps)) return rc;
+    return launch<decode_blank_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, labels, lengths, nq, np);
 }
 
 extern "C" int dtlr_ctc_loss_interleaved(const float* logits, const float* boxes, const int* targets, const int* target_lengths,
@@ -690,12 +680,9 @@ extern "C" int dtlr_ctc_loss_interleaved(const float* logits, const float* boxes
     const size_t lds = (size_t)np * 12 + (size_t)2 * (threads + 2) * 4;
     if (lds > 150 * 1024) return DTLR_ESHAPE;
     const long nrows = (long)B * nq;
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)ctc_interleaved_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(query_sum_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, workspace, nrows, C);
-    hipLaunchKernelGGL(ctc_interleaved_kernel, dim3(B), dim3(threads), lds, (hipStream_t)stream, logits, boxes, workspace, targets,
-                       target_lengths, nll, nq, C, Lmax, eps, filler, np);
-    return check_launch();
+    if (int rc = launch<query_sum_kernel>(dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, workspace, nrows, C)) return rc;
+    return launch<ctc_interleaved_kernel>(dim3(B), dim3(threads), lds, (hipStream_t)stream, logits, boxes, workspace, targets,
+                                          target_lengths, nll, nq, C, Lmax, eps, filler, np);
 }
 
 extern "C" int dtlr_blank_emissions(const float* logits, const float* boxes, float* out, float* workspace,
@@ -707,16 +694,13 @@ extern "C" int dtlr_blank_emissions(const float* logits, const float* boxes, flo
     const int np = next_pow2(nq);
     const size_t lds = (size_t)np * 8;
     if (lds > 150 * 1024) return DTLR_ESHAPE;
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)reading_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
     const long nrows = (long)B * nq;
     float* sums = workspace;                                  // [B * nq] fp32, then [B * nq] int32 (dtlr_blank_emissions_workspace_bytes)
     int* order = reinterpret_cast<int*>(workspace + nrows);
-    hipLaunchKernelGGL(query_sum_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, sums, nrows, C);
-    hipLaunchKernelGGL(reading_order_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, order, nq, np);
-    hipLaunchKernelGGL(blank_emissions_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, sums, order, out,
-                       nrows, nq, C, scale, eps);
-    return check_launch();
+    if (int rc = launch<query_sum_kernel>(dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, sums, nrows, C)) return rc;
+    if (int rc = launch<reading_order_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, order, nq, np)) return rc;
+    return launch<blank_emissions_kernel>(dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, sums, order, out,
+                                          nrows, nq, C, scale, eps);
 }
 
 extern "C" long dtlr_blank_emissions_workspace_bytes(int B, int nq) { return (long)B * nq * 8; }
@@ -732,10 +716,7 @@ extern "C" int dtlr_nms(const float* boxes, const float* scores, float iou_thres
     const size_t words = (size_t)(n * W > np ? n * W : np);
     const size_t lds = words * 8 + (size_t)np * 16 + (size_t)np * 4;
     if (lds > 160 * 1024) return DTLR_ESHAPE;
-    (void)hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, scores, iou_threshold, keep, counts, n, np);
-    return check_launch();
+    return launch<nms_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, scores, iou_threshold, keep, counts, n, np);
 }
 
 extern "C" int dtlr_topk_flat(const float* x, float* values, long* idx_out, int B, long n, int k, int apply_sigmoid, void* stream)
@@ -747,9 +728,8 @@ extern "C" int dtlr_topk_flat(const float* x, float* values, long* idx_out, int 
     int index_bytes = 1;
     while (index_bytes < 4 && (n - 1) >> (8 * index_bytes)) ++index_bytes;
     const size_t fl = (size_t)next_pow2(k) * 8;
-    if (fl > 48 * 1024) { (void)hipFuncSetAttribute((const void*)topk_flat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl); (void)hipGetLastError(); }
-    hipLaunchKernelGGL(topk_flat_kernel, dim3(B), dim3(1024), fl, (hipStream_t)stream, x, values, idx_out, n, k, next_pow2(k), index_bytes, apply_sigmoid);
-    return check_launch();
+    return launch<topk_flat_kernel>(dim3(B), dim3(1024), fl, (hipStream_t)stream, x, values, idx_out, n, k, next_pow2(k), index_bytes, apply_sigmoid,
+                                    (const uint8_t*)nullptr);
 }
 
 /* ---- located decoders -------------------------------------------------------------------------------------------------------- */
@@ -766,16 +746,12 @@ extern "C" int dtlr_decode_blank_located(const float* logits, const float* boxes
     const int np = next_pow2(nq);
     if ((size_t)np * 16 > 150 * 1024) return DTLR_ESHAPE;      // dtlr_decode_blank's limit
     const size_t lds = (size_t)np * 12;
-    (void)hipGetLastError();
-    if (lds > 60 * 1024) (void)hipFuncSetAttribute((const void*)decode_blank_located_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
     const long nrows = (long)B * nq;
     int* raw = reinterpret_cast<int*>(workspace);              // [B * nq] int32 labels, then [B * nq] fp32 scores
     float* top = reinterpret_cast<float*>(workspace) + nrows;
-    hipLaunchKernelGGL(query_label_score_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, raw, top, nrows, C, eps);
-    hipLaunchKernelGGL(decode_blank_located_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, raw, top, src_hw,
-                       labels, query, rank, score, box, lengths, nq, np);
-    return check_launch();
+    if (int rc = launch<query_label_score_kernel>(dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, logits, raw, top, nrows, C, eps)) return rc;
+    return launch<decode_blank_located_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, boxes, raw, top, src_hw,
+                                               labels, query, rank, score, box, lengths, nq, np);
 }
 
 extern "C" int dtlr_decode_nms_located(const float* values, const long* index, const float* boxes, const float* src_hw,
@@ -792,9 +768,6 @@ extern "C" int dtlr_decode_nms_located(const float* values, const long* index, c
     const size_t words = (size_t)(k * W > np ? k * W : np);
     const size_t lds = words * 8 + (size_t)np * 16 + (size_t)np * 8;
     if (lds > 156 * 1024) return DTLR_ESHAPE;
-    (void)hipFuncSetAttribute((const void*)decode_nms_located_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(decode_nms_located_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, values, index, boxes, src_hw,
-                       iou_threshold, score_threshold, labels, query, score, box, lengths, k, np, nq, C);
-    return check_launch();
+    return launch<decode_nms_located_kernel>(dim3(B), dim3(1024), lds, (hipStream_t)stream, values, index, boxes, src_hw,
+                                             iou_threshold, score_threshold, labels, query, score, box, lengths, k, np, nq, C);
 }

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <mutex>
+#include <utility>
 #include "../../include/dtlr_hip.h"
 
 namespace dtlr {
@@ -20,19 +23,35 @@ inline int check_launch() {
     return DTLR_OK;
 }
 
-// One-time per-DEVICE setup (hipFuncSetAttribute is a per-device property: a process that drives several GPUs must repeat it
-// on each): `static DevOnce once; if (once.first()) { ... }`.
-struct DevOnce {
-    unsigned long long mask = 0;
-    bool first() {
+// The one way to launch a kernel: `launch<kern>(grid, block, lds, st, args...)` returns DTLR_OK or DTLR_ELAUNCH (HIP's code is in
+// g_last_hip_error).  It first makes sure that the current device grants this kernel instance `lds` bytes of dynamic LDS
+// (hipFuncAttributeMaxDynamicSharedMemorySize, a property of kernel AND device), then launches and checks.  Each instance remembers the
+// largest size every device has granted it: a fixed-size kernel costs one driver call per device, a variable-size one a call each time
+// its size grows, lds == 0 nothing at all.  A refused grant fails the entry before anything is enqueued.  Growing takes a lock and
+// looks again, so two threads cannot leave the driver with less than the mark says.  A kernel's default arguments do not travel
+// through the template argument: pass them.
+constexpr int kMaxDevices = 64;                // devices past this are served too, with a driver call per launch
+
+template <auto Kernel, class... A>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... args) {
+    if (lds != 0) {
+        static std::atomic<int> granted[kMaxDevices];            // static storage: zero, nothing granted yet
+        static std::mutex growing;
         int d = 0;
-        (void)hipGetDevice(&d);
-        const unsigned long long bit = 1ull << (d & 63);
-        if (mask & bit) return false;
-        mask |= bit;
-        return true;
+        hipError_t e = hipGetDevice(&d);
+        const auto enough = [&] { return (unsigned)d < (unsigned)kMaxDevices && (int)lds <= granted[d].load(std::memory_order_relaxed); };
+        if (e == hipSuccess && !enough()) {
+            std::lock_guard<std::mutex> lock(growing);
+            if (!enough()) {
+                e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e == hipSuccess && (unsigned)d < (unsigned)kMaxDevices) granted[d].store((int)lds, std::memory_order_relaxed);
+            }
+        }
+        if (e != hipSuccess) { (void)hipGetLastError(); g_last_hip_error = (int)e; return DTLR_ELAUNCH; }
     }
-};
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, std::forward<A>(args)...);
+    return check_launch();
+}
 
 // ---- the 16-bit storage / MFMA-operand format of this library ------------------------------------------------------------
 // libdtlr_hip.so is compiled with bf16 as "the" 16-bit format; the same sources compiled with -DDTLR_HALF_IS_F16 give

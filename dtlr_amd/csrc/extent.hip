@@ -47,8 +47,7 @@ extern "C" int dtlr_line_extents(const unsigned char* mask, int* ext, int B, int
     clear_stale_error();
     if (!mask || !ext) return DTLR_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0) return DTLR_EINVAL;
-    hipLaunchKernelGGL(line_extents_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, mask, H, W, ext);
-    return check_launch();
+    return launch<line_extents_kernel>(dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, mask, H, W, ext);
 }
 
 extern "C" int dtlr_zero_outside_extent_nhwc(void* x, const int* ext, int s, int B, int H, int W, int C, int dtype, void* stream)
@@ -63,7 +62,6 @@ extern "C" int dtlr_zero_outside_extent_nhwc(void* x, const int* ext, int s, int
     if (((long)C * esize) % 16 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return DTLR_ESHAPE;
     if (B > 65535) return DTLR_ESHAPE;
     const int nv = (int)((long)C * esize / 16);
-    hipLaunchKernelGGL(zero_outside_extent_kernel, dim3((unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       (uint4*)x, ext, s, H, W, nv);
-    return check_launch();
+    return launch<zero_outside_extent_kernel>(dim3((unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                                              (uint4*)x, ext, s, H, W, nv);
 }

@@ -846,26 +846,18 @@ extern "C" int dtlr_ffn_fused_bf16(const void* X, const void* W1, const float* b
     // experiment builds: DTLR_FFN_V = 1 forces the first structure, 2 the second with TT = 3 only (measurements / tests).
     static const int ver = exp_env_int("DTLR_FFN_V", 0);               // experiment builds only
     if (dbg == 0 && d_ff >= 128 && ver != 1 && (ver == 2 || M > 256 * 128)) {          // one partial round or less: the first structure is as fast
-        static DevOnce attr2;
-        if (attr2.first()) {
-            (void)hipFuncSetAttribute((const void*)ffn2_bf16_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS);
-            (void)hipFuncSetAttribute((const void*)ffn2_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS);
-            (void)hipGetLastError();
-           
-        }
         const uint16_t* Xp = (const uint16_t*)X;
         uint16_t* Yp = (uint16_t*)Y;
         const int NCU = 256;
         long done = 0;
         if (ver == 2) {
-            hipLaunchKernelGGL(ffn2_bf16_kernel<3>, dim3((unsigned)((M + 191) / 192)), dim3(256), F2_LDS, (hipStream_t)stream,
-                               Xp, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yp, M, d_ff);
-            return check_launch();
+            return launch<ffn2_bf16_kernel<3>>(dim3((unsigned)((M + 191) / 192)), dim3(256), F2_LDS, (hipStream_t)stream,
+                                               Xp, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yp, M, d_ff);
         }
         const long full = ((long)M / 192 / NCU) * NCU;                    // workgroups in whole rounds
         if (full > 0) {
-            hipLaunchKernelGGL(ffn2_bf16_kernel<3>, dim3((unsigned)full), dim3(256), F2_LDS, (hipStream_t)stream,
-                               Xp, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yp, (int)(full * 192), d_ff);
+            if (int rc = launch<ffn2_bf16_kernel<3>>(dim3((unsigned)full), dim3(256), F2_LDS, (hipStream_t)stream,
+                                                     Xp, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yp, (int)(full * 192), d_ff)) return rc;
             done = full * 192;
         }
         const long rem = M - done;
@@ -873,13 +865,12 @@ extern "C" int dtlr_ffn_fused_bf16(const void* X, const void* W1, const float* b
             const uint16_t* Xr = Xp + done * 256;
             uint16_t* Yr = Yp + done * 256;
             if (rem <= (long)NCU * 128)
-                hipLaunchKernelGGL(ffn2_bf16_kernel<2>, dim3((unsigned)((rem + 127) / 128)), dim3(256), F2_LDS, (hipStream_t)stream,
-                                   Xr, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yr, (int)rem, d_ff);
-            else
-                hipLaunchKernelGGL(ffn2_bf16_kernel<3>, dim3((unsigned)((rem + 191) / 192)), dim3(256), F2_LDS, (hipStream_t)stream,
-                                   Xr, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yr, (int)rem, d_ff);
+                return launch<ffn2_bf16_kernel<2>>(dim3((unsigned)((rem + 127) / 128)), dim3(256), F2_LDS, (hipStream_t)stream,
+                                                   Xr, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yr, (int)rem, d_ff);
+            return launch<ffn2_bf16_kernel<3>>(dim3((unsigned)((rem + 191) / 192)), dim3(256), F2_LDS, (hipStream_t)stream,
+                                               Xr, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, Yr, (int)rem, d_ff);
         }
-        return check_launch();
+        return DTLR_OK;
     }
     const unsigned grid = (unsigned)((M + 127) / 128);
     // Hidden split (round 5): when the 128-token tiles fill less than half of the chip -- one to a few lines: the latency case -- run
@@ -894,45 +885,37 @@ extern "C" int dtlr_ffn_fused_bf16(const void* X, const void* W1, const float* b
             FfnParts fp{};
             fp.ns = ns;
             for (int p = 0; p <= ns; ++p) fp.cb[p] = (int)((long)nchunk * p / ns);
-            static DevOnce attrp;
-            if (attrp.first()) { (void)hipFuncSetAttribute((const void*)ffn_fused_bf16_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FFN_LDS); (void)hipGetLastError(); }
-            hipLaunchKernelGGL((ffn_fused_bf16_kernel<0, false, true>), dim3(grid * (unsigned)ns), dim3(512), FFN_LDS, (hipStream_t)stream,
-                               (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, reinterpret_cast<uint16_t*>(ws), M, d_ff,
-                               (const float*)nullptr, fp);
-            hipLaunchKernelGGL(ffn_fused_finish_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                               (const float*)ws, ns, (long)M, (const uint16_t*)X, b2, gamma, beta, eps, (uint16_t*)Y);
-            return check_launch();
+            if (int rc = launch<ffn_fused_bf16_kernel<0, false, true>>(dim3(grid * (unsigned)ns), dim3(512), FFN_LDS, (hipStream_t)stream,
+                                                                       (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, reinterpret_cast<uint16_t*>(ws), M, d_ff,
+                                                                       (const float*)nullptr, fp)) return rc;
+            return launch<ffn_fused_finish_kernel>(dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                                                   (const float*)ws, ns, (long)M, (const uint16_t*)X, b2, gamma, beta, eps, (uint16_t*)Y);
         }
     }
 #define FFN_LAUNCH(D)                                                                              \
-    {                                                                                              \
-        static DevOnce attr;                                                                  \
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)ffn_fused_bf16_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, FFN_LDS); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL(ffn_fused_bf16_kernel<D>, dim3(grid), dim3(512), FFN_LDS, (hipStream_t)stream, \
-                           (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, (uint16_t*)Y, M, d_ff, (const float*)nullptr, FfnParts{}); \
-    }
+    return launch<ffn_fused_bf16_kernel<D>>(dim3(grid), dim3(512), FFN_LDS, (hipStream_t)stream,   \
+                                            (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2, b2, gamma, beta, eps, (uint16_t*)Y, M, d_ff, (const float*)nullptr, FfnParts{});
     switch (dbg) {
-    case 1: FFN_LAUNCH(1) break;
-    case 2: FFN_LAUNCH(2) break;
-    case 3: FFN_LAUNCH(3) break;
-    case 4: FFN_LAUNCH(4) break;
-    case 6: FFN_LAUNCH(6) break;
-    case 7: FFN_LAUNCH(7) break;
+    case 1: FFN_LAUNCH(1)
+    case 2: FFN_LAUNCH(2)
+    case 3: FFN_LAUNCH(3)
+    case 4: FFN_LAUNCH(4)
+    case 6: FFN_LAUNCH(6)
+    case 7: FFN_LAUNCH(7)
 #ifdef DTLR_GEMM_ABLATION
-    case 8: FFN_LAUNCH(8) break;
-    case 16: FFN_LAUNCH(16) break;
-    case 32: FFN_LAUNCH(32) break;
-    case 33: FFN_LAUNCH(33) break;
-    case 34: FFN_LAUNCH(34) break;
-    case 48: FFN_LAUNCH(48) break;
-    case 49: FFN_LAUNCH(49) break;
-    case 51: FFN_LAUNCH(51) break;
-    case 55: FFN_LAUNCH(55) break;
+    case 8: FFN_LAUNCH(8)
+    case 16: FFN_LAUNCH(16)
+    case 32: FFN_LAUNCH(32)
+    case 33: FFN_LAUNCH(33)
+    case 34: FFN_LAUNCH(34)
+    case 48: FFN_LAUNCH(48)
+    case 49: FFN_LAUNCH(49)
+    case 51: FFN_LAUNCH(51)
+    case 55: FFN_LAUNCH(55)
 #endif
-    default: FFN_LAUNCH(0) break;
+    default: FFN_LAUNCH(0)
     }
 #undef FFN_LAUNCH
-    return check_launch();
 }
 
 extern "C" int dtlr_box_mlp_refine_bf16(const void* X, const void* W1, const float* b1, const void* W2p, const float* b2,
@@ -941,11 +924,8 @@ extern "C" int dtlr_box_mlp_refine_bf16(const void* X, const void* W1, const flo
     clear_stale_error();
     if (!X || !W1 || !b1 || !W2p || !b2 || !W3 || !b3 || !ref || !out) return DTLR_EINVAL;
     if (M <= 0 || (mode != 0 && mode != 1)) return DTLR_EINVAL;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)ffn_fused_bf16_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FFN_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL((ffn_fused_bf16_kernel<0, true>), dim3((unsigned)((M + 127) / 128)), dim3(512), FFN_LDS, (hipStream_t)stream,
-                       (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2p, b2, W3, b3, (float)mode, (uint16_t*)out, M, 256, ref, FfnParts{});
-    return check_launch();
+    return launch<ffn_fused_bf16_kernel<0, true>>(dim3((unsigned)((M + 127) / 128)), dim3(512), FFN_LDS, (hipStream_t)stream,
+                                                  (const uint16_t*)X, (const uint16_t*)W1, b1, (const uint16_t*)W2p, b2, W3, b3, (float)mode, (uint16_t*)out, M, 256, ref, FfnParts{});
 }
 
 // W [256, 256] row-major bf16 (host) -> the fragment-major image the kernel streams: block (i, ks) = 64 lanes x 8 elements,
@@ -970,11 +950,8 @@ extern "C" int dtlr_proj_ln_bf16(const void* A, const void* W, const float* bias
     if (!A || !W || !bias || !R || !gamma || !beta || !Y) return DTLR_EINVAL;
     if (M <= 0) return DTLR_EINVAL;
     if (d_model != 256) return DTLR_ESHAPE;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)proj_ln_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PLN_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL(proj_ln_bf16_kernel<false>, dim3((unsigned)((M + 63) / 64)), dim3(256), PLN_LDS, (hipStream_t)stream,
-                       (const uint16_t*)A, (const uint16_t*)W, bias, (const uint16_t*)R, gamma, beta, eps, (uint16_t*)Y, M);
-    return check_launch();
+    return launch<proj_ln_bf16_kernel<false>>(dim3((unsigned)((M + 63) / 64)), dim3(256), PLN_LDS, (hipStream_t)stream,
+                                              (const uint16_t*)A, (const uint16_t*)W, bias, (const uint16_t*)R, gamma, beta, eps, (uint16_t*)Y, M);
 }
 
 extern "C" int dtlr_proj_ln_split_bf16(const void* A, const void* W, const float* bias, const unsigned char* keep,
@@ -984,11 +961,8 @@ extern "C" int dtlr_proj_ln_split_bf16(const void* A, const void* W, const float
     if (!A || !W || !bias || !gamma || !beta || !Y3) return DTLR_EINVAL;
     if (M <= 0) return DTLR_EINVAL;
     if (d_model != 256) return DTLR_ESHAPE;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)proj_ln_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PLN_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL(proj_ln_bf16_kernel<true>, dim3((unsigned)((M + 63) / 64)), dim3(256), PLN_LDS, (hipStream_t)stream,
-                       (const uint16_t*)A, (const uint16_t*)W, bias, reinterpret_cast<const uint16_t*>(keep), gamma, beta, eps, (uint16_t*)Y3, M);
-    return check_launch();
+    return launch<proj_ln_bf16_kernel<true>>(dim3((unsigned)((M + 63) / 64)), dim3(256), PLN_LDS, (hipStream_t)stream,
+                                             (const uint16_t*)A, (const uint16_t*)W, bias, reinterpret_cast<const uint16_t*>(keep), gamma, beta, eps, (uint16_t*)Y3, M);
 }
 
 #ifdef DTLR_GEMM_TRACE

@@ -326,24 +326,19 @@ extern "C" int dtlr_ffn32_bf16(const void* X, const void* W1p, const float* b1, 
     if (d_ff < 64 || d_ff > F3_MAX_DFF || (d_ff & 31)) return DTLR_ESHAPE;
     static const int dbg = exp_env_int("DTLR_FFN32_DBG", 0);      // experiment builds only: ablated variants whose results are garbage
 #define F3_LAUNCH(D)                                                                               \
-    {                                                                                              \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)ffn3_bf16_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL(ffn3_bf16_kernel<D>, dim3((unsigned)((M + 255) / 256)), dim3(256), F3_LDS, (hipStream_t)stream,       \
-                           (const uint16_t*)X, (const uint16_t*)W1p, b1, (const uint16_t*)W2p, b2, gamma, beta, eps, (uint16_t*)Y, (int)M, d_ff); \
-    }
+    return launch<ffn3_bf16_kernel<D>>(dim3((unsigned)((M + 255) / 256)), dim3(256), F3_LDS, (hipStream_t)stream, \
+                                       (const uint16_t*)X, (const uint16_t*)W1p, b1, (const uint16_t*)W2p, b2, gamma, beta, eps, (uint16_t*)Y, (int)M, d_ff);
     switch (dbg) {
-        case 1: F3_LAUNCH(1) break;
-        case 2: F3_LAUNCH(2) break;
-        case 3: F3_LAUNCH(3) break;
-        case 4: F3_LAUNCH(4) break;
-        case 7: F3_LAUNCH(7) break;
-        case 8: F3_LAUNCH(8) break;
-        case 24: F3_LAUNCH(24) break;
-        default: F3_LAUNCH(0) break;
+        case 1: F3_LAUNCH(1)
+        case 2: F3_LAUNCH(2)
+        case 3: F3_LAUNCH(3)
+        case 4: F3_LAUNCH(4)
+        case 7: F3_LAUNCH(7)
+        case 8: F3_LAUNCH(8)
+        case 24: F3_LAUNCH(24)
+        default: F3_LAUNCH(0)
     }
 #undef F3_LAUNCH
-    return check_launch();
 }
 
 }  // namespace dtlr

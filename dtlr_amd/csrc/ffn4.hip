@@ -473,8 +473,6 @@ extern "C" int dtlr_ffn4_bf16(const void* X, const void* W1p, const float* b1, c
     if (!X || !W1p || !b1 || !W2p || !b2 || !gamma || !beta || !Y) return DTLR_EINVAL;
     if (M <= 0 || M > 0x7fffffffL) return DTLR_EINVAL;
     if (d_ff < 64 || d_ff > F4_MAX_DFF || (d_ff & 31)) return DTLR_ESHAPE;
-    static DevOnce once;
-    if (once.first()) { (void)hipFuncSetAttribute((const void*)ffn4_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F4_LDS); (void)hipGetLastError(); }
     int dev = 0, cus = 0;
     (void)hipGetDevice(&dev);
     static int cu_cache[64];
@@ -487,9 +485,8 @@ extern "C" int dtlr_ffn4_bf16(const void* X, const void* W1p, const float* b1, c
     static const int lag = exp_env_int("DTLR_FFN4_LAG", 2);     // experiment builds only
     const long NPAIR = (NT + 1) / 2;
     const long G = NPAIR >= cus ? cus : NPAIR;
-    hipLaunchKernelGGL(ffn4_bf16_kernel, dim3((unsigned)G), dim3(256), F4_LDS, (hipStream_t)stream,
-                       (const uint16_t*)X, (const uint16_t*)W1p, b1, (const uint16_t*)W2p, b2, gamma, beta, eps, (uint16_t*)Y, (int)M, d_ff, lag);
-    return check_launch();
+    return launch<ffn4_bf16_kernel>(dim3((unsigned)G), dim3(256), F4_LDS, (hipStream_t)stream,
+                                    (const uint16_t*)X, (const uint16_t*)W1p, b1, (const uint16_t*)W2p, b2, gamma, beta, eps, (uint16_t*)Y, (int)M, d_ff, lag);
 }
 
 }  // namespace dtlr

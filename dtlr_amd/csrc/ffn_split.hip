@@ -305,12 +305,6 @@ extern "C" int dtlr_ffn_split(const void* X, const void* Wp, const float* b1, co
     if (!X || !Wp || !b1 || !b2 || !gamma || !beta || !Y) return DTLR_EINVAL;
     if (M <= 0 || M > 0x7fffffffL) return DTLR_EINVAL;
     if (d_ff < 32 || d_ff > FS_MAX_DFF || (d_ff & 31)) return DTLR_ESHAPE;
-    static DevOnce once;
-    if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)ffn_split_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS);
-        (void)hipFuncSetAttribute((const void*)ffn_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_LDS);
-        (void)hipGetLastError();
-    }
     hipStream_t st = (hipStream_t)stream;
     const long ntiles = (M + 127) / 128;
     // whole rounds of one workgroup per CU on the plain kernel; a last round that fills at most half of the chip is split over the hidden
@@ -325,18 +319,16 @@ extern "C" int dtlr_ffn_split(const void* X, const void* Wp, const float* b1, co
     const long tail_rows = M - full * 128;
     if (ns >= 2) ws = stream_workspace((size_t)ns * tail_rows * 256 * sizeof(float), st);
     if (ns < 2 || !ws) {
-        hipLaunchKernelGGL(ffn_split_kernel<false>, dim3((unsigned)ntiles), dim3(256), FS_LDS, st,
-                           (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, (float*)Y, (int)M, d_ff, FsParts{});
-        return check_launch();
+        return launch<ffn_split_kernel<false>>(dim3((unsigned)ntiles), dim3(256), FS_LDS, st,
+                                               (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, (float*)Y, (int)M, d_ff, FsParts{});
     }
     FsParts fp{};
     fp.ns = ns; fp.tile0 = (int)full;
     for (int p = 0; p <= ns; ++p) fp.cb[p] = (int)(((long)nc2 / 2 * p / ns) * 2);      // even boundaries, cb[0] = 0, cb[ns] = nc2
-    hipLaunchKernelGGL(ffn_split_kernel<false>, dim3((unsigned)full), dim3(256), FS_LDS, st,
-                       (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, (float*)Y, (int)(full * 128), d_ff, FsParts{});
-    hipLaunchKernelGGL(ffn_split_kernel<true>, dim3((unsigned)(rem * ns)), dim3(256), FS_LDS, st,
-                       (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, ws, (int)M, d_ff, fp);
-    hipLaunchKernelGGL(ffn_split_finish_kernel, dim3((unsigned)((tail_rows + 3) / 4)), dim3(256), 0, st,
-                       (const float*)ws, ns, tail_rows, (const float*)X + full * 128 * 256, b2, gamma, beta, eps, (float*)Y + full * 128 * 256);
-    return check_launch();
+    if (int rc = launch<ffn_split_kernel<false>>(dim3((unsigned)full), dim3(256), FS_LDS, st,
+                                                 (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, (float*)Y, (int)(full * 128), d_ff, FsParts{})) return rc;
+    if (int rc = launch<ffn_split_kernel<true>>(dim3((unsigned)(rem * ns)), dim3(256), FS_LDS, st,
+                                                (const float*)X, (const unsigned char*)Wp, b1, b2, gamma, beta, eps, ws, (int)M, d_ff, fp)) return rc;
+    return launch<ffn_split_finish_kernel>(dim3((unsigned)((tail_rows + 3) / 4)), dim3(256), 0, st,
+                                           (const float*)ws, ns, tail_rows, (const float*)X + full * 128 * 256, b2, gamma, beta, eps, (float*)Y + full * 128 * 256);
 }

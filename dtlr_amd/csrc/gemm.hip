@@ -1127,28 +1127,18 @@ static int try_splitk(const void* A, const void* W, const float* bias, const voi
     float* ws = splitk_workspace((size_t)S * M * N * sizeof(float), st);
     if (!ws) return DTLR_OK;                                     // no workspace: fall back to the plain path
     const size_t lds = 4 * TILE_BYTES;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<T, float, false, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipGetLastError(); }
     const unsigned grid = (unsigned)(nN * nM * S);
-    hipLaunchKernelGGL((gemm_ws_kernel<T, float, false, CONV>), dim3(grid), dim3(512), lds, st,
-                       (const T*)A, (const T*)nullptr, (const T*)W, (const float*)nullptr, (const float*)nullptr, (const uint8_t*)nullptr, ws,
-                       M, N, K, 0, nN, nM, 1, cp, S);
-    int rc = check_launch();
-    if (rc != DTLR_OK) return rc;
+    if (int rc = launch<gemm_ws_kernel<T, float, false, CONV>>(dim3(grid), dim3(512), lds, st,
+                                                               (const T*)A, (const T*)nullptr, (const T*)W, (const float*)nullptr, (const float*)nullptr, (const uint8_t*)nullptr, ws,
+                                                               M, N, K, 0, nN, nM, 1, cp, S)) return rc;
     const long n4 = ((long)M * N) / 4;
-    hipLaunchKernelGGL((splitk_reduce_kernel<OutT>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                       (const float*)ws, S, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, flags);
     done = true;
-    return check_launch();
+    return launch<splitk_reduce_kernel<OutT>>(dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                                              (const float*)ws, S, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, flags);
 }
 
-// launch gemm_ws_kernel<T, OutT, A2, CONV, CF> (setting its dynamic-LDS attribute once)
-#define WS_LAUNCH(A2, CONV, CF, GRID, ...)                                                          \
-    {                                                                                              \
-        static DevOnce attr_;                                                                 \
-        if (attr_.first()) { (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<T, OutT, A2, CONV, CF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((gemm_ws_kernel<T, OutT, A2, CONV, CF>), dim3(GRID), dim3(512), lds, st, __VA_ARGS__); \
-    }
+// launch gemm_ws_kernel<T, OutT, A2, CONV, CF> and return its result
+#define WS_LAUNCH(A2, CONV, CF, GRID, ...) return launch<gemm_ws_kernel<T, OutT, A2, CONV, CF>>(dim3(GRID), dim3(512), lds, st, __VA_ARGS__);
 // the flag sets that get a specialised epilogue (bf16 -> bf16 only; everything else runs the generic one)
 // (round 4: also the split-fp32 kernels -- their fp32-out tiles ran the generic epilogue, ~50 VALU + 6 branches per 4-channel group)
 template <typename T, typename OutT> constexpr bool kSpecialise = (sizeof(T) == 2 && sizeof(OutT) == 2) || (kSplit<T> && sizeof(OutT) == 4);
@@ -1190,19 +1180,15 @@ static int try_tall(const void* X, const void* W, const float* bias, const void*
             if (per < 1) per = 1;
             const unsigned grid = (unsigned)((nM + per - 1) / per);
             const size_t lds = 2 * TallCfg<64>::STAGE;
+            done = true;
 #define TALL_LAUNCH(CF)                                                                            \
-            {                                                                                      \
-                static DevOnce once;                                                               \
-                if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_ws_tall_kernel<T, OutT, CONV, CF, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipGetLastError(); } \
-                hipLaunchKernelGGL((gemm_ws_tall_kernel<T, OutT, CONV, CF, 64>), dim3(grid), dim3(512), lds, st, (const T*)X, (const T*)W, bias, \
-                                   (const OutT*)residual, (OutT*)C, M, N, K, flags, nM, per, cp, rr); \
-            }
+            return launch<gemm_ws_tall_kernel<T, OutT, CONV, CF, 64>>(dim3(grid), dim3(512), lds, st, (const T*)X, (const T*)W, bias, \
+                                                                      (const OutT*)residual, (OutT*)C, M, N, K, flags, nM, per, cp, rr);
             if (flags == (EPI_BIAS | EPI_RELU_POST)) TALL_LAUNCH((EPI_BIAS | EPI_RELU_POST))
             else if (flags == EPI_BIAS) TALL_LAUNCH(EPI_BIAS)
             else if constexpr (!kSplit<T>) TALL_LAUNCH(-1)
 #undef TALL_LAUNCH
-            done = true;
-            return check_launch();
+            return DTLR_OK;                                      // split operands: not reached, their two flag sets were checked above
             }
         }
         if constexpr (kSplit<T>) return DTLR_OK;
@@ -1218,21 +1204,16 @@ static int try_tall(const void* X, const void* W, const float* bias, const void*
             if (per < 1) per = 1;
             const unsigned gx = (unsigned)((nM + per - 1) / per);
             const size_t lds = 2 * TallCfg<128>::STAGE;
+            done = true;
 #define TALL_LAUNCH(CF)                                                                            \
-            {                                                                                      \
-                static DevOnce once;                                                               \
-                if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_ws_tall_kernel<T, OutT, CONV, CF, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); (void)hipGetLastError(); } \
-                hipLaunchKernelGGL((gemm_ws_tall_kernel<T, OutT, CONV, CF, 128>), dim3(gx, nN), dim3(TallCfg<128>::NT), lds, st, (const T*)X, (const T*)W, bias, \
-                                   (const OutT*)residual, (OutT*)C, M, N, K, flags, nM, per, cp, rr); \
-            }
+            return launch<gemm_ws_tall_kernel<T, OutT, CONV, CF, 128>>(dim3(gx, nN), dim3(TallCfg<128>::NT), lds, st, (const T*)X, (const T*)W, bias, \
+                                                                       (const OutT*)residual, (OutT*)C, M, N, K, flags, nM, per, cp, rr);
             if (flags == (EPI_BIAS | EPI_RELU_POST)) TALL_LAUNCH((EPI_BIAS | EPI_RELU_POST))
             else if (flags == (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL)) TALL_LAUNCH((EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL))
             else if (flags == EPI_BIAS) TALL_LAUNCH(EPI_BIAS)
             else if (flags == (EPI_BIAS | EPI_RELU)) TALL_LAUNCH((EPI_BIAS | EPI_RELU))
             else TALL_LAUNCH(-1)
 #undef TALL_LAUNCH
-            done = true;
-            return check_launch();
         }
         }
     }
@@ -1251,35 +1232,29 @@ static int launch_conv(const void* X, const void* W, const float* bias, const vo
     const long nwg = (long)nM * nN;
     if (nwg > 0x7fffffffL) return DTLR_ESHAPE;
     const size_t lds = 4 * TILE_BYTES;
-    if constexpr (!kSplit<T>) {
-        static DevOnce attr;
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, OutT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
-    }
-    if (use_ws()) {
-        bool done = false;
-        const int rc = try_splitk<T, OutT, true>(X, W, bias, residual, nullptr, C, M, N, K, flags, cp, st, done);
-        if (rc != DTLR_OK || done) return rc;
-        const int per = plan_chain_ws(nwg);
-        const unsigned grid = (unsigned)(nN * ((nM + per - 1) / per));
-#define CONV_ARGS (const T*)X, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, (const uint8_t*)nullptr, (OutT*)C, M, N, K, flags, nN, nM, per, cp, 1
-        if constexpr (kSpecialise<T, OutT>) {
-            if (flags == (EPI_BIAS | EPI_RELU_POST)) { WS_LAUNCH(false, true, (EPI_BIAS | EPI_RELU_POST), grid, CONV_ARGS) return check_launch(); }
-            if (flags == (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL)) { WS_LAUNCH(false, true, (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL), grid, CONV_ARGS) return check_launch(); }
-            if (flags == EPI_BIAS) { WS_LAUNCH(false, true, EPI_BIAS, grid, CONV_ARGS) return check_launch(); }
+    if (!use_ws()) {
+        if constexpr (kSplit<T>) return DTLR_ESHAPE;             // split operands: the wave-specialised kernel only
+        else {
+            const int per = plan_chain(nwg);
+            const unsigned grid = (unsigned)(nN * ((nM + per - 1) / per));
+            return launch<gemm_nt_kernel<T, OutT, false, true>>(dim3(grid), dim3(256), lds, st,
+                                                                (const T*)X, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, (const uint8_t*)nullptr, (OutT*)C,
+                                                                M, N, K, flags, nN, nM, per, cp);
         }
-        WS_LAUNCH(false, true, -1, grid, CONV_ARGS)
-#undef CONV_ARGS
-        return check_launch();
     }
-    if constexpr (kSplit<T>) return DTLR_ESHAPE;                 // split operands: the wave-specialised kernel only
-    else {
-    const int per = plan_chain(nwg);
+    bool done = false;
+    const int rc = try_splitk<T, OutT, true>(X, W, bias, residual, nullptr, C, M, N, K, flags, cp, st, done);
+    if (rc != DTLR_OK || done) return rc;
+    const int per = plan_chain_ws(nwg);
     const unsigned grid = (unsigned)(nN * ((nM + per - 1) / per));
-    hipLaunchKernelGGL((gemm_nt_kernel<T, OutT, false, true>), dim3(grid), dim3(256), lds, st,
-                       (const T*)X, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, (const uint8_t*)nullptr, (OutT*)C,
-                       M, N, K, flags, nN, nM, per, cp);
-    return check_launch();
+#define CONV_ARGS (const T*)X, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, (const uint8_t*)nullptr, (OutT*)C, M, N, K, flags, nN, nM, per, cp, 1
+    if constexpr (kSpecialise<T, OutT>) {
+        if (flags == (EPI_BIAS | EPI_RELU_POST)) WS_LAUNCH(false, true, (EPI_BIAS | EPI_RELU_POST), grid, CONV_ARGS)
+        if (flags == (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL)) WS_LAUNCH(false, true, (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL), grid, CONV_ARGS)
+        if (flags == EPI_BIAS) WS_LAUNCH(false, true, EPI_BIAS, grid, CONV_ARGS)
     }
+    WS_LAUNCH(false, true, -1, grid, CONV_ARGS)
+#undef CONV_ARGS
 }
 
 template <typename T, typename OutT>
@@ -1311,40 +1286,32 @@ static int launch_gemm(const void* A, const void* A2, const void* W, const float
 #define GEMM_ARGS(A2P) (const T*)A, (const T*)(A2P), (const T*)W, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, K, flags, nN, nM, perw, cp, 1
         if (A2) {
             if constexpr (kSpecialise<T, OutT>) {
-                if (flags == EPI_BIAS) { WS_LAUNCH(true, false, EPI_BIAS, gridw, GEMM_ARGS(A2)) return check_launch(); }
+                if (flags == EPI_BIAS) WS_LAUNCH(true, false, EPI_BIAS, gridw, GEMM_ARGS(A2))
             }
             WS_LAUNCH(true, false, -1, gridw, GEMM_ARGS(A2))
         } else {
             if constexpr (kSpecialise<T, OutT>) {
-                if (flags == EPI_BIAS) { WS_LAUNCH(false, false, EPI_BIAS, gridw, GEMM_ARGS(nullptr)) return check_launch(); }
-                if (flags == (EPI_BIAS | EPI_RELU)) { WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU), gridw, GEMM_ARGS(nullptr)) return check_launch(); }
-                if (flags == (EPI_BIAS | EPI_RELU_POST)) { WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU_POST), gridw, GEMM_ARGS(nullptr)) return check_launch(); }
-                if (flags == (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL)) { WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL), gridw, GEMM_ARGS(nullptr)) return check_launch(); }
+                if (flags == EPI_BIAS) WS_LAUNCH(false, false, EPI_BIAS, gridw, GEMM_ARGS(nullptr))
+                if (flags == (EPI_BIAS | EPI_RELU)) WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU), gridw, GEMM_ARGS(nullptr))
+                if (flags == (EPI_BIAS | EPI_RELU_POST)) WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU_POST), gridw, GEMM_ARGS(nullptr))
+                if (flags == (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL)) WS_LAUNCH(false, false, (EPI_BIAS | EPI_RELU_POST | EPI_RESIDUAL), gridw, GEMM_ARGS(nullptr))
                 if constexpr (kSplit<T>) {
-                    if (flags == EPI_RESIDUAL) { WS_LAUNCH(false, false, EPI_RESIDUAL, gridw, GEMM_ARGS(nullptr)) return check_launch(); }
+                    if (flags == EPI_RESIDUAL) WS_LAUNCH(false, false, EPI_RESIDUAL, gridw, GEMM_ARGS(nullptr))
                 }
             }
             WS_LAUNCH(false, false, -1, gridw, GEMM_ARGS(nullptr))
         }
 #undef GEMM_ARGS
-        return check_launch();
     }
     if constexpr (kSplit<T>) return DTLR_ESHAPE;
     else {
     const int per = plan_chain(nwg);
     const unsigned grid = (unsigned)(nN * ((nM + per - 1) / per));
-    if (A2) {
-        static DevOnce attr_a2;
-        if (attr_a2.first()) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, OutT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
-        hipLaunchKernelGGL((gemm_nt_kernel<T, OutT, true, false>), dim3(grid), dim3(256), lds, st,
-                           (const T*)A, (const T*)A2, (const T*)W, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, K, flags, nN, nM, per, cp);
-    } else {
-        static DevOnce attr;
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, OutT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
-        hipLaunchKernelGGL((gemm_nt_kernel<T, OutT, false, false>), dim3(grid), dim3(256), lds, st,
-                           (const T*)A, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, K, flags, nN, nM, per, cp);
-    }
-    return check_launch();
+    if (A2)
+        return launch<gemm_nt_kernel<T, OutT, true, false>>(dim3(grid), dim3(256), lds, st,
+                                                            (const T*)A, (const T*)A2, (const T*)W, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, K, flags, nN, nM, per, cp);
+    return launch<gemm_nt_kernel<T, OutT, false, false>>(dim3(grid), dim3(256), lds, st,
+                                                         (const T*)A, (const T*)nullptr, (const T*)W, bias, (const OutT*)residual, row_mask, (OutT*)C, M, N, K, flags, nN, nM, per, cp);
     }
 }
 
@@ -1424,8 +1391,7 @@ extern "C" int dtlr_split_pack_weights(const float* w, void* out, long rows, int
     if (!w || !out || rows <= 0 || K <= 0) return DTLR_EINVAL;
     if (K % 32) return DTLR_ESHAPE;
     const long n4 = rows * (K / 4);
-    hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (unsigned char*)out, n4, K);
-    return check_launch();
+    return launch<split_pack_kernel>(dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, (unsigned char*)out, n4, K);
 }
 
 // dtlr_gemm_nt with a row-BROADCAST A2: A2 has a2_rows rows and row m of A is paired with row m % a2_rows (the encoder's
@@ -1499,8 +1465,7 @@ extern "C" int dtlr_gemm_nt_rowmax_lda(const void* A, int lda, const void* W, co
     if (M <= 0 || N <= 0 || K <= 0 || lda < K) return DTLR_EINVAL;
     if ((lda * (in_dtype == DTLR_F32 || in_dtype == DTLR_F32S ? 4 : 2)) & 15) return DTLR_ESHAPE;          // rows must stay 16-byte aligned
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(fill_u32_kernel, dim3((unsigned)(((long)M + 1023) / 1024)), dim3(256), 0, st, reinterpret_cast<uint32_t*>(rowmax), 0xff800000u, (long)M);
-    { const int rc_ = check_launch(); if (rc_ != DTLR_OK) return rc_; }
+    if (int rc = launch<fill_u32_kernel>(dim3((unsigned)(((long)M + 1023) / 1024)), dim3(256), 0, st, reinterpret_cast<uint32_t*>(rowmax), 0xff800000u, (long)M)) return rc;
     const int flags = (bias ? EPI_BIAS : 0) | EPI_ROWMAX;
     if (in_dtype == DTLR_H16) {
         if (K % 64) return DTLR_ESHAPE;

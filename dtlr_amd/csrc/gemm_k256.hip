@@ -408,11 +408,8 @@ extern "C" int dtlr_proj_ln_k256(const void* A, const void* Wp, const float* bia
     const int grid = ntiles < ncu ? ntiles : ncu;
     const int per = (ntiles + grid - 1) / grid;
     const int g2 = (ntiles + per - 1) / per;
-    static DevOnce once;
-    if (once.first()) { (void)hipFuncSetAttribute((const void*)proj_ln_k256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PK_LDS); (void)hipGetLastError(); }
-    hipLaunchKernelGGL(proj_ln_k256_kernel, dim3(g2), dim3(512), PK_LDS, (hipStream_t)stream, (const uint16_t*)A, (const uint16_t*)Wp, bias,
-                       (const uint16_t*)R, gamma, beta, eps, (uint16_t*)Y, M, per);
-    return check_launch();
+    return launch<proj_ln_k256_kernel>(dim3(g2), dim3(512), PK_LDS, (hipStream_t)stream, (const uint16_t*)A, (const uint16_t*)Wp, bias,
+                                       (const uint16_t*)R, gamma, beta, eps, (uint16_t*)Y, M, per);
 }
 
 // W [N, 256] row-major bf16 (host memory) -> fragment order (host memory, N * 256 elements).
@@ -456,13 +453,10 @@ extern "C" int dtlr_gemm_k256(const void* A, const void* Wp, const float* bias, 
     const int n_img = (pos_major && resid && res_rows % K2_TOK == 0 && M % res_rows == 0 && M / res_rows > 1) ? M / res_rows : 0;
 #define K2_LAUNCH(NRT, RES)                                                                        \
     {                                                                                              \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_k256_kernel<NRT, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, K2_LDS); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((gemm_k256_kernel<NRT, RES>), dim3(g2), dim3(512), K2_LDS, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
-                           (const uint16_t*)resid, res_rows, row_mask, (uint16_t*)C, ldc, M, per, n_img);  \
+        return launch<gemm_k256_kernel<NRT, RES>>(dim3(g2), dim3(512), K2_LDS, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
+                                                  (const uint16_t*)resid, res_rows, row_mask, (uint16_t*)C, ldc, M, per, n_img);  \
     }
     if (N == 256) { if (resid) K2_LAUNCH(2, true) else K2_LAUNCH(2, false) }
     else { if (resid) K2_LAUNCH(3, true) else K2_LAUNCH(3, false) }
 #undef K2_LAUNCH
-    return check_launch();
 }

@@ -516,8 +516,7 @@ extern "C" int dtlr_k256s_pack_weights(const float* w, void* out, void* stream)
 {
     clear_stale_error();
     if (!w || !out) return DTLR_EINVAL;
-    hipLaunchKernelGGL(k256s_pack_kernel, dim3(32), dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)out);
-    return check_launch();
+    return launch<k256s_pack_kernel>(dim3(32), dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)out);
 }
 
 // One pass over A [M, 256] fp32 for `nslices` (1..8) output slices (the kernel's notes; dtlr_hip.h documents the structure).
@@ -545,16 +544,8 @@ extern "C" int dtlr_gemm_k256s_multi(const float* A, long M, const dtlr_k256s_sl
     gx = (ntiles + per - 1) / per;
     const int n_img = res_rows > 0 ? (int)(M / res_rows) : 0;
     hipStream_t st = (hipStream_t)stream;
-    if (row_mask) {
-        static DevOnce once;
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_k256s_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS); (void)hipGetLastError(); }
-        hipLaunchKernelGGL((gemm_k256s_multi_kernel<true>), dim3(gx, nslices), dim3(512), KP_LDS, st, A, P, (int)M, per, res_rows, n_img);
-    } else {
-        static DevOnce once;
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_k256s_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, KP_LDS); (void)hipGetLastError(); }
-        hipLaunchKernelGGL((gemm_k256s_multi_kernel<false>), dim3(gx, nslices), dim3(512), KP_LDS, st, A, P, (int)M, per, res_rows, n_img);
-    }
-    return check_launch();
+    if (row_mask) return launch<gemm_k256s_multi_kernel<true>>(dim3(gx, nslices), dim3(512), KP_LDS, st, A, P, (int)M, per, res_rows, n_img);
+    return launch<gemm_k256s_multi_kernel<false>>(dim3(gx, nslices), dim3(512), KP_LDS, st, A, P, (int)M, per, res_rows, n_img);
 }
 
 // A, C (and R) [M, 256] fp32; Wp = dtlr_k256s_pack_weights(W [256, 256]) (256 KB); bias [256] fp32 or NULL.
@@ -576,9 +567,7 @@ extern "C" int dtlr_gemm_k256s(const float* A, const void* Wp, const float* bias
     hipStream_t st = (hipStream_t)stream;
 #define KS_LAUNCH(MODE, HASM, RES, MASK)                                                                                                       \
     {                                                                                                                                       \
-        static DevOnce once;                                                                                                                \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_k256s_kernel<MODE, HASM>, hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((gemm_k256s_kernel<MODE, HASM>), dim3(nwg), dim3(512), KS_LDS, st, A, (const uint16_t*)Wp, bias, RES, MASK, gamma, beta, eps, C, (int)M, per); \
+        return launch<gemm_k256s_kernel<MODE, HASM>>(dim3(nwg), dim3(512), KS_LDS, st, A, (const uint16_t*)Wp, bias, RES, MASK, gamma, beta, eps, C, (int)M, per); \
     }
     if (R) KS_LAUNCH(1, false, R, (const uint8_t*)nullptr)
     else if (gamma && row_mask) KS_LAUNCH(2, true, (const float*)nullptr, row_mask)
@@ -586,5 +575,4 @@ extern "C" int dtlr_gemm_k256s(const float* A, const void* Wp, const float* bias
     else if (row_mask) KS_LAUNCH(0, true, (const float*)nullptr, row_mask)
     else KS_LAUNCH(0, false, (const float*)nullptr, row_mask)
 #undef KS_LAUNCH
-    return check_launch();
 }

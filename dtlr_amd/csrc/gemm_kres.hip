@@ -303,10 +303,9 @@ static int kres_launch(const void* A, const void* Wp, const float* bias, const v
 #define KR_LAUNCH(KB_, NP_, NS_, NBR_)                                                             \
     {                                                                                              \
         constexpr int lds_ = NS_ * (KR_TOK * 64 * KB_ * 2 + KR_TOK * NBR_ * 128);                  \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_kres_kernel<KB_, NP_, NS_, NBR_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((gemm_kres_kernel<KB_, NP_, NS_, NBR_>), dim3(gx, nslice), dim3(512), lds_, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
-                           (const uint16_t*)R, (uint16_t*)C, ld, M, per_x, relu, n_valid, res_rows, n_img); \
+        return launch<gemm_kres_kernel<KB_, NP_, NS_, NBR_>>(dim3(gx, nslice), dim3(512), lds_, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
+                                                             (const uint16_t*)R, (uint16_t*)C, ld, M, per_x, relu, n_valid, res_rows, n_img, \
+                                                             (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const float*)nullptr, (uint16_t*)nullptr, KrS2{0, 0, 0, 0}); \
     }
     if (res_rows > 0) KR_LAUNCH(4, 2, 2, 6)                                 // K = 256, 384 channels as a zero-padded 512 column
     else if (K == 64) {
@@ -319,7 +318,6 @@ static int kres_launch(const void* A, const void* Wp, const float* bias, const v
         if (R) KR_LAUNCH(4, 1, 2, 4) else KR_LAUNCH(4, 1, 4, 0)
     }
 #undef KR_LAUNCH
-    return check_launch();
 }
 
 // A [M, K] bf16 (K = 64 / 128 / 256), Wp from dtlr_gemm_kres_pack_weights, bias [N] fp32 or null, R [M, N] bf16 or null (row stride N),
@@ -356,16 +354,14 @@ extern "C" int dtlr_gemm_kres_chain(const void* A, const void* A2, const void* W
 #define KR_CHAIN(KB_, NS_, NBR_, KB1_, NQ2_)                                                       \
     {                                                                                              \
         constexpr int lds_ = NS_ * (KR_TOK * 64 * KB_ * 2 + KR_TOK * NBR_ * 128) + (NQ2_ > 0 ? KR_TOK * 512 : 0); \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_kres_kernel<KB_, 1, NS_, NBR_, KB1_, NQ2_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((gemm_kres_kernel<KB_, 1, NS_, NBR_, KB1_, NQ2_>), dim3(gx, 1), dim3(512), lds_, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
-                           (const uint16_t*)R, (uint16_t*)C, 256, M, per_x, relu, 256, 0, 0, (const uint16_t*)A2, (const uint16_t*)Wp2, bias2, (uint16_t*)C2); \
+        return launch<gemm_kres_kernel<KB_, 1, NS_, NBR_, KB1_, NQ2_>>(dim3(gx, 1), dim3(512), lds_, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
+                                                                       (const uint16_t*)R, (uint16_t*)C, 256, M, per_x, relu, 256, 0, 0, (const uint16_t*)A2, (const uint16_t*)Wp2, bias2, (uint16_t*)C2, \
+                                                                       KrS2{0, 0, 0, 0}); \
     }
     if (A2) { if (Wp2) KR_CHAIN(2, 4, 0, 1, 1) else KR_CHAIN(2, 4, 0, 1, 0) }
     else if (N2 == 64) KR_CHAIN(1, 3, 4, 0, 1)
     else KR_CHAIN(1, 3, 4, 0, 2)
 #undef KR_CHAIN
-    return check_launch();
 }
 
 // layer2's first bottleneck tail with its STRIDED shortcut convolution as extra K columns (the kernel's KB1 / s2 notes):
@@ -386,12 +382,9 @@ extern "C" int dtlr_gemm_kres_cat_s2(const void* A, const void* X, const void* W
     if (per_x < 1) per_x = 1;
     const int gx = (ntiles + per_x - 1) / per_x;
     constexpr int lds_ = 3 * (KR_TOK * 64 * 6 * 2);
-    static DevOnce once;
-    if (once.first()) { (void)hipFuncSetAttribute((const void*)gemm_kres_kernel<6, 1, 3, 0, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); }
-    hipLaunchKernelGGL((gemm_kres_kernel<6, 1, 3, 0, 2, 0>), dim3(gx, nslice), dim3(512), lds_, (hipStream_t)stream, (const uint16_t*)A, (const uint16_t*)Wp, bias,
-                       (const uint16_t*)nullptr, (uint16_t*)C, 512, M, per_x, relu, 512, 0, 0, (const uint16_t*)X, (const uint16_t*)nullptr, (const float*)nullptr,
-                       (uint16_t*)nullptr, KrS2{Hout, Wout, Hin, Win});
-    return check_launch();
+    return launch<gemm_kres_kernel<6, 1, 3, 0, 2, 0>>(dim3(gx, nslice), dim3(512), lds_, (hipStream_t)stream, (const uint16_t*)A, (const uint16_t*)Wp, bias,
+                                                      (const uint16_t*)nullptr, (uint16_t*)C, 512, M, per_x, relu, 512, 0, 0, (const uint16_t*)X, (const uint16_t*)nullptr, (const float*)nullptr,
+                                                      (uint16_t*)nullptr, KrS2{Hout, Wout, Hin, Win});
 }
 
 // The encoder's [offsets | attention logits] projection with the position term as a row-broadcast residual:

@@ -226,14 +226,12 @@ static int geometry_launch(const unsigned char* mask, const int* ext, int s0, in
     if (B > 65535) return DTLR_ESHAPE;
     const dim3 grid(rows, B);
     if (pos_dtype == DTLR_H16)
-        hipLaunchKernelGGL((geometry_kernel<uint16_t, EXT>), grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
-                           mask_flat, keep, (uint16_t*)pos, valid_ratios, enc_ref, proposals, ext, s0);
-    else if (pos_dtype == DTLR_F32)
-        hipLaunchKernelGGL((geometry_kernel<float, EXT>), grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
-                           mask_flat, keep, (float*)pos, valid_ratios, enc_ref, proposals, ext, s0);
-    else
-        return DTLR_EDTYPE;
-    return check_launch();
+        return launch<geometry_kernel<uint16_t, EXT>>(grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
+                                                      mask_flat, keep, (uint16_t*)pos, valid_ratios, enc_ref, proposals, ext, s0);
+    if (pos_dtype == DTLR_F32)
+        return launch<geometry_kernel<float, EXT>>(grid, dim3(256), 0, (hipStream_t)stream, mask, H, W, lv, S, level_embed, dim_ty, dim_tx,
+                                                   mask_flat, keep, (float*)pos, valid_ratios, enc_ref, proposals, ext, s0);
+    return DTLR_EDTYPE;
 }
 
 extern "C" int dtlr_geometry(const unsigned char* mask, int B, int H, int W, const int* level_hw,

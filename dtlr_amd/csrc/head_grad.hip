@@ -181,11 +181,10 @@ extern "C" int dtlr_head_grad(const float* G, const float* X, float* dW, float* 
     const long nW = (long)C * D;
     float* part = workspace;
     double* partb = reinterpret_cast<double*>(workspace + (long)p.splits * nW);      // 8-byte aligned: D % 64 == 0
-    hipLaunchKernelGGL(head_grad_partial_kernel, dim3((unsigned)(p.tiles_c * p.tiles_d), (unsigned)p.splits), dim3(256), 0, (hipStream_t)stream,
-                       G, X, part, partb, M, C, D, p.tiles_d, p.chunk);
-    hipLaunchKernelGGL(head_grad_reduce_kernel, dim3((unsigned)((nW + C + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       part, partb, dW, db, nW, C, p.splits);
-    return check_launch();
+    if (int rc = launch<head_grad_partial_kernel>(dim3((unsigned)(p.tiles_c * p.tiles_d), (unsigned)p.splits), dim3(256), 0, (hipStream_t)stream,
+                                                  G, X, part, partb, M, C, D, p.tiles_d, p.chunk)) return rc;
+    return launch<head_grad_reduce_kernel>(dim3((unsigned)((nW + C + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                           part, partb, dW, db, nW, C, p.splits);
 }
 
 extern "C" long dtlr_grad_norm_scale_workspace_bytes(void) { return (long)GN_BLOCKS * 8; }
@@ -197,9 +196,8 @@ extern "C" int dtlr_grad_norm_scale(const float* grad, long n, float max_norm, f
     if (reinterpret_cast<uintptr_t>(workspace) & 7) return DTLR_EINVAL;
     long nb = (n + 255) / 256;
     if (nb > GN_BLOCKS) nb = GN_BLOCKS;
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, grad, n, (double*)workspace);
-    hipLaunchKernelGGL(norm_scale_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, max_norm, scale_out);
-    return check_launch();
+    if (int rc = launch<sumsq_partial_kernel>(dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, grad, n, (double*)workspace)) return rc;
+    return launch<norm_scale_kernel>(dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, (int)nb, max_norm, scale_out);
 }
 
 extern "C" int dtlr_adamw_step(float* param, float* exp_avg, float* exp_avg_sq, const float* grad, const float* grad_scale, long n,
@@ -209,7 +207,6 @@ extern "C" int dtlr_adamw_step(float* param, float* exp_avg, float* exp_avg_sq, 
     if (!param || !exp_avg || !exp_avg_sq || !grad || n <= 0 || step <= 0) return DTLR_EINVAL;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, exp_avg, exp_avg_sq, grad,
-                       grad_scale, n, decay, beta1, beta2, eps, (float)((double)lr / bc1), (float)sqrt(bc2));
-    return check_launch();
+    return launch<adamw_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, exp_avg, exp_avg_sq, grad,
+                                grad_scale, n, decay, beta1, beta2, eps, (float)((double)lr / bc1), (float)sqrt(bc2));
 }

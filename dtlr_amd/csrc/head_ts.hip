@@ -188,15 +188,12 @@ extern "C" int dtlr_head_ts(const void* X, int ldx, int a_off, int b_off, const 
     const bool small = (M + HT_TOK - 1) / HT_TOK < 192;
 #define HT_LAUNCH(MODE_, NP_, NW_)                                                                 \
     {                                                                                              \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)head_ts_kernel<MODE_, NP_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((head_ts_kernel<MODE_, NP_, NW_>), dim3((unsigned)((M + 32 * NW_ - 1) / (32 * NW_))), dim3(64 * NW_), lds, st,         \
-                           (const uint16_t*)X, ldx, a_off, b_off, (const unsigned char*)Wp, bias, (float*)out, (int)M, N, nchunk); \
+        return launch<head_ts_kernel<MODE_, NP_, NW_>>(dim3((unsigned)((M + 32 * NW_ - 1) / (32 * NW_))), dim3(64 * NW_), lds, st,         \
+                                                       (const uint16_t*)X, ldx, a_off, b_off, (const unsigned char*)Wp, bias, (float*)out, (int)M, N, nchunk); \
     }
 #define HT_PICK(MODE_, NP_) { if (small) HT_LAUNCH(MODE_, NP_, 4) else HT_LAUNCH(MODE_, NP_, 8) }
     if (mode == 0) { if (nprod == 3) HT_PICK(0, 3) else HT_PICK(0, 2) }
     else { if (nprod == 3) HT_PICK(1, 3) else HT_PICK(1, 2) }
 #undef HT_PICK
 #undef HT_LAUNCH
-    return check_launch();
 }

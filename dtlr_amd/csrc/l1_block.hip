@@ -275,17 +275,14 @@ extern "C" int dtlr_l1_bottleneck(const void* X, int cin, const void* W1p, const
 #define LB_LAUNCH(CATF_, NQ2_)                                                                     \
     {                                                                                              \
         constexpr int lds_ = LB_NSX * 9 * (CATF_ ? 1 : 4) * 1024 + 3 * LB_T1 + LB_T2 + 512 * 4;    \
-        static DevOnce once;                                                                       \
-        if (once.first()) { (void)hipFuncSetAttribute((const void*)l1_bottleneck_kernel<CATF_, NQ2_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_); (void)hipGetLastError(); } \
-        hipLaunchKernelGGL((l1_bottleneck_kernel<CATF_, NQ2_>), dim3(grid), dim3(512), lds_, st, (const uint16_t*)X, (const uint16_t*)W1p, b1, \
-                           (const uint16_t*)W2, b2, (const uint16_t*)W3p, b3, (uint16_t*)OUT, (const uint16_t*)Wnp, bn, (uint16_t*)NEXT, H, W, nseg); \
+        return launch<l1_bottleneck_kernel<CATF_, NQ2_>>(dim3(grid), dim3(512), lds_, st, (const uint16_t*)X, (const uint16_t*)W1p, b1, \
+                                                         (const uint16_t*)W2, b2, (const uint16_t*)W3p, b3, (uint16_t*)OUT, (const uint16_t*)Wnp, bn, (uint16_t*)NEXT, H, W, nseg); \
     }
     if (cin == 64) LB_LAUNCH(true, 0)
     else if (n2 == 0) LB_LAUNCH(false, 0)
     else if (n2 == 64) LB_LAUNCH(false, 1)
     else LB_LAUNCH(false, 2)
 #undef LB_LAUNCH
-    return check_launch();
 }
 
 }  // namespace dtlr

@@ -149,13 +149,13 @@ extern "C" int dtlr_two_stage_gather(const void* om, const float* proposals, con
     const unsigned grid = (unsigned)((rows + 3) / 4);
     if (dtype == DTLR_H16) {
         if (!sel_x) return DTLR_EINVAL;
-        hipLaunchKernelGGL(two_stage_gather_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, om, proposals, idx, sel_raw,
-                           (uint16_t*)sel_x, prop_sel, init_box, S, k, rows);
-    } else if (dtype == DTLR_F32) {
-        hipLaunchKernelGGL(two_stage_gather_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, om, proposals, idx, sel_raw,
-                           (uint16_t*)nullptr, prop_sel, init_box, S, k, rows);
-    } else return DTLR_EDTYPE;
-    return check_launch();
+        return launch<two_stage_gather_kernel<true>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, om, proposals, idx, sel_raw,
+                                                     (uint16_t*)sel_x, prop_sel, init_box, S, k, rows);
+    }
+    if (dtype == DTLR_F32)
+        return launch<two_stage_gather_kernel<false>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, om, proposals, idx, sel_raw,
+                                                      (uint16_t*)nullptr, prop_sel, init_box, S, k, rows);
+    return DTLR_EDTYPE;
 }
 
 extern "C" int dtlr_box_head_refine(const float* h, const float* W, const float* bias, const float* ref, float* out,
@@ -165,8 +165,7 @@ extern "C" int dtlr_box_head_refine(const float* h, const float* W, const float*
     if (!h || !W || !bias || !ref || !out) return DTLR_EINVAL;
     if (rows <= 0 || (mode != 0 && mode != 1)) return DTLR_EINVAL;
     if (hidden != 256) return DTLR_ESHAPE;
-    hipLaunchKernelGGL(box_head_refine_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, h, W, bias, ref, out, rows, mode);
-    return check_launch();
+    return launch<box_head_refine_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, h, W, bias, ref, out, rows, mode);
 }
 
 template <bool UNSCALED_SINE>
@@ -180,11 +179,10 @@ static int query_prep_launch(const float* ref, const float* valid_ratios, const 
     const long grid = (total + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
     if (sine_dtype == DTLR_H16)
-        hipLaunchKernelGGL((query_prep_kernel<uint16_t, UNSCALED_SINE>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (uint16_t*)sine, nq, L, total);
-    else if (sine_dtype == DTLR_F32)
-        hipLaunchKernelGGL((query_prep_kernel<float, UNSCALED_SINE>), dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (float*)sine, nq, L, total);
-    else return DTLR_EDTYPE;
-    return check_launch();
+        return launch<query_prep_kernel<uint16_t, UNSCALED_SINE>>(dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (uint16_t*)sine, nq, L, total);
+    if (sine_dtype == DTLR_F32)
+        return launch<query_prep_kernel<float, UNSCALED_SINE>>(dim3((unsigned)grid), dim3(256), 0, st, ref, valid_ratios, dim_t, ref_in, (float*)sine, nq, L, total);
+    return DTLR_EDTYPE;
 }
 
 extern "C" int dtlr_decoder_query_prep(const float* ref, const float* valid_ratios, const float* dim_t,
@@ -204,6 +202,5 @@ extern "C" int dtlr_box_refine(const float* delta, const float* ref, float* out,
     clear_stale_error();
     if (!delta || !ref || !out) return DTLR_EINVAL;
     if (n <= 0) return DTLR_EINVAL;
-    hipLaunchKernelGGL(box_refine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, delta, ref, out, n);
-    return check_launch();
+    return launch<box_refine_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, delta, ref, out, n);
 }

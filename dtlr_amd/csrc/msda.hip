@@ -516,12 +516,10 @@ static int launch_fused_quad(const void* value, const int64_t* shapes, const int
     const long per_img = (long)Lq * M * 4;
     const int bpi = (per_img % block == 0 && N % 8 == 0) ? (int)(per_img / block) : 0;
     if (ref_dim == 2)
-        hipLaunchKernelGGL((msda_fused_quad_bf16_kernel<OT, 2>), dim3((unsigned)grid), dim3(block), 0, st,
-                           (const uint16_t*)value, shapes, lsi, (const OT*)ow, ref, S, M, Lq, (uint16_t*)out, total, bpi, N, vstride);
-    else
-        hipLaunchKernelGGL((msda_fused_quad_bf16_kernel<OT, 4>), dim3((unsigned)grid), dim3(block), 0, st,
-                           (const uint16_t*)value, shapes, lsi, (const OT*)ow, ref, S, M, Lq, (uint16_t*)out, total, bpi, N, vstride);
-    return check_launch();
+        return launch<msda_fused_quad_bf16_kernel<OT, 2>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                          (const uint16_t*)value, shapes, lsi, (const OT*)ow, ref, S, M, Lq, (uint16_t*)out, total, bpi, N, vstride);
+    return launch<msda_fused_quad_bf16_kernel<OT, 4>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                      (const uint16_t*)value, shapes, lsi, (const OT*)ow, ref, S, M, Lq, (uint16_t*)out, total, bpi, N, vstride);
 }
 
 template <typename T, typename OT, int VEC>
@@ -534,12 +532,10 @@ static int launch_fused(const void* value, const int64_t* shapes, const int64_t*
     const long per_img = (long)Lq * M * (D / VEC);
     const int bpi = (per_img % block == 0 && N % 8 == 0) ? (int)(per_img / block) : 0;
     if (ref_dim == 2)
-        hipLaunchKernelGGL((msda_fused_l4p4_kernel<T, OT, VEC, 2>), dim3((unsigned)grid), dim3(block), 0, st,
-                           (const T*)value, shapes, lsi, (const OT*)ow, ref, S, M, D, Lq, (T*)out, total, bpi, N, vstride);
-    else
-        hipLaunchKernelGGL((msda_fused_l4p4_kernel<T, OT, VEC, 4>), dim3((unsigned)grid), dim3(block), 0, st,
-                           (const T*)value, shapes, lsi, (const OT*)ow, ref, S, M, D, Lq, (T*)out, total, bpi, N, vstride);
-    return check_launch();
+        return launch<msda_fused_l4p4_kernel<T, OT, VEC, 2>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                             (const T*)value, shapes, lsi, (const OT*)ow, ref, S, M, D, Lq, (T*)out, total, bpi, N, vstride);
+    return launch<msda_fused_l4p4_kernel<T, OT, VEC, 4>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                         (const T*)value, shapes, lsi, (const OT*)ow, ref, S, M, D, Lq, (T*)out, total, bpi, N, vstride);
 }
 
 template <typename T, typename LT, typename A, int VEC>
@@ -549,9 +545,8 @@ static int launch_generic(const void* value, const int64_t* shapes, const int64_
     const int block = 256;
     const long grid = (total + block - 1) / block;
     if (grid > 0x7fffffffL) return DTLR_ESHAPE;
-    hipLaunchKernelGGL((msda_fwd_kernel<T, LT, A, VEC>), dim3((unsigned)grid), dim3(block), 0, st,
-                       (const T*)value, shapes, lsi, (const LT*)loc, (const LT*)attn, S, M, D, L, Lq, P, (T*)out, total);
-    return check_launch();
+    return launch<msda_fwd_kernel<T, LT, A, VEC>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                  (const T*)value, shapes, lsi, (const LT*)loc, (const LT*)attn, S, M, D, L, Lq, P, (T*)out, total);
 }
 
 template <typename T, int VEC>
@@ -563,9 +558,8 @@ static int launch_l4p4(const void* value, const int64_t* shapes, const int64_t* 
     if (grid > 0x7fffffffL) return DTLR_ESHAPE;
     const long per_img = (long)Lq * M * (D / VEC);
     const int bpi = (per_img % block == 0 && N % 8 == 0) ? (int)(per_img / block) : 0;
-    hipLaunchKernelGGL((msda_fwd_l4p4_kernel<T, VEC>), dim3((unsigned)grid), dim3(block), 0, st,
-                       (const T*)value, shapes, lsi, (const float*)loc, (const float*)attn, S, M, D, Lq, (T*)out, total, bpi, N);
-    return check_launch();
+    return launch<msda_fwd_l4p4_kernel<T, VEC>>(dim3((unsigned)grid), dim3(block), 0, st,
+                                                (const T*)value, shapes, lsi, (const float*)loc, (const float*)attn, S, M, D, Lq, (T*)out, total, bpi, N);
 }
 
 }  // namespace dtlr

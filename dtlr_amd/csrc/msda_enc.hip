@@ -1278,11 +1278,8 @@ static bool make_plan(const int* hw, int elem, int R, EncPlan& pl) {
 
 template <typename T, typename OT, int VAR = 0, int NT = 256>
 static int launch_enc(const void* value, const void* ow, const float* ref, void* out, const EncPlan& pl, int N, int M, hipStream_t st) {
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)msda_enc_lds_kernel<T, OT, VAR, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-    hipLaunchKernelGGL((msda_enc_lds_kernel<T, OT, VAR, NT>), dim3(pl.ntiles, M, N), dim3(NT), pl.lds, st,
-                       (const T*)value, (const OT*)ow, ref, (T*)out, pl.lv, pl.S, M, pl.TW0, pl.R, pl.tok_off);
-    return check_launch();
+    return launch<msda_enc_lds_kernel<T, OT, VAR, NT>>(dim3(pl.ntiles, M, N), dim3(NT), pl.lds, st,
+                                                       (const T*)value, (const OT*)ow, ref, (T*)out, pl.lv, pl.S, M, pl.TW0, pl.R, pl.tok_off);
 }
 // 16-bit query-phase form: 3 = the third form, 512 threads (the default since round 4: same-box A/B of the step 9.24 -> 9.12 ms, tests green on
 // hardware); experiment builds only (env DTLR_MSDA_ENC_V, read once per process): 0 first form (fp32 accumulators, v_fma_mix), 1 packed-fp16 form
@@ -1320,11 +1317,10 @@ extern "C" int dtlr_msda_encoder_far_samples(const void* ow, const float* ref, c
     if (!make_plan(level_hw, dtype == DTLR_F32 ? 4 : 2, halo, pl)) return DTLR_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     if (ow_dtype == DTLR_F32)
-        hipLaunchKernelGGL(msda_enc_far_count_kernel<float>, dim3(pl.ntiles, M, N), dim3(256), 0, st, (const float*)ow, ref, pl.lv, pl.S, M, pl.TW0, pl.R, counts);
-    else if (ow_dtype == DTLR_H16)
-        hipLaunchKernelGGL(msda_enc_far_count_kernel<uint16_t>, dim3(pl.ntiles, M, N), dim3(256), 0, st, (const uint16_t*)ow, ref, pl.lv, pl.S, M, pl.TW0, pl.R, counts);
-    else return DTLR_EDTYPE;
-    return check_launch();
+        return launch<msda_enc_far_count_kernel<float>>(dim3(pl.ntiles, M, N), dim3(256), 0, st, (const float*)ow, ref, pl.lv, pl.S, M, pl.TW0, pl.R, counts);
+    if (ow_dtype == DTLR_H16)
+        return launch<msda_enc_far_count_kernel<uint16_t>>(dim3(pl.ntiles, M, N), dim3(256), 0, st, (const uint16_t*)ow, ref, pl.lv, pl.S, M, pl.TW0, pl.R, counts);
+    return DTLR_EDTYPE;
 }
 
 extern "C" int dtlr_msda_encoder_forward(const void* value, const void* ow, const float* ref, const int* level_hw,

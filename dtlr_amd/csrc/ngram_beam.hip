@@ -370,11 +370,5 @@ extern "C" int dtlr_ngram_beam(const float* emissions, int B, int T, int V, cons
     A.Tmax = Tmax; A.Lmax = Lmax;                               // Tmax = 0: no span runs a frame, the arena is not touched
     A.labels = labels_out; A.lens = len_out; A.scores = score_out;
     A.arena = reinterpret_cast<int2*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-    static DevOnce once;
-    if (once.first() && hipFuncSetAttribute((const void*)ngram_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return DTLR_ELAUNCH;
-    }
-    hipLaunchKernelGGL(ngram_beam_kernel, dim3((unsigned)n), dim3(THREADS), lds, (hipStream_t)stream, A);
-    return check_launch();
+    return launch<ngram_beam_kernel>(dim3((unsigned)n), dim3(THREADS), lds, (hipStream_t)stream, A);
 }

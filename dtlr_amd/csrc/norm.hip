@@ -124,11 +124,10 @@ static int launch_ln(const void* x, const void* res, const float* gamma, const f
     const int block = 256, rpb = block / 64;
     const long grid = (rows + rpb - 1) / rpb;
     if (grid > 0x7fffffffL) return DTLR_ESHAPE;
-#define LN_CASE(CH) case CH: hipLaunchKernelGGL((layernorm_kernel<T, CH>), dim3((unsigned)grid), dim3(block), 0, st, \
-        (const T*)x, (const T*)res, gamma, beta, (T*)y, rows, eps); break;
+#define LN_CASE(CH) case CH: return launch<layernorm_kernel<T, CH>>(dim3((unsigned)grid), dim3(block), 0, st, \
+        (const T*)x, (const T*)res, gamma, beta, (T*)y, rows, eps);
     switch (C / 256) { LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(8) default: return DTLR_ESHAPE; }
 #undef LN_CASE
-    return check_launch();
 }
 
 }  // namespace dtlr
@@ -148,11 +147,10 @@ extern "C" int dtlr_layernorm(const void* x, const void* residual, const float* 
         const long grid = (rows + 3) / 4;
         if (grid > 0x7fffffffL) return DTLR_ESHAPE;
         if (dtype == DTLR_F32)
-            hipLaunchKernelGGL(layernorm_any_kernel<float>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)x, (const float*)residual, gamma, beta, (float*)y, rows, C, eps);
-        else if (dtype == DTLR_H16)
-            hipLaunchKernelGGL(layernorm_any_kernel<uint16_t>, dim3((unsigned)grid), dim3(256), 0, st, (const uint16_t*)x, (const uint16_t*)residual, gamma, beta, (uint16_t*)y, rows, C, eps);
-        else return DTLR_EDTYPE;
-        return check_launch();
+            return launch<layernorm_any_kernel<float>>(dim3((unsigned)grid), dim3(256), 0, st, (const float*)x, (const float*)residual, gamma, beta, (float*)y, rows, C, eps);
+        if (dtype == DTLR_H16)
+            return launch<layernorm_any_kernel<uint16_t>>(dim3((unsigned)grid), dim3(256), 0, st, (const uint16_t*)x, (const uint16_t*)residual, gamma, beta, (uint16_t*)y, rows, C, eps);
+        return DTLR_EDTYPE;
     }
     switch (dtype) {
     case DTLR_F32: return launch_ln<float>(x, residual, gamma, beta, y, rows, C, eps, st);
@@ -365,13 +363,12 @@ extern "C" int dtlr_groupnorm_tokens_strided(const void* x, const float* gamma, 
     const int rows_per_block = 32;
     const int nblk = (T_tokens + rows_per_block - 1) / rows_per_block;
     if (dtype == DTLR_F32) {
-        hipLaunchKernelGGL((gn_partial_kernel<float>), dim3(nslab, B), dim3(256), 0, st, (const float*)x, (float2*)workspace, T_tokens, rows_per_slab);
-        hipLaunchKernelGGL((gn_apply_kernel<float>), dim3(nblk, B), dim3(256), 0, st, (const float*)x, (const float2*)workspace, gamma, beta, (float*)y, T_tokens, nslab, rows_per_block, eps, ybs);
+        if (int rc = launch<gn_partial_kernel<float>>(dim3(nslab, B), dim3(256), 0, st, (const float*)x, (float2*)workspace, T_tokens, rows_per_slab, GnExt{nullptr, 0, 1})) return rc;
+        return launch<gn_apply_kernel<float>>(dim3(nblk, B), dim3(256), 0, st, (const float*)x, (const float2*)workspace, gamma, beta, (float*)y, T_tokens, nslab, rows_per_block, eps, ybs, GnExt{nullptr, 0, 1});
     } else if (dtype == DTLR_H16) {
-        hipLaunchKernelGGL((gn_partial_kernel<uint16_t>), dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab);
-        hipLaunchKernelGGL((gn_apply_kernel<uint16_t>), dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta, (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs);
+        if (int rc = launch<gn_partial_kernel<uint16_t>>(dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab, GnExt{nullptr, 0, 1})) return rc;
+        return launch<gn_apply_kernel<uint16_t>>(dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta, (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs, GnExt{nullptr, 0, 1});
     } else return DTLR_EDTYPE;
-    return check_launch();
 }
 
 extern "C" int dtlr_groupnorm_tokens_ext(const void* x, const float* gamma, const float* beta, void* y, long y_batch_stride,
@@ -392,15 +389,14 @@ extern "C" int dtlr_groupnorm_tokens_ext(const void* x, const float* gamma, cons
     const int nblk = (T_tokens + rows_per_block - 1) / rows_per_block;
     const GnExt ge{ext, s, Wl};
     if (dtype == DTLR_F32) {
-        hipLaunchKernelGGL((gn_partial_kernel<float, true>), dim3(nslab, B), dim3(256), 0, st, (const float*)x, (float2*)workspace, T_tokens, rows_per_slab, ge);
-        hipLaunchKernelGGL((gn_apply_kernel<float, true>), dim3(nblk, B), dim3(256), 0, st, (const float*)x, (const float2*)workspace, gamma, beta, (float*)y,
-                           T_tokens, nslab, rows_per_block, eps, ybs, ge);
+        if (int rc = launch<gn_partial_kernel<float, true>>(dim3(nslab, B), dim3(256), 0, st, (const float*)x, (float2*)workspace, T_tokens, rows_per_slab, ge)) return rc;
+        return launch<gn_apply_kernel<float, true>>(dim3(nblk, B), dim3(256), 0, st, (const float*)x, (const float2*)workspace, gamma, beta, (float*)y,
+                                                    T_tokens, nslab, rows_per_block, eps, ybs, ge);
     } else if (dtype == DTLR_H16) {
-        hipLaunchKernelGGL((gn_partial_kernel<uint16_t, true>), dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab, ge);
-        hipLaunchKernelGGL((gn_apply_kernel<uint16_t, true>), dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta,
-                           (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs, ge);
+        if (int rc = launch<gn_partial_kernel<uint16_t, true>>(dim3(nslab, B), dim3(256), 0, st, (const uint16_t*)x, (float2*)workspace, T_tokens, rows_per_slab, ge)) return rc;
+        return launch<gn_apply_kernel<uint16_t, true>>(dim3(nblk, B), dim3(256), 0, st, (const uint16_t*)x, (const float2*)workspace, gamma, beta,
+                                                       (uint16_t*)y, T_tokens, nslab, rows_per_block, eps, ybs, ge);
     } else return DTLR_EDTYPE;
-    return check_launch();
 }
 
 extern "C" int dtlr_maxpool3x3s2_nhwc_ext(const void* x, void* y, const float* bias, int relu, const int* ext, int s_in,
@@ -413,14 +409,13 @@ extern "C" int dtlr_maxpool3x3s2_nhwc_ext(const void* x, void* y, const float* b
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DTLR_H16 && C % 8 == 0) {
         const long total = (long)B * Ho * Wo * (C / 8);
-        hipLaunchKernelGGL((maxpool3x3s2_kernel<uint16_t, 8, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           (const uint16_t*)x, (uint16_t*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
+        return launch<maxpool3x3s2_kernel<uint16_t, 8, true>>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                                                              (const uint16_t*)x, (uint16_t*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
     } else if (dtype == DTLR_F32 && C % 4 == 0) {
         const long total = (long)B * Ho * Wo * (C / 4);
-        hipLaunchKernelGGL((maxpool3x3s2_kernel<float, 4, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           (const float*)x, (float*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
+        return launch<maxpool3x3s2_kernel<float, 4, true>>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                                                           (const float*)x, (float*)y, bias, relu, H, W, C, Ho, Wo, total, ext, s_in);
     } else return (dtype == DTLR_H16 || dtype == DTLR_F32) ? DTLR_ESHAPE : DTLR_EDTYPE;
-    return check_launch();
 }
 
 extern "C" int dtlr_maxpool3x3s2_nhwc(const void* x, void* y, const float* bias, int relu, int B, int H, int W, int C, int dtype, void* stream)
@@ -432,12 +427,11 @@ extern "C" int dtlr_maxpool3x3s2_nhwc(const void* x, void* y, const float* bias,
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DTLR_H16 && C % 8 == 0) {
         const long total = (long)B * Ho * Wo * (C / 8);
-        hipLaunchKernelGGL((maxpool3x3s2_kernel<uint16_t, 8>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           (const uint16_t*)x, (uint16_t*)y, bias, relu, H, W, C, Ho, Wo, total);
+        return launch<maxpool3x3s2_kernel<uint16_t, 8>>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                                                        (const uint16_t*)x, (uint16_t*)y, bias, relu, H, W, C, Ho, Wo, total, (const int*)nullptr, 0);
     } else if (dtype == DTLR_F32 && C % 4 == 0) {
         const long total = (long)B * Ho * Wo * (C / 4);
-        hipLaunchKernelGGL((maxpool3x3s2_kernel<float, 4>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           (const float*)x, (float*)y, bias, relu, H, W, C, Ho, Wo, total);
+        return launch<maxpool3x3s2_kernel<float, 4>>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                                                     (const float*)x, (float*)y, bias, relu, H, W, C, Ho, Wo, total, (const int*)nullptr, 0);
     } else return (dtype == DTLR_H16 || dtype == DTLR_F32) ? DTLR_ESHAPE : DTLR_EDTYPE;
-    return check_launch();
 }

@@ -118,6 +118,5 @@ extern "C" int dtlr_preprocess_lines(const unsigned char* src, const long* offse
     PPNorm n;
     for (int c = 0; c < 3; ++c) { n.mean[c] = mean3[c]; n.std[c] = std3[c]; }
     const dim3 grid((Wc + 255) / 256, Hc, B);
-    hipLaunchKernelGGL(preprocess_lines_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, offsets, dims, canvas, mask, Hc, Wc, n);
-    return check_launch();
+    return launch<preprocess_lines_kernel>(grid, dim3(256), 0, (hipStream_t)stream, src, offsets, dims, canvas, mask, Hc, Wc, n);
 }

@@ -483,12 +483,9 @@ extern "C" int dtlr_stem_conv7x7_f32(const float* x, const float* wk, float* y, 
     if (!x || !wk || !y) return DTLR_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0) return DTLR_EINVAL;
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)stem_conv7x7_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS); (void)hipGetLastError(); }
     const dim3 grid((Wo + SF_COLS - 1) / SF_COLS, (Ho + SF_ROWS - 1) / SF_ROWS, B);
     if (grid.y > 65535u || grid.z > 65535u) return DTLR_ESHAPE;
-    hipLaunchKernelGGL(stem_conv7x7_f32_kernel, grid, dim3(256), SF_LDS, (hipStream_t)stream, x, wk, y, H, W, Ho, Wo);
-    return check_launch();
+    return launch<stem_conv7x7_f32_kernel>(grid, dim3(256), SF_LDS, (hipStream_t)stream, x, wk, y, H, W, Ho, Wo);
 }
 
 extern "C" int dtlr_stem_conv7x7_f32s(const float* x, const void* wfrag_hi, const void* wfrag_lo, float* y, int B, int H, int W, void* stream)
@@ -497,13 +494,10 @@ extern "C" int dtlr_stem_conv7x7_f32s(const float* x, const void* wfrag_hi, cons
     if (!x || !wfrag_hi || !wfrag_lo || !y) return DTLR_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0) return DTLR_EINVAL;
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)stem_conv7x7_f32s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEMS_LDS); (void)hipGetLastError(); }
     const dim3 grid((Wo + STEM_COLS - 1) / STEM_COLS, (Ho + STEM_ROWS - 1) / STEM_ROWS, B);
     if (grid.y > 65535u || grid.z > 65535u) return DTLR_ESHAPE;
-    hipLaunchKernelGGL(stem_conv7x7_f32s_kernel, grid, dim3(512), STEMS_LDS, (hipStream_t)stream,
-                       x, (const uint16_t*)wfrag_hi, (const uint16_t*)wfrag_lo, y, H, W, Ho, Wo);
-    return check_launch();
+    return launch<stem_conv7x7_f32s_kernel>(grid, dim3(512), STEMS_LDS, (hipStream_t)stream,
+                                            x, (const uint16_t*)wfrag_hi, (const uint16_t*)wfrag_lo, y, H, W, Ho, Wo);
 }
 
 // conv1.weight (BN scale folded) [64, 3, 7, 7] fp32 (host or device memory readable by the host is NOT assumed: this packs on
@@ -532,13 +526,10 @@ extern "C" int dtlr_stem_conv7x7_pool(const float* x, const void* wfrag, const f
     if (out_dtype != DTLR_H16) return DTLR_EDTYPE;
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
     const int Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)stem_pool_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS); (void)hipGetLastError(); }
     const dim3 grid((Wp + SP_PCOLS - 1) / SP_PCOLS, (Hp + SP_PROWS - 1) / SP_PROWS, B);
     if (grid.y > 65535u || grid.z > 65535u) return DTLR_ESHAPE;
-    hipLaunchKernelGGL(stem_pool_kernel, grid, dim3(512), SP_LDS, (hipStream_t)stream,
-                       x, (const uint16_t*)wfrag, bias, (uint16_t*)y, H, W, Ho, Wo, Hp, Wp);
-    return check_launch();
+    return launch<stem_pool_kernel>(grid, dim3(512), SP_LDS, (hipStream_t)stream,
+                                    x, (const uint16_t*)wfrag, bias, (uint16_t*)y, H, W, Ho, Wo, Hp, Wp);
 }
 
 extern "C" int dtlr_stem_conv7x7(const float* x, const void* wfrag, void* y, int B, int H, int W, int out_dtype, void* stream)
@@ -548,10 +539,7 @@ extern "C" int dtlr_stem_conv7x7(const float* x, const void* wfrag, void* y, int
     if (B <= 0 || H <= 0 || W <= 0) return DTLR_EINVAL;
     if (out_dtype != DTLR_H16) return DTLR_EDTYPE;
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    static DevOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)stem_conv7x7_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, STEM_LDS); (void)hipGetLastError(); }
     const dim3 grid((Wo + STEM_COLS - 1) / STEM_COLS, (Ho + STEM_ROWS - 1) / STEM_ROWS, B);
-    hipLaunchKernelGGL(stem_conv7x7_kernel, grid, dim3(512), STEM_LDS, (hipStream_t)stream,
-                       x, (const uint16_t*)wfrag, (uint16_t*)y, H, W, Ho, Wo);
-    return check_launch();
+    return launch<stem_conv7x7_kernel>(grid, dim3(512), STEM_LDS, (hipStream_t)stream,
+                                       x, (const uint16_t*)wfrag, (uint16_t*)y, H, W, Ho, Wo);
 }

@@ -396,18 +396,16 @@ static int swin_patch_embed_launch(const float* x, const float* w_kE, const floa
     const dim3 grid((Wp + 63) / 64, Hp, B);
     const size_t lds = (size_t)(64 * 49 + 48 * E) * 4;
     hipStream_t st = (hipStream_t)stream;
-#define PE_LAUNCH(OT, EQ, X) hipLaunchKernelGGL((swin_patch_embed_kernel<OT, EQ, X>), grid, dim3(256), lds, st, x, w_kE, bias, gamma, beta, (OT*)out, H, W, Hp, Wp, eps, ext)
+#define PE_LAUNCH(OT, EQ, X) return launch<swin_patch_embed_kernel<OT, EQ, X>>(grid, dim3(256), lds, st, x, w_kE, bias, gamma, beta, (OT*)out, H, W, Hp, Wp, eps, ext)
 #define PE_CASE(EQ) case 4 * EQ: \
         if (ext) { if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ, true); else PE_LAUNCH(float, EQ, true); } \
-        else { if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ, false); else PE_LAUNCH(float, EQ, false); } \
-        break;
+        else { if (out_dtype == DTLR_H16) PE_LAUNCH(uint16_t, EQ, false); else PE_LAUNCH(float, EQ, false); }
     switch (E) {
         PE_CASE(8) PE_CASE(16) PE_CASE(24) PE_CASE(32) PE_CASE(48)
     default: return DTLR_ESHAPE;                               // embed_dim 32 / 64 / 96 / 128 / 192
     }
 #undef PE_CASE
 #undef PE_LAUNCH
-    return check_launch();
 }
 
 extern "C" int dtlr_swin_patch_embed(const float* x, const float* w_kE, const float* bias, const float* gamma, const float* beta,
@@ -434,12 +432,11 @@ static int swin_patch_merge_launch(const void* x, const float* gamma, const floa
     const long rows = (long)B * H2 * W2;
     const unsigned grid = (unsigned)((rows + 3) / 4);
     hipStream_t st = (hipStream_t)stream;
-#define PM_LAUNCH(T, X) hipLaunchKernelGGL((swin_patch_merge_kernel<T, X>), dim3(grid), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, H, W, C, H2, W2, rows, eps, ext, s_in)
+#define PM_LAUNCH(T, X) return launch<swin_patch_merge_kernel<T, X>>(dim3(grid), dim3(256), 0, st, (const T*)x, gamma, beta, (T*)y, H, W, C, H2, W2, rows, eps, ext, s_in)
     if (dtype == DTLR_H16) { if (ext) PM_LAUNCH(uint16_t, true); else PM_LAUNCH(uint16_t, false); }
     else if (dtype == DTLR_F32) { if (ext) PM_LAUNCH(float, true); else PM_LAUNCH(float, false); }
     else return DTLR_EDTYPE;
 #undef PM_LAUNCH
-    return check_launch();
 }
 
 extern "C" int dtlr_swin_patch_merge(const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C,
@@ -472,23 +469,16 @@ static int swin_window_attn_launch(const void* qkv, const float* qkv_bias, const
     const int nW = (P.Hp / window) * P.nWw;
     if (n_heads > 65535 || B > 65535) return DTLR_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
-#define WA_LAUNCH(T, X) hipLaunchKernelGGL((swin_window_attn_kernel<T, X>), dim3(nW, n_heads, B), dim3(256), lds, st, (const T*)qkv, qkv_bias, rpb, (T*)out, P, ext, s)
+#define WA_LAUNCH(T, X) return launch<swin_window_attn_kernel<T, X>>(dim3(nW, n_heads, B), dim3(256), lds, st, (const T*)qkv, qkv_bias, rpb, (T*)out, P, ext, s)
     if (dtype == DTLR_H16) {
         const int lds = SwinLds<uint16_t>::bytes(P.NQ, P.NK);
         if (ext) WA_LAUNCH(uint16_t, true); else WA_LAUNCH(uint16_t, false);
     } else if (dtype == DTLR_F32) {
         const int lds = SwinLds<float>::bytes(P.NQ, P.NK);
-        static DevOnce once;
-        if (once.first()) {
-            (void)hipFuncSetAttribute((const void*)swin_window_attn_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            (void)hipFuncSetAttribute((const void*)swin_window_attn_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            (void)hipGetLastError();
-        }
         if (lds > 96 * 1024) return DTLR_ESHAPE;
-        if (ext) WA_LAUNCH(float, true); else WA_LAUNCH(float, false);
+        if (!ext) WA_LAUNCH(float, false); else WA_LAUNCH(float, true);
     } else return DTLR_EDTYPE;
 #undef WA_LAUNCH
-    return check_launch();
 }
 
 extern "C" int dtlr_swin_window_attn(const void* qkv, const float* qkv_bias, const float* rpb, void* out,
