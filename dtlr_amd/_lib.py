@@ -87,8 +87,8 @@ def read_header(text: str):
     return functions, structs, constants
 
 
-def _read_header_file():
-    path = os.path.join(HERE, "..", "include", "dtlr_hip.h")                 # where build.py fingerprints it
+def _read_header_file(name: str = "dtlr_hip.h"):
+    path = os.path.join(HERE, "..", "include", name)                         # where build.py fingerprints it
     if not os.path.exists(path):
         raise DTLRError(f"{path} is missing: the binding reads every signature from it (it ships with the sources; there is no second table)")
     with open(path) as f:
@@ -99,6 +99,10 @@ def _read_header_file():
 _FUNCTIONS, _STRUCTS, CONSTANTS = _read_header_file()
 # name -> (restype, argtypes): every symbol include/dtlr_hip.h declares
 _SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _FUNCTIONS.items()}
+# include/dtlr_lexicon.h, the second header (the lexicon decoder): read by the same reader into a table of its own, bound at load and
+# reached through launch() / query() like every other entry point; _SIGNATURES, declared_symbols() and CONSTANTS describe dtlr_hip.h alone
+_LEXICON_FUNCTIONS = _read_header_file("dtlr_lexicon.h")[0]
+_LEXICON_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _LEXICON_FUNCTIONS.items()}
 globals().update(CONSTANTS)            # DTLR_OK, DTLR_EINVAL .. DTLR_ELAUNCH; the dtype codes DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S
 
 
@@ -114,7 +118,7 @@ class NgramLM(ctypes.Structure):
 
 def takes_stream(name: str) -> bool:
     """whether the entry point's last parameter is `void *stream` (it is then reached through launch())"""
-    params = _FUNCTIONS[name][1]
+    params = (_FUNCTIONS.get(name) or _LEXICON_FUNCTIONS[name])[1]
     return bool(params) and params[-1] == (c_void_p, "stream")
 
 
@@ -123,7 +127,7 @@ def _load(path: str) -> ctypes.CDLL:
         raise DTLRError(f"{path} not built: run `python -m dtlr_amd.build` (needs hipcc); "
                         "the DTLR HIP path has no CPU/PyTorch fallback")
     L = ctypes.CDLL(path)                  # RTLD_LOCAL: the two builds export the same symbol names and never see each other
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_LEXICON_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the .so is stale -> loud
         fn.restype, fn.argtypes = res, args
     return L

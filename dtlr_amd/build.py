@@ -19,13 +19,17 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
 
+# the C headers: a change to either rebuilds the objects (dtlr_lexicon.h: the lexicon decoder's entry points)
+HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h")]
+
+
 def _sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dtlr_hip.h")]:
+    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS:
         with open(p, "rb") as f:
             h.update(os.path.basename(p).encode() + b"\0" + f.read())   # path-independent: the tree moves on the GPU box
     h.update(" ".join(FLAGS).encode())
@@ -37,7 +41,7 @@ LIB_F16 = os.path.join(HERE, "libdtlr_hip_f16.so")
 
 def _src_hash(src, defs) -> str:
     h = hashlib.sha256()
-    for p in [src] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dtlr_hip.h")]:
+    for p in [src] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(defs).encode())

@@ -574,11 +574,8 @@ def default_ngram_ignore(charset: Sequence) -> List[int]:
     return [i + 1 for i, c in enumerate(charset) if not str(c).isalnum() and str(c) != "'"]
 
 
-def ngram_bundle(args, charset: Sequence, device) -> Optional[Dict]:
-    """What predict_labels(ngram=...) takes, from the command line; None without --ngram-arpa."""
-    if not args.ngram_arpa:
-        return None
-    from . import ngram as NG
+def _ngram_tokens_ignore(args, charset: Sequence):
+    """(tokens, ngram_charset, ignore) of the re-scoring path from --ngram-tokens / --ngram-ignore"""
     if args.ngram_tokens:
         with open(args.ngram_tokens, encoding="utf-8") as f:
             tokens = [line.rstrip("\n") for line in f if line.rstrip("\n")]
@@ -597,8 +594,80 @@ def ngram_bundle(args, charset: Sequence, device) -> Optional[Dict]:
         if missing:
             raise SystemExit(f"--ngram-ignore: {missing} not in the charset")
         ignore = [ngram_charset.index(c, 1) for c in args.ngram_ignore]
+    return tokens, ngram_charset, ignore
+
+
+def ngram_bundle(args, charset: Sequence, device) -> Optional[Dict]:
+    """What predict_labels(ngram=...) takes, from the command line; None without --ngram-arpa."""
+    if not args.ngram_arpa:
+        return None
+    from . import ngram as NG
+    tokens, ngram_charset, ignore = _ngram_tokens_ignore(args, charset)
     dec = NG.DeviceNgramDecoder(tokens, NG.ArpaLM(args.ngram_arpa), args.ngram_weight, args.ngram_beam, args.ngram_beam_token,
                                 blank_token=tokens[0], device=device)
+    return dict(decoder=dec, ignore=ignore, ngram_charset=ngram_charset, no_uppercase_words=args.no_uppercase_words,
+                no_digits=args.no_digits, no_dash=args.no_dash, multiply_pred_logits_by=args.multiply_pred_logits_by)
+
+
+def load_lexicon(path: str):
+    """`--lexicon`: UTF-8, one word per line, optionally `word<TAB>count`; empty lines are dropped.  -> (words, counts or None: counts
+    only when every line carries one)"""
+    words, counts = [], []
+    with open(path, encoding="utf-8") as f:
+        for line in f:
+            line = line.rstrip("\r\n")
+            if not line:
+                continue
+            w, tab, c = line.partition("\t")
+            words.append(w)
+            if tab:
+                try:
+                    counts.append(float(c))
+                except ValueError:
+                    raise SystemExit(f"--lexicon: {line!r}: the count after the tab is no number")
+    if counts and len(counts) != len(words):
+        raise SystemExit("--lexicon: either every line carries `word<TAB>count` or none does")
+    return words, counts or None
+
+
+def check_lexicon_args(args) -> None:
+    """the refusals of the --lexicon flags, before any work (main calls it first); without --lexicon the other three are not read"""
+    if not args.lexicon:
+        return
+    if args.ngram_arpa:
+        raise SystemExit("--lexicon and --ngram-arpa are two decoders for the same word spans: give one")
+    if not 1 <= args.lexicon_nbest <= 8:
+        raise SystemExit(f"--lexicon-nbest {args.lexicon_nbest} outside 1..8")
+    if not 0.0 <= args.lexicon_min_conf <= 1.0:
+        raise SystemExit(f"--lexicon-min-conf {args.lexicon_min_conf} outside 0..1")
+
+
+def lexicon_bundle(args, charset: Sequence, device) -> Optional[Dict]:
+    """What predict_labels(ngram=...) takes when the word spans go to the device lexicon decoder (`--lexicon`): the dict shape of
+    ngram_bundle, tokens and ignore flags included; None without --lexicon.  A word that cannot be packed (a character that is no
+    token, more than 64 characters) is named on stderr and skipped."""
+    if not args.lexicon:
+        return None
+    from . import ngram as NG
+    tokens, ngram_charset, ignore = _ngram_tokens_ignore(args, charset)
+    words, counts = load_lexicon(args.lexicon)
+    good, good_counts = [], []
+    chan_of = {t: c for c, t in enumerate(tokens) if c > 0}
+    for i, w in enumerate(words):
+        try:
+            NG.spell_word(w, chan_of)
+        except ValueError as e:
+            print(f"--lexicon: {e}: skipped", file=sys.stderr)
+            continue
+        if counts is not None and not counts[i] > 0:
+            print(f"--lexicon: {w!r} has the count {counts[i]}: skipped", file=sys.stderr)
+            continue
+        good.append(w)
+        good_counts.append(counts[i] if counts is not None else 1.0)
+    if not good:
+        raise SystemExit(f"--lexicon: {args.lexicon} holds no word that can be spelled with the tokens")
+    dec = NG.DeviceLexiconDecoder(tokens, good, good_counts if counts is not None else None, args.lexicon_prior_weight,
+                                  args.lexicon_min_conf, args.lexicon_nbest, device=device, blank_token=tokens[0])
     return dict(decoder=dec, ignore=ignore, ngram_charset=ngram_charset, no_uppercase_words=args.no_uppercase_words,
                 no_digits=args.no_digits, no_dash=args.no_dash, multiply_pred_logits_by=args.multiply_pred_logits_by)
 
@@ -639,6 +708,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ngram-beam-token", type=int, default=None, help="tokens extended per frame (default: all)")
     ap.add_argument("--ngram-tokens", default=None, help="token table, one per line, channel order (default: <ctc> + the charset, ' ' as <space>)")
     ap.add_argument("--ngram-ignore", default=None, help="characters never re-scored (default: the charset's non-alphanumerics except ')")
+    ap.add_argument("--lexicon", default=None, metavar="FILE",
+                    help="closed-vocabulary decoding of the word spans on the device: UTF-8, one word per line, optionally word<TAB>count; "
+                         "uses --ngram-tokens / --ngram-ignore and the no_* flags; not together with --ngram-arpa")
+    ap.add_argument("--lexicon-min-conf", type=float, default=0.5,
+                    help="a span takes its best word when exp((score - base) / characters) >= this, else it keeps its argmax")
+    ap.add_argument("--lexicon-prior-weight", type=float, default=0.0, help="weight of ln(count / sum of counts) in a word's key")
+    ap.add_argument("--lexicon-nbest", type=int, default=1, help="words returned per span, 1..8")
     ap.add_argument("--multiply_pred_logits_by", type=float, default=1.0)
     ap.add_argument("--no_uppercase_words", action="store_true")
     ap.add_argument("--no_digits", action="store_true")
@@ -664,6 +740,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv: Optional[Sequence[str]] = None) -> Dict:
     args = build_parser().parse_args(argv)
+    check_lexicon_args(args)
     from .dino import DINO, PostProcess
     rank, local, world = ddist.init_from_env()
     if bool(args.spot_words) != bool(args.spot_out):
@@ -706,7 +783,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     images = lambda i: read_rgb(paths[i])                      # noqa: E731
     texts = [t for _, t in rows]
     post = PostProcess(num_select=cfg.num_select, nms_iou_threshold=cfg.nms_iou_threshold)
-    bundle = ngram_bundle(args, charset, dev)
+    bundle = ngram_bundle(args, charset, dev) or lexicon_bundle(args, charset, dev)
     extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
     spot = None

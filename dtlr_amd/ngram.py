@@ -17,7 +17,11 @@ and sends every word's emissions through torchaudio's lexicon CTC beam decoder w
     there is a character-level CTC prefix beam search scored by a back-off character n-gram on the frames of one word.
     `DeviceNgramDecoder` is that search as a HIP kernel (csrc/ngram_beam.hip, dtlr_ngram_beam): every span of a batch in one launch,
     fp64 scores, the LM as a sorted trie in device memory (`pack_lm`).  `get_ngram_predictions_batch` is the batched form of
-    `get_ngram_prediction`: one copy of the argmax rows to the host, one launch, one copy of the records back.
+    `get_ngram_prediction`: one copy of the argmax rows to the host, one launch, one copy of the records back;
+  * the decoder the reference calls is, in its main mode, a WORD-lexicon decoder.  `DeviceLexiconDecoder` is closed-vocabulary decoding
+    of the same word spans on the device (csrc/lexicon.hip, dtlr_lexicon_decode): the best words of a lexicon
+    of tens of thousands of words per span by an exact max-product pass over the lexicon's trie (`pack_lexicon`), through the batched
+    route of `get_ngram_predictions_batch`.
 
 WHAT IS PINNED: (a) to the reference, by vectors its own function bodies produced (G8): emissions, span selection, re-assembly;
 (b) the device decoder's semantics, written down in DESIGN.md section 10: the kernel equals a dict-based fp64 restatement of them, and
@@ -435,6 +439,177 @@ class DeviceNgramDecoder:
         return [[_Hypothesis(self.words(labels[b], lengths[b]), scores[b])] for b in range(B)]
 
 
+# ----------------------------------------------------------------------------------------------------------------------------
+# The device lexicon decoder: for every word span the best words of a closed vocabulary (csrc/lexicon.hip).
+LEXICON_MAX_WORD = 64
+
+
+def spell_word(word: str, chan_of: Dict[str, int]) -> Tuple[int, ...]:
+    """the emission channels of a lexicon word (chan_of: token -> channel, the blank left out; " " is the token <space>).  ValueError,
+    naming the word, when it is empty, longer than 64 characters or holds a character that is no token."""
+    w = str(word)
+    if not w:
+        raise ValueError("pack_lexicon: an empty word ''")
+    if len(w) > LEXICON_MAX_WORD:
+        raise ValueError(f"pack_lexicon: {w!r} has {len(w)} characters, the limit is {LEXICON_MAX_WORD}")
+    z = tuple(chan_of.get(ch, chan_of.get(_lm_word(ch), -1)) for ch in w)
+    if min(z) < 1:
+        raise ValueError(f"pack_lexicon: {w!r} holds the character {w[z.index(min(z))]!r}, which is no token")
+    return z
+
+
+def pack_lexicon(words: Sequence[str], tokens: Sequence[str], blank_token: str = "<ctc>") -> Dict:
+    """The lexicon as the trie dtlr_lexicon_decode reads (include/dtlr_lexicon.h), as CPU tensors.  Pure host code.  A word is a string
+    whose every character is a token (tokens[c] = the string of emission channel c; " " is the token <space>).  Duplicates merge: word
+    id = the rank of a word's first occurrence.  ValueError, naming the word, for an empty word, one longer than 64 characters or one
+    with a character that is no token.  Nodes are sorted by (depth, channels): breadth-first, node 0 the root, parent < child.
+    -> dict(parent, chan, word, depth [n_nodes] int32; depth_start [max depth + 2] int32 (the first node of every depth, then n_nodes);
+    spell [W, Lw] int32 channels, -1 padded; lengths [W] int32; n_words; words: the W strings; spellings: their channels, host lists)."""
+    chan_of = {t: c for c, t in enumerate(tokens) if t != blank_token}
+    seen: Dict[str, int] = {}
+    spellings: List[Tuple[int, ...]] = []
+    for w in words:
+        w = str(w)
+        if w in seen:
+            continue
+        seen[w] = len(spellings)
+        spellings.append(spell_word(w, chan_of))
+    ends = {z: i for i, z in enumerate(spellings)}                            # a character has one channel: distinct words, distinct spellings
+    nodes = {z[:k] for z in spellings for k in range(1, len(z) + 1)}
+    order_list = [()] + sorted(nodes, key=lambda g: (len(g), g))
+    index = {g: i for i, g in enumerate(order_list)}
+    n = len(order_list)
+    dmax = len(order_list[-1])
+    parent, chan, word, depth = [0] * n, [0] * n, [-1] * n, [0] * n
+    depth_start = [n] * (dmax + 2)
+    for i in range(n - 1, -1, -1):                                            # descending: the last write of depth_start[d] is its first node
+        g = order_list[i]
+        depth[i] = len(g)
+        depth_start[len(g)] = i
+        if g:
+            parent[i], chan[i], word[i] = index[g[:-1]], g[-1], ends.get(g, -1)
+    W, Lw = len(spellings), max([len(z) for z in spellings] + [1])
+    spell = torch.full((W, Lw), -1, dtype=torch.int32)
+    for i, z in enumerate(spellings):
+        spell[i, : len(z)] = torch.tensor(z, dtype=torch.int32)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)                # noqa: E731
+    return dict(parent=i32(parent), chan=i32(chan), word=i32(word), depth=i32(depth), depth_start=i32(depth_start), spell=spell,
+                lengths=i32([len(z) for z in spellings]), n_words=W, words=list(seen), spellings=[list(z) for z in spellings])
+
+
+class DeviceLexiconDecoder:
+    """Closed-vocabulary decoding of word spans on the device (dtlr_lexicon_decode; semantics: DESIGN.md section 15): every span gets
+    the lexicon word with the best CTC path over its frames, provided that word is confident enough.  tokens[c] = the string of emission
+    channel c, tokens[0] = the blank; words: the lexicon (pack_lexicon); counts: one positive number per entry of `words` (those of a
+    repeated word add up), prior = prior_weight * ln(count / sum of counts), none when counts is None or prior_weight is 0.
+    decode_spans(emissions [B,T,V] CUDA, spans [(line, first, end)]) -> (labels, lengths, scores) on the device, shaped as
+    DeviceNgramDecoder.decode_spans returns them: a span whose best word has conf = exp((score - base) / characters) >= min_conf gets
+    that word's spelling and score; any other span (out of vocabulary, or no word fits its frames) keeps its own collapsed argmax,
+    whose score is `base`.  One launch per chunk of spans, no copy per span; the emissions stay on the device.
+    nbest_spans: the words, scores and confidences of all nbest.  __call__ and words() keep torchaudio's interface."""
+
+    def __init__(self, tokens: Sequence[str], words: Sequence[str], counts: Optional[Sequence[float]] = None, prior_weight: float = 0.0,
+                 min_conf: float = 0.5, nbest: int = 1, device="cuda", blank_token: str = "<ctc>"):
+        self.tokens = list(tokens)
+        if not self.tokens or self.tokens[0] != blank_token:
+            raise ValueError("DeviceLexiconDecoder: the blank must be emission channel 0 (what dtlr_blank_emissions writes)")
+        if not 1 <= int(nbest) <= 8:
+            raise ValueError("DeviceLexiconDecoder: nbest must be in 1..8")
+        if not 0.0 <= float(min_conf) <= 1.0:
+            raise ValueError("DeviceLexiconDecoder: min_conf must be in 0..1")
+        words = [str(w) for w in words]
+        if not words:
+            raise ValueError("DeviceLexiconDecoder: an empty lexicon")
+        self.packed = pack_lexicon(words, self.tokens, blank_token)
+        self.min_conf, self.nbest, self.prior_weight = float(min_conf), int(nbest), float(prior_weight)
+        self.device = torch.device(device)
+        self.prior = None
+        if counts is not None and self.prior_weight != 0.0:
+            counts = [float(c) for c in counts]
+            if len(counts) != len(words) or any(not c > 0.0 for c in counts):
+                raise ValueError("DeviceLexiconDecoder: counts must hold one positive number per word")
+            wid = {w: i for i, w in enumerate(self.packed["words"])}
+            total = torch.zeros(self.packed["n_words"], dtype=torch.float64)
+            for w, c in zip(words, counts):
+                total[wid[w]] += c
+            self.prior = self.prior_weight * torch.log(total / total.sum())
+        self._on: Dict = {}
+
+    def _tables_on(self, emissions: torch.Tensor) -> Dict:
+        """the trie (checked by ops.lexicon_upload), the spellings, the lengths and the prior on the emissions' device: made once per
+        (device, V) and owned by this decoder"""
+        key = (str(emissions.device), int(emissions.shape[2]))
+        if key not in self._on:
+            from . import ops
+            dev = emissions.device
+            self._on[key] = dict(trie=ops.lexicon_upload(self.packed, key[1], dev), spell=self.packed["spell"].to(dev),
+                                 lengths=self.packed["lengths"].to(dev), prior=self.prior.to(dev) if self.prior is not None else None)
+        return self._on[key]
+
+    def _decode(self, emissions: torch.Tensor, spans):
+        """-> (spans [n,3] int64 on the HOST, count, word, score, base, conf [n,H] on the device): one dtlr_lexicon_decode per chunk"""
+        from . import ops
+        tb = self._tables_on(emissions)
+        sp = torch.as_tensor(spans, dtype=torch.int64, device="cpu").reshape(-1, 3)
+        count, word, score, base = ops.lexicon_decode(emissions, sp, None, self.nbest, tb["prior"], tb["trie"])
+        length = tb["lengths"][word.clamp(min=0).long()].to(torch.float64)
+        conf = torch.where(word >= 0, torch.exp((score - base[:, None]) / length), torch.zeros_like(score))
+        return sp, count, word, score, base, conf
+
+    def decode_spans(self, emissions: torch.Tensor, spans, argmax: Optional[torch.Tensor] = None):
+        """argmax: emissions.argmax(-1) [B,T] on the device, when the caller has it already.  Nothing here waits for the device: the
+        sizes come from the host span table, and both the fallback and the replacement are written without a data-dependent shape."""
+        sp, count, word, score, base, conf = self._decode(emissions, spans)
+        tb = self._tables_on(emissions)
+        n, dev = int(sp.shape[0]), emissions.device
+        Tmax = int((sp[:, 2] - sp[:, 1]).max()) if n else 0
+        Lw = int(tb["spell"].shape[1])
+        Lmax = max(Tmax, Lw, 1)
+        if n == 0:
+            return (torch.full((0, Lmax), -1, dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev),
+                    torch.zeros((0,), dtype=torch.float64, device=dev))
+        sp = sp.to(dev)
+        # every span's collapsed argmax, for all spans at once: frames [first, end) of its line, blanks and repeats dropped; a kept frame
+        # goes to its rank among the kept ones, every other frame to a spare column that is cut off
+        t = sp[:, 1:2] + torch.arange(max(Tmax, 1), device=dev)[None, :]
+        rows = emissions.argmax(-1) if argmax is None else argmax
+        am = rows[sp[:, 0:1], t.clamp(max=emissions.shape[1] - 1)]
+        am = torch.where(t < sp[:, 2:3], am, torch.zeros_like(am))
+        before = torch.cat([torch.zeros_like(am[:, :1]), am[:, :-1]], dim=1)
+        keep = (am != 0) & (am != before)
+        pos = torch.where(keep, keep.cumsum(1) - 1, torch.full_like(am, Lmax))
+        own = torch.full((n, Lmax + 1), -1, dtype=torch.int32, device=dev).scatter_(1, pos, am.to(torch.int32))[:, :Lmax]
+        took = (count > 0) & (conf[:, 0] >= self.min_conf)                    # the best word replaces the argmax
+        w0 = word[:, 0].clamp(min=0).long()
+        best = torch.full((n, Lmax), -1, dtype=torch.int32, device=dev)
+        best[:, :Lw] = tb["spell"][w0]
+        labels = torch.where(took[:, None], best, own)
+        lengths = torch.where(took, tb["lengths"][w0], keep.sum(1).to(torch.int32))
+        scores = torch.where(took, score[:, 0], base)
+        return labels, lengths, scores
+
+    def nbest_spans(self, emissions: torch.Tensor, spans):
+        """-> (words, scores, confs): per span the lists of its count <= nbest words (strings), their acoustic scores (ln p of the best
+        path, without the prior) and confidences, best key first"""
+        _, count, word, score, _, conf = self._decode(emissions, spans)
+        count, word, score, conf = count.cpu().tolist(), word.cpu().tolist(), score.cpu().tolist(), conf.cpu().tolist()
+        names = self.packed["words"]
+        return ([[names[w] for w in word[k][:c]] for k, c in enumerate(count)], [score[k][:c] for k, c in enumerate(count)],
+                [conf[k][:c] for k, c in enumerate(count)])
+
+    def words(self, labels_row: Sequence[int], length: int) -> List[str]:
+        return [self.tokens[int(c)] for c in labels_row[:length]]
+
+    def __call__(self, emissions: torch.Tensor) -> List[List[_Hypothesis]]:
+        B, T = emissions.shape[0], emissions.shape[1]
+        if B == 0 or T == 0:
+            return [[_Hypothesis([], 0.0)] for _ in range(B)]
+        em = emissions if emissions.is_cuda else emissions.to(self.device)
+        labels, lengths, scores = self.decode_spans(em, [(b, 0, T) for b in range(B)])
+        labels, lengths, scores = labels.cpu().tolist(), lengths.cpu().tolist(), scores.cpu().tolist()
+        return [[_Hypothesis(self.words(labels[b], lengths[b]), scores[b])] for b in range(B)]
+
+
 @torch.no_grad()
 def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
                    multiply_pred_logits_by, traces: Optional[List[list]] = None, keep: Optional[Dict] = None) -> List[list]:
@@ -445,7 +620,8 @@ def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset,
     emissions = get_new_pred_logits(outputs, multiply_pred_logits_by)         # [B, T, V] on the device
     if keep is not None:
         keep["emissions"] = emissions
-    rows = emissions.argmax(-1).cpu().tolist()                                # the one copy the host span logic needs
+    argmax = emissions.argmax(-1)
+    rows = argmax.cpu().tolist()                                              # the one copy the host span logic needs
     second = bool(no_uppercase_words or no_digits)
 
     def assemble(b, decode_span, trace=None):
@@ -459,13 +635,16 @@ def _rescore_batch(outputs, decoder: Callable, indices_to_ignore, ngram_charset,
         traces.append([])
         return assemble(b, decode_span, traces[-1])
 
-    if not isinstance(decoder, DeviceNgramDecoder):                           # any callable with torchaudio's interface: one call per span
+    if not hasattr(decoder, "decode_spans"):                                  # any callable with torchaudio's interface: one call per span
         host = emissions.cpu()
         return [final(b, lambda lo, hi, b=b: decoder(host[b, lo:hi][None, :, :])[0][0].words) for b in range(len(rows))]
     spans: List[Tuple[int, int, int]] = []
     for b in range(len(rows)):                                                # pass 1: which spans go to the decoder
         assemble(b, lambda lo, hi, b=b: spans.append((b, lo, hi)) or [])
-    labels, lengths, _ = decoder.decode_spans(emissions, spans)
+    if isinstance(decoder, DeviceLexiconDecoder):                             # its fall-back is the argmax taken above
+        labels, lengths, _ = decoder.decode_spans(emissions, spans, argmax)
+    else:
+        labels, lengths, _ = decoder.decode_spans(emissions, spans)
     labels, lengths = labels.cpu().tolist(), lengths.cpu().tolist()           # the records, one copy each
     found = {sp: decoder.words(labels[k], lengths[k]) for k, sp in enumerate(spans)}
     return [final(b, lambda lo, hi, b=b: found[(b, lo, hi)]) for b in range(len(rows))]
@@ -477,7 +656,8 @@ def get_ngram_predictions_batch(outputs, decoder: Callable, indices_to_ignore, c
     """get_ngram_prediction for a whole batch: emissions by the device kernel, ONE device -> host copy of the [B, T] argmax rows, the
     host span logic per line, ONE dtlr_ngram_beam launch over every span of every line that goes to the decoder, one copy of the
     records back, the same assembly.  Each line's string is the one get_ngram_prediction returns for that line alone with the same
-    decoder.  A decoder that is not a DeviceNgramDecoder is called once per span on host emissions."""
+    decoder.  A decoder without decode_spans (DeviceNgramDecoder and DeviceLexiconDecoder have it) is called once per span on host
+    emissions."""
     items = _rescore_batch(outputs, decoder, indices_to_ignore, ngram_charset, per_word_ngram, no_uppercase_words, no_digits, no_dash,
                            multiply_pred_logits_by)
     if no_uppercase_words or no_digits:

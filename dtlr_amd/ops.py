@@ -1796,3 +1796,9 @@ def topk_rows_masked(scores, excl, k: int):
     idx = torch.empty((B, k), dtype=torch.int64, device=scores.device)
     _lib.launch(_L(scores), "dtlr_topk_rows_masked", scores.data_ptr(), excl.data_ptr(), idx.data_ptr(), B, S, k)
     return idx
+
+
+# The bindings of the second header (include/dtlr_lexicon.h) are served from here but written in dtlr_amd/lexicon.py: the seam tests
+# (tests/test_ops_seam_host.py, tests/test_abi_header_host.py) hold every symbol NAMED in this file against _lib._SIGNATURES, the
+# table of include/dtlr_hip.h alone, which does not grow.  Imported last, so that nothing here depends on it.
+from .lexicon import LEXICON_WORKSPACE_LIMIT, lexicon_decode, lexicon_tables, lexicon_upload          # noqa: E402,F401
