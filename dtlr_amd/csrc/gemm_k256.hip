@@ -251,6 +251,163 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_kernel(
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// An encoder layer's value and [offsets | logits] projections of an unpadded batch in ONE pass over src:
+//     V[m, 0:256] = A[m, :] Wv^T + bv          O[m, 0:384] = A[m, :] Wo^T + R[m % res_rows, :]          (A = src; R = pos Wo^T + bo)
+// Run as two launches (gemm_k256_kernel<2, false>, then gemm_kres.hip's 384-channel column) they read the same 512 bytes per token twice.
+// Here one workgroup computes all 640 channels of a token tile, so the tile comes from HBM once by construction: wave w keeps FIVE row
+// tiles resident (160 VGPRs: 32 channels of Wv, 48 of Wo, both images as dtlr_k256_pack_weights lays them out), and a 64-token tile is
+// walked in four 16-token groups -- 20 accumulator registers instead of 80 -- each finished and stored before the next one starts, every
+// B-fragment read from LDS feeding all five row tiles.
+//   * LDS: a THREE-stage token ring (two tiles in flight; reads are 2/7 of this kernel's traffic) and ONE 64-row residual tile (48 KB,
+//     rows DMA'd like a token tile's: chunk c of row r in slot c ^ (r & 7) of its 128-byte block).  Tiles are walked position-major
+//     (tile t = position tile t / n_img of image t % n_img), so the residual tile changes once per n_img tiles: the wave that sees the
+//     change DMAs the new tile right after the barrier that retires the old one, and waits for it (own pieces, then a second barrier)
+//     between the first group's MFMAs and its epilogue.  No residual load ever sits in a VGPR across a tile.
+//   * vmcnt is counted by hand as above: E = 12 stores per wave and tile, 4 DMA instructions per token tile, and a tile's stores are
+//     never waited for except where the residual tile changes.
+// Both outputs are BIT-identical to the two launches: zero accumulator, k-steps 0..7 on the same MFMA, then V: + bias, round (the !RES
+// path above); O: + 0.0f (gemm_kres_kernel's absent bias), + residual, round (its "epilogue: + bias + residual").  M % 64 == 0.
+constexpr int VO_NS = 3;
+constexpr int VO_RES_OFF = VO_NS * K2_STAGE;                // the residual tile: [8 row groups][6 blocks][8 rows x 128 B]
+constexpr int VO_LDS = VO_RES_OFF + K2_TOK * 768;           // 144 KB
+constexpr int VO_E = 12;                                    // stores per wave and tile: 4 groups x (V: one 16-byte; O: one 16-byte + one 8-byte)
+
+__global__ __launch_bounds__(512, 2) void gemm_k256_vow_kernel(
+    const uint16_t* __restrict__ A, const uint16_t* __restrict__ Wv, const float* __restrict__ bias_v, const uint16_t* __restrict__ Wo,
+    const uint16_t* __restrict__ resid, int res_rows, uint16_t* __restrict__ V, int ldv, uint16_t* __restrict__ O, int M, int tiles_per_wg,
+    int n_img)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char k2_smem[];
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)k2_smem;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = lane & 15, g = lane >> 4;
+    const int ntiles = M / K2_TOK;
+    // workgroup b runs on XCD b % 8; logical ids are contiguous inside an XCD
+    const int nwg = (int)gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = (int)blockIdx.x & 7;
+    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + ((int)blockIdx.x >> 3);
+    const int t_begin = logical * tiles_per_wg;
+    const int t_end = min(t_begin + tiles_per_wg, ntiles);
+    if (t_begin >= t_end) return;
+    const int nt = t_end - t_begin;
+    auto row0 = [&](int t, int pt) -> long { return (long)(t - pt * n_img) * res_rows + (long)pt * K2_TOK; };
+
+    const int dr = lane >> 3, dc = (lane & 7) ^ dr;           // row within a DMA block; SOURCE chunk that lands in slot (lane & 7)
+    auto issue = [&](int t, int slot) {                       // token tile: this wave's blocks j = 4 wave + u (as in gemm_k256_kernel)
+        const long r0 = row0(t, t / n_img);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
+            glds16(A + (r0 + tt8 * 8 + dr) * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * K2_STAGE + j * 1024));
+        }
+    };
+    auto issue_res = [&](int pt) {                            // residual tile: this wave's row group (rows 8 wave ..), 6 blocks
+        const uint16_t* src = resid + ((long)pt * K2_TOK + wave * 8 + dr) * 384 + dc * 8;
+#pragma unroll
+        for (int nb = 0; nb < 6; ++nb) glds16(src + nb * 64, lds_base + (unsigned)(VO_RES_OFF + (wave * 6 + nb) * 1024));
+    };
+    int pt_cur = t_begin / n_img;
+    issue_res(pt_cur);
+    issue(t_begin, 0);
+    if (nt > 1) issue(t_begin + 1, 1);
+    uint4 wv[2][8], wo[3][8];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) wv[rt][ks] = load16(Wv + ((long)((wave * 2 + rt) * 8 + ks) * 64 + lane) * 8);
+#pragma unroll
+    for (int rt = 0; rt < 3; ++rt)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) wo[rt][ks] = load16(Wo + ((long)((wave * 3 + rt) * 8 + ks) * 64 + lane) * 8);
+    float4 bv[2];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+        bv[rt] = bias_v ? *reinterpret_cast<const float4*>(bias_v + (wave * 2 + rt) * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float zero = 0.f;                                         // gemm_kres_kernel's "+ bias" without a bias: kept as an addition
+    wait_vm<0>();
+    // the compiler's own wait for the bias loads belongs HERE, not at their first use inside the ring loop
+    asm volatile("" : "+v"(bv[0].x), "+v"(bv[0].y), "+v"(bv[0].z), "+v"(bv[0].w), "+v"(bv[1].x), "+v"(bv[1].y), "+v"(bv[1].z), "+v"(bv[1].w), "+v"(zero));
+
+    const unsigned rd0 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + ((g ^ (n & 7)) * 16));
+    const unsigned rd1 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + (((4 + g) ^ (n & 7)) * 16));
+    // residual of row tile rt, token n of group tt: bytes o = 96 wave + 32 rt + 8 g .. + 7 of row 16 tt + n -> row group 2 tt + (n >> 3),
+    // block o >> 7, chunk (o >> 4) & 7, half o & 8
+    unsigned rres[3];
+#pragma unroll
+    for (int rt = 0; rt < 3; ++rt) {
+        const int o = 96 * wave + 32 * rt + 8 * g;
+        rres[rt] = (unsigned)(VO_RES_OFF + ((n >> 3) * 6 + (o >> 7)) * 1024 + (n & 7) * 128 + ((((o >> 4) & 7) ^ (n & 7)) * 16) + (o & 8));
+    }
+
+    int slot = 0;
+    for (int i = 0; i < nt; ++i) {
+        const int t = t_begin + i;
+        __builtin_amdgcn_s_barrier();                         // tile i published; stage (i + 2) % 3 and (on a change) the residual tile no longer read
+        const int pt = t / n_img;
+        const bool new_res = pt != pt_cur;
+        pt_cur = pt;
+        const bool more = i + 2 < nt;
+        if (new_res) issue_res(pt);
+        if (more) issue(t + 2, slot == 0 ? 2 : slot - 1);
+        const long trow = row0(t, pt);
+        const unsigned char* sb = k2_smem + slot * K2_STAGE;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            f32x4_t av[2], ao[3];
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) av[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int rt = 0; rt < 3; ++rt) ao[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const uint4 bf = *reinterpret_cast<const uint4*>(sb + ((ks & 1) ? rd1 : rd0) + tt * 8192 + (ks >> 1) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) av[rt] = mma16(wv[rt][ks], bf, av[rt]);
+#pragma unroll
+                for (int rt = 0; rt < 3; ++rt) ao[rt] = mma16(wo[rt][ks], bf, ao[rt]);
+            }
+            if (tt == 0 && new_res) {
+                // my pieces of the new residual tile (older than the token DMA group issued after them), then everybody's
+                if (more) wait_vm<4>(); else wait_vm<0>();
+                __builtin_amdgcn_s_barrier();
+            }
+            const long tok = trow + tt * 16 + n;
+            // ---- V: + bias, round, row tiles (0, 1) paired into a 16-byte store (gemm_k256_kernel's !RES epilogue) --------------------
+            {
+                const uint32_t lo0 = pack_bf16x2(av[0][0] + bv[0].x, av[0][1] + bv[0].y), hi0 = pack_bf16x2(av[0][2] + bv[0].z, av[0][3] + bv[0].w);
+                const uint32_t lo1 = pack_bf16x2(av[1][0] + bv[1].x, av[1][1] + bv[1].y), hi1 = pack_bf16x2(av[1][2] + bv[1].z, av[1][3] + bv[1].w);
+                const auto s0 = __builtin_amdgcn_permlane16_swap(lo0, lo1, false, false);
+                const auto s1 = __builtin_amdgcn_permlane16_swap(hi0, hi1, false, false);
+                *reinterpret_cast<uint4*>(V + tok * (long)ldv + (wave * 2 + (g & 1)) * 16 + 8 * (g >> 1)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            }
+            // ---- O: + 0, + residual (one 8-byte LDS read per row tile), round; row tiles (0, 1) paired, row tile 2 an 8-byte store ----------
+            uint32_t lo[3], hi[3];
+#pragma unroll
+            for (int rt = 0; rt < 3; ++rt) {
+                const uint2 rr = *reinterpret_cast<const uint2*>(k2_smem + rres[rt] + tt * 12288);
+                float v[4] = {ao[rt][0] + zero, ao[rt][1] + zero, ao[rt][2] + zero, ao[rt][3] + zero};
+                v[0] += h16_lo(rr.x); v[1] += h16_hi(rr.x); v[2] += h16_lo(rr.y); v[3] += h16_hi(rr.y);
+                lo[rt] = pack_bf16x2(v[0], v[1]);
+                hi[rt] = pack_bf16x2(v[2], v[3]);
+            }
+            {
+                const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+                const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+                uint16_t* dst = O + tok * 384;
+                *reinterpret_cast<uint4*>(dst + (wave * 3 + (g & 1)) * 16 + 8 * (g >> 1)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                *reinterpret_cast<uint2*>(dst + (wave * 3 + 2) * 16 + 4 * g) = make_uint2(lo[2], hi[2]);
+            }
+        }
+        // my pieces of tile i + 1 must have landed before the next barrier.  Issued after them: tile i - 1's stores, this iteration's DMA
+        // group (if any; a residual tile's pieces were waited for above), this tile's stores.
+        if (more) wait_vm<2 * VO_E + 4>();
+        else if (i + 1 < nt) wait_vm<2 * VO_E>();
+        slot = slot == 2 ? 0 : slot + 1;
+    }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Output projection + residual + LayerNorm in the same weight-resident form:   Y = LayerNorm(R + A W^T + b),  all [M, 256] bf16.
 // (`src = norm1(src + self_attn(...))`, the last op of self_attn being output_proj: models/dino/deformable_transformer.py:810-815,
 // ops/modules/ms_deform_attn.py:124.)  ffn.hip's proj_ln_bf16_kernel keeps the TOKENS in registers and re-streams the 128 KB weight
@@ -412,6 +569,14 @@ extern "C" int dtlr_proj_ln_k256(const void* A, const void* Wp, const float* bia
                                        (const uint16_t*)R, gamma, beta, eps, (uint16_t*)Y, M, per);
 }
 
+// compute units of the current device, asked once (one persistent workgroup per CU)
+static int k2_cu_count()
+{
+    static int cached = 0;
+    if (!cached) { int d = 0; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) cached = p.multiProcessorCount; else cached = 256; (void)hipGetLastError(); }
+    return cached;
+}
+
 // W [N, 256] row-major bf16 (host memory) -> fragment order (host memory, N * 256 elements).
 extern "C" int dtlr_k256_pack_weights(const unsigned short* w_host, unsigned short* wp_host, int N)
 {
@@ -430,21 +595,38 @@ extern "C" int dtlr_k256_pack_weights(const unsigned short* w_host, unsigned sho
     return DTLR_OK;
 }
 
+// value and [offsets | logits] of an unpadded batch in one pass over A (gemm_k256_vow_kernel): dtlr_gemm_k256's N = 640 form.
+//     V[m, 0:256] = A[m, :] Wv^T + bias_v        O[m, :] = A[m, :] Wow^T + R[m % res_rows, :]        A [M, 256], O [M, 384], R [res_rows, 384]
+static int k256_vow_launch(const void* A, const void* Wv, const float* bias_v, const void* Wow, const void* R, int res_rows,
+                           void* V, int ldv, void* O, int M, hipStream_t st)
+{
+    if (ldv < 256 || (ldv & 7)) return DTLR_EINVAL;
+    if ((res_rows % K2_TOK) || (M % res_rows) || (long)res_rows * 384 * 2 >= (1L << 31)) return DTLR_ESHAPE;
+    const int ntiles = M / K2_TOK;
+    const int ncu = k2_cu_count();
+    const int grid = ntiles < ncu ? ntiles : ncu;
+    const int per = (ntiles + grid - 1) / grid;
+    const int g2 = (ntiles + per - 1) / per;
+    return launch<gemm_k256_vow_kernel>(dim3(g2), dim3(512), VO_LDS, st, (const uint16_t*)A, (const uint16_t*)Wv, bias_v,
+                                        (const uint16_t*)Wow, (const uint16_t*)R, res_rows, (uint16_t*)V, ldv, (uint16_t*)O, M, per, M / res_rows);
+}
+
 extern "C" int dtlr_gemm_k256(const void* A, const void* Wp, const float* bias, const void* resid, int res_rows,
                               const unsigned char* row_mask, void* C, int ldc, int M, int N, void* stream)
 {
     clear_stale_error();
     if (!A || !Wp || !C) return DTLR_EINVAL;
+    if (N == 640) {
+        // both encoder projections: Wp = the N = 256 image then the N = 384 image, bias [256], resid [res_rows, 384]; C = V [M, ldc], then
+        // O [M, 384] right behind it
+        if (M <= 0 || !resid || res_rows <= 0 || row_mask) return DTLR_EINVAL;
+        return k256_vow_launch(A, Wp, bias, (const uint16_t*)Wp + 256 * 256, resid, res_rows, C, ldc, (uint16_t*)C + (long)M * ldc, M, (hipStream_t)stream);
+    }
     if (M <= 0 || ldc < N || (ldc & 7)) return DTLR_EINVAL;
     if (resid && (res_rows <= 0 || (long)res_rows * N * 2 >= (1L << 31))) return DTLR_EINVAL;
     if (N != 256 && N != 384) return DTLR_ESHAPE;
     const int ntiles = (M + K2_TOK - 1) / K2_TOK;
-    int ncu = 256;
-    {
-        static int cached = 0;
-        if (!cached) { int d = 0; hipDeviceProp_t p; if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0) cached = p.multiProcessorCount; else cached = 256; (void)hipGetLastError(); }
-        ncu = cached;
-    }
+    const int ncu = k2_cu_count();
     const int grid = ntiles < ncu ? ntiles : ncu;
     const int per = (ntiles + grid - 1) / grid;
     const int g2 = (ntiles + per - 1) / per;

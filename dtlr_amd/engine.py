@@ -147,6 +147,8 @@ class DTLREngine:
         self.l1_block_min_wgs = 256       #         ... for whole batches whose (image, 64-column segment) workgroups fill every round of 256 (one per CU) at
                                           #         least this far.  Measured: 256 workgroups (32 lines of 128 x 2048) 8.63 -> 8.48 ms per step; 64 (8 lines)
                                           #         3.45 -> 3.63 ms: the chain stays.  Fills between those, and counts above 256, are NOT measured.
+        self.use_k256_fused = 1           # 16-bit, unpadded batch: an encoder layer's value and [offsets | logits] projections in ONE pass over src
+                                          #         (ops.gemm_k256_vow: dtlr_gemm_k256, N = 640) instead of dtlr_gemm_k256 + dtlr_gemm_kres_bcast384; bit-identical either way
         self.use_l2_cat = True            # 16-bit: layer2.0's strided shortcut convolution as extra K columns of its tail GEMM
         self.head_ts_min_classes = 1024   # 16-bit engines: class heads with at least this many classes run on the token-stationary kernel (dtlr_head_ts)
         self.head_ts_scores = True        # ... and the two-stage selection scores (row maximum: no logits leave the chip) for EVERY charset: 142 -> 74 us at 166 classes
@@ -737,6 +739,13 @@ class DTLREngine:
             for img, r0, nr in self._image("k256s_slices", name + ".ow"):
                 sl.append(dict(wp=img, out=ow[..., r0:r0 + nr], residual=ow_res[..., r0:r0 + nr]))
             ops.gemm_k256s_multi(query, sl, res_rows=S)
+        if (k256 and getattr(self, "use_k256_fused", 0) and self.use_kres and value is None and ow is None and value_src is query
+                and ow_res is not None and not g["has_padding"] and not k256s and tuple(self.w[name + ".ow.w"].shape) == (384, 256)):
+            rows = ow_res.numel() // 384
+            if rows % 64 == 0 and (query.numel() // 256) % rows == 0:
+                # 16-bit engine, unpadded batch: both projections of src in one launch, all 640 channels of a token tile by one workgroup
+                value, ow = ops.gemm_k256_vow(query, self._image("k256", name + ".value"), self.w[name + ".value.b"],
+                                              self._image("k256", name + ".ow"), ow_res)
         if value is None:
             if k256s:
                 value = ops.gemm_k256s(value_src, self._image("k256s", name + ".value"), self.w[name + ".value.b"],

@@ -247,6 +247,47 @@ def gemm_k256(x, wp, n_out: int, b=None, resid=None, row_mask=None, out=None):
     return out
 
 
+_VOW_IMAGES = {}       # (id(wv_img), id(wow_img)) -> (wv_img, wow_img, versions, [wv_img | wow_img]): see _vow_image
+
+
+def _vow_image(wv_img, wow_img):
+    """the two k256_pack images back to back, as dtlr_gemm_k256's N = 640 form reads them; built once per pair of image tensors (the entry
+    keeps both alive, so their ids cannot be reused, and is rebuilt if either was written in place) -- at most 64 pairs are remembered"""
+    key = (id(wv_img), id(wow_img))
+    ent = _VOW_IMAGES.get(key)
+    ver = (wv_img._version, wow_img._version)
+    if ent is None or ent[0] is not wv_img or ent[1] is not wow_img or ent[2] != ver:
+        if len(_VOW_IMAGES) >= 64:
+            _VOW_IMAGES.clear()
+        ent = _VOW_IMAGES[key] = (wv_img, wow_img, ver, torch.cat([wv_img.reshape(-1), wow_img.reshape(-1)]))
+    return ent[3]
+
+
+@_lib.op
+def gemm_k256_vow(x, wv_img, bv, wow_img, resid):
+    """An encoder layer's value and [offsets | logits] projections in ONE pass over x (dtlr_gemm_k256 with N = 640):
+        value = x @ Wv.T + bv          ow = x @ Wow.T + resid[m % rows]
+    bit-identical to gemm_k256(x, wv_img, 256, bv) and gemm_kres_bcast384(x, kres_pack_bcast384(Wow), resid).  x [..., 256] bf16;
+    wv_img = k256_pack(Wv [256, 256]), wow_img = k256_pack(Wow [384, 256]); resid [rows, 384] bf16, rows % 64 == 0, M % rows == 0.
+    Returns (value [..., 256], ow [..., 384]): two contiguous matrices that share one allocation."""
+    require_cuda(x, "x")
+    assert x.dtype in H16 and x.shape[-1] == 256 and wv_img.dtype == x.dtype and wv_img.numel() == 256 * 256
+    assert wow_img.dtype == x.dtype and wow_img.numel() == 384 * 256
+    assert resid.dtype == x.dtype and resid.is_contiguous() and resid.shape[-1] == 384
+    x = x if x.is_contiguous() else x.contiguous()
+    M, rows = x.numel() // 256, resid.numel() // 384
+    if bv is not None and bv.dtype != torch.float32:
+        bv = bv.float()
+    wp = _vow_image(wv_img, wow_img)
+    buf = torch.empty((M * 640,), dtype=x.dtype, device=x.device)
+    value, ow = buf[:M * 256].view(x.shape[:-1] + (256,)), buf[M * 256:].view(x.shape[:-1] + (384,))
+    nbytes = float(M) * 256 * 2 + 640.0 * 256 * 2 + float(M) * 640 * 2 + float(rows) * 384 * 2
+    with _Timed("gemm_bf16", 2.0 * M * 640 * 256, nbytes, f"k256_vow M{M} N256+384 K256+resb{rows}", symbol="gemm_k256_vow_kernel"):
+        _lib.launch(_L(x), "dtlr_gemm_k256", x.data_ptr(), wp.data_ptr(), 0 if bv is None else bv.data_ptr(), resid.data_ptr(), rows, 0,
+                    buf.data_ptr(), 256, M, 640)
+    return value, ow
+
+
 def kres_supported(M: int, N: int, K: int, dtype) -> bool:
     """Shapes dtlr_gemm_kres takes (the HBM-streaming 1x1 convolutions of the ResNet bottlenecks)."""
     return dtype in H16 and K in (64, 128, 256) and (N % 256 == 0 or N in (64, 128, 192)) and N >= 64 and M >= 16384

@@ -373,7 +373,13 @@ int dtlr_gemm_nt(const void *A, const void *A2, const void *W, const float *bias
  *           (models/dino/ops/modules/ms_deform_attn.py:94-98) and the decoder layers' value_proj(memory) (same file, :94).
  *   A [M,256] bf16 ; Wp = dtlr_k256_pack_weights(W [N,256]) (device copy of the fragment-order image) ; bias [N] fp32 or NULL ;
  *   resid [res_rows, N] bf16 or NULL (M need not be a multiple of res_rows) ; row_mask [M] uint8 or NULL ;
- *   C bf16 with row stride ldc elements (ldc >= N, multiple of 8). */
+ *   C bf16 with row stride ldc elements (ldc >= N, multiple of 8).
+ * N = 640: an encoder layer's value AND [offsets | logits] projections of an unpadded batch in ONE pass over A,
+ *     V[m, 0:256] = A[m,:] . Wv^T + bias          O[m, 0:384] = A[m,:] . Wow^T + resid[m % res_rows, :]
+ *   both bit-identical to dtlr_gemm_k256 (N = 256) and dtlr_gemm_kres_bcast384 on the same A.  Wp = dtlr_k256_pack_weights(Wv [256,256], 256)
+ *   followed by dtlr_k256_pack_weights(Wow [384,256], 384) (640 x 256 elements) ; bias [256] fp32 or NULL ; resid [res_rows, 384], required ;
+ *   row_mask NULL ; C = V [M, ldc] (ldc >= 256, multiple of 8) followed by O [M, 384] at C + M * ldc.  res_rows a multiple of 64 and M a
+ *   multiple of res_rows (DTLR_ESHAPE otherwise: use the two launches). */
 int dtlr_k256_pack_weights(const unsigned short *w_host, unsigned short *wp_host, int N);
 int dtlr_gemm_k256(const void *A, const void *Wp, const float *bias, const void *resid, int res_rows,
                    const unsigned char *row_mask, void *C, int ldc, int M, int N, void *stream);
