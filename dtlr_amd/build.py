@@ -19,8 +19,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
 
-# the C headers: a change to either rebuilds the objects (dtlr_lexicon.h: the lexicon decoder's entry points)
-HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h")]
+# the C headers: a change to any rebuilds the objects (dtlr_lexicon.h: the lexicon decoder's entry points; dtlr_metrics.h: the edit
+# distance's)
+HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h", "dtlr_metrics.h")]
 
 
 def _sources():

@@ -497,10 +497,114 @@ def transcript_labels(texts: Sequence[str], charset: Sequence[str]) -> List[Opti
     return [[index[ch] for ch in t] if all(ch in index for ch in t) else None for t in texts]
 
 
+_NAN = float("nan")                # the one NaN of an empty list's mean: two result dicts then compare equal with ==
+
+
+def _mean_ci(v):
+    return (float(np.mean(v)), float(np.std(v) * 1.96 / np.sqrt(len(v)))) if len(v) else (_NAN, _NAN)
+
+
+def _evaluate_predictions_device(pred_labels, gt_texts, cs: List, dataset: str, metrics: str, unicode_charset: bool, device,
+                                 confusion: Optional["E.ConfusionReport"]) -> Dict:
+    """evaluate_predictions with every dynamic program of the pass on the device: the label pairs (CER, CR's operations, the
+    confusion report's alignment) in one E.edit_align call, the normalised strings and the word-id sequences in a second, then the
+    host path's bookkeeping on the integers that come back."""
+    from . import ops
+    conv =(lambda c: chr(c)) if unicode_charset else (lambda c: c)
+    index: Dict = {}
+    for i, c in enumerate(cs):                                                     # cs.index: the first position of a repeated entry
+        index.setdefault(c, i)
+    string_cer, lines = dataset in CER_DATASETS, []
+    jobs_a, jobs_b, word_ids = [], [], {}
+    for pred, text in zip(pred_labels, gt_texts):
+        if pred is None:
+            continue
+        pred = [int(v) for v in pred]
+        gt = []
+        for c in text:
+            key = ord(c) if unicode_charset else c
+            if key not in index:
+                cs.index(key)                                                      # the host path's ValueError
+            gt.append(index[key])
+        if len(pred) > 0 and len(gt) == 0:
+            raise ValueError("character_error_rate_with_impact: empty ground truth")
+        line = dict(pred=pred, gt=gt, ps="".join(conv(cs[i]) for i in pred), gs="".join(conv(cs[i]) for i in gt))
+        if string_cer:
+            line["string"] = len(jobs_a)
+            jobs_a.append(E.process_pred_string(line["gs"]))
+            jobs_b.append(E.process_pred_string(line["ps"]))
+        if metrics == "default":
+            gw, pw = ([word_ids.setdefault(tuple(w), len(word_ids)) for w in E.split_labels_into_words(z, cs)] for z in (gt, pred))
+            line["words"], line["n_pred_words"] = len(jobs_a), len(pw)
+            jobs_a.append(gw)
+            jobs_b.append(pw)
+        lines.append(line)
+    gts, preds = [ln["gt"] for ln in lines], [ln["pred"] for ln in lines]
+    if confusion is not None:                                                      # the alignments stay on the device: only the table returns
+        on = set(E._device_pairs(gts, preds))
+        dev_lines = [k for k in range(len(lines)) if k in on]
+        a, a_off, b, b_off = ops.edit_align_tables([gts[k] for k in dev_lines], [preds[k] for k in dev_lines])
+        a, b = a.to(device), b.to(device)
+        d, c, n_ops, steps = ops.edit_align(a, a_off, b, b_off, True)
+        confusion.add_device(a, a_off, b, b_off, n_ops, steps)
+        lab_d, lab_c = [None] * len(lines), [None] * len(lines)
+        for k, dk, ck in zip(dev_lines, d.cpu().tolist(), c.cpu().tolist()):
+            lab_d[k], lab_c[k] = dk, tuple(ck)
+        for k in range(len(lines)):
+            if k not in on:                                                        # a line above the device's length limit
+                lab_d[k], lab_c[k] = E.levenshtein(preds[k], gts[k]), E.compute_edit_operations(gts[k], preds[k])
+                confusion.add_alignment(gts[k], preds[k], E.compute_edit_alignment(gts[k], preds[k]))
+    else:
+        lab_d, lab_c, _ = E.edit_align_batch(gts, preds, device)
+    job_d = E.edit_align_batch(jobs_a, jobs_b, device)[0] if jobs_a else []
+
+    CER_list, WER_list, AR_list, CR_list, WA_list = [], [], [], [], []
+    dict_char: Dict[int, int] = {}
+    preds_str, gts_str, dist_sum, len_sum = [], [], 0, 0
+    for k, line in enumerate(lines):
+        pred, gt = line["pred"], line["gt"]
+        if len(pred) > 0:
+            E.character_impact(pred, gt, dict_char)
+            cer_it = lab_d[k] / len(gt)
+        else:
+            cer_it = 1
+        preds_str.append(line["ps"])
+        gts_str.append(line["gs"])
+        if string_cer:
+            dist_sum += job_d[line["string"]]
+            len_sum += len(jobs_a[line["string"]])
+            cer_it = dist_sum / len_sum
+        if metrics == "default":
+            CER_list.append(cer_it)
+            WER_list.append(job_d[line["words"]] / max(line["n_pred_words"], 1))
+        elif metrics == "CER_only":
+            CER_list.append(cer_it)
+        elif metrics == "chinese":
+            CER_list.append(cer_it)
+            AR_list.append(1 - cer_it)
+            CR_list.append((len(gt) - lab_c[k][1] - lab_c[k][2]) / len(gt))
+        elif metrics == "cipher":
+            CER_list.append(cer_it)
+            WA_list.append(E.compute_wa(gt, pred))
+        else:
+            raise ValueError(f"unknown --metrics {metrics}")
+    return dict(CER_list=CER_list, WER_list=WER_list, AR_list=AR_list, CR_list=CR_list, WA_list=WA_list, dict_char=dict_char,
+                list_preds_str=preds_str, list_gt_str=gts_str, cer=_mean_ci(CER_list), wer=_mean_ci(WER_list), ar=_mean_ci(AR_list),
+                cr=_mean_ci(CR_list), wa=_mean_ci(WA_list))
+
+
 def evaluate_predictions(pred_labels: Sequence[Sequence[int]], gt_texts: Sequence[str], charset: Sequence, dataset: str = "IAM",
-                         metrics: str = "default", unicode_charset: bool = False) -> Dict:
-    """The per-sample metric bookkeeping of evaluation.py:495-581 on already decoded predictions."""
+                         metrics: str = "default", unicode_charset: bool = False, device=None,
+                         confusion: Optional["E.ConfusionReport"] = None) -> Dict:
+    """The per-sample metric bookkeeping of evaluation.py:495-581 on already decoded predictions.
+    device (`--device-metrics`): every edit-distance lattice of the pass -- label CER, the normalised strings' distance, the word-level
+    WER, CR's operations -- runs on that device in a few launches for the whole pass instead of line by line in
+    Python; the returned dict equals the host path's with ==, every ratio being formed here from the same integers.
+    confusion: an E.ConfusionReport that takes the label-level alignment (a = ground truth) of every scored line; with a device the
+    alignments are gathered and counted there."""
     cs = list(charset)
+    if device is not None:
+        return _evaluate_predictions_device(pred_labels, gt_texts, cs, dataset, metrics, unicode_charset, device, confusion)
     CER_list, WER_list, AR_list, CR_list, WA_list = [], [], [], [], []
     dict_char: Dict[int, int] = {}
     preds_str, gts_str, dists, lens = [], [], [], []
@@ -536,13 +640,12 @@ def evaluate_predictions(pred_labels: Sequence[Sequence[int]], gt_texts: Sequenc
             WA_list.append(E.compute_wa(gt, list(pred)))
         else:
             raise ValueError(f"unknown --metrics {metrics}")
-
-    def mean_ci(v):
-        return (float(np.mean(v)), float(np.std(v) * 1.96 / np.sqrt(len(v)))) if len(v) else (float("nan"), float("nan"))
+        if confusion is not None:
+            confusion.add_alignment(gt, list(pred), E.compute_edit_alignment(gt, list(pred)))
 
     return dict(CER_list=CER_list, WER_list=WER_list, AR_list=AR_list, CR_list=CR_list, WA_list=WA_list, dict_char=dict_char,
-                list_preds_str=preds_str, list_gt_str=gts_str, cer=mean_ci(CER_list), wer=mean_ci(WER_list), ar=mean_ci(AR_list),
-                cr=mean_ci(CR_list), wa=mean_ci(WA_list))
+                list_preds_str=preds_str, list_gt_str=gts_str, cer=_mean_ci(CER_list), wer=_mean_ci(WER_list), ar=_mean_ci(AR_list),
+                cr=_mean_ci(CR_list), wa=_mean_ci(WA_list))
 
 
 def write_outputs(res: Dict, out_dir: str, dataset: str, TH, NM) -> str:
@@ -735,12 +838,39 @@ def build_parser() -> argparse.ArgumentParser:
                          "pixels and its characters")
     ap.add_argument("--spot-min-conf", type=float, default=0.5, help="a hit needs exp(ratio / length) >= this (0: the best hit of every word)")
     ap.add_argument("--spot-max-hits", type=int, default=4, help="hits per (line, word), 1..16")
+    ap.add_argument("--device-metrics", action="store_true",
+                    help="run the edit-distance lattices of the metrics (CER, WER, CR) on the device, batched over the whole pass; the "
+                         "figures and files are those of the host path")
+    ap.add_argument("--confusion-out", default=None, metavar="FILE.json",
+                    help="also write the confusion report of the label-level alignment of all scored lines: substitutions per (gt, pred), "
+                         "deletions, insertions, recall per character; implies --device-metrics; needs a single decoder setting")
+    ap.add_argument("--confusion-top", type=int, default=50, help="entries kept in each list of --confusion-out, most frequent first")
     return ap
+
+
+def check_metrics_args(args) -> None:
+    """the refusals of --confusion-out / --confusion-top, before any work (main calls it first); without --confusion-out the other is
+    not read"""
+    if not args.confusion_out:
+        return
+    if args.confusion_top < 1:
+        raise SystemExit(f"--confusion-top {args.confusion_top} must be at least 1")
+    if args.NMS_inference and (args.NMS is None or args.TH is None):
+        raise SystemExit("--confusion-out needs one decoder setting (--TH and --NMS, or neither), not the --NMS_inference grid")
+
+
+def write_confusion(path: str, report: "E.ConfusionReport", charset: Sequence, top: int) -> Dict:
+    """`--confusion-out`: ConfusionReport.to_json as one JSON object"""
+    obj = report.to_json(charset, top)
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(obj, f, ensure_ascii=False, indent=1)
+    return obj
 
 
 def main(argv: Optional[Sequence[str]] = None) -> Dict:
     args = build_parser().parse_args(argv)
     check_lexicon_args(args)
+    check_metrics_args(args)
     from .dino import DINO, PostProcess
     rank, local, world = ddist.init_from_env()
     if bool(args.spot_words) != bool(args.spot_out):
@@ -821,7 +951,14 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                 print(f"wrote {k} hits of {len(spot['words'])} words to {args.spot_out}", file=sys.stderr)
                 spot = None
             if rank == 0:
-                res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
+                if args.device_metrics or args.confusion_out:
+                    report = E.ConfusionReport() if args.confusion_out else None
+                    res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode, device=dev, confusion=report)
+                    if report is not None:
+                        write_confusion(args.confusion_out, report, [chr(c) if args.unicode else str(c) for c in charset], args.confusion_top)
+                        print(f"wrote the confusion report of {report.lines} lines to {args.confusion_out}", file=sys.stderr)
+                else:
+                    res = evaluate_predictions(preds, texts, charset, args.dataset, args.metrics, args.unicode)
                 d = write_outputs(res, args.out, args.dataset, TH, NM)
                 tail = f", TH {TH}, NM {NM}" if nms_inference else ""
                 if args.metrics == "chinese":

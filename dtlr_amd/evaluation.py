@@ -605,6 +605,18 @@ def character_error_rate_with_impact(pred: Sequence[int], gt: Sequence[int], imp
     return levenshtein(pred, gt) / len(gt), impact, len(gt)
 
 
+def character_impact(pred: Sequence[int], gt: Sequence[int], impact: Dict[int, int]) -> Dict[int, int]:
+    """the `impact` bookkeeping of character_error_rate_with_impact alone, for a caller that has the distance already"""
+    counts: Dict[int, int] = {}
+    for g_ in gt:
+        counts[int(g_)] = counts.get(int(g_), 0) + 1
+    for p_ in pred:
+        n = len(gt) - counts.get(int(p_), 0)
+        if n:
+            impact[int(p_)] = impact.get(int(p_), 0) + n
+    return impact
+
+
 def compute_wa(gt: Sequence[int], pred: Sequence[int]) -> float:
     """evaluation.py:212-238 (cipher "word accuracy"): matching positions over max(len(gt), 1)."""
     return sum(1 for a, b in zip(gt, pred) if a == b) / max(len(gt), 1)
@@ -638,6 +650,183 @@ def compute_cr(gt: Sequence[int], pred: Sequence[int]) -> float:
     """evaluation.py:283-290 (Chinese correct rate): (len(gt) - deletions - substitutions) / len(gt)."""
     _, dele, sub = compute_edit_operations(gt, pred)
     return (len(gt) - dele - sub) / len(gt)
+
+
+# ----------------------------------------------------------------------- edit distance and alignment on the device (DESIGN.md section 16)
+def compute_edit_alignment(s1: Sequence, s2: Sequence) -> List[Tuple[int, int]]:
+    """The alignment compute_edit_operations counts, step by step in forward order: (i, j) = s1[i] stands against s2[j] (a match when
+    they are equal, a substitution otherwise), (i, -1) = s1[i] is deleted, (-1, j) = s2[j] is inserted.  The host statement of what
+    dtlr_edit_align writes as `ops`."""
+    m, n = len(s1), len(s2)
+    rows = [list(range(n + 1))]
+    for i in range(1, m + 1):
+        prev, cur = rows[-1], [i] + [0] * n
+        for j in range(1, n + 1):
+            cur[j] = prev[j - 1] if s1[i - 1] == s2[j - 1] else 1 + min(prev[j], cur[j - 1], prev[j - 1])
+        rows.append(cur)
+    i, j, steps = m, n, []
+    while i and j:
+        here = rows[i][j]
+        if s1[i - 1] == s2[j - 1] or here == rows[i - 1][j - 1] + 1:
+            steps.append((i - 1, j - 1))
+            i, j = i - 1, j - 1
+        elif here == rows[i - 1][j] + 1:
+            steps.append((i - 1, -1))
+            i -= 1
+        else:
+            steps.append((-1, j - 1))
+            j -= 1
+    return [(-1, k) for k in range(j)] + [(k, -1) for k in range(i)] + steps[::-1]
+
+
+def _device_pairs(a_seqs, b_seqs):
+    """the pairs the device can score (both sides at most EDIT_MAX_LEN elements that are ints inside int32, or str): their indices"""
+    from .metrics import EDIT_MAX_LEN
+
+    def fits(s):
+        if len(s) > EDIT_MAX_LEN:
+            return False
+        return isinstance(s, str) or all(isinstance(v, int) and -(1 << 31) <= v < (1 << 31) for v in s)
+
+    return [k for k, (x, y) in enumerate(zip(a_seqs, b_seqs)) if fits(x) and fits(y)]
+
+
+def edit_align_batch(a_seqs, b_seqs, device="cuda", want_ops: bool = False):
+    """Every pair (a_seqs[p], b_seqs[p]) scored in one pass on `device` (ops.edit_align: the pairs of the whole call in as few launches as
+    the workspace limit allows).  Sequences of ints or str (a str is packed as its code points).  -> (dist: list of int, counts: list
+    of (ins, del, sub), alignments: per pair its list of (i, j) steps, or None without want_ops): levenshtein(a, b),
+    compute_edit_operations(a, b) and compute_edit_alignment(a, b) of every pair.  A pair the device cannot take (a side above
+    ops.EDIT_MAX_LEN, elements that are no int32) is scored by those host functions instead, not refused."""
+    from . import ops
+    a_seqs, b_seqs = list(a_seqs), list(b_seqs)
+    if len(a_seqs) != len(b_seqs):
+        raise ValueError(f"edit_align_batch: {len(a_seqs)} sequences against {len(b_seqs)}")
+    n = len(a_seqs)
+    dist, counts, aligns = [None] * n, [None] * n, [None] * n if want_ops else None
+    on = _device_pairs(a_seqs, b_seqs)
+    taken = set(on)
+    for k in range(n):
+        if k not in taken:
+            dist[k] = levenshtein(a_seqs[k], b_seqs[k])
+            counts[k] = compute_edit_operations(a_seqs[k], b_seqs[k])
+            if want_ops:
+                aligns[k] = compute_edit_alignment(a_seqs[k], b_seqs[k])
+    if on:
+        a, a_off, b, b_off = ops.edit_align_tables([a_seqs[k] for k in on], [b_seqs[k] for k in on])
+        d, c, n_ops, steps = ops.edit_align(a.to(device), a_off, b.to(device), b_off, want_ops)
+        d, c = d.cpu().tolist(), c.cpu().tolist()
+        if want_ops:
+            n_ops, steps, start = n_ops.cpu().tolist(), steps.cpu().numpy(), (a_off + b_off).tolist()
+        for q, k in enumerate(on):
+            dist[k], counts[k] = d[q], tuple(c[q])
+            if want_ops:
+                aligns[k] = [tuple(r) for r in steps[start[q]: start[q] + n_ops[q]].tolist()]
+    return dist, counts, aligns
+
+
+def edit_distances(a_seqs, b_seqs, device="cuda") -> List[int]:
+    """levenshtein(a, b) of every pair, on the device (edit_align_batch)"""
+    return edit_align_batch(a_seqs, b_seqs, device)[0]
+
+
+def edit_operations(a_seqs, b_seqs, device="cuda") -> List[Tuple[int, int, int]]:
+    """compute_edit_operations(a, b) = (insertions, deletions, substitutions) of every pair, on the device (edit_align_batch)"""
+    return edit_align_batch(a_seqs, b_seqs, device)[1]
+
+
+def edit_alignments(a_seqs, b_seqs, device="cuda") -> List[List[Tuple[int, int]]]:
+    """compute_edit_alignment(a, b) of every pair, on the device (edit_align_batch)"""
+    return edit_align_batch(a_seqs, b_seqs, device, True)[2]
+
+
+class ConfusionReport:
+    """Which characters a recogniser confuses, drops and invents: accumulated from alignments of (gt, pred) with a = gt, the way
+    compute_cr calls compute_edit_operations.  sub[(g, p)]: g was read as p; dele[g]: g has no partner; ins[p]: p has no partner;
+    n[g]: occurrences of g in the ground truth; correct[g]: those that stand against an equal character.  The keys are the sequences'
+    elements (label indices in the harness)."""
+
+    def __init__(self):
+        self.sub: Dict[Tuple[int, int], int] = {}
+        self.dele: Dict[int, int] = {}
+        self.ins: Dict[int, int] = {}
+        self.n: Dict[int, int] = {}
+        self.correct: Dict[int, int] = {}
+        self.lines = 0
+
+    def add_counted(self, rows, lines: int = 0) -> "ConfusionReport":
+        """rows of (g, p, count): a step of the alignments and how often it occurred; g None = an insertion of p, p None = a deletion of g"""
+        for g, p, c in rows:
+            c = int(c)
+            if g is None:
+                self.ins[int(p)] = self.ins.get(int(p), 0) + c
+                continue
+            g = int(g)
+            self.n[g] = self.n.get(g, 0) + c
+            if p is None:
+                self.dele[g] = self.dele.get(g, 0) + c
+            elif int(p) == g:
+                self.correct[g] = self.correct.get(g, 0) + c
+            else:
+                self.sub[(g, int(p))] = self.sub.get((g, int(p)), 0) + c
+        self.lines += int(lines)
+        return self
+
+    def add_alignment(self, gt: Sequence[int], pred: Sequence[int], steps: Sequence[Tuple[int, int]]) -> "ConfusionReport":
+        """one line's alignment (compute_edit_alignment(gt, pred), or edit_alignments's) on the host"""
+        return self.add_counted(((None if i < 0 else gt[i], None if j < 0 else pred[j], 1) for i, j in steps), 1)
+
+    def add_device(self, a, a_off, b, b_off, n_ops, ops) -> "ConfusionReport":
+        """The alignments of a whole ops.edit_align call (a = the ground truths; a_off, b_off the HOST offsets, everything else on the
+        device): the gather through `ops` and the counting run on the device, only the counted table of distinct (g, p) comes back."""
+        dev = a.device
+        ao, bo = a_off.to(dev), b_off.to(dev)
+        start = ao[:-1] + bo[:-1]                                                  # first slot of every pair
+        S = int(a_off[-1]) + int(b_off[-1])
+        n = int(n_ops.numel())
+        if S and n:
+            slot = torch.arange(S, device=dev)
+            pair = (torch.searchsorted(start.contiguous(), slot, right=True) - 1).clamp(min=0)
+            # equal starts (pairs without slots) resolve to the last of them: only a pair that owns slots is ever looked at
+            keep = (slot - start[pair]) < n_ops[pair].long()
+            pair, st = pair[keep], ops[keep].long()
+            none = -(1 << 40)                                                      # no int32: the partner of an insertion / a deletion
+            ax = torch.cat([a.long(), torch.full((1,), none, dtype=torch.int64, device=dev)])      # [-1] = none
+            bx = torch.cat([b.long(), torch.full((1,), none, dtype=torch.int64, device=dev)])
+            g = ax[torch.where(st[:, 0] >= 0, ao[pair] + st[:, 0], -1)]
+            p = bx[torch.where(st[:, 1] >= 0, bo[pair] + st[:, 1], -1)]
+            keys, cnt = torch.unique(torch.stack([g, p], dim=1), dim=0, return_counts=True)
+            table = torch.cat([keys, cnt[:, None]], dim=1).cpu().tolist()
+            self.add_counted((None if g_ == none else g_, None if p_ == none else p_, c) for g_, p_, c in table)
+        self.lines += n
+        return self
+
+    def recall(self, g: int) -> float:
+        return self.correct.get(g, 0) / self.n[g]
+
+    def totals(self) -> Dict[str, int]:
+        """ins / del / sub: the sums over the lines of compute_edit_operations(gt, pred); n: ground-truth characters; correct: n - del - sub"""
+        return {"lines": self.lines, "n": sum(self.n.values()), "correct": sum(self.correct.values()), "ins": sum(self.ins.values()),
+                "del": sum(self.dele.values()), "sub": sum(self.sub.values())}
+
+    def __eq__(self, other):
+        return isinstance(other, ConfusionReport) and all(getattr(self, k) == getattr(other, k) for k in ("sub", "dele", "ins", "n", "correct", "lines"))
+
+    def to_json(self, charset: Optional[Sequence] = None, top: int = 50) -> Dict:
+        """The object `--confusion-out` writes.  Every list is sorted by count descending, then by (gt, pred) label ascending, and cut to
+        its first `top` entries; charset given: entries also carry the characters."""
+        cs = list(charset) if charset is not None else None
+        name = lambda v: {} if cs is None else {"c": str(cs[v])}                                         # noqa: E731
+
+        def ranked(d):
+            return sorted(d.items(), key=lambda kv: (-kv[1], kv[0]))[: int(top)]
+
+        return {"totals": self.totals(),
+                "substitutions": [{"gt": g, "pred": p, "count": c, **({} if cs is None else {"gt_c": str(cs[g]), "pred_c": str(cs[p])})}
+                                  for (g, p), c in ranked(self.sub)],
+                "deletions": [{"gt": g, "count": c, **name(g)} for g, c in ranked(self.dele)],
+                "insertions": [{"pred": p, "count": c, **name(p)} for p, c in ranked(self.ins)],
+                "characters": [{"gt": g, "n": c, "correct": self.correct.get(g, 0), "recall": self.recall(g), **name(g)}
+                               for g, c in ranked(self.n)]}
 
 
 _WER_PUNCT = re.compile(r"""([\[\]{}/\()"'&+*=<>?.;:,!\-—_€#%°])""")

@@ -1843,3 +1843,5 @@ def topk_rows_masked(scores, excl, k: int):
 # (tests/test_ops_seam_host.py, tests/test_abi_header_host.py) hold every symbol NAMED in this file against _lib._SIGNATURES, the
 # table of include/dtlr_hip.h alone, which does not grow.  Imported last, so that nothing here depends on it.
 from .lexicon import LEXICON_WORKSPACE_LIMIT, lexicon_decode, lexicon_tables, lexicon_upload          # noqa: E402,F401
+# the third header (include/dtlr_metrics.h), the same way: written in dtlr_amd/metrics.py
+from .metrics import EDIT_MAX_LEN, EDIT_WORKSPACE_LIMIT, edit_align, edit_align_chunks, edit_align_tables   # noqa: E402,F401
