@@ -106,6 +106,9 @@ _LEXICON_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, param
 # include/dtlr_metrics.h, the third header (edit distance and alignment): the same again; its one constant stays in its own table too
 _METRICS_FUNCTIONS, _, METRICS_CONSTANTS = _read_header_file("dtlr_metrics.h")
 _METRICS_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _METRICS_FUNCTIONS.items()}
+# include/dtlr_wordbeam.h, the fourth header (the word beam search): the same again
+_WORDBEAM_FUNCTIONS = _read_header_file("dtlr_wordbeam.h")[0]
+_WORDBEAM_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _WORDBEAM_FUNCTIONS.items()}
 globals().update(CONSTANTS)            # DTLR_OK, DTLR_EINVAL .. DTLR_ELAUNCH; the dtype codes DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S
 
 
@@ -121,7 +124,7 @@ class NgramLM(ctypes.Structure):
 
 def takes_stream(name: str) -> bool:
     """whether the entry point's last parameter is `void *stream` (it is then reached through launch())"""
-    params = (_FUNCTIONS.get(name) or _LEXICON_FUNCTIONS.get(name) or _METRICS_FUNCTIONS[name])[1]
+    params = (_FUNCTIONS.get(name) or _LEXICON_FUNCTIONS.get(name) or _METRICS_FUNCTIONS.get(name) or _WORDBEAM_FUNCTIONS[name])[1]
     return bool(params) and params[-1] == (c_void_p, "stream")
 
 
@@ -130,7 +133,8 @@ def _load(path: str) -> ctypes.CDLL:
         raise DTLRError(f"{path} not built: run `python -m dtlr_amd.build` (needs hipcc); "
                         "the DTLR HIP path has no CPU/PyTorch fallback")
     L = ctypes.CDLL(path)                  # RTLD_LOCAL: the two builds export the same symbol names and never see each other
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_LEXICON_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_LEXICON_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items())
+                              + list(_WORDBEAM_SIGNATURES.items())):
         fn = getattr(L, name)          # AttributeError if the .so is stale -> loud
         fn.restype, fn.argtypes = res, args
     return L

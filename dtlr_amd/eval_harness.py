@@ -130,6 +130,8 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
     (DINO.forward(per_line=True)): every line gets the result it gets alone.
     ngram (`--ngram-arpa`): the bundle of ngram_bundle(); the batch's lines are then re-scored by the device n-gram beam decoder
     (ngram.rescored_labels_batch: one launch over every word span of the batch) instead of decoded by the blank / NMS decoder.
+    A bundle of word_beam_bundle() (`--word-beam-lexicon`) sends the batch's whole lines to the device word beam search instead
+    (ngram.word_beam_labels_batch).
     spot (`--spot-words`): the bundle of spot_bundle(); every batch's output is also searched for its keywords (spot_batch)."""
     lazy = callable(images)
     if lazy and sizes is None:
@@ -150,7 +152,7 @@ def predict_labels(model, images, batch: int = 32, exact: bool = True, TH: Optio
             spot_batch(spot, out, samples, idx)
         if ngram is not None:
             from . import ngram as NG
-            preds = NG.rescored_labels_batch(out, ngram)
+            preds = NG.word_beam_labels_batch(out, ngram) if ngram.get("word_beam") else NG.rescored_labels_batch(out, ngram)
         else:
             preds = E.decode_nms(out, postprocessor, TH, NM) if (TH is not None and NM is not None) else E.decode_blank(out)
         for i, p in zip(idx, preds):
@@ -775,6 +777,48 @@ def lexicon_bundle(args, charset: Sequence, device) -> Optional[Dict]:
                 no_digits=args.no_digits, no_dash=args.no_dash, multiply_pred_logits_by=args.multiply_pred_logits_by)
 
 
+def check_word_beam_args(args) -> None:
+    """the refusals of the --word-beam flags, before any work (main calls it first); without --word-beam-lexicon the others are not read"""
+    if not args.word_beam_lexicon:
+        if args.word_beam_arpa:
+            raise SystemExit("--word-beam-arpa needs --word-beam-lexicon: the word n-gram scores the dictionary's words")
+        return
+    if args.ngram_arpa or args.lexicon:
+        raise SystemExit("--word-beam-lexicon decodes whole lines, --ngram-arpa and --lexicon the word spans of the argmax: give one")
+    if args.layout_out or args.layout_align:
+        raise SystemExit("--word-beam-lexicon has no located output: not together with --layout-out / --layout-align")
+    if not 1 <= args.word_beam_beam <= 64:
+        raise SystemExit(f"--word-beam-beam {args.word_beam_beam} outside 1..64")
+    if args.word_beam_beam_token is not None and args.word_beam_beam_token < 0:
+        raise SystemExit(f"--word-beam-beam-token {args.word_beam_beam_token} is negative")
+
+
+def word_beam_bundle(args, charset: Sequence, device) -> Optional[Dict]:
+    """What predict_labels(ngram=...) takes when whole lines go to the device word beam search (`--word-beam-lexicon`); None without
+    it.  A word that cannot be packed (a character that is no token, more than 64 characters) is named on stderr and skipped; counts in
+    the file are not used.  Separators: every channel no dictionary word uses."""
+    if not args.word_beam_lexicon:
+        return None
+    from . import ngram as NG
+    tokens, _, _ = _ngram_tokens_ignore(args, charset)
+    words, _ = load_lexicon(args.word_beam_lexicon)
+    good = []
+    chan_of = {t: c for c, t in enumerate(tokens) if c > 0}
+    for w in words:
+        try:
+            NG.spell_word(w, chan_of, "--word-beam-lexicon")
+        except ValueError as e:
+            print(f"{e}: skipped", file=sys.stderr)
+            continue
+        good.append(w)
+    if not good:
+        raise SystemExit(f"--word-beam-lexicon: {args.word_beam_lexicon} holds no word that can be spelled with the tokens")
+    lm = NG.ArpaLM(args.word_beam_arpa) if args.word_beam_arpa else None
+    dec = NG.DeviceWordBeamDecoder(tokens, good, lm, args.word_beam_weight if lm is not None else 0.0, args.word_beam_beam,
+                                   args.word_beam_beam_token, lookahead=not args.word_beam_no_lookahead, blank_token=tokens[0], device=device)
+    return dict(decoder=dec, word_beam=True, multiply_pred_logits_by=args.multiply_pred_logits_by)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m dtlr_amd.evaluation", description=__doc__.split("\n\n")[0])
     # the reference's flags (evaluation.py:15-27)
@@ -818,6 +862,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="a span takes its best word when exp((score - base) / characters) >= this, else it keeps its argmax")
     ap.add_argument("--lexicon-prior-weight", type=float, default=0.0, help="weight of ln(count / sum of counts) in a word's key")
     ap.add_argument("--lexicon-nbest", type=int, default=1, help="words returned per span, 1..8")
+    ap.add_argument("--word-beam-lexicon", default=None, metavar="FILE",
+                    help="word beam search of the WHOLE line on the device: only the words of FILE (the format of --lexicon), with "
+                         "separators between them; uses --ngram-tokens; not together with --ngram-arpa, --lexicon, --layout-out, --layout-align")
+    ap.add_argument("--word-beam-arpa", default=None, metavar="FILE", help="word-level n-gram in ARPA text that scores the word sequence")
+    ap.add_argument("--word-beam-weight", type=float, default=0.5, help="weight of the word n-gram")
+    ap.add_argument("--word-beam-beam", type=int, default=50, help="beam size, 1..64")
+    ap.add_argument("--word-beam-beam-token", type=int, default=None, help="tokens extended per frame (default: all)")
+    ap.add_argument("--word-beam-no-lookahead", action="store_true",
+                    help="rank a hypothesis inside a word without the best unigram of the words it can still become")
     ap.add_argument("--multiply_pred_logits_by", type=float, default=1.0)
     ap.add_argument("--no_uppercase_words", action="store_true")
     ap.add_argument("--no_digits", action="store_true")
@@ -870,6 +923,7 @@ def write_confusion(path: str, report: "E.ConfusionReport", charset: Sequence, t
 def main(argv: Optional[Sequence[str]] = None) -> Dict:
     args = build_parser().parse_args(argv)
     check_lexicon_args(args)
+    check_word_beam_args(args)
     check_metrics_args(args)
     from .dino import DINO, PostProcess
     rank, local, world = ddist.init_from_env()
@@ -913,7 +967,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     images = lambda i: read_rgb(paths[i])                      # noqa: E731
     texts = [t for _, t in rows]
     post = PostProcess(num_select=cfg.num_select, nms_iou_threshold=cfg.nms_iou_threshold)
-    bundle = ngram_bundle(args, charset, dev) or lexicon_bundle(args, charset, dev)
+    bundle = ngram_bundle(args, charset, dev) or lexicon_bundle(args, charset, dev) or word_beam_bundle(args, charset, dev)
     extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
     spot = None

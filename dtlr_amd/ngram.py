@@ -21,7 +21,10 @@ and sends every word's emissions through torchaudio's lexicon CTC beam decoder w
   * the decoder the reference calls is, in its main mode, a WORD-lexicon decoder.  `DeviceLexiconDecoder` is closed-vocabulary decoding
     of the same word spans on the device (csrc/lexicon.hip, dtlr_lexicon_decode): the best words of a lexicon
     of tens of thousands of words per span by an exact max-product pass over the lexicon's trie (`pack_lexicon`), through the batched
-    route of `get_ngram_predictions_batch`.
+    route of `get_ngram_predictions_batch`;
+  * both of these work on word spans the argmax has already cut.  `DeviceWordBeamDecoder` decodes the WHOLE line against a dictionary
+    and a word-level n-gram on the device (csrc/word_beam.hip, dtlr_word_beam, DESIGN.md section 17: Scheidl et al., "Word Beam
+    Search", 2018), so a space the model missed or invented can be repaired; `word_beam_labels_batch` is its batched route.
 
 WHAT IS PINNED: (a) to the reference, by vectors its own function bodies produced (G8): emissions, span selection, re-assembly;
 (b) the device decoder's semantics, written down in DESIGN.md section 10: the kernel equals a dict-based fp64 restatement of them, and
@@ -444,17 +447,17 @@ class DeviceNgramDecoder:
 LEXICON_MAX_WORD = 64
 
 
-def spell_word(word: str, chan_of: Dict[str, int]) -> Tuple[int, ...]:
+def spell_word(word: str, chan_of: Dict[str, int], what: str = "pack_lexicon") -> Tuple[int, ...]:
     """the emission channels of a lexicon word (chan_of: token -> channel, the blank left out; " " is the token <space>).  ValueError,
     naming the word, when it is empty, longer than 64 characters or holds a character that is no token."""
     w = str(word)
     if not w:
-        raise ValueError("pack_lexicon: an empty word ''")
+        raise ValueError(f"{what}: an empty word ''")
     if len(w) > LEXICON_MAX_WORD:
-        raise ValueError(f"pack_lexicon: {w!r} has {len(w)} characters, the limit is {LEXICON_MAX_WORD}")
+        raise ValueError(f"{what}: {w!r} has {len(w)} characters, the limit is {LEXICON_MAX_WORD}")
     z = tuple(chan_of.get(ch, chan_of.get(_lm_word(ch), -1)) for ch in w)
     if min(z) < 1:
-        raise ValueError(f"pack_lexicon: {w!r} holds the character {w[z.index(min(z))]!r}, which is no token")
+        raise ValueError(f"{what}: {w!r} holds the character {w[z.index(min(z))]!r}, which is no token")
     return z
 
 
@@ -608,6 +611,140 @@ class DeviceLexiconDecoder:
         labels, lengths, scores = self.decode_spans(em, [(b, 0, T) for b in range(B)])
         labels, lengths, scores = labels.cpu().tolist(), lengths.cpu().tolist(), scores.cpu().tolist()
         return [[_Hypothesis(self.words(labels[b], lengths[b]), scores[b])] for b in range(B)]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# The device word beam search: whole lines against a dictionary and a word n-gram (csrc/word_beam.hip).
+def pack_word_trie(words: Sequence[str], tokens: Sequence[str], lm: Optional[ArpaLM] = None, separators: Optional[Sequence[str]] = None,
+                   blank_token: str = "<ctc>") -> Dict:
+    """The dictionary as the trie dtlr_word_beam reads (include/dtlr_wordbeam.h), as CPU tensors.  Pure host code.  A word is a string
+    whose every character is a token (spell_word); duplicates merge: word id = the rank of a word's first occurrence.  ValueError,
+    naming the word, for an empty word, one longer than 64 characters, one with a character that is no token or one that holds a
+    separator.  Nodes are sorted by (depth, channels): node 0 the root, parent < child, a node's children contiguous and sorted by
+    channel.  separators: the tokens that stand between words; every other non-blank channel is then a word character.  None: a channel
+    is a word character iff some word uses it, every other one a separator.  lm: a WORD-level model; ahead[node] = the largest
+    lm.score((), word) of the words at or below the node, 0 at the root and everywhere without lm.
+    -> dict(child_lo, child_hi, chan, word [n_nodes] int32; ahead [n_nodes] fp64; cls [V] int32; n_words; words; spellings)."""
+    V = len(tokens)
+    chan_of = {t: c for c, t in enumerate(tokens) if t != blank_token}
+    seen: Dict[str, int] = {}
+    spellings: List[Tuple[int, ...]] = []
+    for w in words:
+        w = str(w)
+        if w in seen:
+            continue
+        seen[w] = len(spellings)
+        spellings.append(spell_word(w, chan_of, "pack_word_trie"))
+    names = list(seen)
+    if separators is None:
+        used = {c for z in spellings for c in z}
+        cls = [0] + [1 if c in used else 2 for c in range(1, V)]
+    else:
+        sep = set()
+        for t in separators:
+            c = chan_of.get(t, chan_of.get(_lm_word(t), -1))
+            if c < 1:
+                raise ValueError(f"pack_word_trie: the separator {t!r} is no token")
+            sep.add(c)
+        cls = [0] + [2 if c in sep else 1 for c in range(1, V)]
+        for w, z in zip(names, spellings):
+            if sep.intersection(z):
+                raise ValueError(f"pack_word_trie: {w!r} holds a separator")
+    ends = {z: i for i, z in enumerate(spellings)}
+    nodes = {z[:k] for z in spellings for k in range(1, len(z) + 1)}
+    order_list = [()] + sorted(nodes, key=lambda g: (len(g), g))
+    index = {g: i for i, g in enumerate(order_list)}
+    n = len(order_list)
+    lo, hi, chan, word, ahead = [0] * n, [0] * n, [0] * n, [-1] * n, [float("-inf")] * n
+    for i, z in enumerate(spellings):
+        s = float(lm.score((), names[i])) if lm is not None else 0.0
+        for k in range(1, len(z) + 1):
+            j = index[z[:k]]
+            ahead[j] = max(ahead[j], min(s, 0.0))
+    ahead[0] = 0.0
+    for i in range(n - 1, 0, -1):                     # descending: the last write of lo[parent] is its first child
+        g = order_list[i]
+        par = index[g[:-1]]
+        lo[par] = i
+        hi[par] = max(hi[par], i + 1)
+        chan[i], word[i] = g[-1], ends.get(g, -1)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)                # noqa: E731
+    return dict(child_lo=i32(lo), child_hi=i32(hi), chan=i32(chan), word=i32(word), ahead=torch.tensor(ahead, dtype=torch.float64),
+                cls=i32(cls), n_words=len(spellings), words=names, spellings=[list(z) for z in spellings])
+
+
+class DeviceWordBeamDecoder:
+    """Word beam search on the device (dtlr_word_beam; semantics: DESIGN.md section 17): CTC prefix beam search over whole lines whose
+    hypotheses are dictionary words with separators between them, scored by an optional word-level back-off n-gram.  tokens[c] = the
+    string of emission channel c, tokens[0] = the blank; words: the dictionary (pack_word_trie; may be empty: every channel is then a
+    separator); lm: an ArpaLM over the words as they are written in `words`; separators: see pack_word_trie.
+    decode_lines(emissions [B,T,V] CUDA, spans [(line, first, end)]) -> (labels, lengths, scores) on the device, all spans in one launch;
+    a span whose final beam holds no complete hypothesis has length -1, score -inf and labels -1.
+    __call__(emissions [B,T,V], CUDA or CPU) keeps torchaudio's interface: [[hypothesis]] with .words (token strings) and .score."""
+
+    def __init__(self, tokens: Sequence[str], words: Sequence[str], lm: Optional[ArpaLM] = None, lm_weight: float = 0.0, beam_size: int = 50,
+                 beam_size_token: Optional[int] = None, separators: Optional[Sequence[str]] = None, lookahead: bool = True,
+                 bos: Optional[bool] = None, eos: Optional[bool] = None, blank_token: str = "<ctc>", device="cuda"):
+        self.tokens = list(tokens)
+        if not self.tokens or self.tokens[0] != blank_token:
+            raise ValueError("DeviceWordBeamDecoder: the blank must be emission channel 0 (what dtlr_blank_emissions writes)")
+        if not 1 <= int(beam_size) <= 64:
+            raise ValueError("DeviceWordBeamDecoder: beam_size must be in 1..64")
+        self.lm_weight, self.beam_size, self.beam_size_token = float(lm_weight), int(beam_size), int(beam_size_token or 0)
+        self.lookahead = bool(lookahead)
+        self.device = torch.device(device)
+        self.trie = pack_word_trie(words, self.tokens, lm, separators, blank_token)
+        self.packed = pack_lm(lm, ["<ctc>"] + self.trie["words"], "<ctc>") if lm is not None else None
+        self.bos = bool(self.packed and self.packed["has_bos"]) if bos is None else bool(bos)
+        self.eos = bool(self.packed and self.packed["has_eos"]) if eos is None else bool(eos)
+        self._on: Dict = {}
+
+    def _tables_on(self, emissions: torch.Tensor) -> Dict:
+        """the dictionary (checked by ops.word_beam_upload) and the LM on the emissions' device: made once per (device, V)"""
+        key = (str(emissions.device), int(emissions.shape[2]))
+        if key not in self._on:
+            from . import ops
+            dev = emissions.device
+            lm = None
+            if self.packed is not None:
+                lm = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in self.packed.items() if k != "_host"}
+            self._on[key] = dict(trie=ops.word_beam_upload(self.trie, key[1], dev), lm=lm)
+        return self._on[key]
+
+    def decode_lines(self, emissions: torch.Tensor, spans):
+        from . import ops
+        tb = self._tables_on(emissions)
+        return ops.word_beam(emissions, spans, tb["trie"], tb["lm"], self.lm_weight, self.beam_size, self.beam_size_token, self.bos,
+                             self.eos, self.lookahead)
+
+    def words(self, labels_row: Sequence[int], length: int) -> List[str]:
+        return [self.tokens[int(c)] for c in labels_row[:max(length, 0)]]
+
+    def __call__(self, emissions: torch.Tensor) -> List[List[_Hypothesis]]:
+        B, T = emissions.shape[0], emissions.shape[1]
+        if B == 0:
+            return []
+        em = emissions if emissions.is_cuda else emissions.to(self.device)
+        labels, lengths, scores = self.decode_lines(em, [(b, 0, T) for b in range(B)])
+        labels, lengths, scores = labels.cpu().tolist(), lengths.cpu().tolist(), scores.cpu().tolist()
+        return [[_Hypothesis(self.words(labels[b], lengths[b]), scores[b])] for b in range(B)]
+
+
+@torch.no_grad()
+def word_beam_labels_batch(outputs, bundle: Dict) -> List[List[int]]:
+    """The lines of a batch decoded by the word beam search as LABEL ids (channel - 1), for the evaluation harness: `bundle` =
+    dict(decoder=DeviceWordBeamDecoder, multiply_pred_logits_by).  Emissions by the device kernel, ONE dtlr_word_beam launch over the
+    whole lines, one copy of the records back.  A line without a complete hypothesis (length -1) keeps the blank decoder's own reading
+    (evaluation.decode_blank)."""
+    dec = bundle["decoder"]
+    emissions = get_new_pred_logits(outputs, bundle.get("multiply_pred_logits_by", 1.0))
+    B, T = emissions.shape[0], emissions.shape[1]
+    if B == 0:
+        return []
+    labels, lengths, _ = dec.decode_lines(emissions, [(b, 0, T) for b in range(B)])
+    labels, lengths = labels.cpu().tolist(), lengths.cpu().tolist()
+    own = E.decode_blank(outputs) if min(lengths) < 0 else None
+    return [[c - 1 for c in labels[b][:lengths[b]]] if lengths[b] >= 0 else list(own[b]) for b in range(B)]
 
 
 @torch.no_grad()

@@ -1845,3 +1845,5 @@ def topk_rows_masked(scores, excl, k: int):
 from .lexicon import LEXICON_WORKSPACE_LIMIT, lexicon_decode, lexicon_tables, lexicon_upload          # noqa: E402,F401
 # the third header (include/dtlr_metrics.h), the same way: written in dtlr_amd/metrics.py
 from .metrics import EDIT_MAX_LEN, EDIT_WORKSPACE_LIMIT, edit_align, edit_align_chunks, edit_align_tables   # noqa: E402,F401
+# the fourth header (include/dtlr_wordbeam.h), the same way: written in dtlr_amd/wordbeam.py
+from .wordbeam import word_beam, word_beam_tables, word_beam_upload          # noqa: E402,F401
