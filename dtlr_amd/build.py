@@ -20,8 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wal
 
 
 # the C headers: a change to any rebuilds the objects (dtlr_lexicon.h: the lexicon decoder's entry points; dtlr_metrics.h: the edit
-# distance's; dtlr_wordbeam.h: the word beam search's)
-HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h", "dtlr_metrics.h", "dtlr_wordbeam.h")]
+# distance's; dtlr_wordbeam.h: the word beam search's; dtlr_lm.h: the radix sort's and the n-gram estimator's)
+HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h", "dtlr_metrics.h", "dtlr_wordbeam.h", "dtlr_lm.h")]
 
 
 def _sources():

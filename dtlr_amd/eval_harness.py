@@ -703,12 +703,19 @@ def _ngram_tokens_ignore(args, charset: Sequence):
 
 
 def ngram_bundle(args, charset: Sequence, device) -> Optional[Dict]:
-    """What predict_labels(ngram=...) takes, from the command line; None without --ngram-arpa."""
-    if not args.ngram_arpa:
+    """What predict_labels(ngram=...) takes, from the command line; None without --ngram-arpa / --ngram-train-text."""
+    if not args.ngram_arpa and not args.ngram_train_text:
         return None
     from . import ngram as NG
     tokens, ngram_charset, ignore = _ngram_tokens_ignore(args, charset)
-    dec = NG.DeviceNgramDecoder(tokens, NG.ArpaLM(args.ngram_arpa), args.ngram_weight, args.ngram_beam, args.ngram_beam_token,
+    if args.ngram_train_text:
+        from . import lmtrain
+        with open(args.ngram_train_text, encoding="utf-8") as f:
+            lines = lmtrain.char_lines(f, keep=[str(c) for c in charset])
+        lm = lmtrain.train_ngram(lines, args.ngram_order, device=device).to_arpa_lm()
+    else:
+        lm = NG.ArpaLM(args.ngram_arpa)
+    dec = NG.DeviceNgramDecoder(tokens, lm, args.ngram_weight, args.ngram_beam, args.ngram_beam_token,
                                 blank_token=tokens[0], device=device)
     return dict(decoder=dec, ignore=ignore, ngram_charset=ngram_charset, no_uppercase_words=args.no_uppercase_words,
                 no_digits=args.no_digits, no_dash=args.no_dash, multiply_pred_logits_by=args.multiply_pred_logits_by)
@@ -739,7 +746,7 @@ def check_lexicon_args(args) -> None:
     """the refusals of the --lexicon flags, before any work (main calls it first); without --lexicon the other three are not read"""
     if not args.lexicon:
         return
-    if args.ngram_arpa:
+    if args.ngram_arpa or args.ngram_train_text:
         raise SystemExit("--lexicon and --ngram-arpa are two decoders for the same word spans: give one")
     if not 1 <= args.lexicon_nbest <= 8:
         raise SystemExit(f"--lexicon-nbest {args.lexicon_nbest} outside 1..8")
@@ -783,7 +790,7 @@ def check_word_beam_args(args) -> None:
         if args.word_beam_arpa:
             raise SystemExit("--word-beam-arpa needs --word-beam-lexicon: the word n-gram scores the dictionary's words")
         return
-    if args.ngram_arpa or args.lexicon:
+    if args.ngram_arpa or args.ngram_train_text or args.lexicon:
         raise SystemExit("--word-beam-lexicon decodes whole lines, --ngram-arpa and --lexicon the word spans of the argmax: give one")
     if args.layout_out or args.layout_align:
         raise SystemExit("--word-beam-lexicon has no located output: not together with --layout-out / --layout-align")
@@ -849,7 +856,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--size", type=int, default=EVAL_SIZE, help="eval resize: short side (config/coco_transformer.py:1)")
     ap.add_argument("--max_size", type=int, default=EVAL_MAX_SIZE, help="eval resize: long-side cap (config/coco_transformer.py:2)")
     # n-gram re-scoring (the reference's ngram/ path; ngram/IAM.yaml: 6-gram character model, weight 0.25, per word)
-    ap.add_argument("--ngram-arpa", default=None, help="character n-gram in ARPA text: switches re-scoring by the device beam decoder on")
+    lm_source = ap.add_mutually_exclusive_group()               # one character n-gram: read, or trained here
+    lm_source.add_argument("--ngram-arpa", default=None, help="character n-gram in ARPA text: switches re-scoring by the device beam decoder on")
+    lm_source.add_argument("--ngram-train-text", default=None, metavar="FILE",
+                           help="instead of --ngram-arpa: train the character n-gram on the device from this UTF-8 text (dtlr_amd.lmtrain, "
+                                "level char-word: every word a line of its characters, characters outside the charset dropped)")
+    ap.add_argument("--ngram-order", type=int, default=5, help="order of the model --ngram-train-text trains, 1..8")
     ap.add_argument("--ngram-weight", type=float, default=0.25)
     ap.add_argument("--ngram-beam", type=int, default=50, help="beam size, 1..64")
     ap.add_argument("--ngram-beam-token", type=int, default=None, help="tokens extended per frame (default: all)")

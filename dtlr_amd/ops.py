@@ -1847,3 +1847,5 @@ from .lexicon import LEXICON_WORKSPACE_LIMIT, lexicon_decode, lexicon_tables, le
 from .metrics import EDIT_MAX_LEN, EDIT_WORKSPACE_LIMIT, edit_align, edit_align_chunks, edit_align_tables   # noqa: E402,F401
 # the fourth header (include/dtlr_wordbeam.h), the same way: written in dtlr_amd/wordbeam.py
 from .wordbeam import word_beam, word_beam_tables, word_beam_upload          # noqa: E402,F401
+# the fifth header (include/dtlr_lm.h), the same way: written in dtlr_amd/lmtrain.py
+from .lmtrain import SORT_TILE, lm_tables, sort_u64          # noqa: E402,F401
