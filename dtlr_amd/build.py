@@ -22,6 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wal
 # the C headers: a change to any rebuilds the objects (dtlr_lexicon.h: the lexicon decoder's entry points; dtlr_metrics.h: the edit
 # distance's; dtlr_wordbeam.h: the word beam search's; dtlr_lm.h: the radix sort's and the n-gram estimator's)
 HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_hip.h", "dtlr_lexicon.h", "dtlr_metrics.h", "dtlr_wordbeam.h", "dtlr_lm.h")]
+# the headers after the fifth (dtlr_pattern.h: the regular-expression decoder's entry points).  HEADERS is pinned at its five entries by
+# the host test of the fifth header, so later headers join the fingerprint and the objects' hashes through this second list
+MORE_HEADERS = [os.path.join(HERE, "..", "include", h) for h in ("dtlr_pattern.h",)]
 
 
 def _sources():
@@ -30,7 +33,7 @@ def _sources():
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS:
+    for p in _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS + MORE_HEADERS:
         with open(p, "rb") as f:
             h.update(os.path.basename(p).encode() + b"\0" + f.read())   # path-independent: the tree moves on the GPU box
     h.update(" ".join(FLAGS).encode())
@@ -42,7 +45,7 @@ LIB_F16 = os.path.join(HERE, "libdtlr_hip_f16.so")
 
 def _src_hash(src, defs) -> str:
     h = hashlib.sha256()
-    for p in [src] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS:
+    for p in [src] + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + HEADERS + MORE_HEADERS:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(defs).encode())

@@ -445,10 +445,13 @@ def write_aligned(path: str, ids: Sequence[str], lines: Sequence[Optional["E.Loc
     return k
 
 
-def spot_bundle(words: Sequence[str], charset: Sequence[str], min_conf: float = 0.5, max_hits: int = 4) -> Dict:
+def spot_bundle(words: Sequence[str], charset: Sequence[str], min_conf: float = 0.5, max_hits: int = 4,
+                patterns: Sequence[str] = (), bonus: Optional[float] = None) -> Dict:
     """What predict_labels / predict_located take as `spot`: the words that can be searched (1..32 characters, all in the charset) as
     label lists, and `hits`: image index -> its KeywordHits, filled batch by batch.  A word that cannot be searched is named on stderr
-    and skipped."""
+    and skipped.  patterns (`--spot-patterns`): expressions in the dialect of dtlr_amd/pattern.py, compiled here against the charset;
+    one that does not compile, or that accepts the empty string, is named on stderr and skipped.  bonus (`--spot-length-bonus`): the
+    expressions' length bonus, None = -ln(min_conf)."""
     if not 1 <= int(max_hits) <= 16:
         raise ValueError(f"--spot-max-hits {max_hits} outside 1..16")
     if not 0.0 <= float(min_conf) <= 1.0:
@@ -462,7 +465,29 @@ def spot_bundle(words: Sequence[str], charset: Sequence[str], min_conf: float = 
         else:
             kept.append(w)
             keywords.append(z)
-    return dict(words=kept, keywords=keywords, min_conf=float(min_conf), max_hits=int(max_hits), hits={})
+    regexes, automata = [], []
+    if patterns:
+        from .pattern import compile_pattern
+        for rx in patterns:
+            try:
+                auto = compile_pattern(rx, list(charset))
+            except ValueError as e:
+                print(f"--spot-patterns: {e}: skipped", file=sys.stderr)
+                continue
+            if auto.accepts_empty:
+                print(f"--spot-patterns: pattern {rx!r} accepts the empty string: skipped", file=sys.stderr)
+                continue
+            regexes.append(rx)
+            automata.append(auto)
+    return dict(words=kept, keywords=keywords, min_conf=float(min_conf), max_hits=int(max_hits), hits={}, patterns=regexes,
+                automata=automata, bonus=None if bonus is None else float(bonus), charset=list(charset))
+
+
+def load_spot_patterns(path: str) -> List[str]:
+    """`--spot-patterns`: one expression per line, UTF-8; empty lines are dropped, a repeated expression is searched once"""
+    with open(path, encoding="utf-8") as f:
+        lines = [ln.rstrip("\r\n") for ln in f]
+    return list(dict.fromkeys(ln for ln in lines if ln))
 
 
 def load_spot_words(path: str) -> List[str]:
@@ -474,21 +499,30 @@ def load_spot_words(path: str) -> List[str]:
 
 @torch.no_grad()
 def spot_batch(spot: Dict, out, samples, idx: Sequence[int]) -> None:
-    """search the batch's output for the bundle's keywords (E.spot_keywords, eps = 0.003, boxes in the source images' pixels)"""
-    if not spot["keywords"]:
+    """search the batch's output for the bundle's keywords (E.spot_keywords, eps = 0.003, boxes in the source images' pixels) and
+    then for its expressions (E.spot_patterns): a line's word hits come first"""
+    if not spot["keywords"] and not spot.get("automata"):
         return
     hw = torch.tensor(samples.orig_sizes, dtype=torch.float32)
-    for i, hits in zip(idx, E.spot_keywords(out, spot["keywords"], spot["min_conf"], spot["max_hits"], 0.003, hw)):
-        spot["hits"][i] = hits
+    if spot["keywords"]:
+        for i, hits in zip(idx, E.spot_keywords(out, spot["keywords"], spot["min_conf"], spot["max_hits"], 0.003, hw)):
+            spot["hits"][i] = hits
+    if spot.get("automata"):
+        found = E.spot_patterns(out, spot["automata"], spot["charset"], spot["min_conf"], spot["max_hits"], spot["bonus"], 0.003, hw)
+        for i, hits in zip(idx, found):
+            spot["hits"][i] = spot["hits"].get(i, []) + hits if spot["keywords"] else hits
 
 
 def write_spotted(path: str, ids: Sequence[str], spot: Dict, charset: Sequence[str]) -> int:
-    """`--spot-out`: one JSON object per hit, in dataset order, then the word list's, then best first.  -> hits written."""
+    """`--spot-out`: one JSON object per hit, in dataset order, then the word list's (and after the words the expressions'), then
+    best first.  -> hits written."""
     k = 0
+    regexes = spot.get("patterns") or []
     with open(path, "w", encoding="utf-8") as f:
         for i, line_id in enumerate(ids):
             for hit in spot["hits"].get(i, ()):
-                f.write(json.dumps(E.keyword_hit_to_json(hit, charset, line_id), ensure_ascii=False) + "\n")
+                regex = regexes[hit.pattern] if hit.pattern is not None else None
+                f.write(json.dumps(E.keyword_hit_to_json(hit, charset, line_id, regex), ensure_ascii=False) + "\n")
                 k += 1
     return k
 
@@ -898,6 +932,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "JSON with \"decoder\": \"align\", each character where the best CTC path puts it, plus \"logp\" and \"feasible\"")
     ap.add_argument("--spot-words", default=None, metavar="FILE",
                     help="keyword spotting: the words to look for in every line, one per line (UTF-8); needs --spot-out; single process only")
+    ap.add_argument("--spot-patterns", default=None, metavar="FILE",
+                    help="regular-expression spotting: the expressions to look for in every line, one per line (UTF-8; literals, classes, "
+                         "\\d \\w \\s, groups, |, * + ? {m,n}); shares --spot-out, --spot-min-conf and --spot-max-hits with --spot-words; "
+                         "single process only")
+    ap.add_argument("--spot-length-bonus", type=float, default=None,
+                    help="what every character adds to the key an expression's hits grow and are ranked by (default: -ln of --spot-min-conf, "
+                         "0 without a bar)")
     ap.add_argument("--spot-out", default=None, metavar="FILE.jsonl",
                     help="one JSON object per hit: the line's id, the word, conf, ratio, the ranks it covers, its box in the source image's "
                          "pixels and its characters")
@@ -939,10 +980,12 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     check_metrics_args(args)
     from .dino import DINO, PostProcess
     rank, local, world = ddist.init_from_env()
-    if bool(args.spot_words) != bool(args.spot_out):
-        raise SystemExit("--spot-words and --spot-out go together")
+    if bool(args.spot_words or args.spot_patterns) != bool(args.spot_out):
+        raise SystemExit(f"--spot-{'patterns' if args.spot_patterns and not args.spot_words else 'words'} and --spot-out go together")
     if args.spot_words and world > 1:
         raise SystemExit(f"--spot-words runs in a single process (this job has {world} ranks): hits are not merged across ranks")
+    if args.spot_patterns and world > 1:
+        raise SystemExit(f"--spot-patterns runs in a single process (this job has {world} ranks): hits are not merged across ranks")
     if not torch.cuda.is_available():
         raise SystemExit("dtlr_amd.evaluation needs an MI355X (no CPU path)")
     torch.cuda.set_device(local)
@@ -983,9 +1026,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     extra = {"ngram": bundle} if bundle is not None else {}
     last = {}
     spot = None
-    if args.spot_words:
+    if args.spot_words or args.spot_patterns:
         cs_str = [chr(c) if args.unicode else str(c) for c in charset]
-        spot = spot_bundle(load_spot_words(args.spot_words), cs_str, args.spot_min_conf, args.spot_max_hits)
+        spot = spot_bundle(load_spot_words(args.spot_words) if args.spot_words else [], cs_str, args.spot_min_conf, args.spot_max_hits,
+                           load_spot_patterns(args.spot_patterns) if args.spot_patterns else (), args.spot_length_bonus)
     if args.layout_out and len(list_TH) * len(list_NM) > 1:
         raise SystemExit("--layout-out needs one decoder setting (--TH and --NMS, or neither), not the --NMS_inference grid")
     if args.align_out:                                         # the transcripts against the model's output; apart from the decoders
@@ -1014,7 +1058,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                                        rank=rank, world=world, sizes=sizes, per_line=args.batching == "ragged", spot=spot, **extra)
             if spot is not None:                               # the first pass over the images carries the search
                 k = write_spotted(args.spot_out, [name for name, _ in rows], spot, cs_str)
-                print(f"wrote {k} hits of {len(spot['words'])} words to {args.spot_out}", file=sys.stderr)
+                what = f"{len(spot['words'])} words" + (f" and {len(spot['patterns'])} patterns" if args.spot_patterns else "")
+                print(f"wrote {k} hits of {what} to {args.spot_out}", file=sys.stderr)
                 spot = None
             if rank == 0:
                 if args.device_metrics or args.confusion_out:

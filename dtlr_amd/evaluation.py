@@ -401,6 +401,7 @@ class KeywordHit:
     conf: float
     box: Box
     chars: List[LocatedChar]
+    pattern: Optional[int] = None          # a hit of spot_patterns: the expression's index in the list (then `keyword` holds it too)
 
 
 def _spot_tables(keywords: Sequence[Sequence[int]], C: int, min_conf: float):
@@ -488,20 +489,137 @@ def spot_keywords(outputs, keywords: Sequence[Sequence[int]], min_conf: float = 
     return lines
 
 
-def keyword_hit_to_json(hit: KeywordHit, charset: Sequence, line_id: str) -> Dict:
+def keyword_hit_to_json(hit: KeywordHit, charset: Sequence, line_id: str, regex: Optional[str] = None) -> Dict:
     """The object `--spot-out` writes for one hit: the line's id, the word, its confidence and ratio, the first and the last rank
-    (frame in reading order) it covers, its box and its characters (each as in `--align-out`)."""
+    (frame in reading order) it covers, its box and its characters (each as in `--align-out`).  A hit of an expression
+    (hit.pattern is set) also carries "pattern" and, when handed in, the expression's text as "regex"; a word hit's object has
+    neither."""
     cs = list(charset)
-    return {"id": line_id, "word": "".join(str(cs[c.label]) for c in hit.chars), "keyword": hit.keyword, "line": hit.line,
-            "conf": hit.conf, "ratio": hit.ratio, "start": hit.start, "end": hit.end, "box": list(hit.box),
-            "chars": [{"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query, "rank": c.rank,
-                       "first": c.first, "last": c.last} for c in hit.chars]}
+    obj = {"id": line_id, "word": "".join(str(cs[c.label]) for c in hit.chars), "keyword": hit.keyword, "line": hit.line,
+           "conf": hit.conf, "ratio": hit.ratio, "start": hit.start, "end": hit.end, "box": list(hit.box),
+           "chars": [{"c": str(cs[c.label]), "label": c.label, "score": c.score, "box": list(c.box), "query": c.query, "rank": c.rank,
+                      "first": c.first, "last": c.last} for c in hit.chars]}
+    if hit.pattern is not None:
+        obj["pattern"] = hit.pattern
+        if regex is not None:
+            obj["regex"] = regex
+    return obj
 
 
 def keyword_hit_from_json(obj: Dict) -> KeywordHit:
     """the KeywordHit a `--spot-out` object was written from"""
     chars = [LocatedChar(c["label"], c["score"], tuple(c["box"]), c["query"], c["rank"], c["first"], c["last"]) for c in obj["chars"]]
-    return KeywordHit(obj["keyword"], obj["line"], obj["start"], obj["end"], obj["ratio"], obj["conf"], tuple(obj["box"]), chars)
+    return KeywordHit(obj["keyword"], obj["line"], obj["start"], obj["end"], obj["ratio"], obj["conf"], tuple(obj["box"]), chars,
+                      obj.get("pattern"))
+
+
+# ------------------------------------------------------------------- regular expressions over the lattice (DESIGN.md section 19)
+@dataclasses.dataclass
+class PatternRead:
+    """The best string of an expression's language over a line or span: `labels` = its label indices (None when no string of the
+    language fits the frames), `logp` = ln p of its best path (-inf then), `conf` = exp((logp - base) / max(len, 1)): the geometric
+    mean per character of the likelihood ratio against the frame-wise argmax path, in (0, 1] (0 when nothing fits)."""
+    labels: Optional[List[int]]
+    logp: float
+    conf: float
+
+
+def _automaton(pattern, charset):
+    from . import pattern as P
+    return pattern if isinstance(pattern, P.Automaton) else P.compile_pattern(pattern, charset)
+
+
+@torch.no_grad()
+def decode_pattern(outputs, pattern, charset: Sequence[str], eps: float = 0.003, spans=None, bonus: float = 0.0) -> List[PatternRead]:
+    """The best string of an expression's language for every line of the batch, or for every span (line, first rank, one past the
+    last) when `spans` is given (dtlr_pattern_decode over the emissions of dtlr_blank_emissions, chunked under ALIGN_EMISSION_BYTES).
+    pattern: the expression's text in the dialect of dtlr_amd/pattern.py, compiled against `charset`, or a compiled Automaton.  bonus:
+    what every character adds to the key candidates are compared by (logp is without it)."""
+    import math
+    from . import ops
+    from . import pattern as P
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    B, nq, C = logits.shape
+    sp = [(b, 0, nq) for b in range(B)] if spans is None else [(int(b), int(lo), int(hi)) for b, lo, hi in spans]
+    if any(not (0 <= b < B and 0 <= lo <= hi <= nq) for b, lo, hi in sp):
+        raise ValueError(f"decode_pattern: a span outside the batch of {B} lines of {nq} queries")
+    tables = P.pattern_upload(_automaton(pattern, charset), C + 1, logits.device)
+    chunk = max(1, ALIGN_EMISSION_BYTES // (nq * (C + 1) * 4))
+    out: List[Optional[PatternRead]] = [None] * len(sp)
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        mine = [k for k, (b, _, _) in enumerate(sp) if b0 <= b < b1]
+        if not mine:
+            continue
+        em = ops.blank_emissions(logits[b0:b1], boxes[b0:b1], eps)
+        rec = {k: v.cpu().tolist() for k, v in ops.pattern_decode(em, [(sp[k][0] - b0, sp[k][1], sp[k][2]) for k in mine], tables, bonus).items()}
+        del em
+        for i, k in enumerate(mine):
+            n = rec["length"][i]
+            if n < 0:
+                out[k] = PatternRead(None, float("-inf"), 0.0)
+            else:
+                out[k] = PatternRead([c - 1 for c in rec["labels"][i][:n]], rec["score"][i], math.exp((rec["score"][i] - rec["base"][i]) / max(n, 1)))
+    return out
+
+
+@torch.no_grad()
+def spot_patterns(outputs, patterns: Sequence, charset: Sequence[str], min_conf: float = 0.5, max_hits: int = 4,
+                  bonus: Optional[float] = None, eps: float = 0.003, src_hw=None) -> List[List[KeywordHit]]:
+    """Every occurrence of every expression in every line of the batch, one list of KeywordHits per line in (expression, best hit
+    first) order (dtlr_pattern_search over the emissions of dtlr_blank_emissions).  patterns: texts in the dialect of
+    dtlr_amd/pattern.py, compiled against `charset`, or compiled Automata; one that accepts the empty string raises ValueError.  A hit
+    needs conf = exp(ratio / characters) >= min_conf.  bonus: what every character adds to the key hits grow and are ranked by; None =
+    -ln(min_conf), 0 when min_conf is 0: a hit then grows over a character exactly when that character alone clears the bar.  A
+    hit's string is dtlr_pattern_decode's over its frames [start, end + 1) with the same bonus; its characters and boxes come from
+    dtlr_ctc_align of that string over the same frames of the plain lattice, as spot_records(with_chars=True) takes a word's.  In a
+    hit, `keyword` and `pattern` both hold the expression's index."""
+    import math
+    from . import ops
+    from . import pattern as P
+    logits, boxes = outputs["pred_logits"], outputs["pred_boxes"]
+    B, nq, C = logits.shape
+    if not 0.0 <= float(min_conf) <= 1.0:
+        raise ValueError(f"spot: min_conf {min_conf} outside 0..1")
+    if not 1 <= int(max_hits) <= 16:
+        raise ValueError(f"spot: max_hits {max_hits} outside 1..16")
+    bonus = P.default_bonus(float(min_conf)) if bonus is None else float(bonus)
+    tables = [P.pattern_upload(_automaton(p, charset), C + 1, logits.device) for p in patterns]
+    for tb in tables:
+        if tb["accepts_empty"]:
+            raise ValueError(f"spot: the pattern {tb['regex']!r} accepts the empty string: it is found everywhere")
+    lines: List[List[KeywordHit]] = [[] for _ in range(B)]
+    if not tables or B == 0:
+        return lines
+    order = ops.reading_order(boxes)
+    allbox = query_boxes_xyxy(boxes, src_hw)
+    chunk = max(1, ALIGN_EMISSION_BYTES // (nq * (C + 1) * 4))
+    for b0 in range(0, B, chunk):
+        b1 = min(B, b0 + chunk)
+        em = ops.blank_emissions(logits[b0:b1], boxes[b0:b1], eps)
+        for p, tb in enumerate(tables):
+            rec = {k: v.cpu().tolist() for k, v in ops.pattern_search(em, tb, min_conf, max_hits, bonus).items()}
+            idx = [(b, h) for b in range(b1 - b0) for h in range(rec["count"][b])]
+            if not idx:
+                continue
+            spans = [(b, rec["start"][b][h], rec["end"][b][h] + 1) for b, h in idx]
+            dec = ops.pattern_decode(em, spans, tb, bonus)
+            lens = dec["length"].cpu().clamp(min=0)
+            Lmax = max(int(lens.max()), 1)
+            al = ops.ctc_align(em, spans, dec["labels"][:, :Lmax].clamp(min=1).long().cpu(), lens, False)
+            line = torch.tensor([b0 + b for b, _ in idx], dtype=torch.int64)
+            query, box = gather_aligned(al["peak"], order, allbox, line)
+            host = {k: v.cpu().tolist() for k, v in dict(labels=dec["labels"], query=query, rank=al["peak"], first=al["first"],
+                                                         last=al["last"], score=al["prob"], box=box).items()}
+            for k, (b, h) in enumerate(idx):
+                n = int(lens[k])
+                z = [c - 1 for c in host["labels"][k][:n]]
+                chars = aligned_chars(z, *(host[key][k] for key in ("query", "rank", "first", "last", "score", "box")), n)
+                ratio = rec["ratio"][b][h]
+                lines[b0 + b].append(KeywordHit(p, b0 + b, rec["start"][b][h], rec["end"][b][h], ratio,
+                                                math.exp(ratio / max(rec["nchar"][b][h], 1)), union_box([c.box for c in chars]), chars, p))
+        del em
+    return lines
 
 
 def labels_to_string(labels: Sequence[int], charset: Sequence[str]) -> str:

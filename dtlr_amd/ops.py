@@ -1849,3 +1849,6 @@ from .metrics import EDIT_MAX_LEN, EDIT_WORKSPACE_LIMIT, edit_align, edit_align_
 from .wordbeam import word_beam, word_beam_tables, word_beam_upload          # noqa: E402,F401
 # the fifth header (include/dtlr_lm.h), the same way: written in dtlr_amd/lmtrain.py
 from .lmtrain import SORT_TILE, lm_tables, sort_u64          # noqa: E402,F401
+# the sixth header (include/dtlr_pattern.h), the same way: written in dtlr_amd/pattern.py, with the compiler of its automata
+from .pattern import (PATTERN_WORKSPACE_LIMIT, compile_pattern, pattern_decode, pattern_search, pattern_tables,          # noqa: E402,F401
+                      pattern_upload, words_automaton)
