@@ -114,10 +114,20 @@ class HeadTrainer:
     parameters without one (no weight decay on them), so leaving them alone is not a deviation.
 
     step / step_cached return {"loss_CTC": 0-d fp32 CUDA tensor} -- the loss BEFORE the update, as the reference logs it; reading it is
-    the caller's (only) host synchronisation.  max_norm None or <= 0: no clipping."""
+    the caller's (only) host synchronisation.  max_norm None or <= 0: no clipping.
+
+    loss: "ctc" (default: the above, unchanged), "set" or "ctc+set".  The set modes train against the reference's detection criterion
+    (dtlr_amd/criterion.py: Hungarian matching of the main output against the line's character boxes, then the sigmoid focal loss):
+    step / step_cached take `target_boxes` (per line [T,4] cxcywh in 0..1, one box a label) as well, the head's dlogits is
+    CTC_loss_coef dCTC + cls_loss_coef dfocal (the coefficients of config/Latin_CTC.py:77,81, both 1), the matcher's costs are the
+    reference's (set_cost_class 2, set_cost_bbox 5, set_cost_giou 2, focal_alpha 0.25), and the returned dict also carries loss_ce,
+    loss_bbox, loss_giou, cardinality_error and class_error of the main output.  The matcher reads the solver's status: one host
+    synchronisation a step.  A third deviation, in the set modes only:
+      * the focal loss is taken on the main output only, because `return_hidden` returns the last decoder layer's states.  The
+        reference also sums the auxiliary layers' and the intermediate output's loss_ce, which reach the shared head too."""
 
     def __init__(self, model, lr: float = 1e-5, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_norm: Optional[float] = 0.01):
+                 max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0):
         if not model.dec_pred_class_embed_share:
             raise NotImplementedError("HeadTrainer: written for dec_pred_class_embed_share (every shipped config)")
         head = model.class_embed[0]
@@ -126,6 +136,13 @@ class HeadTrainer:
         self.model = model
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
         self.max_norm = float(max_norm) if max_norm is not None else 0.0
+        if loss not in ("ctc", "set", "ctc+set"):
+            raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
+        self.loss, self.CTC_loss_coef, self.cls_loss_coef = loss, float(CTC_loss_coef), float(cls_loss_coef)
+        self.matcher = None
+        if loss != "ctc":
+            from .criterion import HungarianMatcher
+            self.matcher = HungarianMatcher(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0, focal_alpha=0.25)
         self.C, self.D = int(head.weight.shape[0]), int(head.weight.shape[1])
         dev = head.weight.device
         n = self.C * self.D + self.C
@@ -160,21 +177,40 @@ class HeadTrainer:
         return out["hs"], out["pred_boxes"]
 
     @torch.no_grad()
-    def step(self, samples, target_labels: Sequence[Sequence[int]], per_line: bool = False) -> Dict[str, torch.Tensor]:
+    def step(self, samples, target_labels: Sequence[Sequence[int]], per_line: bool = False, target_boxes=None) -> Dict[str, torch.Tensor]:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         out = self.model(samples, per_line=per_line, return_hidden=True)
-        return self._update(out["pred_logits"], out["hs"], out["pred_boxes"], target_labels)
+        return self._update(out["pred_logits"], out["hs"], out["pred_boxes"], target_labels, target_boxes)
 
     @torch.no_grad()
-    def step_cached(self, hs: torch.Tensor, boxes: torch.Tensor, target_labels: Sequence[Sequence[int]]) -> Dict[str, torch.Tensor]:
+    def step_cached(self, hs: torch.Tensor, boxes: torch.Tensor, target_labels: Sequence[Sequence[int]], target_boxes=None) -> Dict[str, torch.Tensor]:
         """The same step on cached decoder states: only the class head runs forward."""
         logits = self._engine()._class_head(hs)
-        return self._update(logits, hs, boxes, target_labels)
+        return self._update(logits, hs, boxes, target_labels, target_boxes)
 
-    def _update(self, logits, hs, boxes, target_labels):
+    def _set_backward(self, logits, boxes, target_labels, target_boxes):
+        """the main output's set losses and cls_loss_coef x the focal loss's gradient with respect to the logits"""
+        if target_boxes is None:
+            raise ValueError(f"HeadTrainer(loss={self.loss!r}): the step needs target_boxes")
+        tg = ops.set_targets([{"labels": torch.as_tensor(l, dtype=torch.int64), "boxes": torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)}
+                              for l, b in zip(target_labels, target_boxes)], logits.device, self.C)
+        match = self.matcher.match(logits, boxes, tg)
+        r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [[self.cls_loss_coef, 0.0, 0.0]], [True], self.matcher.focal_alpha)
+        v = r["losses"][0]
+        return {"loss_ce": v[0], "loss_bbox": v[1], "loss_giou": v[2], "cardinality_error": v[5], "class_error": v[6]}, r["dlogits"][0]
+
+    def _update(self, logits, hs, boxes, target_labels, target_boxes=None):
         self.last_outputs = {"pred_logits": logits, "pred_boxes": boxes}
-        loss, dlogits = E.loss_ctc_backward(self.last_outputs, target_labels)
+        if self.loss == "ctc":
+            loss, dlogits = E.loss_ctc_backward(self.last_outputs, target_labels)
+            result = {"loss_CTC": loss}
+        else:
+            result, dlogits = self._set_backward(logits, boxes, target_labels, target_boxes)
+            if self.loss == "ctc+set":
+                loss, dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
+                dlogits.add_(dctc, alpha=self.CTC_loss_coef)
+                result["loss_CTC"] = loss
         ops.head_grad(dlogits.view(-1, self.C), hs.reshape(-1, self.D), out=self.grad)
         clip = self.max_norm > 0
         if clip:
@@ -182,7 +218,7 @@ class HeadTrainer:
         self.step_count += 1
         ops.adamw_step(self.param, self.exp_avg, self.exp_avg_sq, self.grad, self.step_count, self.lr, self.betas, self.eps,
                        self.weight_decay, grad_scale=self.scale if clip else None)
-        return {"loss_CTC": loss}
+        return result
 
     # -- state -------------------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict:
@@ -236,6 +272,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--limit", type=int, default=0, help="train on the first N lines only")
     ap.add_argument("--size", type=int, default=EVAL_SIZE)
     ap.add_argument("--max_size", type=int, default=EVAL_MAX_SIZE)
+    ap.add_argument("--loss", default="ctc", choices=["ctc", "set", "ctc+set"],
+                    help="ctc: the CTC loss (default); set: Hungarian matching against character boxes + the focal loss; ctc+set: both")
+    ap.add_argument("--boxes-from", default="labels", choices=["labels", "align"],
+                    help="where the set loss's character boxes come from: labels = the --boxes file; align = the CTC forced alignment of "
+                         "each transcript under the initial head (evaluation.align_ctc), lines without a feasible alignment are skipped")
+    ap.add_argument("--boxes", default=None, help="JSON {image id: [[cx, cy, w, h], ...]}: one box a character, normalised to 0..1 (--boxes-from labels)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
 
@@ -253,6 +295,41 @@ def save_checkpoint(path: str, model, charset: Sequence, trainer: Optional[HeadT
     if trainer is not None:
         ck["trainer"] = trainer.state_dict()
     torch.save(ck, path)
+
+
+def load_char_boxes(args, trainer: HeadTrainer, rows, labels, batches, load_batch, per_line: bool):
+    """The set loss's targets: line index -> [T,4] cxcywh boxes in 0..1, one a label, and the batches without the lines that have none.
+    --boxes-from labels: the --boxes file.  --boxes-from align: the forced alignment of each transcript on the forward under the
+    initial head (evaluation.align_ctc_records); a line whose transcript does not fit is skipped, the count goes to the log."""
+    boxes: Dict[int, torch.Tensor] = {}
+    if args.boxes_from == "labels":
+        import json
+        if not args.boxes:
+            raise SystemExit("--loss set / ctc+set with --boxes-from labels needs --boxes")
+        with open(args.boxes, encoding="utf-8") as f:
+            table = json.load(f)
+        for i, (name, _) in enumerate(rows):
+            b = torch.as_tensor(table[name], dtype=torch.float32).reshape(-1, 4)
+            if b.shape[0] != len(labels[i]):
+                raise SystemExit(f"--boxes: {name} has {b.shape[0]} boxes for {len(labels[i])} characters")
+            boxes[i] = b
+        return boxes, batches
+    skipped = 0
+    trainer._engine()
+    for idx in batches:
+        with torch.no_grad():
+            out = trainer.model(load_batch(idx), per_line=per_line)
+        rec = E.align_ctc_records(out, [labels[i] for i in idx])
+        lengths, xyxy = rec["lengths"].cpu().tolist(), rec["box"].cpu()
+        for k, i in enumerate(idx):
+            if lengths[k] < 0:
+                skipped += 1
+                continue
+            b = xyxy[k, : lengths[k]]
+            boxes[i] = torch.stack([(b[:, 0] + b[:, 2]) / 2, (b[:, 1] + b[:, 3]) / 2, b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], dim=1)
+    print(f"--boxes-from align: {skipped} of {len(rows)} lines have no feasible alignment and are skipped", flush=True)
+    kept = [[i for i in idx if i in boxes] for idx in batches]
+    return boxes, [idx for idx in kept if idx]
 
 
 def main(argv: Optional[Sequence[str]] = None) -> Dict:
@@ -282,7 +359,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         new_class_head(model, len(charset), w0, b0)
     else:
         new_class_head(model, len(charset))
-    trainer = HeadTrainer(model, lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_max_norm)
+    trainer = HeadTrainer(model, lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_max_norm, loss=args.loss)
 
     rows = H.load_labels(args.labels, args.mode)
     if args.limit:
@@ -293,6 +370,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     per_line = args.batching == "ragged"
     batches = H.plan_batches(sizes, args.batch, args.batching == "exact", args.size, args.max_size)
     tf = EvalTransform(args.size, args.max_size)
+    char_boxes: Dict[int, torch.Tensor] = {}
+    if args.loss != "ctc":
+        char_boxes, batches = load_char_boxes(args, trainer, rows, labels, batches, lambda idx: tf([H.read_rgb(paths[i]) for i in idx], device=dev),
+                                              per_line)
     total = args.max_steps if args.max_steps is not None else (args.epochs if args.epochs is not None else 1) * len(batches)
     rng = np.random.Generator(np.random.PCG64(args.seed))
     cached: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -303,17 +384,19 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
                 break
             idx = batches[int(bi)]
             tl = [labels[i] for i in idx]
+            tb = [char_boxes[i] for i in idx] if args.loss != "ctc" else None
             if args.cache_features:
                 if int(bi) not in cached:
                     cached[int(bi)] = trainer.cache(tf([H.read_rgb(paths[i]) for i in idx], device=dev), per_line=per_line)
-                r = trainer.step_cached(*cached[int(bi)], tl)
+                r = trainer.step_cached(*cached[int(bi)], tl, tb)
             else:
-                r = trainer.step(tf([H.read_rgb(paths[i]) for i in idx], device=dev), tl, per_line=per_line)
+                r = trainer.step(tf([H.read_rgb(paths[i]) for i in idx], device=dev), tl, per_line=per_line, target_boxes=tb)
             step += 1
             if step % max(args.log_every, 1) == 0 or step == total:
                 ev = E.evaluate_ctc_step(trainer.last_outputs, tl)            # the batch's loss and CER before this step's update
-                last = {"step": step, "loss_CTC": float(r["loss_CTC"].item()), "cer": ev["cer_sum"] / max(ev["n"], 1)}
-                print(f"step {step}/{total}  loss_CTC {last['loss_CTC']:.6f}  train CER {last['cer']:.4f}", flush=True)
+                last = {"step": step, **{k: float(v.item()) for k, v in r.items()}, "cer": ev["cer_sum"] / max(ev["n"], 1)}
+                shown = "  ".join(f"{k} {last[k]:.6f}" for k in ("loss_CTC", "loss_ce") if k in last)
+                print(f"step {step}/{total}  {shown}  train CER {last['cer']:.4f}", flush=True)
     trainer.write_back()
     save_checkpoint(args.out, model, charset, trainer)
     print(f"wrote {args.out}", file=sys.stderr)

@@ -1852,3 +1852,5 @@ from .lmtrain import SORT_TILE, lm_tables, sort_u64          # noqa: E402,F401
 # the sixth header (include/dtlr_pattern.h), the same way: written in dtlr_amd/pattern.py, with the compiler of its automata
 from .pattern import (PATTERN_WORKSPACE_LIMIT, compile_pattern, pattern_decode, pattern_search, pattern_tables,          # noqa: E402,F401
                       pattern_upload, words_automaton)
+# the seventh header (include/dtlr_setloss.h), the same way: written in dtlr_amd/setloss.py (the set criterion's three operators)
+from .setloss import SetTargets, hungarian, set_cost, set_loss, set_targets          # noqa: E402,F401
