@@ -15,6 +15,10 @@ step is: the frozen forward this package already has, the CTC loss's gradient wi
 (dtlr_ctc_loss_interleaved_backward), dW = dlogits^T hs (dtlr_head_grad), clip (dtlr_grad_norm_scale), AdamW (dtlr_adamw_step) -- four
 HIP entry points, no backward through the trunk.  Nothing in a step waits for the device: the host's part is packing the label lists
 into the targets tensor and its (pageable) copy to the device; the loss stays a device tensor until the caller reads it.
+
+With the detection criterion (--loss set | ctc+set) the same trainer also trains the shared box head `bbox_embed` and takes the losses of
+every decoder output (--train class,box, --aux-loss): still no backward through the trunk, whose states are
+constants of both heads' gradients (dtlr_box_refine_grad, dtlr_box_mlp_grad).
 """
 from __future__ import annotations
 
@@ -123,11 +127,42 @@ class HeadTrainer:
     reference's (set_cost_class 2, set_cost_bbox 5, set_cost_giou 2, focal_alpha 0.25), and the returned dict also carries loss_ce,
     loss_bbox, loss_giou, cardinality_error and class_error of the main output.  The matcher reads the solver's status: one host
     synchronisation a step.  A third deviation, in the set modes only:
-      * the focal loss is taken on the main output only, because `return_hidden` returns the last decoder layer's states.  The
-        reference also sums the auxiliary layers' and the intermediate output's loss_ce, which reach the shared head too."""
+      * by default the focal loss is taken on the main output only.  The reference also sums the auxiliary layers' and the intermediate
+        output's loss_ce, which reach the shared head too: aux_loss=True adds the auxiliary layers (not the intermediate output, whose
+        heads are the two-stage ones).
+
+    train: a subset of {"class", "box"} (default: the class head alone, the above unchanged in bits).  "box" also trains the shared box
+    head `bbox_embed` against bbox_loss_coef x L1 + giou_loss_coef x GIoU of the matched pairs (5 and 2,
+    config/Latin_CTC.py:79-80), exactly and with the trunk frozen: every use of the box head's output inside the trunk is detached in
+    the reference, so the decoder states are constants of this gradient too; "look forward twice" makes an output's box depend on the MLP
+    at two layers' states, both are followed (ops.box_refine_grad, ops.box_mlp_grad).  It needs a set loss (the CTC loss has no gradient
+    for boxes) and the full forward every step (the forward depends on the box head: no cache / step_cached).
+    aux_loss=True: every decoder output is matched and weighted as the reference weighs it (the same coefficients for every layer); False:
+    only the main output's row of weights is non-zero -- its box gradient still reaches the state one layer below.  With either, the
+    matcher runs on all decoder outputs in one launch, the trained parameters, their moments and their gradient share ONE flat buffer
+    ([class W | class b | box W0 | b0 | W1 | b1 | W2 | b2]), the clip norm is taken over all of it (closer to the reference's global
+    clip than the head's own) and one AdamW launch updates it.  The returned dict also carries loss_ce_<l>, loss_bbox_<l>,
+    loss_giou_<l> of auxiliary output l, and `last_states` keeps the step's hs_all, tgt_all, refs, stacked outputs and match_q."""
 
     def __init__(self, model, lr: float = 1e-5, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0):
+                 max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0,
+                 train: Sequence[str] = ("class",), aux_loss: bool = False, bbox_loss_coef: float = 5.0, giou_loss_coef: float = 2.0):
+        train = (train,) if isinstance(train, str) else tuple(train)
+        if not train or set(train) - {"class", "box"}:
+            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of ('class', 'box')")
+        if loss not in ("ctc", "set", "ctc+set"):
+            raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
+        if "box" in train and loss == "ctc":
+            raise ValueError("HeadTrainer(train=('box', ..)): the CTC loss has no gradient for boxes -- loss must be 'set' or 'ctc+set'")
+        if aux_loss and loss == "ctc":
+            raise ValueError("HeadTrainer(aux_loss=True): the CTC loss is taken on the main output only -- loss must be 'set' or 'ctc+set'")
+        if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
+            raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
+                                      "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
+        self.train = tuple(k for k in ("class", "box") if k in train)
+        self.aux_loss = bool(aux_loss)
+        self.bbox_loss_coef, self.giou_loss_coef = float(bbox_loss_coef), float(giou_loss_coef)
+        self.every_output = "box" in self.train or self.aux_loss          # the step reads every decoder layer's states
         if not model.dec_pred_class_embed_share:
             raise NotImplementedError("HeadTrainer: written for dec_pred_class_embed_share (every shipped config)")
         head = model.class_embed[0]
@@ -136,8 +171,6 @@ class HeadTrainer:
         self.model = model
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
         self.max_norm = float(max_norm) if max_norm is not None else 0.0
-        if loss not in ("ctc", "set", "ctc+set"):
-            raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
         self.loss, self.CTC_loss_coef, self.cls_loss_coef = loss, float(CTC_loss_coef), float(cls_loss_coef)
         self.matcher = None
         if loss != "ctc":
@@ -145,33 +178,63 @@ class HeadTrainer:
             self.matcher = HungarianMatcher(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0, focal_alpha=0.25)
         self.C, self.D = int(head.weight.shape[0]), int(head.weight.shape[1])
         dev = head.weight.device
-        n = self.C * self.D + self.C
-        self.param = torch.cat([head.weight.detach().float().reshape(-1), head.bias.detach().float().reshape(-1)]).to(dev).contiguous()
+        self.n_class = self.C * self.D + self.C if "class" in self.train else 0
+        self.n_box = ops.BOX_GRAD_FLOATS if "box" in self.train else 0
+        n = self.n_class + self.n_box
+        parts = [head.weight.detach().float().reshape(-1), head.bias.detach().float().reshape(-1)] if self.n_class else []
+        if self.n_box:
+            mlp = model.bbox_embed[0]
+            if [tuple(l.weight.shape) for l in mlp.layers] != [(256, 256), (256, 256), (4, 256)]:
+                raise NotImplementedError("HeadTrainer(train=('box', ..)): the box head is not the MLP 256 -> 256 -> 256 -> 4")
+            for l in mlp.layers:
+                parts += [l.weight.detach().float().reshape(-1), l.bias.detach().float().reshape(-1)]
+        self.param = torch.cat(parts).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.scale = torch.ones(2, dtype=torch.float32, device=dev)         # (clip coefficient, gradient norm) of the last step
         self.step_count = 0
         self.last_outputs: Optional[Dict[str, torch.Tensor]] = None         # pred_logits / pred_boxes of the last step (before its update)
+        self.last_states: Optional[Dict] = None                             # every_output: hs_all, tgt_all, refs, stacked outputs, match_q of the last step
 
     # -- the master head ---------------------------------------------------------------------------------------------------------
     @property
     def weight(self) -> torch.Tensor:
+        if not self.n_class:
+            return self.model.class_embed[0].weight.detach()
         return self.param[: self.C * self.D].view(self.C, self.D)
 
     @property
     def bias(self) -> torch.Tensor:
-        return self.param[self.C * self.D:]
+        if not self.n_class:
+            return self.model.class_embed[0].bias.detach()
+        return self.param[self.C * self.D: self.C * self.D + self.C]
+
+    def box_head(self) -> List[torch.Tensor]:
+        """the master box head as views of the flat buffer: [W0, b0, W1, b1, W2, b2] (train includes "box")"""
+        if not self.n_box:
+            raise RuntimeError("HeadTrainer: the box head is not trained (train=('class',))")
+        out, o = [], self.n_class
+        for shape in ops.BOX_HEAD_SHAPES:
+            k = int(np.prod(shape))
+            out.append(self.param[o:o + k].view(shape))
+            o += k
+        return out
 
     def _engine(self):
         eng = self.model.engine()
-        eng.set_class_head(self.weight, self.bias)
+        if self.n_class:
+            eng.set_class_head(self.weight, self.bias)
+        if self.n_box:
+            bh = self.box_head()
+            eng.set_box_head(bh[0::2], bh[1::2])
         return eng
 
     # -- steps -------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def cache(self, samples, per_line: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """(hs [B,nq,hidden] in the engine's dtype, pred_boxes [B,nq,4]) of a batch: the frozen trunk's part of a step."""
+        self._no_cache("cache")
         self._engine()
         out = self.model(samples, per_line=per_line, return_hidden=True)
         return out["hs"], out["pred_boxes"]
@@ -180,21 +243,81 @@ class HeadTrainer:
     def step(self, samples, target_labels: Sequence[Sequence[int]], per_line: bool = False, target_boxes=None) -> Dict[str, torch.Tensor]:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
+        if self.every_output:
+            return self._update_every(self.model(samples, per_line=per_line, return_hidden="all"), target_labels, target_boxes)
         out = self.model(samples, per_line=per_line, return_hidden=True)
         return self._update(out["pred_logits"], out["hs"], out["pred_boxes"], target_labels, target_boxes)
 
     @torch.no_grad()
     def step_cached(self, hs: torch.Tensor, boxes: torch.Tensor, target_labels: Sequence[Sequence[int]], target_boxes=None) -> Dict[str, torch.Tensor]:
         """The same step on cached decoder states: only the class head runs forward."""
+        self._no_cache("step_cached")
         logits = self._engine()._class_head(hs)
         return self._update(logits, hs, boxes, target_labels, target_boxes)
 
-    def _set_backward(self, logits, boxes, target_labels, target_boxes):
-        """the main output's set losses and cls_loss_coef x the focal loss's gradient with respect to the logits"""
+    def _no_cache(self, what):
+        if "box" in self.train:
+            raise ValueError(f"HeadTrainer.{what}: the forward depends on the box head being trained -- use step()")
+        if self.aux_loss:
+            raise ValueError(f"HeadTrainer.{what}: aux_loss needs every decoder layer's states, the cache holds the last layer's -- use step()")
+
+    def _set_targets(self, target_labels, target_boxes, device):
         if target_boxes is None:
             raise ValueError(f"HeadTrainer(loss={self.loss!r}): the step needs target_boxes")
-        tg = ops.set_targets([{"labels": torch.as_tensor(l, dtype=torch.int64), "boxes": torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)}
-                              for l, b in zip(target_labels, target_boxes)], logits.device, self.C)
+        return ops.set_targets([{"labels": torch.as_tensor(l, dtype=torch.int64), "boxes": torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)}
+                                for l, b in zip(target_labels, target_boxes)], device, self.C)
+
+    def _update_every(self, out, target_labels, target_boxes):
+        """the step over every decoder output: the set losses of all L outputs, dW of the class head summed over the weighted outputs,
+        the box head's gradient at its 2 L - 1 applications, one clip and one AdamW over the flat buffer"""
+        hs_all, tgt_all, refs = out["hs_all"], out["tgt_all"], out["refs"]
+        L = len(hs_all)
+        logits = torch.stack([a["pred_logits"] for a in out["aux_outputs"]] + [out["pred_logits"]])
+        boxes = torch.stack([a["pred_boxes"] for a in out["aux_outputs"]] + [out["pred_boxes"]])
+        B, nq = int(logits.shape[1]), int(logits.shape[2])
+        self.last_outputs = {"pred_logits": out["pred_logits"], "pred_boxes": out["pred_boxes"]}
+        tg = self._set_targets(target_labels, target_boxes, logits.device)
+        match = self.matcher.match(logits, boxes, tg)
+        self.last_states = {"hs_all": hs_all, "tgt_all": tgt_all, "refs": refs, "pred_logits": logits, "pred_boxes": boxes, "match_q": match}
+        used = [l for l in range(L) if self.aux_loss or l == L - 1]
+        row = [self.cls_loss_coef if self.n_class else 0.0, self.bbox_loss_coef if self.n_box else 0.0, self.giou_loss_coef if self.n_box else 0.0]
+        r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [row if l in used else [0.0, 0.0, 0.0] for l in range(L)],
+                         [bool(self.n_class) and l in used for l in range(L)], self.matcher.focal_alpha)
+        v = r["losses"]
+        result = {"loss_ce": v[L - 1, 0], "loss_bbox": v[L - 1, 1], "loss_giou": v[L - 1, 2], "cardinality_error": v[L - 1, 5], "class_error": v[L - 1, 6]}
+        for l in range(L - 1):
+            result.update({f"loss_ce_{l}": v[l, 0], f"loss_bbox_{l}": v[l, 1], f"loss_giou_{l}": v[l, 2]})
+        if self.loss == "ctc+set":
+            if self.n_class:
+                result["loss_CTC"], dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
+                r["dlogits"][L - 1].add_(dctc, alpha=self.CTC_loss_coef)
+            else:
+                result["loss_CTC"] = E.loss_ctc(self.last_outputs, target_labels)
+        if self.n_class:
+            G = torch.cat([r["dlogits"][l].view(-1, self.C) for l in used])
+            X = torch.cat([hs_all[l].reshape(-1, self.D) for l in used])
+            ops.head_grad(G, X, out=self.grad[: self.n_class])
+        if self.n_box:
+            dz, du = ops.box_refine_grad(r["dboxes"], boxes, torch.stack(refs[:L]))
+            below = [l for l in used if l >= 1]                                  # look forward twice: output l's box also reads f(t_(l-1))
+            xs = [hs_all[l].reshape(-1, self.D) for l in used] + [tgt_all[l - 1].reshape(-1, self.D) for l in below]
+            dys = [dz[l] for l in used] + [du[l - 1] for l in below]
+            rows = ops.match_rows(match, nq, B)[used + below]
+            ops.box_mlp_grad(xs, dys, self.box_head(), rows=rows, out=self.grad[self.n_class:])
+        self._clip_and_step()
+        return result
+
+    def _clip_and_step(self):
+        clip = self.max_norm > 0
+        if clip:
+            ops.grad_norm_scale(self.grad, self.max_norm, out=self.scale)
+        self.step_count += 1
+        ops.adamw_step(self.param, self.exp_avg, self.exp_avg_sq, self.grad, self.step_count, self.lr, self.betas, self.eps,
+                       self.weight_decay, grad_scale=self.scale if clip else None)
+
+    def _set_backward(self, logits, boxes, target_labels, target_boxes):
+        """the main output's set losses and cls_loss_coef x the focal loss's gradient with respect to the logits"""
+        tg = self._set_targets(target_labels, target_boxes, logits.device)
         match = self.matcher.match(logits, boxes, tg)
         r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [[self.cls_loss_coef, 0.0, 0.0]], [True], self.matcher.focal_alpha)
         v = r["losses"][0]
@@ -212,34 +335,52 @@ class HeadTrainer:
                 dlogits.add_(dctc, alpha=self.CTC_loss_coef)
                 result["loss_CTC"] = loss
         ops.head_grad(dlogits.view(-1, self.C), hs.reshape(-1, self.D), out=self.grad)
-        clip = self.max_norm > 0
-        if clip:
-            ops.grad_norm_scale(self.grad, self.max_norm, out=self.scale)
-        self.step_count += 1
-        ops.adamw_step(self.param, self.exp_avg, self.exp_avg_sq, self.grad, self.step_count, self.lr, self.betas, self.eps,
-                       self.weight_decay, grad_scale=self.scale if clip else None)
+        self._clip_and_step()
         return result
 
     # -- state -------------------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict:
-        return {"head": self.param.detach().cpu().clone(), "exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone(),
-                "step": int(self.step_count), "num_classes": self.C, "hidden_dim": self.D}
+        """"head" / "exp_avg" / "exp_avg_sq": the class head [W | b] and its moments, as before the box head could be trained (the
+        moments are empty when the class head is not trained); "box_head" / "box_exp_avg" / "box_exp_avg_sq": the same of the box head
+        [W0 | b0 | W1 | b1 | W2 | b2], present when it is trained."""
+        nc = self.n_class
+        sd = {"head": torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
+              "exp_avg": self.exp_avg[:nc].cpu().clone(), "exp_avg_sq": self.exp_avg_sq[:nc].cpu().clone(),
+              "step": int(self.step_count), "num_classes": self.C, "hidden_dim": self.D}
+        if self.n_box:
+            sd.update({"train": list(self.train), "box_head": self.param[nc:].detach().cpu().clone(), "box_exp_avg": self.exp_avg[nc:].cpu().clone(),
+                       "box_exp_avg_sq": self.exp_avg_sq[nc:].cpu().clone()})
+        return sd
 
     def load_state_dict(self, sd: Dict) -> None:
         if int(sd["num_classes"]) != self.C or int(sd["hidden_dim"]) != self.D:
             raise ValueError(f"HeadTrainer.load_state_dict: the state is of a Linear({sd['hidden_dim']} -> {sd['num_classes']}), "
                              f"this trainer's head is Linear({self.D} -> {self.C})")
-        self.param.copy_(sd["head"])
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        nc = self.n_class
+        if nc:
+            self.param[:nc].copy_(sd["head"])
+            if sd["exp_avg"].numel() == nc:                                 # empty: written by a trainer of the box head alone
+                self.exp_avg[:nc].copy_(sd["exp_avg"])
+                self.exp_avg_sq[:nc].copy_(sd["exp_avg_sq"])
+        if self.n_box and "box_head" in sd:                                 # absent: a state written before the box head could be trained --
+            self.param[nc:].copy_(sd["box_head"])                           # the box head then stays the model's, its moments zero
+            self.exp_avg[nc:].copy_(sd["box_exp_avg"])
+            self.exp_avg_sq[nc:].copy_(sd["box_exp_avg_sq"])
         self.step_count = int(sd["step"])
 
     @torch.no_grad()
     def write_back(self):
-        """Copy the master head into model.class_embed (the shared Linear): model.state_dict() then is the adapted checkpoint."""
-        head = self.model.class_embed[0]
-        head.weight.copy_(self.weight)
-        head.bias.copy_(self.bias)
+        """Copy the master heads into model.class_embed (the shared Linear) and, when trained, model.bbox_embed (the shared MLP: every
+        aliased state-dict key carries the new values): model.state_dict() then is the adapted checkpoint."""
+        if self.n_class:
+            head = self.model.class_embed[0]
+            head.weight.copy_(self.weight)
+            head.bias.copy_(self.bias)
+        if self.n_box:
+            bh = self.box_head()
+            for i, layer in enumerate(self.model.bbox_embed[0].layers):
+                layer.weight.copy_(bh[2 * i])
+                layer.bias.copy_(bh[2 * i + 1])
         self.model._engine = None                                           # the packed model is rebuilt from the new parameters
         return self.model
 
@@ -278,6 +419,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="where the set loss's character boxes come from: labels = the --boxes file; align = the CTC forced alignment of "
                          "each transcript under the initial head (evaluation.align_ctc), lines without a feasible alignment are skipped")
     ap.add_argument("--boxes", default=None, help="JSON {image id: [[cx, cy, w, h], ...]}: one box a character, normalised to 0..1 (--boxes-from labels)")
+    ap.add_argument("--train", default="class", help="the heads to train, comma-separated: class (default), box (the shared box head; needs "
+                                                     "--loss set or ctc+set and the full forward every step), or class,box")
+    ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
 
@@ -333,7 +477,17 @@ def load_char_boxes(args, trainer: HeadTrainer, rows, labels, batches, load_batc
 
 
 def main(argv: Optional[Sequence[str]] = None) -> Dict:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    train = tuple(k.strip() for k in args.train.split(",") if k.strip())
+    if not train or set(train) - {"class", "box"}:
+        ap.error(f"--train {args.train}: a comma-separated subset of class, box")
+    if "box" in train and args.cache_features:
+        ap.error("--cache-features cannot train the box head: the forward depends on it")
+    if ("box" in train or args.aux_loss) and args.loss == "ctc":
+        ap.error("--train box / --aux-loss need --loss set or ctc+set")
+    if args.aux_loss and args.cache_features:
+        ap.error("--cache-features keeps the last decoder layer's states only: not with --aux-loss")
     from . import eval_harness as H
     from . import weights as W
     from .config import DTLRConfig
@@ -359,7 +513,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         new_class_head(model, len(charset), w0, b0)
     else:
         new_class_head(model, len(charset))
-    trainer = HeadTrainer(model, lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_max_norm, loss=args.loss)
+    trainer = HeadTrainer(model, lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_max_norm, loss=args.loss,
+                          train=train, aux_loss=args.aux_loss)
 
     rows = H.load_labels(args.labels, args.mode)
     if args.limit:
@@ -395,7 +550,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
             if step % max(args.log_every, 1) == 0 or step == total:
                 ev = E.evaluate_ctc_step(trainer.last_outputs, tl)            # the batch's loss and CER before this step's update
                 last = {"step": step, **{k: float(v.item()) for k, v in r.items()}, "cer": ev["cer_sum"] / max(ev["n"], 1)}
-                shown = "  ".join(f"{k} {last[k]:.6f}" for k in ("loss_CTC", "loss_ce") if k in last)
+                shown = "  ".join(f"{k} {last[k]:.6f}" for k in ("loss_CTC", "loss_ce", "loss_bbox", "loss_giou") if k in last)
                 print(f"step {step}/{total}  {shown}  train CER {last['cer']:.4f}", flush=True)
     trainer.write_back()
     save_checkpoint(args.out, model, charset, trainer)

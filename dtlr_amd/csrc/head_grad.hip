@@ -12,103 +12,25 @@
 // sums alone.  M is split over workgroups so that the grid fills the chip; the partial tiles (fp32; the bias partials fp64) go to the
 // caller's workspace and a second kernel adds them in split order -- no float atomics, two runs give the same bits.
 #include "dtlr_common.h"
+#include "head_grad_tile.h"
 
 namespace dtlr {
 
-constexpr int HG_TC = 64, HG_TD = 64, HG_MK = 32, HG_MAX_SPLITS = 64;
-
-struct HgPlan { int tiles_c, tiles_d, splits; long chunk; };
-static inline HgPlan hg_plan(long M, int C, int D)
-{
-    HgPlan p;
-    p.tiles_c = (C + HG_TC - 1) / HG_TC;
-    p.tiles_d = D / HG_TD;
-    long want = 1024 / ((long)p.tiles_c * p.tiles_d);
-    if (want < 1) want = 1;
-    if (want > HG_MAX_SPLITS) want = HG_MAX_SPLITS;
-    long chunk = (M + want - 1) / want;
-    chunk = ((chunk + HG_MK - 1) / HG_MK) * HG_MK;
-    p.chunk = chunk;
-    p.splits = (int)((M + chunk - 1) / chunk);
-    return p;
-}
-
-// grid (tiles_c * tiles_d, splits): part[split][C][D] and partb[split][C]
+// grid (tiles_c * tiles_d, splits): part[split][C][D] and partb[split][C] (head_grad_tile.h: the routine dtlr_box_mlp_grad shares)
 __global__ __launch_bounds__(256) void head_grad_partial_kernel(const float* __restrict__ G, const float* __restrict__ X,
                                                                 float* __restrict__ part, double* __restrict__ partb,
                                                                 long M, int C, int D, int tiles_d, long chunk)
 {
     __shared__ __attribute__((aligned(16))) float Gs[HG_MK][HG_TC];
     __shared__ __attribute__((aligned(16))) float Xs[HG_MK][HG_TD];
-    const int tc = blockIdx.x / tiles_d, td = blockIdx.x - tc * tiles_d;
-    const int cbase = tc * HG_TC, dbase = td * HG_TD;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;                     // features 4 tx .. 4 tx + 3, channels 4 ty .. 4 ty + 3
-    const long m0 = (long)blockIdx.y * chunk;
-    const long m1 = m0 + chunk < M ? m0 + chunk : M;
-    double acc[4][4], accb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { accb[i] = 0.0; for (int j = 0; j < 4; ++j) acc[i][j] = 0.0; }
-    for (long ms = m0; ms < m1; ms += HG_MK) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < HG_MK * HG_TC / 256; ++u) {                         // G: scalar loads (rows of C floats have no alignment)
-            const int e = u * 256 + threadIdx.x, r = e >> 6, c = e & 63;
-            const long m = ms + r;
-            Gs[r][c] = (m < m1 && cbase + c < C) ? G[m * C + cbase + c] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HG_MK * HG_TD / 4 / 256; ++u) {                     // X: rows of D floats, D % 64 == 0
-            const int e = u * 256 + threadIdx.x, r = e >> 4, d4 = e & 15;
-            const long m = ms + r;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m < m1) v = *reinterpret_cast<const float4*>(X + m * D + dbase + 4 * d4);
-            *reinterpret_cast<float4*>(&Xs[r][4 * d4]) = v;
-        }
-        __syncthreads();
-        float a[4][4], ab[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ab[i] = 0.f; for (int j = 0; j < 4; ++j) a[i][j] = 0.f; }
-#pragma unroll 8
-        for (int r = 0; r < HG_MK; ++r) {
-            const float4 g = *reinterpret_cast<const float4*>(&Gs[r][4 * ty]);
-            const float4 x = *reinterpret_cast<const float4*>(&Xs[r][4 * tx]);
-            const float gv[4] = {g.x, g.y, g.z, g.w}, xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ab[i] += gv[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[i][j] = fmaf(gv[i], xv[j], a[i][j]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { accb[i] += (double)ab[i]; for (int j = 0; j < 4; ++j) acc[i][j] += (double)a[i][j]; }
-    }
-    float* po = part + (long)blockIdx.y * C * D;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = cbase + 4 * ty + i;
-        if (c < C) {
-            *reinterpret_cast<float4*>(po + (long)c * D + dbase + 4 * tx) = make_float4((float)acc[i][0], (float)acc[i][1], (float)acc[i][2], (float)acc[i][3]);
-            if (td == 0 && tx == 0) partb[(long)blockIdx.y * C + c] = accb[i];
-        }
-    }
+    hg_partial_tile(Gs, Xs, G, X, part, partb, nullptr, M, C, D, tiles_d, chunk, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // dW | db = the partials added in split order
 __global__ __launch_bounds__(256) void head_grad_reduce_kernel(const float* __restrict__ part, const double* __restrict__ partb,
                                                                float* __restrict__ dW, float* __restrict__ db, long nW, int C, int splits)
 {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < nW) {
-        double a = 0.0;
-        for (int s = 0; s < splits; ++s) a += (double)part[(long)s * nW + i];
-        dW[i] = (float)a;
-    } else if (i < nW + C) {
-        const long c = i - nW;
-        double a = 0.0;
-        for (int s = 0; s < splits; ++s) a += partb[(long)s * C + c];
-        db[c] = (float)a;
-    }
+    hg_reduce(part, partb, dW, db, nW, C, splits, (long)blockIdx.x * 256 + threadIdx.x);
 }
 
 constexpr int GN_BLOCKS = 256;

@@ -312,7 +312,8 @@ class DINO(nn.Module):
         """samples: NestedTensor | Tensor[B,3,H,W] | list[Tensor[3,h,w]] (models/dino/dino.py:270-288).
         targets must be None (inference; denoising queries are training-only, dn_components.py:135-140).
         per_line: every line gets the result it would get alone (DTLREngine.forward); the reference's padded-batch semantics otherwise.
-        return_hidden: add out["hs"], the decoder states the class head multiplies (DTLREngine.forward)."""
+        return_hidden: add out["hs"], the decoder states the class head multiplies; "all": also hs_all, tgt_all and refs of every decoder
+        layer, with the auxiliary outputs (DTLREngine.forward)."""
         if targets is not None:
             raise NotImplementedError("dtlr_amd.DINO is inference-only: targets must be None")
         if self.training:
@@ -322,10 +323,11 @@ class DINO(nn.Module):
         eng = self.engine()
         x, mask = samples.decompose()
         ops.require_cuda(x, "samples")
+        every = isinstance(return_hidden, str)
         out = eng.forward(x.float(), mask, forced_topk=forced_topk, want_aux=self.return_aux, return_debug=return_debug,
                           has_padding=getattr(samples, "has_padding", True), per_line=per_line, sizes=getattr(samples, "sizes", None),
                           return_hidden=return_hidden)
-        if not self.return_aux:
+        if not self.return_aux and not every:
             out["aux_outputs"] = []
         return out
 

@@ -467,6 +467,27 @@ class DTLREngine:
         self._drop_images("class")
         self.num_classes = int(weight.shape[0])
 
+    @torch.no_grad()
+    def set_box_head(self, weights, biases) -> None:
+        """Replace the decoder's box head (bbox_embed: the 3-layer MLP shared by the decoder layers and by the refinement of the reference
+        points) in the packed model without re-packing anything else -- set_class_head's counterpart.  weights: three tensors [256,256],
+        [256,256], [4,256]; biases: [256], [256], [4].  `bbox{0,1,2}.w / .b` are swapped, with the split engine's packing and the 16-bit
+        engines' `.wh` copies of the two hidden layers, and the images derived from them are dropped, to be rebuilt by the next forward.  A
+        forward after this equals, bit for bit, the forward of a fresh engine built from the updated state dict.  The two-stage box head
+        (`enc_bbox*`) is untouched."""
+        d = self.cfg.hidden_dim
+        want = [((d, d), (d,)), ((d, d), (d,)), ((4, d), (4,))]
+        if len(weights) != 3 or len(biases) != 3 or [(tuple(w.shape), tuple(b.shape)) for w, b in zip(weights, biases)] != want:
+            raise ValueError(f"set_box_head: the weights / biases do not form the MLP {d} -> {d} -> {d} -> 4")
+        for i, (wt, b) in enumerate(zip(weights, biases)):
+            self._put(f"bbox{i}.w", wt.detach().clone(), torch.float32)      # copies: the engine never aliases the caller's buffers
+            self._put(f"bbox{i}.b", b.detach().clone(), torch.float32)
+            if i < 2 and self.split:
+                self.w[f"bbox{i}.w"] = ops.split_pack(self.w[f"bbox{i}.w"])
+            if i < 2 and self.dtype in ops.H16:
+                self._put(f"bbox{i}.wh", wt.detach())
+            self._drop_images(f"bbox{i}")
+
     def _class_head(self, hs):
         """class_embed on decoder states (models/dino/dino.py:349-352), fp32 logits.  bf16 engine: the states are exact bf16
         values, so [hs | hs] . [W_hi | W_lo]^T on the bf16 matrix cores is the fp32-weight product to ~2^-16 relative -- the
@@ -925,11 +946,12 @@ class DTLREngine:
             return True
         return False
 
-    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False):
+    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None):
         """TransformerDecoder.forward + DeformableTransformerDecoderLayer
         (deformable_transformer.py:652-766, 882-997), batch-first.  vall: value_proj(memory) of all layers when the caller already
         computed it (forward() does, on a side stream under the two-stage selection).  per_line: the query position embedding is the
-        sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios."""
+        sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios.  tgt_all: a list that
+        receives every layer's un-normed output (what the box head's refinement of the reference points reads)."""
         cfg = self.cfg
         B = memory.shape[0]
         ref = ts["ref_unsig"].sigmoid()
@@ -970,6 +992,8 @@ class DTLREngine:
             refs.append(ref)
             if dbg is not None:                                        # tools/error_budget.py: per-layer state
                 dbg.setdefault("tgt", []).append(tgt)
+            if tgt_all is not None:
+                tgt_all.append(tgt)
             if want_aux or n == cfg.dec_layers - 1:
                 hs.append(self._ln("dec.norm", tgt))
             else:
@@ -1101,7 +1125,10 @@ class DTLREngine:
         treated as padded and runs on one stream.  `sizes`: the host's (h, w) of every line, when known -- a line with fewer encoder
         tokens than queries cannot run alone and raises ValueError.
         return_hidden: also return out["hs"], the last decoder layer's normalised output [B,nq,hidden] in the engine's dtype -- what the
-        class head multiplies (dtlr_amd/adapt.py trains the head on it); no extra launch."""
+        class head multiplies (dtlr_amd/adapt.py trains the head on it); no extra launch.  return_hidden="all" (implies want_aux): also
+        out["hs_all"], the normalised output of every decoder layer (hs_all[-1] is out["hs"]), out["tgt_all"], the same before
+        decoder.norm, and out["refs"], the dec_layers + 1 reference points [B,nq,4] fp32 -- everything the box head's gradient needs
+        (DESIGN.md section 21); the tensors the forward makes anyway, no extra launch beyond want_aux's."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1156,8 +1183,15 @@ class DTLREngine:
         ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line)
-        out = self.heads(hs, refs, ts, want_aux, return_hidden)
+        if return_hidden not in (False, True, "all"):
+            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all'")
+        every = isinstance(return_hidden, str)
+        want_aux = want_aux or every
+        tgt_all = [] if every else None
+        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all)
+        out = self.heads(hs, refs, ts, want_aux, bool(return_hidden))
+        if every:
+            out["hs_all"], out["tgt_all"], out["refs"] = list(hs), tgt_all, list(refs)
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

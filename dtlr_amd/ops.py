@@ -1854,3 +1854,5 @@ from .pattern import (PATTERN_WORKSPACE_LIMIT, compile_pattern, pattern_decode, 
                       pattern_upload, words_automaton)
 # the seventh header (include/dtlr_setloss.h), the same way: written in dtlr_amd/setloss.py (the set criterion's three operators)
 from .setloss import SetTargets, hungarian, set_cost, set_loss, set_targets          # noqa: E402,F401
+# the eighth header (include/dtlr_boxgrad.h), the same way: written in dtlr_amd/boxgrad.py (the box head's gradient with the trunk frozen)
+from .boxgrad import BOX_GRAD_FLOATS, BOX_GRAD_MAX_APPS, BOX_HEAD_SHAPES, box_mlp_grad, box_refine_grad, match_rows          # noqa: E402,F401
