@@ -19,6 +19,10 @@ into the targets tensor and its (pageable) copy to the device; the loss stays a 
 With the detection criterion (--loss set | ctc+set) the same trainer also trains the shared box head `bbox_embed` and takes the losses of
 every decoder output (--train class,box, --aux-loss): still no backward through the trunk, whose states are
 constants of both heads' gradients (dtlr_box_refine_grad, dtlr_box_mlp_grad).
+
+--train ..,tail also trains the decoder's tail: linear1, linear2 and norm3 of the last decoder layer and
+transformer.decoder.norm, everything the loss reaches without crossing an attention.  Its gradient starts from the last layer's state after
+norm1, a constant of the frozen trunk (dtlr_head_dx, dtlr_box_mlp_dx, dtlr_ln_backward, dtlr_ffn_recompute, dtlr_ffn_grad).
 """
 from __future__ import annotations
 
@@ -142,14 +146,25 @@ class HeadTrainer:
     matcher runs on all decoder outputs in one launch, the trained parameters, their moments and their gradient share ONE flat buffer
     ([class W | class b | box W0 | b0 | W1 | b1 | W2 | b2]), the clip norm is taken over all of it (closer to the reference's global
     clip than the head's own) and one AdamW launch updates it.  The returned dict also carries loss_ce_<l>, loss_bbox_<l>,
-    loss_giou_<l> of auxiliary output l, and `last_states` keeps the step's hs_all, tgt_all, refs, stacked outputs and match_q."""
+    loss_giou_<l> of auxiliary output l, and `last_states` keeps the step's hs_all, tgt_all, refs, stacked outputs and match_q.
+
+    train may also name "tail" (DESIGN.md section 22): linear1, linear2 and norm3 of the LAST decoder layer and transformer.decoder.norm,
+    1,051,904 parameters at dim_feedforward 2048 -- everything after the last cross-attention, which the loss reaches without a backward
+    through an attention.  The flat buffer grows to [class | box | W1 | b1 | W2 | b2 | norm3.w | norm3.b | dec_norm.w | dec_norm.b], still
+    under one clip norm and one AdamW launch with uniform decay.  It works with every loss ("ctc" reaches the tail through dlogits alone)
+    and with or without aux_loss (decoder.norm's affine parameters then take gradient from every output).  With a set loss the box terms
+    are weighted with bbox_loss_coef / giou_loss_coef whether or not "box" is trained: the tail moves pred_boxes through the decoder
+    states, and likewise the class terms whether or not "class" is.  The gradient is the fp32 function's at the engine's states: the
+    last layer's state after norm1 and the lower layers' outputs are the engine's, the FFN's output and norm3's are recomputed in fp32
+    from the master weights.  With "tail" and neither "box" nor aux_loss, `cache` returns (the last layer's FFN input, its reference
+    points) and `step_cached` runs DTLREngine.tail_forward on them: the same step without the trunk."""
 
     def __init__(self, model, lr: float = 1e-5, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0,
                  train: Sequence[str] = ("class",), aux_loss: bool = False, bbox_loss_coef: float = 5.0, giou_loss_coef: float = 2.0):
         train = (train,) if isinstance(train, str) else tuple(train)
-        if not train or set(train) - {"class", "box"}:
-            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of ('class', 'box')")
+        if not train or set(train) - {"class", "box", "tail"}:
+            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of ('class', 'box', 'tail')")
         if loss not in ("ctc", "set", "ctc+set"):
             raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
         if "box" in train and loss == "ctc":
@@ -159,10 +174,10 @@ class HeadTrainer:
         if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
             raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
                                       "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
-        self.train = tuple(k for k in ("class", "box") if k in train)
+        self.train = tuple(k for k in ("class", "box", "tail") if k in train)
         self.aux_loss = bool(aux_loss)
         self.bbox_loss_coef, self.giou_loss_coef = float(bbox_loss_coef), float(giou_loss_coef)
-        self.every_output = "box" in self.train or self.aux_loss          # the step reads every decoder layer's states
+        self.every_output = "box" in self.train or "tail" in self.train or self.aux_loss          # the step reads every decoder layer's states
         if not model.dec_pred_class_embed_share:
             raise NotImplementedError("HeadTrainer: written for dec_pred_class_embed_share (every shipped config)")
         head = model.class_embed[0]
@@ -180,7 +195,21 @@ class HeadTrainer:
         dev = head.weight.device
         self.n_class = self.C * self.D + self.C if "class" in self.train else 0
         self.n_box = ops.BOX_GRAD_FLOATS if "box" in self.train else 0
-        n = self.n_class + self.n_box
+        self.n_tail, self.F = 0, 0
+        if "tail" in self.train:
+            layers = model.transformer.decoder.layers
+            last = layers[len(layers) - 1]
+            if getattr(model.cfg, "transformer_activation", "relu") != "relu" or getattr(model.cfg, "dropout", 0.0) != 0.0:
+                raise NotImplementedError("HeadTrainer(train=('tail', ..)): written for the ReLU FFN without dropout (every shipped config)")
+            if any(o is last or o.linear1.weight is last.linear1.weight or o.linear2.weight is last.linear2.weight or o.norm3.weight is last.norm3.weight
+                   for o in list(layers)[:-1]):
+                raise NotImplementedError("HeadTrainer(train=('tail', ..)): the decoder layers share parameters -- the last layer's FFN is then "
+                                          "not the tail alone")
+            self.F = int(last.linear1.weight.shape[0])
+            if [tuple(p.shape) for p in self._tail_modules_params()] != list(ops.tail_shapes(self.F)) or self.D != 256:
+                raise NotImplementedError("HeadTrainer(train=('tail', ..)): the tail is not linear1 [F,256], linear2 [256,F], norm3 [256], decoder.norm [256]")
+            self.n_tail = ops.tail_floats(self.F)
+        n = self.n_class + self.n_box + self.n_tail
         parts = [head.weight.detach().float().reshape(-1), head.bias.detach().float().reshape(-1)] if self.n_class else []
         if self.n_box:
             mlp = model.bbox_embed[0]
@@ -188,6 +217,8 @@ class HeadTrainer:
                 raise NotImplementedError("HeadTrainer(train=('box', ..)): the box head is not the MLP 256 -> 256 -> 256 -> 4")
             for l in mlp.layers:
                 parts += [l.weight.detach().float().reshape(-1), l.bias.detach().float().reshape(-1)]
+        if self.n_tail:
+            parts += [p.detach().float().reshape(-1) for p in self._tail_modules_params()]
         self.param = torch.cat(parts).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -221,6 +252,30 @@ class HeadTrainer:
             o += k
         return out
 
+    def _tail_modules_params(self) -> List[torch.Tensor]:
+        """the model's eight tail parameters in the flat order (ops.TAIL_NAMES)"""
+        dec = self.model.transformer.decoder
+        last = dec.layers[len(dec.layers) - 1]
+        return [last.linear1.weight, last.linear1.bias, last.linear2.weight, last.linear2.bias, last.norm3.weight, last.norm3.bias,
+                dec.norm.weight, dec.norm.bias]
+
+    def tail(self) -> List[torch.Tensor]:
+        """the master tail as views of the flat buffer: [W1, b1, W2, b2, norm3.w, norm3.b, dec_norm.w, dec_norm.b] (train includes "tail")"""
+        if not self.n_tail:
+            raise RuntimeError("HeadTrainer: the decoder tail is not trained (train lacks 'tail')")
+        out, o = [], self.n_class + self.n_box
+        for shape in ops.tail_shapes(self.F):
+            k = int(np.prod(shape))
+            out.append(self.param[o:o + k].view(shape))
+            o += k
+        return out
+
+    def _box_weights(self) -> List[torch.Tensor]:
+        """the box MLP the forward runs: the master when it is trained, else the model's"""
+        if self.n_box:
+            return self.box_head()
+        return [p.detach().float() for l in self.model.bbox_embed[0].layers for p in (l.weight, l.bias)]
+
     def _engine(self):
         eng = self.model.engine()
         if self.n_class:
@@ -228,14 +283,22 @@ class HeadTrainer:
         if self.n_box:
             bh = self.box_head()
             eng.set_box_head(bh[0::2], bh[1::2])
+        if self.n_tail:
+            t = self.tail()
+            eng.set_decoder_tail(t[0:2], t[2:4], t[4:6], t[6:8])
         return eng
 
     # -- steps -------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def cache(self, samples, per_line: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(hs [B,nq,hidden] in the engine's dtype, pred_boxes [B,nq,4]) of a batch: the frozen trunk's part of a step."""
+        """(hs [B,nq,hidden] in the engine's dtype, pred_boxes [B,nq,4]) of a batch: the frozen trunk's part of a step.  With "tail"
+        trained the trunk ends one block earlier: (tail_in [B,nq,hidden], the last decoder layer's FFN input, and ref_last [B,nq,4], that
+        layer's reference points)."""
         self._no_cache("cache")
         self._engine()
+        if self.n_tail:                                                     # (the last layer's FFN input, its reference points): tail_forward's arguments
+            out = self.model(samples, per_line=per_line, return_hidden="tail")
+            return out["tail_in"], out["refs"][len(out["hs_all"]) - 1]
         out = self.model(samples, per_line=per_line, return_hidden=True)
         return out["hs"], out["pred_boxes"]
 
@@ -244,14 +307,20 @@ class HeadTrainer:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         if self.every_output:
-            return self._update_every(self.model(samples, per_line=per_line, return_hidden="all"), target_labels, target_boxes)
+            return self._update_every(self.model(samples, per_line=per_line, return_hidden="tail" if self.n_tail else "all"), target_labels,
+                                      target_boxes)
         out = self.model(samples, per_line=per_line, return_hidden=True)
         return self._update(out["pred_logits"], out["hs"], out["pred_boxes"], target_labels, target_boxes)
 
     @torch.no_grad()
     def step_cached(self, hs: torch.Tensor, boxes: torch.Tensor, target_labels: Sequence[Sequence[int]], target_boxes=None) -> Dict[str, torch.Tensor]:
-        """The same step on cached decoder states: only the class head runs forward."""
+        """The same step on cached decoder states: only the class head runs forward -- with "tail" trained, on cache()'s (tail_in,
+        ref_last): the last FFN, the norms and both heads run forward (DTLREngine.tail_forward), in the bits of the full step."""
         self._no_cache("step_cached")
+        if self.n_tail:                                                     # hs, boxes: cache()'s (tail_in, ref_last) -- the main output alone
+            o = self._engine().tail_forward(hs, boxes)
+            return self._update_every({"hs_all": [o["hs"]], "tgt_all": [None], "refs": [boxes], "aux_outputs": [], "tail_in": hs,
+                                       "pred_logits": o["pred_logits"], "pred_boxes": o["pred_boxes"]}, target_labels, target_boxes)
         logits = self._engine()._class_head(hs)
         return self._update(logits, hs, boxes, target_labels, target_boxes)
 
@@ -276,34 +345,56 @@ class HeadTrainer:
         boxes = torch.stack([a["pred_boxes"] for a in out["aux_outputs"]] + [out["pred_boxes"]])
         B, nq = int(logits.shape[1]), int(logits.shape[2])
         self.last_outputs = {"pred_logits": out["pred_logits"], "pred_boxes": out["pred_boxes"]}
-        tg = self._set_targets(target_labels, target_boxes, logits.device)
-        match = self.matcher.match(logits, boxes, tg)
-        self.last_states = {"hs_all": hs_all, "tgt_all": tgt_all, "refs": refs, "pred_logits": logits, "pred_boxes": boxes, "match_q": match}
         used = [l for l in range(L) if self.aux_loss or l == L - 1]
-        row = [self.cls_loss_coef if self.n_class else 0.0, self.bbox_loss_coef if self.n_box else 0.0, self.giou_loss_coef if self.n_box else 0.0]
-        r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [row if l in used else [0.0, 0.0, 0.0] for l in range(L)],
-                         [bool(self.n_class) and l in used for l in range(L)], self.matcher.focal_alpha)
-        v = r["losses"]
-        result = {"loss_ce": v[L - 1, 0], "loss_bbox": v[L - 1, 1], "loss_giou": v[L - 1, 2], "cardinality_error": v[L - 1, 5], "class_error": v[L - 1, 6]}
-        for l in range(L - 1):
-            result.update({f"loss_ce_{l}": v[l, 0], f"loss_bbox_{l}": v[l, 1], f"loss_giou_{l}": v[l, 2]})
-        if self.loss == "ctc+set":
-            if self.n_class:
-                result["loss_CTC"], dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
-                r["dlogits"][L - 1].add_(dctc, alpha=self.CTC_loss_coef)
-            else:
-                result["loss_CTC"] = E.loss_ctc(self.last_outputs, target_labels)
+        cls_on, box_on = bool(self.n_class or self.n_tail), bool(self.n_box or self.n_tail)      # the tail moves both outputs through the states
+        self.last_states = {"hs_all": hs_all, "tgt_all": tgt_all, "refs": refs, "pred_logits": logits, "pred_boxes": boxes}
+        if self.n_tail:
+            self.last_states["tail_in"] = out["tail_in"]
+        match = r = None
+        if self.loss == "ctc":                                                  # train includes "tail": the CTC loss reaches it through dlogits alone
+            result = {}
+            result["loss_CTC"], dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
+            dlogits = {L - 1: dctc}
+        else:
+            tg = self._set_targets(target_labels, target_boxes, logits.device)
+            match = self.matcher.match(logits, boxes, tg)
+            self.last_states["match_q"] = match
+            row = [self.cls_loss_coef if cls_on else 0.0, self.bbox_loss_coef if box_on else 0.0, self.giou_loss_coef if box_on else 0.0]
+            r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [row if l in used else [0.0, 0.0, 0.0] for l in range(L)],
+                             [cls_on and l in used for l in range(L)], self.matcher.focal_alpha)
+            v = r["losses"]
+            result = {"loss_ce": v[L - 1, 0], "loss_bbox": v[L - 1, 1], "loss_giou": v[L - 1, 2], "cardinality_error": v[L - 1, 5], "class_error": v[L - 1, 6]}
+            for l in range(L - 1):
+                result.update({f"loss_ce_{l}": v[l, 0], f"loss_bbox_{l}": v[l, 1], f"loss_giou_{l}": v[l, 2]})
+            if self.loss == "ctc+set":
+                if cls_on:
+                    result["loss_CTC"], dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
+                    r["dlogits"][L - 1].add_(dctc, alpha=self.CTC_loss_coef)
+                else:
+                    result["loss_CTC"] = E.loss_ctc(self.last_outputs, target_labels)
+            dlogits = {l: r["dlogits"][l] for l in used} if cls_on else {}
+        G = torch.cat([dlogits[l].view(-1, self.C) for l in used]) if dlogits else None
         if self.n_class:
-            G = torch.cat([r["dlogits"][l].view(-1, self.C) for l in used])
             X = torch.cat([hs_all[l].reshape(-1, self.D) for l in used])
             ops.head_grad(G, X, out=self.grad[: self.n_class])
-        if self.n_box:
+        dz = None
+        if box_on and r is not None:
             dz, du = ops.box_refine_grad(r["dboxes"], boxes, torch.stack(refs[:L]))
+        if self.n_box:
             below = [l for l in used if l >= 1]                                  # look forward twice: output l's box also reads f(t_(l-1))
             xs = [hs_all[l].reshape(-1, self.D) for l in used] + [tgt_all[l - 1].reshape(-1, self.D) for l in below]
             dys = [dz[l] for l in used] + [du[l - 1] for l in below]
             rows = ops.match_rows(match, nq, B)[used + below]
-            ops.box_mlp_grad(xs, dys, self.box_head(), rows=rows, out=self.grad[self.n_class:])
+            ops.box_mlp_grad(xs, dys, self.box_head(), rows=rows, out=self.grad[self.n_class: self.n_class + self.n_box])
+        if self.n_tail:
+            # the gradient at h_l of every weighted output: the class head's input gradient, plus the box MLP's on the matched rows;
+            # the terms at t_(l-1) (look forward twice) land on frozen states and are dropped
+            M = B * nq
+            dh = ops.head_dx(G, self.weight) if G is not None else torch.zeros((len(used) * M, self.D), dtype=torch.float32, device=logits.device)
+            if dz is not None:
+                ops.box_mlp_dx([hs_all[l].reshape(-1, self.D) for l in used], [dz[l] for l in used], [dh[k * M:(k + 1) * M] for k in range(len(used))],
+                               self._box_weights(), rows=ops.match_rows(match, nq, B)[used])
+            ops.tail_grad(out["tail_in"], [tgt_all[l] for l in used if l < L - 1], dh, self.tail(), out=self.grad[self.n_class + self.n_box:])
         self._clip_and_step()
         return result
 
@@ -347,9 +438,15 @@ class HeadTrainer:
         sd = {"head": torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
               "exp_avg": self.exp_avg[:nc].cpu().clone(), "exp_avg_sq": self.exp_avg_sq[:nc].cpu().clone(),
               "step": int(self.step_count), "num_classes": self.C, "hidden_dim": self.D}
+        nb = nc + self.n_box
+        if self.n_box or self.n_tail:
+            sd["train"] = list(self.train)
         if self.n_box:
-            sd.update({"train": list(self.train), "box_head": self.param[nc:].detach().cpu().clone(), "box_exp_avg": self.exp_avg[nc:].cpu().clone(),
-                       "box_exp_avg_sq": self.exp_avg_sq[nc:].cpu().clone()})
+            sd.update({"box_head": self.param[nc:nb].detach().cpu().clone(), "box_exp_avg": self.exp_avg[nc:nb].cpu().clone(),
+                       "box_exp_avg_sq": self.exp_avg_sq[nc:nb].cpu().clone()})
+        if self.n_tail:                                                     # "tail": [W1 | b1 | W2 | b2 | norm3.w | norm3.b | dec_norm.w | dec_norm.b]
+            sd.update({"tail": self.param[nb:].detach().cpu().clone(), "tail_exp_avg": self.exp_avg[nb:].cpu().clone(),
+                       "tail_exp_avg_sq": self.exp_avg_sq[nb:].cpu().clone(), "dim_feedforward": self.F})
         return sd
 
     def load_state_dict(self, sd: Dict) -> None:
@@ -363,9 +460,16 @@ class HeadTrainer:
                 self.exp_avg[:nc].copy_(sd["exp_avg"])
                 self.exp_avg_sq[:nc].copy_(sd["exp_avg_sq"])
         if self.n_box and "box_head" in sd:                                 # absent: a state written before the box head could be trained --
-            self.param[nc:].copy_(sd["box_head"])                           # the box head then stays the model's, its moments zero
-            self.exp_avg[nc:].copy_(sd["box_exp_avg"])
-            self.exp_avg_sq[nc:].copy_(sd["box_exp_avg_sq"])
+            self.param[nc:nc + self.n_box].copy_(sd["box_head"])            # the box head then stays the model's, its moments zero
+            self.exp_avg[nc:nc + self.n_box].copy_(sd["box_exp_avg"])
+            self.exp_avg_sq[nc:nc + self.n_box].copy_(sd["box_exp_avg_sq"])
+        if self.n_tail and "tail" in sd:                                    # absent: an older state -- the tail stays the model's, its moments zero
+            nb = nc + self.n_box
+            if sd["tail"].numel() != self.n_tail:
+                raise ValueError(f"HeadTrainer.load_state_dict: the state's tail has {sd['tail'].numel()} elements, this trainer's {self.n_tail}")
+            self.param[nb:].copy_(sd["tail"])
+            self.exp_avg[nb:].copy_(sd["tail_exp_avg"])
+            self.exp_avg_sq[nb:].copy_(sd["tail_exp_avg_sq"])
         self.step_count = int(sd["step"])
 
     @torch.no_grad()
@@ -381,6 +485,9 @@ class HeadTrainer:
             for i, layer in enumerate(self.model.bbox_embed[0].layers):
                 layer.weight.copy_(bh[2 * i])
                 layer.bias.copy_(bh[2 * i + 1])
+        if self.n_tail:
+            for p, v in zip(self._tail_modules_params(), self.tail()):
+                p.copy_(v)
         self.model._engine = None                                           # the packed model is rebuilt from the new parameters
         return self.model
 
@@ -420,7 +527,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "each transcript under the initial head (evaluation.align_ctc), lines without a feasible alignment are skipped")
     ap.add_argument("--boxes", default=None, help="JSON {image id: [[cx, cy, w, h], ...]}: one box a character, normalised to 0..1 (--boxes-from labels)")
     ap.add_argument("--train", default="class", help="the heads to train, comma-separated: class (default), box (the shared box head; needs "
-                                                     "--loss set or ctc+set and the full forward every step), or class,box")
+                                                     "--loss set or ctc+set and the full forward every step), tail (the last decoder "
+                                                     "layer's FFN and norm3 and decoder.norm; any loss), e.g. class,box,tail")
     ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
@@ -480,8 +588,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     ap = build_parser()
     args = ap.parse_args(argv)
     train = tuple(k.strip() for k in args.train.split(",") if k.strip())
-    if not train or set(train) - {"class", "box"}:
-        ap.error(f"--train {args.train}: a comma-separated subset of class, box")
+    if not train or set(train) - {"class", "box", "tail"}:
+        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail")
     if "box" in train and args.cache_features:
         ap.error("--cache-features cannot train the box head: the forward depends on it")
     if ("box" in train or args.aux_loss) and args.loss == "ctc":

@@ -488,6 +488,38 @@ class DTLREngine:
                 self._put(f"bbox{i}.wh", wt.detach())
             self._drop_images(f"bbox{i}")
 
+    @torch.no_grad()
+    def set_decoder_tail(self, linear1, linear2, norm3, decoder_norm) -> None:
+        """Replace the decoder's tail -- linear1, linear2 and norm3 of the LAST decoder layer and transformer.decoder.norm, each a
+        (weight, bias) pair -- in the packed model without re-packing anything else: set_box_head's counterpart.
+        `dec{L-1}.ff1 / ff2` are swapped as _put_linear packs them (the engine dtype, the split engine's hi + lo image and its kept fp32
+        source), `dec{L-1}.norm3` and `dec.norm` in fp32, and the images derived from the two linears (`ffn32`, `ffn_split`, `ffn_w2`, ..)
+        are dropped, to be rebuilt by the next forward.  A forward after this equals, bit for bit, the forward of a fresh engine built from
+        the updated state dict."""
+        d, q = self.cfg.hidden_dim, f"dec{self.cfg.dec_layers - 1}."
+        F = int(linear1[0].shape[0]) if linear1[0].dim() == 2 else -1
+        want = [((F, d), (F,)), ((d, F), (d,)), ((d,), (d,)), ((d,), (d,))]
+        if [tuple(tuple(t.shape) for t in pair) for pair in (linear1, linear2, norm3, decoder_norm)] != want or F != int(self.w[q + "ff1.b"].numel()):
+            raise ValueError(f"set_decoder_tail: not linear1 [{self.w[q + 'ff1.b'].numel()},{d}], linear2 [{d},{self.w[q + 'ff1.b'].numel()}], "
+                             f"norm3 [{d}] and decoder.norm [{d}], each with its bias")
+        for name in (q + "ff", q + "ff1", q + "ff2"):                         # before the puts: a split engine's kept fp32 sources are (kind, name) entries too
+            self._drop_images(name)
+        self._put_linear(q + "ff1", linear1[0].detach().clone(), linear1[1].detach().clone())      # copies: the engine never aliases the caller's buffers
+        self._put_linear(q + "ff2", linear2[0].detach().clone(), linear2[1].detach().clone())
+        for name, (wt, b) in ((q + "norm3", norm3), ("dec.norm", decoder_norm)):
+            self._put(name + ".w", wt.detach().clone(), torch.float32)
+            self._put(name + ".b", b.detach().clone(), torch.float32)
+
+    @torch.no_grad()
+    def tail_forward(self, tail_in, ref_last) -> Dict[str, torch.Tensor]:
+        """The main output from the last decoder layer's FFN input on (forward(return_hidden="tail")'s out["tail_in"], in the engine's
+        dtype) and that layer's reference points out["refs"][dec_layers - 1]: _ffn + norm3 -> decoder.norm -> class head -> box head, the
+        launches the forward itself makes there, so pred_logits / pred_boxes / hs equal the forward's in bits.  The cached training step of
+        the tail (dtlr_amd/adapt.py) runs this instead of the trunk."""
+        tgt = self._ffn(f"dec{self.cfg.dec_layers - 1}.", "norm3", tail_in)
+        hs = self._ln("dec.norm", tgt)
+        return {"pred_logits": self._class_head(hs), "pred_boxes": self._refine(hs, ref_last), "hs": hs}
+
     def _class_head(self, hs):
         """class_embed on decoder states (models/dino/dino.py:349-352), fp32 logits.  bf16 engine: the states are exact bf16
         values, so [hs | hs] . [W_hi | W_lo]^T on the bf16 matrix cores is the fp32-weight product to ~2^-16 relative -- the
@@ -946,12 +978,13 @@ class DTLREngine:
             return True
         return False
 
-    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None):
+    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None, tail_in=None):
         """TransformerDecoder.forward + DeformableTransformerDecoderLayer
         (deformable_transformer.py:652-766, 882-997), batch-first.  vall: value_proj(memory) of all layers when the caller already
         computed it (forward() does, on a side stream under the two-stage selection).  per_line: the query position embedding is the
         sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios.  tgt_all: a list that
-        receives every layer's un-normed output (what the box head's refinement of the reference points reads)."""
+        receives every layer's un-normed output (what the box head's refinement of the reference points reads).  tail_in: a list that
+        receives the last layer's FFN input (its state after norm1: what the tail's gradient starts from)."""
         cfg = self.cfg
         B = memory.shape[0]
         ref = ts["ref_unsig"].sigmoid()
@@ -986,6 +1019,8 @@ class DTLREngine:
             a = self._msda_module(q + "attn", tgt, qpos, ref_in, memory, g, cfg.dec_n_points, value=vall[..., n * C:(n + 1) * C])
             tgt = self._proj_ln(q + "attn.out", q + "norm1", a, tgt)
             # ffn
+            if tail_in is not None and n == cfg.dec_layers - 1:
+                tail_in.append(tgt)
             tgt = self._ffn(q, "norm3", tgt)
             # iterative box refinement (734-756)
             ref = self._refine(tgt, ref)
@@ -1128,7 +1163,9 @@ class DTLREngine:
         class head multiplies (dtlr_amd/adapt.py trains the head on it); no extra launch.  return_hidden="all" (implies want_aux): also
         out["hs_all"], the normalised output of every decoder layer (hs_all[-1] is out["hs"]), out["tgt_all"], the same before
         decoder.norm, and out["refs"], the dec_layers + 1 reference points [B,nq,4] fp32 -- everything the box head's gradient needs
-        (DESIGN.md section 21); the tensors the forward makes anyway, no extra launch beyond want_aux's."""
+        (DESIGN.md section 21); the tensors the forward makes anyway, no extra launch beyond want_aux's.  return_hidden="tail": "all", and
+        out["tail_in"], the last decoder layer's state after norm1 [B,nq,hidden] in the engine's dtype -- the input of that layer's FFN,
+        where the tail's gradient starts; again a tensor the forward already has."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1183,15 +1220,18 @@ class DTLREngine:
         ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        if return_hidden not in (False, True, "all"):
-            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all'")
+        if return_hidden not in (False, True, "all", "tail"):
+            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail'")
         every = isinstance(return_hidden, str)
         want_aux = want_aux or every
         tgt_all = [] if every else None
-        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all)
+        tail_in = [] if return_hidden == "tail" else None
+        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in)
         out = self.heads(hs, refs, ts, want_aux, bool(return_hidden))
         if every:
             out["hs_all"], out["tgt_all"], out["refs"] = list(hs), tgt_all, list(refs)
+        if tail_in is not None:
+            out["tail_in"] = tail_in[0]
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

@@ -1856,3 +1856,6 @@ from .pattern import (PATTERN_WORKSPACE_LIMIT, compile_pattern, pattern_decode, 
 from .setloss import SetTargets, hungarian, set_cost, set_loss, set_targets          # noqa: E402,F401
 # the eighth header (include/dtlr_boxgrad.h), the same way: written in dtlr_amd/boxgrad.py (the box head's gradient with the trunk frozen)
 from .boxgrad import BOX_GRAD_FLOATS, BOX_GRAD_MAX_APPS, BOX_HEAD_SHAPES, box_mlp_grad, box_refine_grad, match_rows          # noqa: E402,F401
+# the ninth header (include/dtlr_tailgrad.h), the same way: written in dtlr_amd/tailgrad.py (the decoder tail's gradient with the trunk frozen)
+from .tailgrad import (TAIL_NAMES, box_mlp_dx, ffn_grad, ffn_recompute, head_dx, ln_backward, tail_floats, tail_grad,            # noqa: E402,F401
+                       tail_shapes)

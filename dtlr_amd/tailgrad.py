@@ -1,0 +1,204 @@
+"""The operators of the ninth C header, include/dtlr_tailgrad.h (the gradient of the decoder's tail -- the last decoder layer's FFN and
+norm3, decoder.norm -- with the trunk frozen), over the launch seam of dtlr_amd/_lib.py: `_lib.launch` /
+`_lib.query` name each symbol once, `@_lib.op` scopes a call to the device of its first tensor.  dtlr_amd/ops.py serves these functions
+under its own name too (ops.head_dx, ops.box_mlp_dx, ops.ln_backward, ops.ffn_recompute, ops.ffn_grad, ops.tail_grad);
+dtlr_amd/adapt.py's HeadTrainer trains the tail on them."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+
+TAIL_HIDDEN = _lib.TAILGRAD_CONSTANTS["DTLR_TAIL_HIDDEN"]
+TAIL_MAX_FFN = _lib.TAILGRAD_CONSTANTS["DTLR_TAIL_MAX_FFN"]
+TAIL_MAX_CLASSES = _lib.TAILGRAD_CONSTANTS["DTLR_TAIL_MAX_CLASSES"]
+TAIL_MAX_APPS = _lib.TAILGRAD_CONSTANTS["DTLR_TAIL_MAX_APPS"]
+# the flat order of the tail's parameters: linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm
+TAIL_NAMES = ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm3.weight", "norm3.bias", "decoder.norm.weight",
+              "decoder.norm.bias")
+LN_EPS = 1e-5
+
+_DT = {torch.float32: _lib.DTLR_F32, torch.bfloat16: _lib.DTLR_BF16, torch.float16: _lib.DTLR_F16}
+
+
+def tail_shapes(F: int):
+    """the shapes of TAIL_NAMES at dim_feedforward = F"""
+    d = TAIL_HIDDEN
+    return ((F, d), (F,), (d, F), (d,), (d,), (d,), (d,), (d,))
+
+
+def tail_floats(F: int) -> int:
+    """the length of the flat tail [W1 | b1 | W2 | b2 | norm3.w | norm3.b | dec_norm.w | dec_norm.b]"""
+    return 2 * TAIL_HIDDEN * F + F + 5 * TAIL_HIDDEN
+
+
+def _gpu(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"dtlr_amd: {what} must live on the GPU (no CPU path; got device {t.device})")
+    return t
+
+
+def _f32(t, what):
+    return _gpu(t, what).float().contiguous()
+
+
+def _rows(x, what):
+    """x [..., 256] of a supported dtype -> ([M,256] contiguous, M)"""
+    _gpu(x, what)
+    if x.dtype not in _DT or x.shape[-1] != TAIL_HIDDEN or x.numel() == 0:
+        raise ValueError(f"{what}: {tuple(x.shape)} {x.dtype} is not [.., {TAIL_HIDDEN}] in fp32 / bf16 / fp16")
+    x = x.contiguous().view(-1, TAIL_HIDDEN)
+    return x, int(x.shape[0])
+
+
+def _workspace(nbytes, dev, what):
+    if nbytes <= 0:
+        raise _lib.DTLRError(f"{what}: unsupported shape")
+    return torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+
+
+@_lib.op
+def head_dx(g, w, out: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """dtlr_head_dx: g [M,C] fp32 (dlogits; the rows of several outputs stacked), w [C,256] fp32 (the class head's master weight) ->
+    dh [M,256] fp32 = g w, or out += g w with accumulate."""
+    g, w = _f32(g, "dlogits"), _f32(w, "the class head's weight")
+    if g.dim() != 2 or w.dim() != 2 or w.shape[0] != g.shape[1] or g.shape[0] < 1:
+        raise ValueError(f"head_dx: dlogits {tuple(g.shape)} against a weight {tuple(w.shape)}")
+    M, C = int(g.shape[0]), int(g.shape[1])
+    if out is None:
+        if accumulate:
+            raise ValueError("head_dx: accumulate needs out")
+        out = torch.empty((M, TAIL_HIDDEN), dtype=torch.float32, device=g.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == M * TAIL_HIDDEN and out.device == g.device
+    _lib.launch(_lib.lib(), "dtlr_head_dx", g.data_ptr(), w.data_ptr(), out.data_ptr(), M, C, int(bool(accumulate)))
+    return out
+
+
+@_lib.op
+def box_mlp_dx(xs: Sequence[torch.Tensor], dzs: Sequence[torch.Tensor], dhs: Sequence[torch.Tensor], weights: Sequence[torch.Tensor],
+               rows: Optional[torch.Tensor] = None):
+    """dtlr_box_mlp_dx: the box MLP's input gradient ADDED into dhs[a] [M,256] fp32 (contiguous, distinct buffers) on the listed rows of
+    each application (xs[a] [M,256] in one dtype, dzs[a] [M,4] fp32: ops.box_refine_grad's dz).  weights: the fp32 masters (W0, b0, W1,
+    b1, W2[, b2]).  rows: None (every row) or [A,R] int32 (ops.match_rows), entries outside [0, M) skipped; a row is listed once."""
+    A = len(xs)
+    if A < 1 or A > TAIL_MAX_APPS or len(dzs) != A or len(dhs) != A:
+        raise _lib.DTLRError(f"box_mlp_dx: {A} applications with {len(dzs)} gradients and {len(dhs)} outputs (1..{TAIL_MAX_APPS})")
+    x0, M = _rows(xs[0], "box_mlp_dx: x")
+    dev, dt = x0.device, x0.dtype
+    xs = [_rows(x, "box_mlp_dx: x")[0] for x in xs]
+    dzs = [d.contiguous() for d in dzs]
+    for x, d, o in zip(xs, dzs, dhs):
+        if x.dtype != dt or x.device != dev or d.device != dev or d.dtype != torch.float32 or x.shape[0] != M or d.numel() != M * 4 \
+                or o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() != M * TAIL_HIDDEN:
+            raise ValueError(f"box_mlp_dx: x {tuple(x.shape)} {x.dtype}, dz {tuple(d.shape)} {d.dtype}, dh {tuple(o.shape)} {o.dtype}")
+    ws_ = [w.contiguous() for w in weights[:5]]
+    if [tuple(w.shape) for w in ws_] != [(256, 256), (256,), (256, 256), (256,), (4, 256)] or any(w.dtype != torch.float32 or w.device != dev for w in ws_):
+        raise ValueError(f"box_mlp_dx: the weights must be the fp32 box MLP 256 -> 256 -> 256 -> 4 on {dev}")
+    R = 0
+    if rows is not None:
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != A or rows.device != dev or rows.shape[1] < 1:
+            raise ValueError(f"box_mlp_dx: rows must be [{A}, R] int32 on {dev}")
+        rows = rows.contiguous()
+        R = int(rows.shape[1])
+    L = _lib.lib(dt)
+    ws = _workspace(_lib.query(L, "dtlr_box_mlp_dx_workspace_bytes", A, M, R), dev, f"dtlr_box_mlp_dx A={A} M={M} R={R}")
+    xp = (ctypes.c_void_p * A)(*[x.data_ptr() for x in xs])
+    dp = (ctypes.c_void_p * A)(*[d.data_ptr() for d in dzs])
+    op = (ctypes.c_void_p * A)(*[o.data_ptr() for o in dhs])
+    _lib.launch(L, "dtlr_box_mlp_dx", xp, dp, op, rows.data_ptr() if rows is not None else None, A, M, R, _DT[dt], ws_[0].data_ptr(),
+                ws_[1].data_ptr(), ws_[2].data_ptr(), ws_[3].data_ptr(), ws_[4].data_ptr(), ws.data_ptr())
+    return list(dhs)
+
+
+@_lib.op
+def ln_backward(x, gamma, g, dx_row0: Optional[int] = 0, eps: float = LN_EPS, dgamma: Optional[torch.Tensor] = None,
+                dbeta: Optional[torch.Tensor] = None):
+    """dtlr_ln_backward: x [M,256] (fp32 / bf16 / fp16: the LayerNorm's input), gamma [256], g [M,256] fp32 (the gradient at its output)
+    -> (dx [M - dx_row0, 256] fp32 of the rows from dx_row0 on, or None when dx_row0 is None; dgamma [256]; dbeta [256]).  dgamma /
+    dbeta: fp32 buffers of 256 to fill (views of a flat gradient)."""
+    x, M = _rows(x, "ln_backward: x")
+    dev = x.device
+    gamma, g = _f32(gamma, "gamma"), _f32(g, "g").view(-1, TAIL_HIDDEN)
+    if gamma.numel() != TAIL_HIDDEN or g.shape[0] != M or (dx_row0 is not None and not 0 <= dx_row0 < M):
+        raise ValueError(f"ln_backward: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, g {tuple(g.shape)}, dx_row0 {dx_row0}")
+    dx = torch.empty((M - dx_row0, TAIL_HIDDEN), dtype=torch.float32, device=dev) if dx_row0 is not None else None
+    dgamma = torch.empty((TAIL_HIDDEN,), dtype=torch.float32, device=dev) if dgamma is None else dgamma
+    dbeta = torch.empty((TAIL_HIDDEN,), dtype=torch.float32, device=dev) if dbeta is None else dbeta
+    for t in (dgamma, dbeta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == TAIL_HIDDEN and t.device == dev
+    L = _lib.lib(x.dtype)
+    ws = _workspace(_lib.query(L, "dtlr_ln_backward_workspace_bytes", M), dev, f"dtlr_ln_backward M={M}")
+    _lib.launch(L, "dtlr_ln_backward", x.data_ptr(), _DT[x.dtype], gamma.data_ptr(), g.data_ptr(), dx.data_ptr() if dx is not None else None,
+                int(dx_row0 or 0), dgamma.data_ptr(), dbeta.data_ptr(), M, float(eps), ws.data_ptr())
+    return dx, dgamma, dbeta
+
+
+def _ffn_weights(weights, dev, what):
+    ws_ = [w.contiguous() for w in weights]
+    F = int(ws_[0].shape[0]) if ws_ and ws_[0].dim() == 2 else 0
+    if len(ws_) != 4 or [tuple(w.shape) for w in ws_] != list(tail_shapes(F)[:4]) or any(w.dtype != torch.float32 or w.device != dev for w in ws_):
+        raise ValueError(f"{what}: the weights must be fp32 (W1 [F,256], b1 [F], W2 [256,F], b2 [256]) on {dev}")
+    return ws_, F
+
+
+@_lib.op
+def ffn_recompute(u, weights: Sequence[torch.Tensor]):
+    """dtlr_ffn_recompute: u [M,256] (fp32 / bf16 / fp16: the last decoder layer's state after norm1), the fp32 masters (W1, b1, W2, b2)
+    -> (h [M,F] fp32 = relu(W1 u + b1), y [M,256] fp32 = u + W2 h + b2)."""
+    u, M = _rows(u, "ffn_recompute: u")
+    (w1, b1, w2, b2), F = _ffn_weights(weights, u.device, "ffn_recompute")
+    L = _lib.lib(u.dtype)
+    ws = _workspace(_lib.query(L, "dtlr_ffn_recompute_workspace_bytes", M, F), u.device, f"dtlr_ffn_recompute M={M} F={F}")
+    h = torch.empty((M, F), dtype=torch.float32, device=u.device)
+    y = torch.empty((M, TAIL_HIDDEN), dtype=torch.float32, device=u.device)
+    _lib.launch(L, "dtlr_ffn_recompute", u.data_ptr(), _DT[u.dtype], w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), h.data_ptr(),
+                y.data_ptr(), M, F, ws.data_ptr())
+    return h, y
+
+
+@_lib.op
+def ffn_grad(u, h, dy, w2, out: Optional[torch.Tensor] = None):
+    """dtlr_ffn_grad: u [M,256], h [M,F] fp32 (ffn_recompute's), dy [M,256] fp32 (the gradient at y), w2 [256,F] fp32 -> the flat
+    gradient [dW1 | db1 | dW2 | db2] fp32 (out: a buffer of 2 * 256 * F + F + 256 to fill).  Reproducible run to run."""
+    u, M = _rows(u, "ffn_grad: u")
+    dev = u.device
+    h, dy, w2 = _f32(h, "h"), _f32(dy, "dy").view(-1, TAIL_HIDDEN), _f32(w2, "W2")
+    F = int(w2.shape[1]) if w2.dim() == 2 else 0
+    if tuple(w2.shape) != (TAIL_HIDDEN, F) or tuple(h.shape) != (M, F) or dy.shape[0] != M:
+        raise ValueError(f"ffn_grad: u {tuple(u.shape)}, h {tuple(h.shape)}, dy {tuple(dy.shape)}, W2 {tuple(w2.shape)}")
+    n = 2 * TAIL_HIDDEN * F + F + TAIL_HIDDEN
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n and out.device == dev
+    L = _lib.lib(u.dtype)
+    ws = _workspace(_lib.query(L, "dtlr_ffn_grad_workspace_bytes", M, F, _DT[u.dtype]), dev, f"dtlr_ffn_grad M={M} F={F}")
+    _lib.launch(L, "dtlr_ffn_grad", u.data_ptr(), _DT[u.dtype], h.data_ptr(), dy.data_ptr(), w2.data_ptr(), out.data_ptr(), M, F, ws.data_ptr())
+    return out
+
+
+def tail_grad(u, t_below: Sequence[torch.Tensor], dh, tail: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None):
+    """The whole chain of DESIGN.md section 22 below the heads.  u [M,256]: the last decoder layer's FFN input (the engine's state);
+    t_below: the un-normed outputs t_l [M,256] of the decoder outputs l < L - 1 that carry loss weight, in order (empty without
+    aux_loss); dh [(len(t_below) + 1) M, 256] fp32: the gradient at h_l of those outputs and then of the main one (ops.head_dx,
+    ops.box_mlp_dx); tail: the eight fp32 masters in TAIL_NAMES' order.  -> the flat gradient [tail_floats(F)] fp32 (out: a buffer to
+    fill).  y and t_(L-1) are recomputed in fp32 from u and the masters, never read back from the engine."""
+    from . import ops
+    w1, b1, w2, b2, g3, be3, gd, _ = tail
+    F = int(w1.shape[0])
+    n_ffn = 2 * TAIL_HIDDEN * F + F + TAIL_HIDDEN
+    if out is None:
+        out = torch.empty((tail_floats(F),), dtype=torch.float32, device=u.device)
+    assert out.numel() == tail_floats(F) and out.dtype == torch.float32 and out.is_contiguous()
+    v = [out[n_ffn + k * TAIL_HIDDEN: n_ffn + (k + 1) * TAIL_HIDDEN] for k in range(4)]
+    u2 = u.reshape(-1, TAIL_HIDDEN)
+    M = int(u2.shape[0])
+    h, y = ffn_recompute(u2, (w1, b1, w2, b2))
+    t_last = ops.layernorm(y, g3.clone(), be3.clone(), LN_EPS)               # copies: dtlr_layernorm wants 16-byte aligned gamma / beta, views of a flat buffer need not be
+    x = torch.cat([t.reshape(-1, TAIL_HIDDEN).float() for t in t_below] + [t_last]) if len(t_below) else t_last
+    dt, _, _ = ln_backward(x, gd, dh, dx_row0=len(t_below) * M, dgamma=v[2], dbeta=v[3])
+    dy, _, _ = ln_backward(y, g3, dt, dx_row0=0, dgamma=v[0], dbeta=v[1])
+    ffn_grad(u2, h, dy, w2, out=out[:n_ffn])
+    return out
