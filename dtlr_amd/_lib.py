@@ -215,6 +215,28 @@ def query(L, name: str, *args):
     return getattr(L, name)(*args)
 
 
+# What the bindings of the gradient headers (boxgrad.py, tailgrad.py) share: the dtype codes of their activations, the fp32 operand
+# check, and a workspace of whole 16-byte units (the entry points refuse a workspace that is not 16-byte aligned).
+DT = {torch.float32: CONSTANTS["DTLR_F32"], torch.bfloat16: CONSTANTS["DTLR_BF16"], torch.float16: CONSTANTS["DTLR_F16"]}
+
+
+def gpu(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"dtlr_amd: {what} must live on the GPU (no CPU path; got device {t.device})")
+    return t
+
+
+def f32(t, what):
+    return gpu(t, what).float().contiguous()
+
+
+def workspace(nbytes, dev, what):
+    """query()'s byte count -> an fp32 buffer of at least that size; DTLRError where the entry point reports no size for the shape"""
+    if nbytes <= 0:
+        raise DTLRError(f"{what}: unsupported shape")
+    return torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+
+
 def op(fn):
     """Decorator of every binding that reaches the library with tensors: it runs with the device of its FIRST tensor argument
     current (not whatever device happens to be), so that `launch` picks up that device's current stream -- a model moved to cuda:1

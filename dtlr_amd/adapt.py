@@ -28,7 +28,8 @@ from __future__ import annotations
 
 import argparse
 import sys
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -103,6 +104,58 @@ def new_class_head(model, num_classes: int, weight: Optional[torch.Tensor] = Non
     return model
 
 
+TRAINABLE = ("class", "box", "tail")        # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
+
+
+@dataclass
+class ParamGroup:
+    """One trained group of HeadTrainer's flat buffer: the model's parameters in flat order, their shapes, where the group lies in the
+    buffer, its state-dict keys (values, exp_avg, exp_avg_sq) and how its master views are handed to the engine."""
+    params: List[torch.Tensor]
+    shapes: List[Tuple[int, ...]]
+    offset: int
+    n: int
+    keys: Tuple[str, str, str]
+    attach: Callable
+
+    def of(self, flat: torch.Tensor) -> torch.Tensor:
+        """the group's slice of a flat buffer (param, a moment or grad)"""
+        return flat[self.offset: self.offset + self.n]
+
+    def views(self, flat: torch.Tensor) -> List[torch.Tensor]:
+        """the group's tensors as views of a flat buffer, in flat order"""
+        out, o = [], self.offset
+        for shape in self.shapes:
+            k = int(np.prod(shape))
+            out.append(flat[o:o + k].view(shape))
+            o += k
+        return out
+
+
+def _model_params(model, name: str) -> List[torch.Tensor]:
+    """group name -> the model's parameters in the flat order: the shared class head [W, b]; the shared box MLP [W0, b0, W1, b1, W2,
+    b2]; the tail (ops.TAIL_NAMES): linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm"""
+    if name == "class":
+        return [model.class_embed[0].weight, model.class_embed[0].bias]
+    if name == "box":
+        return [p for l in model.bbox_embed[0].layers for p in (l.weight, l.bias)]
+    dec = model.transformer.decoder
+    last = dec.layers[len(dec.layers) - 1]
+    return [last.linear1.weight, last.linear1.bias, last.linear2.weight, last.linear2.bias, last.norm3.weight, last.norm3.bias,
+            dec.norm.weight, dec.norm.bias]
+
+
+# group name -> (its state-dict keys, how its master views reach the engine)
+_GROUPS = {"class": (("head", "exp_avg", "exp_avg_sq"), lambda eng, v: eng.set_class_head(v[0], v[1])),
+           "box": (("box_head", "box_exp_avg", "box_exp_avg_sq"), lambda eng, v: eng.set_box_head(v[0::2], v[1::2])),
+           "tail": (("tail", "tail_exp_avg", "tail_exp_avg_sq"), lambda eng, v: eng.set_decoder_tail(v[0:2], v[2:4], v[4:6], v[6:8]))}
+
+
+def _cat(ts):
+    """torch.cat, without the copy when there is one tensor (the step over one output)"""
+    return ts[0] if len(ts) == 1 else torch.cat(ts)
+
+
 class HeadTrainer:
     """Trains `model.class_embed` (the Linear shared by the decoder layers) against the CTC loss with AdamW, everything on the device.
 
@@ -157,14 +210,23 @@ class HeadTrainer:
     states, and likewise the class terms whether or not "class" is.  The gradient is the fp32 function's at the engine's states: the
     last layer's state after norm1 and the lower layers' outputs are the engine's, the FFN's output and norm3's are recomputed in fp32
     from the master weights.  With "tail" and neither "box" nor aux_loss, `cache` returns (the last layer's FFN input, its reference
-    points) and `step_cached` runs DTLREngine.tail_forward on them: the same step without the trunk."""
+    points) and `step_cached` runs DTLREngine.tail_forward on them: the same step without the trunk.
+
+    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", in this order) to its ParamGroup: the model's
+    parameters in flat order, their shapes, the group's offset and length in the flat buffers (param, exp_avg, exp_avg_sq, grad), its
+    state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail(), _engine(), the step's gradient slices,
+    state_dict / load_state_dict and write_back read that table and nothing else knows an offset.  There is ONE step routine, `_update`,
+    over the L decoder outputs it is given: every output of return_hidden="all" / "tail", or -- the class head on the main output, and
+    every cached step -- the one-output dict `_main_output` builds (L = 1: no loss_*_<l> keys, nothing stacked or concatenated, the
+    four operators of the module docstring with the same arguments).  `last_states` is therefore filled after every step, the default
+    one included (hs_all = [hs], tgt_all = [None], refs = [None] or the cached reference points)."""
 
     def __init__(self, model, lr: float = 1e-5, weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0,
                  train: Sequence[str] = ("class",), aux_loss: bool = False, bbox_loss_coef: float = 5.0, giou_loss_coef: float = 2.0):
         train = (train,) if isinstance(train, str) else tuple(train)
-        if not train or set(train) - {"class", "box", "tail"}:
-            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of ('class', 'box', 'tail')")
+        if not train or set(train) - set(TRAINABLE):
+            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of {TRAINABLE!r}")
         if loss not in ("ctc", "set", "ctc+set"):
             raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
         if "box" in train and loss == "ctc":
@@ -174,7 +236,7 @@ class HeadTrainer:
         if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
             raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
                                       "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
-        self.train = tuple(k for k in ("class", "box", "tail") if k in train)
+        self.train = tuple(k for k in TRAINABLE if k in train)
         self.aux_loss = bool(aux_loss)
         self.bbox_loss_coef, self.giou_loss_coef = float(bbox_loss_coef), float(giou_loss_coef)
         self.every_output = "box" in self.train or "tail" in self.train or self.aux_loss          # the step reads every decoder layer's states
@@ -192,10 +254,7 @@ class HeadTrainer:
             from .criterion import HungarianMatcher
             self.matcher = HungarianMatcher(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0, focal_alpha=0.25)
         self.C, self.D = int(head.weight.shape[0]), int(head.weight.shape[1])
-        dev = head.weight.device
-        self.n_class = self.C * self.D + self.C if "class" in self.train else 0
-        self.n_box = ops.BOX_GRAD_FLOATS if "box" in self.train else 0
-        self.n_tail, self.F = 0, 0
+        self.F = 0
         if "tail" in self.train:
             layers = model.transformer.decoder.layers
             last = layers[len(layers) - 1]
@@ -206,86 +265,59 @@ class HeadTrainer:
                 raise NotImplementedError("HeadTrainer(train=('tail', ..)): the decoder layers share parameters -- the last layer's FFN is then "
                                           "not the tail alone")
             self.F = int(last.linear1.weight.shape[0])
-            if [tuple(p.shape) for p in self._tail_modules_params()] != list(ops.tail_shapes(self.F)) or self.D != 256:
-                raise NotImplementedError("HeadTrainer(train=('tail', ..)): the tail is not linear1 [F,256], linear2 [256,F], norm3 [256], decoder.norm [256]")
-            self.n_tail = ops.tail_floats(self.F)
-        n = self.n_class + self.n_box + self.n_tail
-        parts = [head.weight.detach().float().reshape(-1), head.bias.detach().float().reshape(-1)] if self.n_class else []
-        if self.n_box:
-            mlp = model.bbox_embed[0]
-            if [tuple(l.weight.shape) for l in mlp.layers] != [(256, 256), (256, 256), (4, 256)]:
+        # the ONE table of what is trained: every slice of param / exp_avg / exp_avg_sq / grad below is a lookup in it
+        self.groups: Dict[str, ParamGroup] = {}
+        n = 0
+        for name in self.train:
+            params = _model_params(model, name)
+            g = ParamGroup(params, [tuple(p.shape) for p in params], n, sum(p.numel() for p in params), *_GROUPS[name])
+            if name == "box" and g.shapes != list(ops.BOX_HEAD_SHAPES):
                 raise NotImplementedError("HeadTrainer(train=('box', ..)): the box head is not the MLP 256 -> 256 -> 256 -> 4")
-            for l in mlp.layers:
-                parts += [l.weight.detach().float().reshape(-1), l.bias.detach().float().reshape(-1)]
-        if self.n_tail:
-            parts += [p.detach().float().reshape(-1) for p in self._tail_modules_params()]
-        self.param = torch.cat(parts).to(dev).contiguous()
+            if name == "tail" and (g.shapes != list(ops.tail_shapes(self.F)) or self.D != 256):
+                raise NotImplementedError("HeadTrainer(train=('tail', ..)): the tail is not linear1 [F,256], linear2 [256,F], norm3 [256], decoder.norm [256]")
+            self.groups[name] = g
+            n += g.n
+        self.n_class, self.n_box, self.n_tail = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE)
+        dev = head.weight.device
+        self.param = torch.cat([p.detach().float().reshape(-1) for g in self.groups.values() for p in g.params]).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.scale = torch.ones(2, dtype=torch.float32, device=dev)         # (clip coefficient, gradient norm) of the last step
         self.step_count = 0
         self.last_outputs: Optional[Dict[str, torch.Tensor]] = None         # pred_logits / pred_boxes of the last step (before its update)
-        self.last_states: Optional[Dict] = None                             # every_output: hs_all, tgt_all, refs, stacked outputs, match_q of the last step
+        self.last_states: Optional[Dict] = None                             # hs_all, tgt_all, refs, stacked outputs, match_q of the last step
 
-    # -- the master head ---------------------------------------------------------------------------------------------------------
+    # -- the masters: views of the flat buffer -------------------------------------------------------------------------------------
+    def _views(self, name: str, untrained: str) -> List[torch.Tensor]:
+        if name not in self.groups:
+            raise RuntimeError(untrained)
+        return self.groups[name].views(self.param)
+
     @property
     def weight(self) -> torch.Tensor:
-        if not self.n_class:
-            return self.model.class_embed[0].weight.detach()
-        return self.param[: self.C * self.D].view(self.C, self.D)
+        return self.groups["class"].views(self.param)[0] if self.n_class else self.model.class_embed[0].weight.detach()
 
     @property
     def bias(self) -> torch.Tensor:
-        if not self.n_class:
-            return self.model.class_embed[0].bias.detach()
-        return self.param[self.C * self.D: self.C * self.D + self.C]
+        return self.groups["class"].views(self.param)[1] if self.n_class else self.model.class_embed[0].bias.detach()
 
     def box_head(self) -> List[torch.Tensor]:
         """the master box head as views of the flat buffer: [W0, b0, W1, b1, W2, b2] (train includes "box")"""
-        if not self.n_box:
-            raise RuntimeError("HeadTrainer: the box head is not trained (train=('class',))")
-        out, o = [], self.n_class
-        for shape in ops.BOX_HEAD_SHAPES:
-            k = int(np.prod(shape))
-            out.append(self.param[o:o + k].view(shape))
-            o += k
-        return out
-
-    def _tail_modules_params(self) -> List[torch.Tensor]:
-        """the model's eight tail parameters in the flat order (ops.TAIL_NAMES)"""
-        dec = self.model.transformer.decoder
-        last = dec.layers[len(dec.layers) - 1]
-        return [last.linear1.weight, last.linear1.bias, last.linear2.weight, last.linear2.bias, last.norm3.weight, last.norm3.bias,
-                dec.norm.weight, dec.norm.bias]
+        return self._views("box", "HeadTrainer: the box head is not trained (train=('class',))")
 
     def tail(self) -> List[torch.Tensor]:
         """the master tail as views of the flat buffer: [W1, b1, W2, b2, norm3.w, norm3.b, dec_norm.w, dec_norm.b] (train includes "tail")"""
-        if not self.n_tail:
-            raise RuntimeError("HeadTrainer: the decoder tail is not trained (train lacks 'tail')")
-        out, o = [], self.n_class + self.n_box
-        for shape in ops.tail_shapes(self.F):
-            k = int(np.prod(shape))
-            out.append(self.param[o:o + k].view(shape))
-            o += k
-        return out
+        return self._views("tail", "HeadTrainer: the decoder tail is not trained (train lacks 'tail')")
 
     def _box_weights(self) -> List[torch.Tensor]:
         """the box MLP the forward runs: the master when it is trained, else the model's"""
-        if self.n_box:
-            return self.box_head()
-        return [p.detach().float() for l in self.model.bbox_embed[0].layers for p in (l.weight, l.bias)]
+        return self.box_head() if self.n_box else [p.detach().float() for p in _model_params(self.model, "box")]
 
     def _engine(self):
         eng = self.model.engine()
-        if self.n_class:
-            eng.set_class_head(self.weight, self.bias)
-        if self.n_box:
-            bh = self.box_head()
-            eng.set_box_head(bh[0::2], bh[1::2])
-        if self.n_tail:
-            t = self.tail()
-            eng.set_decoder_tail(t[0:2], t[2:4], t[4:6], t[6:8])
+        for g in self.groups.values():
+            g.attach(eng, g.views(self.param))
         return eng
 
     # -- steps -------------------------------------------------------------------------------------------------------------------
@@ -307,22 +339,29 @@ class HeadTrainer:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         if self.every_output:
-            return self._update_every(self.model(samples, per_line=per_line, return_hidden="tail" if self.n_tail else "all"), target_labels,
-                                      target_boxes)
-        out = self.model(samples, per_line=per_line, return_hidden=True)
-        return self._update(out["pred_logits"], out["hs"], out["pred_boxes"], target_labels, target_boxes)
+            out = self.model(samples, per_line=per_line, return_hidden="tail" if self.n_tail else "all")
+        else:                                                               # the class head on the main output: the last state is all the step reads
+            o = self.model(samples, per_line=per_line, return_hidden=True)
+            out = self._main_output(o["hs"], o["pred_logits"], o["pred_boxes"])
+        return self._update(out, target_labels, target_boxes)
 
     @torch.no_grad()
     def step_cached(self, hs: torch.Tensor, boxes: torch.Tensor, target_labels: Sequence[Sequence[int]], target_boxes=None) -> Dict[str, torch.Tensor]:
         """The same step on cached decoder states: only the class head runs forward -- with "tail" trained, on cache()'s (tail_in,
         ref_last): the last FFN, the norms and both heads run forward (DTLREngine.tail_forward), in the bits of the full step."""
         self._no_cache("step_cached")
-        if self.n_tail:                                                     # hs, boxes: cache()'s (tail_in, ref_last) -- the main output alone
+        if self.n_tail:                                                     # hs, boxes: cache()'s (tail_in, ref_last)
             o = self._engine().tail_forward(hs, boxes)
-            return self._update_every({"hs_all": [o["hs"]], "tgt_all": [None], "refs": [boxes], "aux_outputs": [], "tail_in": hs,
-                                       "pred_logits": o["pred_logits"], "pred_boxes": o["pred_boxes"]}, target_labels, target_boxes)
-        logits = self._engine()._class_head(hs)
-        return self._update(logits, hs, boxes, target_labels, target_boxes)
+            out = self._main_output(o["hs"], o["pred_logits"], o["pred_boxes"], ref=boxes, tail_in=hs)
+        else:
+            out = self._main_output(hs, self._engine()._class_head(hs), boxes)
+        return self._update(out, target_labels, target_boxes)
+
+    @staticmethod
+    def _main_output(hs, logits, boxes, ref=None, **more):
+        """what return_hidden="all" would hold of a decoder with the main output alone (L = 1); ref: that output's reference points,
+        which only the box gradient reads"""
+        return {"hs_all": [hs], "tgt_all": [None], "refs": [ref], "aux_outputs": [], "pred_logits": logits, "pred_boxes": boxes, **more}
 
     def _no_cache(self, what):
         if "box" in self.train:
@@ -336,13 +375,15 @@ class HeadTrainer:
         return ops.set_targets([{"labels": torch.as_tensor(l, dtype=torch.int64), "boxes": torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)}
                                 for l, b in zip(target_labels, target_boxes)], device, self.C)
 
-    def _update_every(self, out, target_labels, target_boxes):
-        """the step over every decoder output: the set losses of all L outputs, dW of the class head summed over the weighted outputs,
-        the box head's gradient at its 2 L - 1 applications, one clip and one AdamW over the flat buffer"""
+    def _update(self, out, target_labels, target_boxes):
+        """THE step, over the L decoder outputs `out` holds (return_hidden="all" / "tail", or _main_output's L = 1): the losses, dW of
+        the class head summed over the weighted outputs, the box head's gradient at its 2 L - 1 applications, the tail's chain, then one
+        clip and one AdamW over the flat buffer.  With L = 1 and the class head alone this is the four-operator chain of the module
+        docstring: nothing is stacked or concatenated, the set losses see one row of weights."""
         hs_all, tgt_all, refs = out["hs_all"], out["tgt_all"], out["refs"]
         L = len(hs_all)
-        logits = torch.stack([a["pred_logits"] for a in out["aux_outputs"]] + [out["pred_logits"]])
-        boxes = torch.stack([a["pred_boxes"] for a in out["aux_outputs"]] + [out["pred_boxes"]])
+        logits = _cat([a["pred_logits"][None] for a in out["aux_outputs"]] + [out["pred_logits"][None]])
+        boxes = _cat([a["pred_boxes"][None] for a in out["aux_outputs"]] + [out["pred_boxes"][None]])
         B, nq = int(logits.shape[1]), int(logits.shape[2])
         self.last_outputs = {"pred_logits": out["pred_logits"], "pred_boxes": out["pred_boxes"]}
         used = [l for l in range(L) if self.aux_loss or l == L - 1]
@@ -351,7 +392,7 @@ class HeadTrainer:
         if self.n_tail:
             self.last_states["tail_in"] = out["tail_in"]
         match = r = None
-        if self.loss == "ctc":                                                  # train includes "tail": the CTC loss reaches it through dlogits alone
+        if self.loss == "ctc":                                                  # the CTC loss reaches the tail through dlogits alone
             result = {}
             result["loss_CTC"], dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
             dlogits = {L - 1: dctc}
@@ -373,10 +414,9 @@ class HeadTrainer:
                 else:
                     result["loss_CTC"] = E.loss_ctc(self.last_outputs, target_labels)
             dlogits = {l: r["dlogits"][l] for l in used} if cls_on else {}
-        G = torch.cat([dlogits[l].view(-1, self.C) for l in used]) if dlogits else None
+        G = _cat([dlogits[l].view(-1, self.C) for l in used]) if dlogits else None
         if self.n_class:
-            X = torch.cat([hs_all[l].reshape(-1, self.D) for l in used])
-            ops.head_grad(G, X, out=self.grad[: self.n_class])
+            ops.head_grad(G, _cat([hs_all[l].reshape(-1, self.D) for l in used]), out=self.groups["class"].of(self.grad))
         dz = None
         if box_on and r is not None:
             dz, du = ops.box_refine_grad(r["dboxes"], boxes, torch.stack(refs[:L]))
@@ -385,7 +425,7 @@ class HeadTrainer:
             xs = [hs_all[l].reshape(-1, self.D) for l in used] + [tgt_all[l - 1].reshape(-1, self.D) for l in below]
             dys = [dz[l] for l in used] + [du[l - 1] for l in below]
             rows = ops.match_rows(match, nq, B)[used + below]
-            ops.box_mlp_grad(xs, dys, self.box_head(), rows=rows, out=self.grad[self.n_class: self.n_class + self.n_box])
+            ops.box_mlp_grad(xs, dys, self.box_head(), rows=rows, out=self.groups["box"].of(self.grad))
         if self.n_tail:
             # the gradient at h_l of every weighted output: the class head's input gradient, plus the box MLP's on the matched rows;
             # the terms at t_(l-1) (look forward twice) land on frozen states and are dropped
@@ -394,99 +434,55 @@ class HeadTrainer:
             if dz is not None:
                 ops.box_mlp_dx([hs_all[l].reshape(-1, self.D) for l in used], [dz[l] for l in used], [dh[k * M:(k + 1) * M] for k in range(len(used))],
                                self._box_weights(), rows=ops.match_rows(match, nq, B)[used])
-            ops.tail_grad(out["tail_in"], [tgt_all[l] for l in used if l < L - 1], dh, self.tail(), out=self.grad[self.n_class + self.n_box:])
-        self._clip_and_step()
-        return result
-
-    def _clip_and_step(self):
+            ops.tail_grad(out["tail_in"], [tgt_all[l] for l in used if l < L - 1], dh, self.tail(), out=self.groups["tail"].of(self.grad))
         clip = self.max_norm > 0
         if clip:
             ops.grad_norm_scale(self.grad, self.max_norm, out=self.scale)
         self.step_count += 1
         ops.adamw_step(self.param, self.exp_avg, self.exp_avg_sq, self.grad, self.step_count, self.lr, self.betas, self.eps,
                        self.weight_decay, grad_scale=self.scale if clip else None)
-
-    def _set_backward(self, logits, boxes, target_labels, target_boxes):
-        """the main output's set losses and cls_loss_coef x the focal loss's gradient with respect to the logits"""
-        tg = self._set_targets(target_labels, target_boxes, logits.device)
-        match = self.matcher.match(logits, boxes, tg)
-        r = ops.set_loss(logits, boxes, tg, match, max(float(sum(tg.sizes)), 1.0), [[self.cls_loss_coef, 0.0, 0.0]], [True], self.matcher.focal_alpha)
-        v = r["losses"][0]
-        return {"loss_ce": v[0], "loss_bbox": v[1], "loss_giou": v[2], "cardinality_error": v[5], "class_error": v[6]}, r["dlogits"][0]
-
-    def _update(self, logits, hs, boxes, target_labels, target_boxes=None):
-        self.last_outputs = {"pred_logits": logits, "pred_boxes": boxes}
-        if self.loss == "ctc":
-            loss, dlogits = E.loss_ctc_backward(self.last_outputs, target_labels)
-            result = {"loss_CTC": loss}
-        else:
-            result, dlogits = self._set_backward(logits, boxes, target_labels, target_boxes)
-            if self.loss == "ctc+set":
-                loss, dctc = E.loss_ctc_backward(self.last_outputs, target_labels)
-                dlogits.add_(dctc, alpha=self.CTC_loss_coef)
-                result["loss_CTC"] = loss
-        ops.head_grad(dlogits.view(-1, self.C), hs.reshape(-1, self.D), out=self.grad)
-        self._clip_and_step()
         return result
 
     # -- state -------------------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict:
-        """"head" / "exp_avg" / "exp_avg_sq": the class head [W | b] and its moments, as before the box head could be trained (the
-        moments are empty when the class head is not trained); "box_head" / "box_exp_avg" / "box_exp_avg_sq": the same of the box head
-        [W0 | b0 | W1 | b1 | W2 | b2], present when it is trained."""
-        nc = self.n_class
-        sd = {"head": torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
-              "exp_avg": self.exp_avg[:nc].cpu().clone(), "exp_avg_sq": self.exp_avg_sq[:nc].cpu().clone(),
-              "step": int(self.step_count), "num_classes": self.C, "hidden_dim": self.D}
-        nb = nc + self.n_box
-        if self.n_box or self.n_tail:
-            sd["train"] = list(self.train)
-        if self.n_box:
-            sd.update({"box_head": self.param[nc:nb].detach().cpu().clone(), "box_exp_avg": self.exp_avg[nc:nb].cpu().clone(),
-                       "box_exp_avg_sq": self.exp_avg_sq[nc:nb].cpu().clone()})
-        if self.n_tail:                                                     # "tail": [W1 | b1 | W2 | b2 | norm3.w | norm3.b | dec_norm.w | dec_norm.b]
-            sd.update({"tail": self.param[nb:].detach().cpu().clone(), "tail_exp_avg": self.exp_avg[nb:].cpu().clone(),
-                       "tail_exp_avg_sq": self.exp_avg_sq[nb:].cpu().clone(), "dim_feedforward": self.F})
+        """"head" / "exp_avg" / "exp_avg_sq": the class head [W | b] and its moments, as before the box head could be trained (without
+        "class" in train: the model's head and empty moments); "box_head" / "box_exp_avg" / "box_exp_avg_sq" and "tail" / "tail_exp_avg" /
+        "tail_exp_avg_sq": the same of the box head [W0 | b0 | W1 | b1 | W2 | b2] and of the tail [W1 | b1 | W2 | b2 | norm3.w | norm3.b |
+        dec_norm.w | dec_norm.b], present when they are trained."""
+        t = {key: g.of(flat).detach().cpu().clone() for g in self.groups.values() for key, flat in zip(g.keys, (self.param, self.exp_avg, self.exp_avg_sq))}
+        if not self.n_class:
+            t.update(head=torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
+                     exp_avg=torch.zeros(0), exp_avg_sq=torch.zeros(0))
+        sd = {key: t.pop(key) for key in _GROUPS["class"][0]}
+        sd.update({"step": int(self.step_count), "num_classes": self.C, "hidden_dim": self.D})
+        if t:
+            sd.update({"train": list(self.train), **t})
+        if self.n_tail:
+            sd["dim_feedforward"] = self.F
         return sd
 
     def load_state_dict(self, sd: Dict) -> None:
         if int(sd["num_classes"]) != self.C or int(sd["hidden_dim"]) != self.D:
             raise ValueError(f"HeadTrainer.load_state_dict: the state is of a Linear({sd['hidden_dim']} -> {sd['num_classes']}), "
                              f"this trainer's head is Linear({self.D} -> {self.C})")
-        nc = self.n_class
-        if nc:
-            self.param[:nc].copy_(sd["head"])
-            if sd["exp_avg"].numel() == nc:                                 # empty: written by a trainer of the box head alone
-                self.exp_avg[:nc].copy_(sd["exp_avg"])
-                self.exp_avg_sq[:nc].copy_(sd["exp_avg_sq"])
-        if self.n_box and "box_head" in sd:                                 # absent: a state written before the box head could be trained --
-            self.param[nc:nc + self.n_box].copy_(sd["box_head"])            # the box head then stays the model's, its moments zero
-            self.exp_avg[nc:nc + self.n_box].copy_(sd["box_exp_avg"])
-            self.exp_avg_sq[nc:nc + self.n_box].copy_(sd["box_exp_avg_sq"])
-        if self.n_tail and "tail" in sd:                                    # absent: an older state -- the tail stays the model's, its moments zero
-            nb = nc + self.n_box
-            if sd["tail"].numel() != self.n_tail:
-                raise ValueError(f"HeadTrainer.load_state_dict: the state's tail has {sd['tail'].numel()} elements, this trainer's {self.n_tail}")
-            self.param[nb:].copy_(sd["tail"])
-            self.exp_avg[nb:].copy_(sd["tail_exp_avg"])
-            self.exp_avg_sq[nb:].copy_(sd["tail_exp_avg_sq"])
+        for g in self.groups.values():
+            key, m, v = g.keys
+            if key not in sd:                                               # a state written before this group could be trained: it stays
+                continue                                                    # the model's, its moments zero
+            if sd[key].numel() != g.n:
+                raise ValueError(f"HeadTrainer.load_state_dict: the state's {key} has {sd[key].numel()} elements, this trainer's {g.n}")
+            g.of(self.param).copy_(sd[key])
+            if sd[m].numel():                                               # empty: written by a trainer that did not train the class head
+                g.of(self.exp_avg).copy_(sd[m])
+                g.of(self.exp_avg_sq).copy_(sd[v])
         self.step_count = int(sd["step"])
 
     @torch.no_grad()
     def write_back(self):
         """Copy the master heads into model.class_embed (the shared Linear) and, when trained, model.bbox_embed (the shared MLP: every
         aliased state-dict key carries the new values): model.state_dict() then is the adapted checkpoint."""
-        if self.n_class:
-            head = self.model.class_embed[0]
-            head.weight.copy_(self.weight)
-            head.bias.copy_(self.bias)
-        if self.n_box:
-            bh = self.box_head()
-            for i, layer in enumerate(self.model.bbox_embed[0].layers):
-                layer.weight.copy_(bh[2 * i])
-                layer.bias.copy_(bh[2 * i + 1])
-        if self.n_tail:
-            for p, v in zip(self._tail_modules_params(), self.tail()):
+        for g in self.groups.values():
+            for p, v in zip(g.params, g.views(self.param)):
                 p.copy_(v)
         self.model._engine = None                                           # the packed model is rebuilt from the new parameters
         return self.model
@@ -588,7 +584,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     ap = build_parser()
     args = ap.parse_args(argv)
     train = tuple(k.strip() for k in args.train.split(",") if k.strip())
-    if not train or set(train) - {"class", "box", "tail"}:
+    if not train or set(train) - set(TRAINABLE):
         ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail")
     if "box" in train and args.cache_features:
         ap.error("--cache-features cannot train the box head: the forward depends on it")

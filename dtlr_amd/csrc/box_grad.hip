@@ -18,16 +18,16 @@
 //   than Tmax) are holes that sit together at the end of each line and mostly fill whole tiles, which are skipped.  Skipping at tile
 //   granularity alone would not do: with 60 of 900 rows live, two thirds of all 32-row tiles of the dense order hold a live row.
 #include "dtlr_common.h"
+#include "grad_rows.h"
 #include "head_grad_tile.h"
 #include "../../include/dtlr_boxgrad.h"
 
 namespace dtlr {
 
-constexpr int BG_D = 256, BG_TR = HG_MK, BG_LD = 36;          // BG_LD: row pitch of the [k][row] LDS images (16-byte rows, 8 banks apart)
-constexpr long BG_NW = (long)BG_D * BG_D;
-constexpr long BG_OFF_W0 = 0, BG_OFF_W1 = BG_NW + BG_D, BG_OFF_W2 = 2 * (BG_NW + BG_D);
-static_assert(BG_OFF_W2 + 4 * BG_D + 4 == DTLR_BOX_GRAD_FLOATS, "flat gradient layout");
-static_assert(BG_TR == 32, "one mask bit a row");
+constexpr long BG_NW = (long)GR_D * GR_D;
+constexpr long BG_OFF_W0 = 0, BG_OFF_W1 = BG_NW + GR_D, BG_OFF_W2 = 2 * (BG_NW + GR_D);
+static_assert(BG_OFF_W2 + 4 * GR_D + 4 == DTLR_BOX_GRAD_FLOATS, "flat gradient layout");
+static_assert(GR_TR == 32 && GR_TR == HG_MK, "one mask bit a row, one stage of the d^T x products a tile");
 
 __global__ __launch_bounds__(256) void box_refine_grad_kernel(const float* __restrict__ g, const float* __restrict__ p, const float* __restrict__ r,
                                                               float* __restrict__ dz, float* __restrict__ du, long n, long total, float eps)
@@ -55,23 +55,23 @@ struct BgWs { float *W0T, *W1T, *Xc, *H0c, *H1c, *DA0c, *DA1c, *DYc, *part0, *pa
 static inline BgWs bg_ws(float* ws, long Rp, int splits)
 {
     BgWs w;
-    const long ntiles = Rp / BG_TR, nlive = (ntiles + 3) / 4 * 4;
+    const long ntiles = Rp / GR_TR, nlive = (ntiles + 3) / 4 * 4;
     float* p = ws;
     w.W0T = p; p += BG_NW;
     w.W1T = p; p += BG_NW;
     w.live = reinterpret_cast<int*>(p); p += nlive;
-    w.Xc = p; p += Rp * BG_D;
-    w.H0c = p; p += Rp * BG_D;
-    w.H1c = p; p += Rp * BG_D;
-    w.DA0c = p; p += Rp * BG_D;
-    w.DA1c = p; p += Rp * BG_D;
+    w.Xc = p; p += Rp * GR_D;
+    w.H0c = p; p += Rp * GR_D;
+    w.H1c = p; p += Rp * GR_D;
+    w.DA0c = p; p += Rp * GR_D;
+    w.DA1c = p; p += Rp * GR_D;
     w.DYc = p; p += Rp * 4;
     w.part0 = p; p += (long)splits * BG_NW;
     w.part1 = p; p += (long)splits * BG_NW;
-    w.part2 = p; p += (long)splits * 4 * BG_D;                // every count above is a multiple of 4 floats: p stays 16-byte aligned
+    w.part2 = p; p += (long)splits * 4 * GR_D;                // every count above is a multiple of 4 floats: p stays 16-byte aligned
     double* q = reinterpret_cast<double*>(p);
-    w.pb0 = q; q += (long)splits * BG_D;
-    w.pb1 = q; q += (long)splits * BG_D;
+    w.pb0 = q; q += (long)splits * GR_D;
+    w.pb1 = q; q += (long)splits * GR_D;
     w.pb2 = q; q += (long)splits * 4;
     w.bytes = (long)(reinterpret_cast<char*>(q) - reinterpret_cast<char*>(ws));
     return w;
@@ -82,38 +82,19 @@ __global__ __launch_bounds__(256) void box_mlp_transpose_kernel(const float* __r
 {
     const int i = blockIdx.x * 256 + threadIdx.x;               // grid: 2 * 256 blocks ; element (k, n) of a transpose
     const int which = i >> 16, e = i & 0xffff, k = e >> 8, n = e & 255;
-    (which ? W1T : W0T)[e] = (which ? W1 : W0)[n * BG_D + k];
+    (which ? W1T : W0T)[e] = (which ? W1 : W0)[n * GR_D + k];
 }
 
-// acc[r] = sum_k Wt[k][n] buf[k][r]: the weight column read coalesced over n, the activations broadcast from LDS; 32 terms in one fp32
-// accumulator, the eight blocks added in order
-__device__ __forceinline__ void bg_matvec(const float* __restrict__ Wt, const float* buf, float (&acc)[BG_TR], int n)
+// acc[r] = sum_k Wt[k][n] buf[k][r] over the 256 rows of a transposed weight: the stages of 32 terms added in order in fp32, 32-bit
+// indices (grad_rows.h)
+__device__ __forceinline__ void bg_matvec(const float* __restrict__ Wt, const float* buf, float (&acc)[GR_TR], int n)
 {
 #pragma unroll
-    for (int r = 0; r < BG_TR; ++r) acc[r] = 0.f;
-    for (int kc = 0; kc < BG_D; kc += 32) {
-        float c[BG_TR];
-#pragma unroll
-        for (int r = 0; r < BG_TR; ++r) c[r] = 0.f;
-#pragma unroll 4
-        for (int k = kc; k < kc + 32; ++k) {
-            const float w = Wt[k * BG_D + n];
-            const float4* row = reinterpret_cast<const float4*>(buf + k * BG_LD);
-#pragma unroll
-            for (int q = 0; q < BG_TR / 4; ++q) {
-                const float4 v = row[q];
-                c[4 * q] = fmaf(w, v.x, c[4 * q]);
-                c[4 * q + 1] = fmaf(w, v.y, c[4 * q + 1]);
-                c[4 * q + 2] = fmaf(w, v.z, c[4 * q + 2]);
-                c[4 * q + 3] = fmaf(w, v.w, c[4 * q + 3]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < BG_TR; ++r) acc[r] += c[r];
-    }
+    for (int r = 0; r < GR_TR; ++r) acc[r] = 0.f;
+    gr_mac<float, false, int>(Wt, GR_D, n, true, buf, GR_D, GR_D, acc);
 }
 
-// grid: one workgroup a tile of 32 list entries of one application ; dynamic LDS 2 x [256][BG_LD] floats
+// grid: one workgroup a tile of 32 list entries of one application ; dynamic LDS 2 x [256][GR_LD] floats
 __global__ __launch_bounds__(256) void box_mlp_rows_kernel(BgApps apps, const int* __restrict__ rows, long M, long R, long Rpad, int x_h16,
                                                            const float* __restrict__ W0T, const float* __restrict__ b0,
                                                            const float* __restrict__ W1T, const float* __restrict__ b1,
@@ -124,14 +105,14 @@ __global__ __launch_bounds__(256) void box_mlp_rows_kernel(BgApps apps, const in
 {
     extern __shared__ __attribute__((aligned(16))) float bg_lds[];
     float* bufA = bg_lds;
-    float* bufB = bg_lds + BG_D * BG_LD;
-    __shared__ __attribute__((aligned(16))) float dys[BG_TR][4];
-    __shared__ long ridx[BG_TR];
-    const long tile = blockIdx.x, tiles_app = Rpad / BG_TR;
+    float* bufB = bg_lds + GR_D * GR_LD;
+    __shared__ __attribute__((aligned(16))) float dys[GR_TR][4];
+    __shared__ long ridx[GR_TR];
+    const long tile = blockIdx.x, tiles_app = Rpad / GR_TR;
     const int a = (int)(tile / tiles_app), n = threadIdx.x;
-    const long k0 = (tile - (long)a * tiles_app) * BG_TR;
+    const long k0 = (tile - (long)a * tiles_app) * GR_TR;
     int nz = 0;
-    if (n < BG_TR) {
+    if (n < GR_TR) {
         const long k = k0 + n;
         long idx = -1;
         if (k < R) idx = rows ? (long)rows[(long)a * R + k] : k;
@@ -147,55 +128,55 @@ __global__ __launch_bounds__(256) void box_mlp_rows_kernel(BgApps apps, const in
         return;
     }
     if (n == 0) live[tile] = 1;
-    const long base = tile * BG_TR;                             // the tile's rows in the compacted buffers
-    if (n < BG_TR * 4) DYc[base * 4 + n] = dys[n >> 2][n & 3];
-    {
+    const long base = tile * GR_TR;                             // the tile's rows in the compacted buffers
+    if (n < GR_TR * 4) DYc[base * 4 + n] = dys[n >> 2][n & 3];
+    {                                                           // not gr_load: through it the compiler schedules this loop differently
         const float* xf = static_cast<const float*>(apps.x[a]);
         const uint16_t* xh = static_cast<const uint16_t*>(apps.x[a]);
 #pragma unroll 4
-        for (int r = 0; r < BG_TR; ++r) {
+        for (int r = 0; r < GR_TR; ++r) {
             const long idx = ridx[r];
             float v = 0.f;
-            if (idx >= 0) v = x_h16 ? bf16_to_f32(xh[idx * BG_D + n]) : xf[idx * BG_D + n];
-            bufA[n * BG_LD + r] = v;
-            Xc[(base + r) * BG_D + n] = v;
+            if (idx >= 0) v = x_h16 ? bf16_to_f32(xh[idx * GR_D + n]) : xf[idx * GR_D + n];
+            bufA[n * GR_LD + r] = v;
+            Xc[(base + r) * GR_D + n] = v;
         }
     }
     __syncthreads();
-    float acc[BG_TR];
+    float acc[GR_TR];
     unsigned m0 = 0;
     bg_matvec(W0T, bufA, acc, n);
     {
         const float bn = b0[n];
 #pragma unroll
-        for (int r = 0; r < BG_TR; ++r) {
+        for (int r = 0; r < GR_TR; ++r) {
             float v = acc[r] + bn;
             if (v > 0.f) m0 |= 1u << r; else v = 0.f;
-            bufB[n * BG_LD + r] = v;
-            H0c[(base + r) * BG_D + n] = v;
+            bufB[n * GR_LD + r] = v;
+            H0c[(base + r) * GR_D + n] = v;
         }
     }
     __syncthreads();
     bg_matvec(W1T, bufB, acc, n);
     {
         const float bn = b1[n];
-        const float w20 = W2[n], w21 = W2[BG_D + n], w22 = W2[2 * BG_D + n], w23 = W2[3 * BG_D + n];
+        const float w20 = W2[n], w21 = W2[GR_D + n], w22 = W2[2 * GR_D + n], w23 = W2[3 * GR_D + n];
 #pragma unroll
-        for (int r = 0; r < BG_TR; ++r) {
+        for (int r = 0; r < GR_TR; ++r) {
             const float v = acc[r] + bn;
             const bool pos = v > 0.f;
-            H1c[(base + r) * BG_D + n] = pos ? v : 0.f;
+            H1c[(base + r) * GR_D + n] = pos ? v : 0.f;
             const float4 d = *reinterpret_cast<const float4*>(dys[r]);
             const float dh = fmaf(d.w, w23, fmaf(d.z, w22, fmaf(d.y, w21, d.x * w20)));
             const float da = pos ? dh : 0.f;
-            DA1c[(base + r) * BG_D + n] = da;
-            bufA[n * BG_LD + r] = da;                           // bufA's x was last read before the barrier above
+            DA1c[(base + r) * GR_D + n] = da;
+            bufA[n * GR_LD + r] = da;                           // bufA's x was last read before the barrier above
         }
     }
     __syncthreads();
     bg_matvec(W1, bufA, acc, n);                                // dh0[r][n] = sum_m W1[m][n] da1[r][m]
 #pragma unroll
-    for (int r = 0; r < BG_TR; ++r) DA0c[(base + r) * BG_D + n] = ((m0 >> r) & 1u) ? acc[r] : 0.f;
+    for (int r = 0; r < GR_TR; ++r) DA0c[(base + r) * GR_D + n] = ((m0 >> r) & 1u) ? acc[r] : 0.f;
 }
 
 struct BgProb { const float* G; const float* X; float* part; double* partb; int C; };
@@ -206,9 +187,9 @@ __global__ __launch_bounds__(256) void box_mlp_partial_kernel(BgProb p0, BgProb 
     __shared__ __attribute__((aligned(16))) float Gs[HG_MK][HG_TC];
     __shared__ __attribute__((aligned(16))) float Xs[HG_MK][HG_TD];
     const BgProb p = blockIdx.z == 0 ? p0 : blockIdx.z == 1 ? p1 : p2;
-    const int tiles_d = BG_D / HG_TD;
+    const int tiles_d = GR_D / HG_TD;
     if ((int)blockIdx.x >= ((p.C + HG_TC - 1) / HG_TC) * tiles_d) return;
-    hg_partial_tile(Gs, Xs, p.G, p.X, p.part, p.partb, live, Rp, p.C, BG_D, tiles_d, chunk, (int)blockIdx.x, (int)blockIdx.y);
+    hg_partial_tile(Gs, Xs, p.G, p.X, p.part, p.partb, live, Rp, p.C, GR_D, tiles_d, chunk, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 __global__ __launch_bounds__(256) void box_mlp_reduce_kernel(BgProb p0, BgProb p1, BgProb p2, float* __restrict__ grad, int splits)
@@ -217,7 +198,7 @@ __global__ __launch_bounds__(256) void box_mlp_reduce_kernel(BgProb p0, BgProb p
     if (i >= DTLR_BOX_GRAD_FLOATS) return;
     const int z = i < BG_OFF_W1 ? 0 : i < BG_OFF_W2 ? 1 : 2;
     const BgProb p = z == 0 ? p0 : z == 1 ? p1 : p2;
-    const long off = z == 0 ? BG_OFF_W0 : z == 1 ? BG_OFF_W1 : BG_OFF_W2, nW = (long)p.C * BG_D;
+    const long off = z == 0 ? BG_OFF_W0 : z == 1 ? BG_OFF_W1 : BG_OFF_W2, nW = (long)p.C * GR_D;
     hg_reduce(p.part, p.partb, grad + off, grad + off + nW, nW, p.C, splits, i - off);
 }
 
@@ -227,10 +208,10 @@ static inline BgPlan bg_plan(int A, long M, int R)
     BgPlan q{};
     if (A < 1 || A > DTLR_BOX_GRAD_MAX_APPS || M <= 0) return q;
     q.R = R > 0 ? (long)R : M;
-    q.Rpad = (q.R + BG_TR - 1) / BG_TR * BG_TR;
+    q.Rpad = (q.R + GR_TR - 1) / GR_TR * GR_TR;
     q.Rp = (long)A * q.Rpad;
     if (q.Rp > 0x7fffffffl || M > 0x7fffffffl) return q;
-    const HgPlan h = hg_plan(q.Rp, BG_D, BG_D);
+    const HgPlan h = hg_plan(q.Rp, GR_D, GR_D);
     q.splits = h.splits;
     q.chunk = h.chunk;
     q.ok = true;
@@ -284,11 +265,11 @@ extern "C" int dtlr_box_mlp_grad(const void* x_ptrs, const void* dy_ptrs, const 
     const BgWs w = bg_ws(static_cast<float*>(workspace), q.Rp, q.splits);
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = launch<box_mlp_transpose_kernel>(dim3(512), dim3(256), 0, st, W0, W1, w.W0T, w.W1T)) return rc;
-    const size_t lds = (size_t)2 * BG_D * BG_LD * sizeof(float);
-    if (int rc = launch<box_mlp_rows_kernel>(dim3((unsigned)(q.Rp / BG_TR)), dim3(256), lds, st, apps, rows, M, q.R, q.Rpad,
+    const size_t lds = (size_t)2 * GR_D * GR_LD * sizeof(float);
+    if (int rc = launch<box_mlp_rows_kernel>(dim3((unsigned)(q.Rp / GR_TR)), dim3(256), lds, st, apps, rows, M, q.R, q.Rpad,
                                              (int)(x_dtype != DTLR_F32), (const float*)w.W0T, b0, (const float*)w.W1T, b1, W1, W2, w.live,
                                              w.Xc, w.H0c, w.H1c, w.DA0c, w.DA1c, w.DYc)) return rc;
-    const BgProb p0{w.DA0c, w.Xc, w.part0, w.pb0, BG_D}, p1{w.DA1c, w.H0c, w.part1, w.pb1, BG_D}, p2{w.DYc, w.H1c, w.part2, w.pb2, 4};
+    const BgProb p0{w.DA0c, w.Xc, w.part0, w.pb0, GR_D}, p1{w.DA1c, w.H0c, w.part1, w.pb1, GR_D}, p2{w.DYc, w.H1c, w.part2, w.pb2, 4};
     if (int rc = launch<box_mlp_partial_kernel>(dim3(16, (unsigned)q.splits, 3), dim3(256), 0, st, p0, p1, p2, (const int*)w.live, q.Rp, q.chunk)) return rc;
     return launch<box_mlp_reduce_kernel>(dim3((DTLR_BOX_GRAD_FLOATS + 255) / 256), dim3(256), 0, st, p0, p1, p2, grad, q.splits);
 }

@@ -16,45 +16,13 @@
 // The LayerNorm backward is one wavefront a row; its column sums are taken 32 rows at a time in fp32 by each wavefront, then in fp64,
 // and the workgroups' partials are added in workgroup order by a second kernel.  No float atomics anywhere.
 #include "dtlr_common.h"
+#include "grad_rows.h"
 #include "head_grad_tile.h"
 #include "../../include/dtlr_tailgrad.h"
 
 namespace dtlr {
 
-constexpr int TG_D = DTLR_TAIL_HIDDEN, TG_TR = 32, TG_LD = 36;   // TG_LD: row pitch of the [k][row] LDS images (16-byte rows, 8 banks apart)
-static_assert(TG_D == 256 && TG_TR == HG_MK, "one thread a column, one stage 32 rows");
-
-// acc[r] += sum_(k < klen) Wt[k][n] buf[k][r]: 32 terms in fp32, the stages in fp64.  Rows k >= kvalid of Wt are not read (buf holds
-// zeros there) ; a thread without a column (nvalid false) reads no weight at all.  klen % 32 == 0.
-__device__ __forceinline__ void tg_mac(const float* __restrict__ Wt, long ldw, int n, bool nvalid, const float* buf, int klen, int kvalid,
-                                       double (&acc)[TG_TR])
-{
-    for (int kc = 0; kc < klen; kc += 32) {
-        float c[TG_TR];
-#pragma unroll
-        for (int r = 0; r < TG_TR; ++r) c[r] = 0.f;
-#pragma unroll 4
-        for (int k = kc; k < kc + 32; ++k) {
-            const float w = (nvalid && k < kvalid) ? Wt[(long)k * ldw + n] : 0.f;
-            const float4* row = reinterpret_cast<const float4*>(buf + k * TG_LD);
-#pragma unroll
-            for (int q = 0; q < TG_TR / 4; ++q) {
-                const float4 v = row[q];
-                c[4 * q] = fmaf(w, v.x, c[4 * q]);
-                c[4 * q + 1] = fmaf(w, v.y, c[4 * q + 1]);
-                c[4 * q + 2] = fmaf(w, v.z, c[4 * q + 2]);
-                c[4 * q + 3] = fmaf(w, v.w, c[4 * q + 3]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < TG_TR; ++r) acc[r] += (double)c[r];
-    }
-}
-
-__device__ __forceinline__ float tg_load(const void* p, int h16, long i)
-{
-    return h16 ? bf16_to_f32(static_cast<const uint16_t*>(p)[i]) : static_cast<const float*>(p)[i];
-}
+static_assert(GR_D == DTLR_TAIL_HIDDEN && GR_TR == HG_MK, "one thread a column, one stage 32 rows");
 
 // out[m][n] = epi(sum_k A[m][k] Wt[k][n] + bias[n] + res[m][n]) ; epi: ReLU (relu), zero where mask[m][n] <= 0 (mask, pitch ldo), added
 // to what out holds (accumulate).  A [M, K] pitch K (a_h16: 16-bit), res [M, N] pitch N (res_h16).  grid (ceil(M / 32), ceil(N / 256)).
@@ -63,33 +31,33 @@ __global__ __launch_bounds__(256) void tg_rows_gemm_kernel(const void* __restric
                                                            int res_h16, const float* __restrict__ mask, float* out, long ldo, int relu,
                                                            int accumulate)
 {
-    __shared__ __attribute__((aligned(16))) float As[32 * TG_LD];
-    const long m0 = (long)blockIdx.x * TG_TR;
+    __shared__ __attribute__((aligned(16))) float As[32 * GR_LD];
+    const long m0 = (long)blockIdx.x * GR_TR;
     const int n = (int)blockIdx.y * 256 + threadIdx.x;
     const bool nvalid = n < N;
     const int sr = threadIdx.x >> 3, sk = (threadIdx.x & 7) * 4;                 // staging: row sr, columns sk .. sk + 3 of the chunk
     const long sm = m0 + sr;
-    double acc[TG_TR];
+    double acc[GR_TR];
 #pragma unroll
-    for (int r = 0; r < TG_TR; ++r) acc[r] = 0.0;
+    for (int r = 0; r < GR_TR; ++r) acc[r] = 0.0;
     for (int kc = 0; kc < K; kc += 32) {
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int k = kc + sk + j;
-            As[(sk + j) * TG_LD + sr] = (sm < M && k < K) ? tg_load(A, a_h16, sm * K + k) : 0.f;
+            As[(sk + j) * GR_LD + sr] = (sm < M && k < K) ? gr_load(A, a_h16, sm * K + k) : 0.f;
         }
         __syncthreads();
-        tg_mac(Wt + (long)kc * ldw, ldw, n, nvalid, As, 32, K - kc, acc);
+        gr_mac<double, true, long>(Wt + (long)kc * ldw, ldw, n, nvalid, As, 32, K - kc, acc);
     }
     if (!nvalid) return;
     const double bn = bias ? (double)bias[n] : 0.0;
 #pragma unroll
-    for (int r = 0; r < TG_TR; ++r) {                               // fully unrolled: acc stays in registers
+    for (int r = 0; r < GR_TR; ++r) {                               // fully unrolled: acc stays in registers
         const long m = m0 + r;
         if (m >= M) continue;
         double v = acc[r] + bn;
-        if (res) v += (double)tg_load(res, res_h16, m * N + n);
+        if (res) v += (double)gr_load(res, res_h16, m * N + n);
         float f = (float)v;
         if (relu && !(f > 0.f)) f = 0.f;
         if (mask && !(mask[m * ldo + n] > 0.f)) f = 0.f;
@@ -119,7 +87,7 @@ __global__ __launch_bounds__(256) void tg_cast_kernel(const uint16_t* __restrict
 // ------------------------------------------------------------------------------------------------------------ the box MLP's dx
 struct TgApps { const void* x[DTLR_TAIL_MAX_APPS]; const float* dz[DTLR_TAIL_MAX_APPS]; float* dh[DTLR_TAIL_MAX_APPS]; };
 
-// grid: one workgroup a tile of 32 list entries of one application ; dynamic LDS 2 x [256][TG_LD] floats
+// grid: one workgroup a tile of 32 list entries of one application ; dynamic LDS 2 x [256][GR_LD] floats
 __global__ __launch_bounds__(256) void tg_box_dx_kernel(TgApps apps, const int* __restrict__ rows, long M, long R, long Rpad, int x_h16,
                                                         const float* __restrict__ W0T, const float* __restrict__ b0,
                                                         const float* __restrict__ W1T, const float* __restrict__ b1,
@@ -127,14 +95,14 @@ __global__ __launch_bounds__(256) void tg_box_dx_kernel(TgApps apps, const int* 
 {
     extern __shared__ __attribute__((aligned(16))) float tg_lds[];
     float* bufA = tg_lds;
-    float* bufB = tg_lds + TG_D * TG_LD;
-    __shared__ __attribute__((aligned(16))) float dzs[TG_TR][4];
-    __shared__ long ridx[TG_TR];
-    const long tile = blockIdx.x, tiles_app = Rpad / TG_TR;
+    float* bufB = tg_lds + GR_D * GR_LD;
+    __shared__ __attribute__((aligned(16))) float dzs[GR_TR][4];
+    __shared__ long ridx[GR_TR];
+    const long tile = blockIdx.x, tiles_app = Rpad / GR_TR;
     const int a = (int)(tile / tiles_app), n = threadIdx.x;
-    const long k0 = (tile - (long)a * tiles_app) * TG_TR;
+    const long k0 = (tile - (long)a * tiles_app) * GR_TR;
     int nz = 0;
-    if (n < TG_TR) {
+    if (n < GR_TR) {
         const long k = k0 + n;
         long idx = -1;
         if (k < R) idx = rows ? (long)rows[(long)a * R + k] : k;
@@ -147,54 +115,54 @@ __global__ __launch_bounds__(256) void tg_box_dx_kernel(TgApps apps, const int* 
     }
     if (!__syncthreads_or(nz)) return;                              // workgroup-uniform
 #pragma unroll 4
-    for (int r = 0; r < TG_TR; ++r) {
+    for (int r = 0; r < GR_TR; ++r) {
         const long idx = ridx[r];
-        bufA[n * TG_LD + r] = idx >= 0 ? tg_load(apps.x[a], x_h16, idx * TG_D + n) : 0.f;
+        bufA[n * GR_LD + r] = idx >= 0 ? gr_load(apps.x[a], x_h16, idx * GR_D + n) : 0.f;
     }
     __syncthreads();
-    double acc[TG_TR];
+    double acc[GR_TR];
     unsigned m0 = 0;
 #pragma unroll
-    for (int r = 0; r < TG_TR; ++r) acc[r] = 0.0;
-    tg_mac(W0T, TG_D, n, true, bufA, TG_D, TG_D, acc);
+    for (int r = 0; r < GR_TR; ++r) acc[r] = 0.0;
+    gr_mac<double, true, long>(W0T, GR_D, n, true, bufA, GR_D, GR_D, acc);
     {
         const double bn = (double)b0[n];
 #pragma unroll
-        for (int r = 0; r < TG_TR; ++r) {
+        for (int r = 0; r < GR_TR; ++r) {
             float v = (float)(acc[r] + bn);
             if (v > 0.f) m0 |= 1u << r; else v = 0.f;
-            bufB[n * TG_LD + r] = v;
+            bufB[n * GR_LD + r] = v;
             acc[r] = 0.0;
         }
     }
     __syncthreads();
-    tg_mac(W1T, TG_D, n, true, bufB, TG_D, TG_D, acc);
+    gr_mac<double, true, long>(W1T, GR_D, n, true, bufB, GR_D, GR_D, acc);
     {
         const double bn = (double)b1[n];
-        const float w20 = W2[n], w21 = W2[TG_D + n], w22 = W2[2 * TG_D + n], w23 = W2[3 * TG_D + n];
+        const float w20 = W2[n], w21 = W2[GR_D + n], w22 = W2[2 * GR_D + n], w23 = W2[3 * GR_D + n];
 #pragma unroll
-        for (int r = 0; r < TG_TR; ++r) {
+        for (int r = 0; r < GR_TR; ++r) {
             const bool pos = (float)(acc[r] + bn) > 0.f;
             const float4 d = *reinterpret_cast<const float4*>(dzs[r]);
             const float dh1 = fmaf(d.w, w23, fmaf(d.z, w22, fmaf(d.y, w21, d.x * w20)));
-            bufA[n * TG_LD + r] = pos ? dh1 : 0.f;                  // bufA's x was last read before the barrier above
+            bufA[n * GR_LD + r] = pos ? dh1 : 0.f;                  // bufA's x was last read before the barrier above
             acc[r] = 0.0;
         }
     }
     __syncthreads();
-    tg_mac(W1, TG_D, n, true, bufA, TG_D, TG_D, acc);               // dh0[r][n] = sum_m W1[m][n] da1[r][m]
+    gr_mac<double, true, long>(W1, GR_D, n, true, bufA, GR_D, GR_D, acc);               // dh0[r][n] = sum_m W1[m][n] da1[r][m]
 #pragma unroll
-    for (int r = 0; r < TG_TR; ++r) {
-        bufB[n * TG_LD + r] = ((m0 >> r) & 1u) ? (float)acc[r] : 0.f;     // bufB's h0 was last read before the barrier above
+    for (int r = 0; r < GR_TR; ++r) {
+        bufB[n * GR_LD + r] = ((m0 >> r) & 1u) ? (float)acc[r] : 0.f;     // bufB's h0 was last read before the barrier above
         acc[r] = 0.0;
     }
     __syncthreads();
-    tg_mac(W0, TG_D, n, true, bufB, TG_D, TG_D, acc);               // dx[r][n] = sum_m W0[m][n] da0[r][m]
+    gr_mac<double, true, long>(W0, GR_D, n, true, bufB, GR_D, GR_D, acc);               // dx[r][n] = sum_m W0[m][n] da0[r][m]
     float* dh = apps.dh[a];
 #pragma unroll
-    for (int r = 0; r < TG_TR; ++r) {
+    for (int r = 0; r < GR_TR; ++r) {
         const long idx = ridx[r];
-        if (idx >= 0) dh[idx * TG_D + n] += (float)acc[r];
+        if (idx >= 0) dh[idx * GR_D + n] += (float)acc[r];
     }
 }
 
@@ -205,10 +173,10 @@ template <int H16>
 __device__ __forceinline__ void ln_load4(const void* x, long row, int lane, float (&v)[4])
 {
     if (H16) {
-        const uint2 t = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(x) + row * TG_D + 4 * lane);
+        const uint2 t = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(x) + row * GR_D + 4 * lane);
         v[0] = h16_lo(t.x); v[1] = h16_hi(t.x); v[2] = h16_lo(t.y); v[3] = h16_hi(t.y);
     } else {
-        const float4 t = *reinterpret_cast<const float4*>(static_cast<const float*>(x) + row * TG_D + 4 * lane);
+        const float4 t = *reinterpret_cast<const float4*>(static_cast<const float*>(x) + row * GR_D + 4 * lane);
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     }
 }
@@ -220,7 +188,7 @@ __global__ __launch_bounds__(256) void tg_ln_bwd_kernel(const void* __restrict__
                                                         float* __restrict__ dx, long dx_row0, long M, float eps, long rows_wg,
                                                         double* __restrict__ part)
 {
-    __shared__ double red[4][2 * TG_D];
+    __shared__ double red[4][2 * GR_D];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float gav[4] = {gamma[4 * lane], gamma[4 * lane + 1], gamma[4 * lane + 2], gamma[4 * lane + 3]};      // gamma may be a view of a flat buffer: no alignment
     double dsg[4] = {0.0, 0.0, 0.0, 0.0}, dsb[4] = {0.0, 0.0, 0.0, 0.0};
@@ -234,21 +202,21 @@ __global__ __launch_bounds__(256) void tg_ln_bwd_kernel(const void* __restrict__
             if (row >= M) break;
             float v[4];
             ln_load4<H16>(x, row, lane, v);
-            const float4 gt = *reinterpret_cast<const float4*>(g + row * TG_D + 4 * lane);
+            const float4 gt = *reinterpret_cast<const float4*>(g + row * GR_D + 4 * lane);
             const float gv[4] = {gt.x, gt.y, gt.z, gt.w};
-            const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / TG_D);
+            const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / GR_D);
             float q = 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[j] -= mean; q += v[j] * v[j]; }
-            const float rstd = rsqrtf(wave_sum(q) * (1.0f / TG_D) + eps);
+            const float rstd = rsqrtf(wave_sum(q) * (1.0f / GR_D) + eps);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[j] *= rstd; sg[j] = fmaf(gv[j], v[j], sg[j]); sb[j] += gv[j]; }
             if (dx && row >= dx_row0) {
                 float qv[4], s1 = 0.f, s2 = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { qv[j] = gav[j] * gv[j]; s1 += qv[j]; s2 = fmaf(qv[j], v[j], s2); }
-                const float m1 = wave_sum(s1) * (1.0f / TG_D), m2 = wave_sum(s2) * (1.0f / TG_D);
-                *reinterpret_cast<float4*>(dx + (row - dx_row0) * TG_D + 4 * lane) =
+                const float m1 = wave_sum(s1) * (1.0f / GR_D), m2 = wave_sum(s2) * (1.0f / GR_D);
+                *reinterpret_cast<float4*>(dx + (row - dx_row0) * GR_D + 4 * lane) =
                     make_float4(rstd * (qv[0] - m1 - v[0] * m2), rstd * (qv[1] - m1 - v[1] * m2), rstd * (qv[2] - m1 - v[2] * m2),
                                 rstd * (qv[3] - m1 - v[3] * m2));
             }
@@ -257,18 +225,18 @@ __global__ __launch_bounds__(256) void tg_ln_bwd_kernel(const void* __restrict__
         for (int j = 0; j < 4; ++j) { dsg[j] += (double)sg[j]; dsb[j] += (double)sb[j]; }
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { red[wave][4 * lane + j] = dsg[j]; red[wave][TG_D + 4 * lane + j] = dsb[j]; }
+    for (int j = 0; j < 4; ++j) { red[wave][4 * lane + j] = dsg[j]; red[wave][GR_D + 4 * lane + j] = dsb[j]; }
     __syncthreads();
-    for (int c = threadIdx.x; c < 2 * TG_D; c += 256)
-        part[(long)blockIdx.x * 2 * TG_D + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+    for (int c = threadIdx.x; c < 2 * GR_D; c += 256)
+        part[(long)blockIdx.x * 2 * GR_D + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
 }
 
 __global__ __launch_bounds__(256) void tg_ln_reduce_kernel(const double* __restrict__ part, int nwg, float* __restrict__ dgamma, float* __restrict__ dbeta)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;                   // grid 2: c < 512
     double a = 0.0;
-    for (int b = 0; b < nwg; ++b) a += part[(long)b * 2 * TG_D + c];
-    if (c < TG_D) dgamma[c] = (float)a; else dbeta[c - TG_D] = (float)a;
+    for (int b = 0; b < nwg; ++b) a += part[(long)b * 2 * GR_D + c];
+    if (c < GR_D) dgamma[c] = (float)a; else dbeta[c - GR_D] = (float)a;
 }
 
 struct LnPlan { long rows_wg; int nwg; };
@@ -307,7 +275,7 @@ __global__ __launch_bounds__(256) void tg_ffn_reduce_kernel(TgProb p0, TgProb p1
 static inline bool tg_ffn_ok(long M, int F) { return M > 0 && M <= 0x7fffffffl && F >= 64 && F <= DTLR_TAIL_MAX_FFN && F % 64 == 0; }
 static inline bool tg_dtype_ok(int dt) { return dt == DTLR_F32 || dt == DTLR_H16; }
 static inline bool tg_mis(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-static inline unsigned tg_tiles(long M) { return (unsigned)((M + TG_TR - 1) / TG_TR); }
+static inline unsigned tg_tiles(long M) { return (unsigned)((M + GR_TR - 1) / GR_TR); }
 
 // the workspace of dtlr_ffn_grad
 struct FgWs { float *da, *u32, *part0, *part1; double *pb0, *pb1; long bytes; };
@@ -316,12 +284,12 @@ static inline FgWs fg_ws(float* ws, long M, int F, bool cast, int splits)
     FgWs w;
     float* p = ws;
     w.da = p; p += M * F;
-    w.u32 = p; p += cast ? (M * TG_D + 3) / 4 * 4 : 0;
-    w.part0 = p; p += (long)splits * F * TG_D;
-    w.part1 = p; p += (long)splits * F * TG_D;                    // every count above is a multiple of 4 floats: p stays 16-byte aligned
+    w.u32 = p; p += cast ? (M * GR_D + 3) / 4 * 4 : 0;
+    w.part0 = p; p += (long)splits * F * GR_D;
+    w.part1 = p; p += (long)splits * F * GR_D;                    // every count above is a multiple of 4 floats: p stays 16-byte aligned
     double* q = reinterpret_cast<double*>(p);
     w.pb0 = q; q += (long)splits * F;
-    w.pb1 = q; q += (long)splits * TG_D;
+    w.pb1 = q; q += (long)splits * GR_D;
     w.bytes = (long)(reinterpret_cast<char*>(q) - reinterpret_cast<char*>(ws));
     return w;
 }
@@ -335,21 +303,21 @@ extern "C" int dtlr_head_dx(const float* G, const float* W, float* dh, long M, i
     clear_stale_error();
     if (!G || !W || !dh || M <= 0 || C <= 0) return DTLR_EINVAL;
     if (C > DTLR_TAIL_MAX_CLASSES || M > 0x7fffffffl) return DTLR_ESHAPE;
-    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, (hipStream_t)stream, (const void*)G, 0, M, C, W, (long)TG_D, TG_D,
-                                       (const float*)nullptr, (const void*)nullptr, 0, (const float*)nullptr, dh, (long)TG_D, 0, accumulate != 0);
+    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, (hipStream_t)stream, (const void*)G, 0, M, C, W, (long)GR_D, GR_D,
+                                       (const float*)nullptr, (const void*)nullptr, 0, (const float*)nullptr, dh, (long)GR_D, 0, accumulate != 0);
 }
 
 static inline long tg_box_rpad(int A, long M, int R)
 {
     if (A < 1 || A > DTLR_TAIL_MAX_APPS || M <= 0 || M > 0x7fffffffl) return 0;
     const long r = R > 0 ? (long)R : M;
-    const long rpad = (r + TG_TR - 1) / TG_TR * TG_TR;
+    const long rpad = (r + GR_TR - 1) / GR_TR * GR_TR;
     return (long)A * rpad > 0x7fffffffl ? 0 : rpad;
 }
 
 extern "C" long dtlr_box_mlp_dx_workspace_bytes(int A, long M, int R)
 {
-    return tg_box_rpad(A, M, R) ? 2l * TG_D * TG_D * (long)sizeof(float) : 0;
+    return tg_box_rpad(A, M, R) ? 2l * GR_D * GR_D * (long)sizeof(float) : 0;
 }
 
 extern "C" int dtlr_box_mlp_dx(const void* x_ptrs, const void* dz_ptrs, const void* dh_ptrs, const int* rows, int A, long M, int R, int x_dtype,
@@ -371,19 +339,19 @@ extern "C" int dtlr_box_mlp_dx(const void* x_ptrs, const void* dz_ptrs, const vo
         if (tg_mis(apps.x[a], x_dtype == DTLR_F32 ? 3 : 1)) return DTLR_EINVAL;
     }
     float* W0T = static_cast<float*>(workspace);
-    float* W1T = W0T + TG_D * TG_D;
+    float* W1T = W0T + GR_D * GR_D;
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W0, W0T, TG_D, TG_D)) return rc;
-    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W1, W1T, TG_D, TG_D)) return rc;
-    const size_t lds = (size_t)2 * TG_D * TG_LD * sizeof(float);
-    return launch<tg_box_dx_kernel>(dim3((unsigned)((long)A * rpad / TG_TR)), dim3(256), lds, st, apps, rows, M, rows ? (long)R : M, rpad,
+    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W0, W0T, GR_D, GR_D)) return rc;
+    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W1, W1T, GR_D, GR_D)) return rc;
+    const size_t lds = (size_t)2 * GR_D * GR_LD * sizeof(float);
+    return launch<tg_box_dx_kernel>(dim3((unsigned)((long)A * rpad / GR_TR)), dim3(256), lds, st, apps, rows, M, rows ? (long)R : M, rpad,
                                     (int)(x_dtype != DTLR_F32), (const float*)W0T, b0, (const float*)W1T, b1, W0, W1, W2);
 }
 
 extern "C" long dtlr_ln_backward_workspace_bytes(long M)
 {
     if (M <= 0 || M > (1l << 40)) return 0;
-    return (long)ln_plan(M).nwg * 2 * TG_D * (long)sizeof(double);
+    return (long)ln_plan(M).nwg * 2 * GR_D * (long)sizeof(double);
 }
 
 extern "C" int dtlr_ln_backward(const void* x, int x_dtype, const float* gamma, const float* g, float* dx, long dx_row0, float* dgamma,
@@ -407,7 +375,7 @@ extern "C" int dtlr_ln_backward(const void* x, int x_dtype, const float* gamma, 
 
 extern "C" long dtlr_ffn_recompute_workspace_bytes(long M, int F)
 {
-    return tg_ffn_ok(M, F) ? 2l * F * TG_D * (long)sizeof(float) : 0;
+    return tg_ffn_ok(M, F) ? 2l * F * GR_D * (long)sizeof(float) : 0;
 }
 
 extern "C" int dtlr_ffn_recompute(const void* u, int u_dtype, const float* W1, const float* b1, const float* W2, const float* b2, float* h,
@@ -419,21 +387,21 @@ extern "C" int dtlr_ffn_recompute(const void* u, int u_dtype, const float* W1, c
     if (!tg_ffn_ok(M, F)) return DTLR_ESHAPE;
     if (tg_mis(u, u_dtype == DTLR_F32 ? 3 : 1) || tg_mis(h, 3) || tg_mis(y, 3) || tg_mis(workspace, 15)) return DTLR_EINVAL;
     float* W1T = static_cast<float*>(workspace);                   // [256][F]
-    float* W2T = W1T + (long)F * TG_D;                              // [F][256]
+    float* W2T = W1T + (long)F * GR_D;                              // [F][256]
     const hipStream_t st = (hipStream_t)stream;
     const int h16 = u_dtype != DTLR_F32;
-    if (int rc = launch<tg_transpose_kernel>(dim3(TG_D / 32, (unsigned)(F / 32)), dim3(256), 0, st, W1, W1T, F, TG_D)) return rc;
-    if (int rc = launch<tg_transpose_kernel>(dim3((unsigned)(F / 32), TG_D / 32), dim3(256), 0, st, W2, W2T, TG_D, F)) return rc;
-    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, u, h16, M, TG_D, (const float*)W1T,
+    if (int rc = launch<tg_transpose_kernel>(dim3(GR_D / 32, (unsigned)(F / 32)), dim3(256), 0, st, W1, W1T, F, GR_D)) return rc;
+    if (int rc = launch<tg_transpose_kernel>(dim3((unsigned)(F / 32), GR_D / 32), dim3(256), 0, st, W2, W2T, GR_D, F)) return rc;
+    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, u, h16, M, GR_D, (const float*)W1T,
                                              (long)F, F, b1, (const void*)nullptr, 0, (const float*)nullptr, h, (long)F, 1, 0)) return rc;
-    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, st, (const void*)h, 0, M, F, (const float*)W2T, (long)TG_D, TG_D, b2,
-                                       u, h16, (const float*)nullptr, y, (long)TG_D, 0, 0);
+    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, st, (const void*)h, 0, M, F, (const float*)W2T, (long)GR_D, GR_D, b2,
+                                       u, h16, (const float*)nullptr, y, (long)GR_D, 0, 0);
 }
 
 extern "C" long dtlr_ffn_grad_workspace_bytes(long M, int F, int u_dtype)
 {
     if (!tg_ffn_ok(M, F) || !tg_dtype_ok(u_dtype)) return 0;
-    return fg_ws(nullptr, M, F, u_dtype != DTLR_F32, hg_plan(M, F, TG_D).splits).bytes;
+    return fg_ws(nullptr, M, F, u_dtype != DTLR_F32, hg_plan(M, F, GR_D).splits).bytes;
 }
 
 extern "C" int dtlr_ffn_grad(const void* u, int u_dtype, const float* h, const float* dy, const float* W2, float* grad, long M, int F,
@@ -445,21 +413,21 @@ extern "C" int dtlr_ffn_grad(const void* u, int u_dtype, const float* h, const f
     if (!tg_ffn_ok(M, F)) return DTLR_ESHAPE;
     if (tg_mis(u, u_dtype == DTLR_F32 ? 15 : 1) || tg_mis(h, 15) || tg_mis(dy, 15) || tg_mis(grad, 3) || tg_mis(workspace, 15)) return DTLR_EINVAL;
     const bool cast = u_dtype != DTLR_F32;
-    const HgPlan hp = hg_plan(M, F, TG_D);                          // tiles_c tiles_d = 4 F / 64 for both products: one plan
+    const HgPlan hp = hg_plan(M, F, GR_D);                          // tiles_c tiles_d = 4 F / 64 for both products: one plan
     const FgWs w = fg_ws(static_cast<float*>(workspace), M, F, cast, hp.splits);
     const hipStream_t st = (hipStream_t)stream;
     // da = [h > 0] (dy W2): W2 [256][F] is k-major for this product
-    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, (const void*)dy, 0, M, TG_D, W2, (long)F,
+    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, (const void*)dy, 0, M, GR_D, W2, (long)F,
                                              F, (const float*)nullptr, (const void*)nullptr, 0, h, w.da, (long)F, 0, 0)) return rc;
     const float* u32 = static_cast<const float*>(u);
     if (cast) {
-        const long n = M * TG_D;
+        const long n = M * GR_D;
         if (int rc = launch<tg_cast_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint16_t*>(u), w.u32, n)) return rc;
         u32 = w.u32;
     }
-    const TgProb p0{w.da, u32, w.part0, w.pb0, F, TG_D}, p1{dy, h, w.part1, w.pb1, TG_D, F};
+    const TgProb p0{w.da, u32, w.part0, w.pb0, F, GR_D}, p1{dy, h, w.part1, w.pb1, GR_D, F};
     const unsigned tiles = (unsigned)(4 * (F / 64));
     if (int rc = launch<tg_ffn_partial_kernel>(dim3(tiles, (unsigned)hp.splits, 2), dim3(256), 0, st, p0, p1, M, hp.chunk)) return rc;
-    const long total = 2l * F * TG_D + F + TG_D;
+    const long total = 2l * F * GR_D + F + GR_D;
     return launch<tg_ffn_reduce_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p0, p1, grad, hp.splits);
 }

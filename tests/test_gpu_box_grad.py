@@ -309,16 +309,55 @@ def test_trainer_class_and_box_steps_vs_fp64(dtype):
             assert moved > 0 and e_dev <= 4 * e_cpu, (dtype, k, name, e_dev, e_cpu)
 
 
+def _chain_step(model, matcher, loss, buf, k, imgs, labels, tboxes, max_norm):
+    """One default step assembled from the public operators on the flat buffers buf = (param, exp_avg, exp_avg_sq, grad, scale): the
+    chain dtlr_amd/adapt.py's module docstring promises, written out without the trainer"""
+    from dtlr_amd import evaluation as E
+    from dtlr_amd import ops
+    param, m, v, grad, scale = buf
+    head = model.class_embed[0]
+    C, D = head.weight.shape
+    model.engine().set_class_head(param[: C * D].view(C, D), param[C * D:])
+    with torch.no_grad():
+        out = model(imgs, return_hidden=True)
+    result = {}
+    if loss != "ctc":
+        tg = ops.set_targets([{"labels": torch.as_tensor(l, dtype=torch.int64), "boxes": torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4)}
+                              for l, b in zip(labels, tboxes)], out["pred_logits"].device, C)
+        match = matcher.match(out["pred_logits"], out["pred_boxes"], tg)
+        r = ops.set_loss(out["pred_logits"], out["pred_boxes"], tg, match, max(float(sum(tg.sizes)), 1.0), [[1.0, 0.0, 0.0]], [True], matcher.focal_alpha)
+        w, dlogits = r["losses"][0], r["dlogits"][0]
+        result = {"loss_ce": w[0], "loss_bbox": w[1], "loss_giou": w[2], "cardinality_error": w[5], "class_error": w[6]}
+    if "ctc" in loss:
+        result["loss_CTC"], dctc = E.loss_ctc_backward(out, labels)
+        dlogits = dctc if loss == "ctc" else dlogits.add_(dctc, alpha=1.0)
+    ops.head_grad(dlogits.view(-1, C), out["hs"].reshape(-1, D), out=grad)
+    ops.grad_norm_scale(grad, max_norm, out=scale)
+    ops.adamw_step(param, m, v, grad, k, LR, (0.9, 0.999), 1e-8, WD, grad_scale=scale)
+    return result
+
+
 def test_trainer_defaults_are_bit_identical():
-    """train=("class",), aux_loss=False is the trainer built without the new arguments, in bits, in every loss mode"""
-    for loss in ("ctc", "ctc+set"):
+    """train=("class",), aux_loss=False is the trainer built without the new arguments, in bits, in every loss mode -- and both are, in
+    bits, the chain of public operators the module docstring promises (forward after set_class_head, CTC backward and / or matching +
+    set loss on the single output, head_grad, grad_norm_scale, adamw_step) run on flat buffers of its own"""
+    from dtlr_amd.criterion import HungarianMatcher
+    for loss in ("ctc", "set", "ctc+set"):
         _, a, imgs, targets = _trainer("f32", max_norm=0.5, loss=loss)
         _, b, _, _ = _trainer("f32", max_norm=0.5, loss=loss, train=("class",), aux_loss=False, bbox_loss_coef=5.0, giou_loss_coef=2.0)
+        _, c, _, _ = _trainer("f32", max_norm=0.5, loss=loss)               # the third arm: c's model, never c's steps
+        head = c.model.class_embed[0]
+        n = head.weight.numel() + head.bias.numel()
+        buf = [torch.cat([head.weight.detach().reshape(-1), head.bias.detach().reshape(-1)]).float().clone()]
+        buf += [torch.zeros(n, device=DEV) for _ in range(3)] + [torch.ones(2, device=DEV)]
+        matcher = HungarianMatcher(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0, focal_alpha=0.25)
         labels, tboxes = [t["labels"].tolist() for t in targets], [t["boxes"] for t in targets]
-        for _ in range(2):
+        for k in (1, 2):
             ra, rb = a.step(imgs, labels, target_boxes=tboxes), b.step(imgs, labels, target_boxes=tboxes)
-            assert set(ra) == set(rb) and all(torch.equal(ra[k], rb[k]) for k in ra)
+            rc = _chain_step(c.model, matcher, loss, buf, k, imgs, labels, tboxes, 0.5)
+            assert set(ra) == set(rb) == set(rc) and all(torch.equal(ra[key], rb[key]) and torch.equal(ra[key], rc[key]) for key in ra), (loss, k)
         assert torch.equal(a.param, b.param) and torch.equal(a.exp_avg_sq, b.exp_avg_sq) and a.param.numel() == 23 * 257
+        assert torch.equal(a.param, buf[0]) and torch.equal(a.exp_avg, buf[1]) and torch.equal(a.exp_avg_sq, buf[2]), loss
         assert set(a.state_dict()) == {"head", "exp_avg", "exp_avg_sq", "step", "num_classes", "hidden_dim"}
 
 

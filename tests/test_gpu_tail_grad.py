@@ -364,22 +364,29 @@ def test_trainer_step_gradient_vs_fp64(dtype):
     assert abs(float(tr.scale[1]) - norm) <= 1e-4 * norm
 
 
-@pytest.mark.parametrize("loss,train", [("ctc", ("tail",)), ("ctc+set", ("class", "tail")), ("set", ("tail",))])
+@pytest.mark.parametrize("loss,train", [("ctc", ("tail",)), ("ctc+set", ("class", "tail")), ("set", ("tail",)), ("ctc", ("class",)),
+                                        ("ctc+set", ("class",))])
 def test_step_cached_equals_step_in_bits(loss, train):
     """With "tail" and neither "box" nor aux_loss, cache() returns (tail_in, ref_last) and step_cached on them leaves the parameters,
-    the moments and the losses the full step leaves, in bits, step after step"""
+    the moments and the losses the full step leaves, in bits, step after step.  With the class head alone cache() returns (hs,
+    pred_boxes), and the same holds."""
     _, a, imgs, targets = _trainer("bf16", max_norm=0.5, loss=loss, train=train)
     _, b, _, _ = _trainer("bf16", max_norm=0.5, loss=loss, train=train)
     labels, tboxes = [t["labels"].tolist() for t in targets], [t["boxes"] for t in targets]
     tb = None if loss == "ctc" else tboxes
     tail_in, ref_last = b.cache(imgs)
     assert tail_in.shape == (len(imgs), 30, 256) and ref_last.shape == (len(imgs), 30, 4)
+    if "tail" not in train:
+        assert a.param.numel() == 23 * 257 and torch.equal(ref_last, a.model(imgs)["pred_boxes"])        # (hs, pred_boxes)
     for k in range(3):
         ra, rb = a.step(imgs, labels, target_boxes=tb), b.step_cached(tail_in, ref_last, labels, tb)
         assert set(rb) <= set(ra) and all(torch.equal(ra[key], rb[key]) for key in rb), (k, ra, rb)
         assert torch.equal(a.grad, b.grad) and torch.equal(a.param, b.param) and torch.equal(a.exp_avg_sq, b.exp_avg_sq), k
         assert torch.equal(a.last_outputs["pred_logits"], b.last_outputs["pred_logits"])
-    assert float((a.tail()[0] - _tail_params(a.model)[0].detach()).abs().max()) > 0                  # the master moved, the module not yet
+    if "tail" in train:
+        assert float((a.tail()[0] - _tail_params(a.model)[0].detach()).abs().max()) > 0              # the master moved, the module not yet
+    else:
+        assert float((a.weight - a.model.class_embed[0].weight.detach()).abs().max()) > 0
 
 
 def test_trainer_without_tail_is_unchanged_in_bits():
