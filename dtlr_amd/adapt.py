@@ -23,6 +23,11 @@ constants of both heads' gradients (dtlr_box_refine_grad, dtlr_box_mlp_grad).
 --train ..,tail also trains the decoder's tail: linear1, linear2 and norm3 of the last decoder layer and
 transformer.decoder.norm, everything the loss reaches without crossing an attention.  Its gradient starts from the last layer's state after
 norm1, a constant of the frozen trunk (dtlr_head_dx, dtlr_box_mlp_dx, dtlr_ln_backward, dtlr_ffn_recompute, dtlr_ffn_grad).
+
+--train ..,tail,cross goes one block deeper: the last decoder layer's deformable cross-attention -- its sampling_offsets,
+attention_weights and output_proj -- and the norm1 after it, the parameters that place a query on a character.  Everything below the block
+(the state after norm2, the query position embedding, the reference points, the value map) is a constant of the frozen trunk, and of the
+deformable attention's backward only the two gathers are needed (dtlr_cross_recompute, dtlr_msda_query_grad, dtlr_cross_dow).
 """
 from __future__ import annotations
 
@@ -104,7 +109,7 @@ def new_class_head(model, num_classes: int, weight: Optional[torch.Tensor] = Non
     return model
 
 
-TRAINABLE = ("class", "box", "tail")        # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
+TRAINABLE = ("class", "box", "tail", "cross")        # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
 
 
 @dataclass
@@ -134,13 +139,18 @@ class ParamGroup:
 
 def _model_params(model, name: str) -> List[torch.Tensor]:
     """group name -> the model's parameters in the flat order: the shared class head [W, b]; the shared box MLP [W0, b0, W1, b1, W2,
-    b2]; the tail (ops.TAIL_NAMES): linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm"""
+    b2]; the tail (ops.TAIL_NAMES): linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm; the cross block
+    (ops.CROSS_NAMES): sampling_offsets, attention_weights and output_proj of the last decoder layer's cross_attn, then its norm1"""
     if name == "class":
         return [model.class_embed[0].weight, model.class_embed[0].bias]
     if name == "box":
         return [p for l in model.bbox_embed[0].layers for p in (l.weight, l.bias)]
     dec = model.transformer.decoder
     last = dec.layers[len(dec.layers) - 1]
+    if name == "cross":
+        a = last.cross_attn
+        return [a.sampling_offsets.weight, a.sampling_offsets.bias, a.attention_weights.weight, a.attention_weights.bias, a.output_proj.weight,
+                a.output_proj.bias, last.norm1.weight, last.norm1.bias]
     return [last.linear1.weight, last.linear1.bias, last.linear2.weight, last.linear2.bias, last.norm3.weight, last.norm3.bias,
             dec.norm.weight, dec.norm.bias]
 
@@ -148,7 +158,8 @@ def _model_params(model, name: str) -> List[torch.Tensor]:
 # group name -> (its state-dict keys, how its master views reach the engine)
 _GROUPS = {"class": (("head", "exp_avg", "exp_avg_sq"), lambda eng, v: eng.set_class_head(v[0], v[1])),
            "box": (("box_head", "box_exp_avg", "box_exp_avg_sq"), lambda eng, v: eng.set_box_head(v[0::2], v[1::2])),
-           "tail": (("tail", "tail_exp_avg", "tail_exp_avg_sq"), lambda eng, v: eng.set_decoder_tail(v[0:2], v[2:4], v[4:6], v[6:8]))}
+           "tail": (("tail", "tail_exp_avg", "tail_exp_avg_sq"), lambda eng, v: eng.set_decoder_tail(v[0:2], v[2:4], v[4:6], v[6:8])),
+           "cross": (("cross", "cross_exp_avg", "cross_exp_avg_sq"), lambda eng, v: eng.set_decoder_cross(v[0:2], v[2:4], v[4:6], v[6:8]))}
 
 
 def _cat(ts):
@@ -212,9 +223,20 @@ class HeadTrainer:
     from the master weights.  With "tail" and neither "box" nor aux_loss, `cache` returns (the last layer's FFN input, its reference
     points) and `step_cached` runs DTLREngine.tail_forward on them: the same step without the trunk.
 
-    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", in this order) to its ParamGroup: the model's
+    train may also name "cross" (DESIGN.md section 23), with "tail": sampling_offsets, attention_weights and output_proj of the LAST decoder
+    layer's cross-attention and the norm1 after it, 164,992 parameters -- where a query looks.  The flat buffer grows by [so.W | so.b | aw.W |
+    aw.b | out.W | out.b | norm1.w | norm1.b], under the same clip norm and AdamW launch.  It needs "tail" (the gradient passes through the
+    FFN chain either way), works with every loss and with or without aux_loss (the auxiliary outputs do not depend on the last layer), and
+    needs the full forward every step: the cache would have to hold the batch's value map (no cache / step_cached).  The block's inputs
+    -- the state after norm2, the query position embedding, the reference points, the value map -- are the engine's (forward's
+    return_hidden="cross"); everything from there up is recomputed in fp32 from the masters (ops.cross_recompute), and the tail's chain then
+    starts from THIS recomputed state after norm1, not from the engine's.  Of the deformable attention's backward only the gradients with
+    respect to the sampling locations and the attention weights are taken (ops.msda_query_grad); the one with respect to the value map
+    leads to frozen parameters only.
+
+    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", "cross", in this order) to its ParamGroup: the model's
     parameters in flat order, their shapes, the group's offset and length in the flat buffers (param, exp_avg, exp_avg_sq, grad), its
-    state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail(), _engine(), the step's gradient slices,
+    state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail() / cross(), _engine(), the step's gradient slices,
     state_dict / load_state_dict and write_back read that table and nothing else knows an offset.  There is ONE step routine, `_update`,
     over the L decoder outputs it is given: every output of return_hidden="all" / "tail", or -- the class head on the main output, and
     every cached step -- the one-output dict `_main_output` builds (L = 1: no loss_*_<l> keys, nothing stacked or concatenated, the
@@ -233,6 +255,9 @@ class HeadTrainer:
             raise ValueError("HeadTrainer(train=('box', ..)): the CTC loss has no gradient for boxes -- loss must be 'set' or 'ctc+set'")
         if aux_loss and loss == "ctc":
             raise ValueError("HeadTrainer(aux_loss=True): the CTC loss is taken on the main output only -- loss must be 'set' or 'ctc+set'")
+        if "cross" in train and "tail" not in train:
+            raise ValueError("HeadTrainer(train=('cross', ..)): 'cross' requires 'tail' -- the gradient of the cross-attention block passes "
+                             "through the last FFN and the norms either way")
         if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
             raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
                                       "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
@@ -265,6 +290,17 @@ class HeadTrainer:
                 raise NotImplementedError("HeadTrainer(train=('tail', ..)): the decoder layers share parameters -- the last layer's FFN is then "
                                           "not the tail alone")
             self.F = int(last.linear1.weight.shape[0])
+        if "cross" in self.train:
+            layers = model.transformer.decoder.layers
+            last = layers[len(layers) - 1]
+            if any(o.cross_attn is last.cross_attn or o.cross_attn.output_proj.weight is last.cross_attn.output_proj.weight or o.norm1.weight is last.norm1.weight
+                   for o in list(layers)[:-1]):
+                raise NotImplementedError("HeadTrainer(train=('cross', ..)): the decoder layers share parameters -- the last layer's cross-attention is "
+                                          "then not the block alone")
+            geometry = tuple(getattr(model.cfg, k, None) for k in ("dec_n_points", "nheads", "num_feature_levels"))
+            if geometry != (4, 8, 4):
+                raise NotImplementedError(f"HeadTrainer(train=('cross', ..)): written for dec_n_points 4, nheads 8, num_feature_levels 4 (every "
+                                          f"shipped config), not {geometry}")
         # the ONE table of what is trained: every slice of param / exp_avg / exp_avg_sq / grad below is a lookup in it
         self.groups: Dict[str, ParamGroup] = {}
         n = 0
@@ -275,9 +311,12 @@ class HeadTrainer:
                 raise NotImplementedError("HeadTrainer(train=('box', ..)): the box head is not the MLP 256 -> 256 -> 256 -> 4")
             if name == "tail" and (g.shapes != list(ops.tail_shapes(self.F)) or self.D != 256):
                 raise NotImplementedError("HeadTrainer(train=('tail', ..)): the tail is not linear1 [F,256], linear2 [256,F], norm3 [256], decoder.norm [256]")
+            if name == "cross" and (tuple(g.shapes) != ops.CROSS_SHAPES or self.D != 256):
+                raise NotImplementedError("HeadTrainer(train=('cross', ..)): the block is not sampling_offsets [256,256], attention_weights [128,256], "
+                                          "output_proj [256,256], norm1 [256]")
             self.groups[name] = g
             n += g.n
-        self.n_class, self.n_box, self.n_tail = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE)
+        self.n_class, self.n_box, self.n_tail, self.n_cross = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE)
         dev = head.weight.device
         self.param = torch.cat([p.detach().float().reshape(-1) for g in self.groups.values() for p in g.params]).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -310,6 +349,11 @@ class HeadTrainer:
         """the master tail as views of the flat buffer: [W1, b1, W2, b2, norm3.w, norm3.b, dec_norm.w, dec_norm.b] (train includes "tail")"""
         return self._views("tail", "HeadTrainer: the decoder tail is not trained (train lacks 'tail')")
 
+    def cross(self) -> List[torch.Tensor]:
+        """the master cross-attention block as views of the flat buffer: [so.W, so.b, aw.W, aw.b, out.W, out.b, norm1.w, norm1.b] (train
+        includes "cross")"""
+        return self._views("cross", "HeadTrainer: the cross-attention block is not trained (train lacks 'cross')")
+
     def _box_weights(self) -> List[torch.Tensor]:
         """the box MLP the forward runs: the master when it is trained, else the model's"""
         return self.box_head() if self.n_box else [p.detach().float() for p in _model_params(self.model, "box")]
@@ -339,7 +383,7 @@ class HeadTrainer:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         if self.every_output:
-            out = self.model(samples, per_line=per_line, return_hidden="tail" if self.n_tail else "all")
+            out = self.model(samples, per_line=per_line, return_hidden="cross" if self.n_cross else "tail" if self.n_tail else "all")
         else:                                                               # the class head on the main output: the last state is all the step reads
             o = self.model(samples, per_line=per_line, return_hidden=True)
             out = self._main_output(o["hs"], o["pred_logits"], o["pred_boxes"])
@@ -364,6 +408,8 @@ class HeadTrainer:
         return {"hs_all": [hs], "tgt_all": [None], "refs": [ref], "aux_outputs": [], "pred_logits": logits, "pred_boxes": boxes, **more}
 
     def _no_cache(self, what):
+        if "cross" in self.train:
+            raise ValueError(f"HeadTrainer.{what}: the cross-attention block reads the batch's value map, which the cache does not hold -- use step()")
         if "box" in self.train:
             raise ValueError(f"HeadTrainer.{what}: the forward depends on the box head being trained -- use step()")
         if self.aux_loss:
@@ -391,6 +437,8 @@ class HeadTrainer:
         self.last_states = {"hs_all": hs_all, "tgt_all": tgt_all, "refs": refs, "pred_logits": logits, "pred_boxes": boxes}
         if self.n_tail:
             self.last_states["tail_in"] = out["tail_in"]
+        if self.n_cross:
+            self.last_states["cross_in"] = out["cross_in"]
         match = r = None
         if self.loss == "ctc":                                                  # the CTC loss reaches the tail through dlogits alone
             result = {}
@@ -434,7 +482,16 @@ class HeadTrainer:
             if dz is not None:
                 ops.box_mlp_dx([hs_all[l].reshape(-1, self.D) for l in used], [dz[l] for l in used], [dh[k * M:(k + 1) * M] for k in range(len(used))],
                                self._box_weights(), rows=ops.match_rows(match, nq, B)[used])
-            ops.tail_grad(out["tail_in"], [tgt_all[l] for l in used if l < L - 1], dh, self.tail(), out=self.groups["tail"].of(self.grad))
+            t_below = [tgt_all[l] for l in used if l < L - 1]
+            if self.n_cross:
+                # the block below the tail: everything from the state after norm2 upward is recomputed in fp32 from the masters, the tail's
+                # chain starts from that u and hands back the gradient at it
+                ci = out["cross_in"]
+                rec = ops.cross_recompute(ci["s"], ci["qpos"], ci["ref_in"], ci["value"], ci["shapes"], ci["lsi"], self.cross())
+                _, grad_u = ops.tail_grad(rec["u"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad), return_du=True)
+                ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad))
+            else:
+                ops.tail_grad(out["tail_in"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad))
         clip = self.max_norm > 0
         if clip:
             ops.grad_norm_scale(self.grad, self.max_norm, out=self.scale)
@@ -448,7 +505,8 @@ class HeadTrainer:
         """"head" / "exp_avg" / "exp_avg_sq": the class head [W | b] and its moments, as before the box head could be trained (without
         "class" in train: the model's head and empty moments); "box_head" / "box_exp_avg" / "box_exp_avg_sq" and "tail" / "tail_exp_avg" /
         "tail_exp_avg_sq": the same of the box head [W0 | b0 | W1 | b1 | W2 | b2] and of the tail [W1 | b1 | W2 | b2 | norm3.w | norm3.b |
-        dec_norm.w | dec_norm.b], present when they are trained."""
+        dec_norm.w | dec_norm.b], present when they are trained; "cross" / "cross_exp_avg" / "cross_exp_avg_sq": likewise the cross-attention
+        block [so.W | so.b | aw.W | aw.b | out.W | out.b | norm1.w | norm1.b]."""
         t = {key: g.of(flat).detach().cpu().clone() for g in self.groups.values() for key, flat in zip(g.keys, (self.param, self.exp_avg, self.exp_avg_sq))}
         if not self.n_class:
             t.update(head=torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
@@ -524,7 +582,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--boxes", default=None, help="JSON {image id: [[cx, cy, w, h], ...]}: one box a character, normalised to 0..1 (--boxes-from labels)")
     ap.add_argument("--train", default="class", help="the heads to train, comma-separated: class (default), box (the shared box head; needs "
                                                      "--loss set or ctc+set and the full forward every step), tail (the last decoder "
-                                                     "layer's FFN and norm3 and decoder.norm; any loss), e.g. class,box,tail")
+                                                     "layer's FFN and norm3 and decoder.norm; any loss), cross (that layer's cross-attention "
+                                                     "and norm1; needs tail and the full forward every step), e.g. class,box,tail,cross")
     ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
@@ -585,7 +644,11 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     args = ap.parse_args(argv)
     train = tuple(k.strip() for k in args.train.split(",") if k.strip())
     if not train or set(train) - set(TRAINABLE):
-        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail")
+        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail, cross")
+    if "cross" in train and "tail" not in train:
+        ap.error("--train cross needs tail: the gradient of the cross-attention block passes through the last FFN either way")
+    if "cross" in train and args.cache_features:
+        ap.error("--cache-features cannot train the cross-attention block: it reads the batch's value map")
     if "box" in train and args.cache_features:
         ap.error("--cache-features cannot train the box head: the forward depends on it")
     if ("box" in train or args.aux_loss) and args.loss == "ctc":

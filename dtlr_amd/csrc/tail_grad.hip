@@ -283,7 +283,7 @@ static inline FgWs fg_ws(float* ws, long M, int F, bool cast, int splits)
 {
     FgWs w;
     float* p = ws;
-    w.da = p; p += M * F;
+    w.da = p; p += M * F;                                        // FIRST: include/dtlr_tailgrad.h promises da at the workspace's head
     w.u32 = p; p += cast ? (M * GR_D + 3) / 4 * 4 : 0;
     w.part0 = p; p += (long)splits * F * GR_D;
     w.part1 = p; p += (long)splits * F * GR_D;                    // every count above is a multiple of 4 floats: p stays 16-byte aligned

@@ -511,6 +511,29 @@ class DTLREngine:
             self._put(name + ".b", b.detach().clone(), torch.float32)
 
     @torch.no_grad()
+    def set_decoder_cross(self, sampling_offsets, attention_weights, output_proj, norm1) -> None:
+        """Replace the LAST decoder layer's cross-attention block -- its sampling_offsets, attention_weights and output_proj and the norm1
+        after it, each a (weight, bias) pair -- in the packed model without re-packing anything else: set_decoder_tail's counterpart
+        (DESIGN.md section 23).  `dec{L-1}.attn.ow` (the 384 x 256 concatenation [sampling_offsets ; attention_weights] and its bias) and
+        `dec{L-1}.attn.out` are swapped as _put_linear packs them, `dec{L-1}.norm1` in fp32, and only the images derived from the two
+        linears are dropped, to be rebuilt by the next forward.  A forward after this equals, bit for bit, the forward of a fresh engine
+        built from the updated state dict."""
+        d, q = self.cfg.hidden_dim, f"dec{self.cfg.dec_layers - 1}."
+        n_off, n_log = (int(t.numel()) for t in (sampling_offsets[1], attention_weights[1]))
+        want = [((n_off, d), (n_off,)), ((n_log, d), (n_log,)), ((d, d), (d,)), ((d,), (d,))]
+        if [tuple(tuple(t.shape) for t in pair) for pair in (sampling_offsets, attention_weights, output_proj, norm1)] != want \
+                or n_off != 2 * n_log or n_off + n_log != int(self.w[q + "attn.ow.b"].numel()):
+            raise ValueError(f"set_decoder_cross: not sampling_offsets [2n,{d}], attention_weights [n,{d}] with 3n = {self.w[q + 'attn.ow.b'].numel()}, "
+                             f"output_proj [{d},{d}] and norm1 [{d}], each with its bias")
+        for name in (q + "attn.ow", q + "attn.out"):                          # before the puts: a split engine's kept fp32 sources are (kind, name) entries too
+            self._drop_images(name)
+        self._put_linear(q + "attn.ow", torch.cat([sampling_offsets[0].detach(), attention_weights[0].detach()], 0),      # cat copies: the engine never
+                         torch.cat([sampling_offsets[1].detach(), attention_weights[1].detach()], 0))                     # aliases the caller's buffers
+        self._put_linear(q + "attn.out", output_proj[0].detach().clone(), output_proj[1].detach().clone())
+        self._put(q + "norm1.w", norm1[0].detach().clone(), torch.float32)
+        self._put(q + "norm1.b", norm1[1].detach().clone(), torch.float32)
+
+    @torch.no_grad()
     def tail_forward(self, tail_in, ref_last) -> Dict[str, torch.Tensor]:
         """The main output from the last decoder layer's FFN input on (forward(return_hidden="tail")'s out["tail_in"], in the engine's
         dtype) and that layer's reference points out["refs"][dec_layers - 1]: _ffn + norm3 -> decoder.norm -> class head -> box head, the
@@ -978,13 +1001,14 @@ class DTLREngine:
             return True
         return False
 
-    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None, tail_in=None):
+    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None, tail_in=None, cross_in=None):
         """TransformerDecoder.forward + DeformableTransformerDecoderLayer
         (deformable_transformer.py:652-766, 882-997), batch-first.  vall: value_proj(memory) of all layers when the caller already
         computed it (forward() does, on a side stream under the two-stage selection).  per_line: the query position embedding is the
         sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios.  tgt_all: a list that
         receives every layer's un-normed output (what the box head's refinement of the reference points reads).  tail_in: a list that
-        receives the last layer's FFN input (its state after norm1: what the tail's gradient starts from)."""
+        receives the last layer's FFN input (its state after norm1: what the tail's gradient starts from).  cross_in: a dict that receives
+        the inputs of the last layer's cross-attention block (forward(return_hidden="cross"))."""
         cfg = self.cfg
         B = memory.shape[0]
         ref = ts["ref_unsig"].sigmoid()
@@ -1016,6 +1040,9 @@ class DTLREngine:
             a = ops.mha(qk, v, cfg.nheads, split=self.split)
             tgt = self._proj_ln(q + "sa.out", q + "norm2", a, tgt)
             # deformable cross attention
+            if cross_in is not None and n == cfg.dec_layers - 1:
+                cross_in.update(s=tgt, qpos=qpos, ref_in=ref_in, value=vall[..., n * C:(n + 1) * C].unflatten(-1, (cfg.nheads, C // cfg.nheads)),
+                                shapes=g["shapes"], lsi=g["lsi"])
             a = self._msda_module(q + "attn", tgt, qpos, ref_in, memory, g, cfg.dec_n_points, value=vall[..., n * C:(n + 1) * C])
             tgt = self._proj_ln(q + "attn.out", q + "norm1", a, tgt)
             # ffn
@@ -1165,7 +1192,11 @@ class DTLREngine:
         decoder.norm, and out["refs"], the dec_layers + 1 reference points [B,nq,4] fp32 -- everything the box head's gradient needs
         (DESIGN.md section 21); the tensors the forward makes anyway, no extra launch beyond want_aux's.  return_hidden="tail": "all", and
         out["tail_in"], the last decoder layer's state after norm1 [B,nq,hidden] in the engine's dtype -- the input of that layer's FFN,
-        where the tail's gradient starts; again a tensor the forward already has."""
+        where the tail's gradient starts; again a tensor the forward already has.  return_hidden="cross": "tail", and
+        out["cross_in"], the inputs of the last decoder layer's cross-attention block: {"s": its state after norm2,
+        "qpos": the query position embedding [B,nq,hidden], both in the engine's dtype; "ref_in": reference_points_input [B,nq,L,4] fp32;
+        "value": that layer's slice of the projected value map [B,S,heads,hidden/heads], a view; "shapes", "lsi": the level shapes and
+        starts} -- tensors the forward already has, no extra launch."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1220,18 +1251,21 @@ class DTLREngine:
         ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        if return_hidden not in (False, True, "all", "tail"):
-            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail'")
+        if return_hidden not in (False, True, "all", "tail", "cross"):
+            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail', 'cross'")
         every = isinstance(return_hidden, str)
         want_aux = want_aux or every
         tgt_all = [] if every else None
-        tail_in = [] if return_hidden == "tail" else None
-        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in)
+        tail_in = [] if return_hidden in ("tail", "cross") else None
+        cross_in = {} if return_hidden == "cross" else None
+        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in, cross_in=cross_in)
         out = self.heads(hs, refs, ts, want_aux, bool(return_hidden))
         if every:
             out["hs_all"], out["tgt_all"], out["refs"] = list(hs), tgt_all, list(refs)
         if tail_in is not None:
             out["tail_in"] = tail_in[0]
+        if cross_in is not None:
+            out["cross_in"] = cross_in
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

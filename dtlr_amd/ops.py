@@ -1859,3 +1859,5 @@ from .boxgrad import BOX_GRAD_FLOATS, BOX_GRAD_MAX_APPS, BOX_HEAD_SHAPES, box_ml
 # the ninth header (include/dtlr_tailgrad.h), the same way: written in dtlr_amd/tailgrad.py (the decoder tail's gradient with the trunk frozen)
 from .tailgrad import (TAIL_NAMES, box_mlp_dx, ffn_grad, ffn_recompute, head_dx, ln_backward, tail_floats, tail_grad,            # noqa: E402,F401
                        tail_shapes)
+# the tenth header (include/dtlr_crossgrad.h), the same way: written in dtlr_amd/crossgrad.py (the last decoder layer's cross-attention gradient)
+from .crossgrad import CROSS_FLOATS, CROSS_NAMES, CROSS_SHAPES, cross_dow, cross_grad, cross_recompute, msda_query_grad          # noqa: E402,F401

@@ -121,9 +121,11 @@ def ffn_recompute(u, weights: Sequence[torch.Tensor]):
 
 
 @_lib.op
-def ffn_grad(u, h, dy, w2, out: Optional[torch.Tensor] = None):
+def ffn_grad(u, h, dy, w2, out: Optional[torch.Tensor] = None, return_da: bool = False):
     """dtlr_ffn_grad: u [M,256], h [M,F] fp32 (ffn_recompute's), dy [M,256] fp32 (the gradient at y), w2 [256,F] fp32 -> the flat
-    gradient [dW1 | db1 | dW2 | db2] fp32 (out: a buffer of 2 * 256 * F + F + 256 to fill).  Reproducible run to run."""
+    gradient [dW1 | db1 | dW2 | db2] fp32 (out: a buffer of 2 * 256 * F + F + 256 to fill).  Reproducible run to run.  return_da: ->
+    (the gradient, da [M,F] fp32 = [h > 0] (dy W2)): the head of the call's workspace, where the entry point leaves it -- the same
+    launches, nothing computed twice."""
     u, M = _rows(u, "ffn_grad: u")
     dev = u.device
     h, dy, w2 = _lib.f32(h, "h"), _lib.f32(dy, "dy").view(-1, TAIL_HIDDEN), _lib.f32(w2, "W2")
@@ -137,15 +139,17 @@ def ffn_grad(u, h, dy, w2, out: Optional[torch.Tensor] = None):
     L = _lib.lib(u.dtype)
     ws = _lib.workspace(_lib.query(L, "dtlr_ffn_grad_workspace_bytes", M, F, _lib.DT[u.dtype]), dev, f"dtlr_ffn_grad M={M} F={F}")
     _lib.launch(L, "dtlr_ffn_grad", u.data_ptr(), _lib.DT[u.dtype], h.data_ptr(), dy.data_ptr(), w2.data_ptr(), out.data_ptr(), M, F, ws.data_ptr())
-    return out
+    return (out, ws[:M * F].view(M, F)) if return_da else out
 
 
-def tail_grad(u, t_below: Sequence[torch.Tensor], dh, tail: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None):
+def tail_grad(u, t_below: Sequence[torch.Tensor], dh, tail: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None, return_du: bool = False):
     """The whole chain of DESIGN.md section 22 below the heads.  u [M,256]: the last decoder layer's FFN input (the engine's state);
     t_below: the un-normed outputs t_l [M,256] of the decoder outputs l < L - 1 that carry loss weight, in order (empty without
     aux_loss); dh [(len(t_below) + 1) M, 256] fp32: the gradient at h_l of those outputs and then of the main one (ops.head_dx,
     ops.box_mlp_dx); tail: the eight fp32 masters in TAIL_NAMES' order.  -> the flat gradient [tail_floats(F)] fp32 (out: a buffer to
-    fill).  y and t_(L-1) are recomputed in fp32 from u and the masters, never read back from the engine."""
+    fill).  y and t_(L-1) are recomputed in fp32 from u and the masters, never read back from the engine.  return_du: -> (the gradient,
+    du [M,256] fp32 = dy + da W1, the gradient at u: what the block below the tail starts from); without it the
+    launches and the bits are as they were."""
     from . import ops
     w1, b1, w2, b2, g3, be3, gd, _ = tail
     F = int(w1.shape[0])
@@ -161,5 +165,8 @@ def tail_grad(u, t_below: Sequence[torch.Tensor], dh, tail: Sequence[torch.Tenso
     x = torch.cat([t.reshape(-1, TAIL_HIDDEN).float() for t in t_below] + [t_last]) if len(t_below) else t_last
     dt, _, _ = ln_backward(x, gd, dh, dx_row0=len(t_below) * M, dgamma=v[2], dbeta=v[3])
     dy, _, _ = ln_backward(y, g3, dt, dx_row0=0, dgamma=v[0], dbeta=v[1])
-    ffn_grad(u2, h, dy, w2, out=out[:n_ffn])
-    return out
+    if not return_du:
+        ffn_grad(u2, h, dy, w2, out=out[:n_ffn])
+        return out
+    _, da = ffn_grad(u2, h, dy, w2, out=out[:n_ffn], return_da=True)
+    return out, head_dx(da, w1, out=dy, accumulate=True)                      # du = dy + da W1, into dy's buffer (the chain is done with it)

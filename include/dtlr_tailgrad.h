@@ -63,7 +63,8 @@ extern "C" {
  * dtlr_ffn_grad: from u [M,256] (u_dtype), h [M,F] (dtlr_ffn_recompute's), dy [M,256] fp32 (the gradient at y) and W2, the flat
  *   gradient grad [2 * 256 * F + F + 256] = [dW1 | db1 | dW2 | db2], every element written:
  *     db2 = sum dy ;  dW2 = dy^T h ;  da = [h > 0] (dy W2) ;  db1 = sum da ;  dW1 = da^T u.
- *   workspace: dtlr_ffn_grad_workspace_bytes(M, F, u_dtype) bytes (it holds da [M,F]). */
+ *   workspace: dtlr_ffn_grad_workspace_bytes(M, F, u_dtype) bytes.  CONTRACT: on return its first M F floats are
+ *   da [M,F] row-major (dtlr_amd's ops.ffn_grad(return_da=True) reads it there: the gradient at u is dy + da W1). */
 int dtlr_head_dx(const float *G, const float *W, float *dh, long M, int C, int accumulate, void *stream);
 long dtlr_box_mlp_dx_workspace_bytes(int A, long M, int R);
 int dtlr_box_mlp_dx(const void *x_ptrs, const void *dz_ptrs, const void *dh_ptrs, const int *rows, int A, long M, int R, int x_dtype,
