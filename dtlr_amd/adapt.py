@@ -28,6 +28,11 @@ norm1, a constant of the frozen trunk (dtlr_head_dx, dtlr_box_mlp_dx, dtlr_ln_ba
 attention_weights and output_proj -- and the norm1 after it, the parameters that place a query on a character.  Everything below the block
 (the state after norm2, the query position embedding, the reference points, the value map) is a constant of the frozen trunk, and of the
 deformable attention's backward only the two gathers are needed (dtlr_cross_recompute, dtlr_msda_query_grad, dtlr_cross_dow).
+
+--train ..,tail,cross,self trains the last decoder layer whole: its self-attention -- in_proj, out_proj -- and the norm2
+after it, where the character queries of a line talk to each other.  The layer's input state and the query position embedding are the
+constants of the frozen trunk; everything from there up is recomputed in fp32 from the masters (dtlr_self_recompute), the cross block then
+starts from THAT state after norm2, and the attention core's backward is dtlr_mha_grad.
 """
 from __future__ import annotations
 
@@ -109,7 +114,8 @@ def new_class_head(model, num_classes: int, weight: Optional[torch.Tensor] = Non
     return model
 
 
-TRAINABLE = ("class", "box", "tail", "cross")        # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
+TRAINABLE = ("class", "box", "tail", "cross")        # the groups up to DESIGN.md section 23, in the flat buffer's order
+TRAINABLE_ALL = TRAINABLE + ("self",)                # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
 
 
 @dataclass
@@ -140,13 +146,17 @@ class ParamGroup:
 def _model_params(model, name: str) -> List[torch.Tensor]:
     """group name -> the model's parameters in the flat order: the shared class head [W, b]; the shared box MLP [W0, b0, W1, b1, W2,
     b2]; the tail (ops.TAIL_NAMES): linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm; the cross block
-    (ops.CROSS_NAMES): sampling_offsets, attention_weights and output_proj of the last decoder layer's cross_attn, then its norm1"""
+    (ops.CROSS_NAMES): sampling_offsets, attention_weights and output_proj of the last decoder layer's cross_attn, then its norm1; the self
+    block (ops.SELF_NAMES): in_proj and out_proj of the last decoder layer's self_attn, then its norm2"""
     if name == "class":
         return [model.class_embed[0].weight, model.class_embed[0].bias]
     if name == "box":
         return [p for l in model.bbox_embed[0].layers for p in (l.weight, l.bias)]
     dec = model.transformer.decoder
     last = dec.layers[len(dec.layers) - 1]
+    if name == "self":
+        a = last.self_attn
+        return [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, last.norm2.weight, last.norm2.bias]
     if name == "cross":
         a = last.cross_attn
         return [a.sampling_offsets.weight, a.sampling_offsets.bias, a.attention_weights.weight, a.attention_weights.bias, a.output_proj.weight,
@@ -159,7 +169,8 @@ def _model_params(model, name: str) -> List[torch.Tensor]:
 _GROUPS = {"class": (("head", "exp_avg", "exp_avg_sq"), lambda eng, v: eng.set_class_head(v[0], v[1])),
            "box": (("box_head", "box_exp_avg", "box_exp_avg_sq"), lambda eng, v: eng.set_box_head(v[0::2], v[1::2])),
            "tail": (("tail", "tail_exp_avg", "tail_exp_avg_sq"), lambda eng, v: eng.set_decoder_tail(v[0:2], v[2:4], v[4:6], v[6:8])),
-           "cross": (("cross", "cross_exp_avg", "cross_exp_avg_sq"), lambda eng, v: eng.set_decoder_cross(v[0:2], v[2:4], v[4:6], v[6:8]))}
+           "cross": (("cross", "cross_exp_avg", "cross_exp_avg_sq"), lambda eng, v: eng.set_decoder_cross(v[0:2], v[2:4], v[4:6], v[6:8])),
+           "self": (("self", "self_exp_avg", "self_exp_avg_sq"), lambda eng, v: eng.set_decoder_self(v[0], v[1], v[2:4], v[4:6]))}
 
 
 def _cat(ts):
@@ -234,9 +245,17 @@ class HeadTrainer:
     respect to the sampling locations and the attention weights are taken (ops.msda_query_grad); the one with respect to the value map
     leads to frozen parameters only.
 
-    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", "cross", in this order) to its ParamGroup: the model's
+    train may also name "self" (DESIGN.md section 24), with "cross" (and so "tail"): in_proj and out_proj of the LAST decoder layer's
+    self-attention and the norm2 after it, 263,680 parameters -- the last decoder layer is then trained whole, and layers 0 .. L-2, the encoder
+    and the backbone are the constants.  The flat buffer grows by [in_proj.W | in_proj.b | out_proj.W | out_proj.b | norm2.w | norm2.b] at its
+    end, under the same clip norm and AdamW launch.  The block's inputs -- the layer's input state and the query position embedding -- are the
+    engine's (forward's return_hidden="self"); everything from there up is recomputed in fp32 from the masters (ops.self_recompute), the cross
+    block's chain starts from THIS recomputed state after norm2 and hands back the gradient at it (ops.cross_grad's return_ds), and the
+    attention core's backward is ops.mha_grad.  The terms that land on the layer's input are dropped.  No cache / step_cached.
+
+    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", "cross", "self", in this order) to its ParamGroup: the model's
     parameters in flat order, their shapes, the group's offset and length in the flat buffers (param, exp_avg, exp_avg_sq, grad), its
-    state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail() / cross(), _engine(), the step's gradient slices,
+    state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail() / cross() / self_block(), _engine(), the step's gradient slices,
     state_dict / load_state_dict and write_back read that table and nothing else knows an offset.  There is ONE step routine, `_update`,
     over the L decoder outputs it is given: every output of return_hidden="all" / "tail", or -- the class head on the main output, and
     every cached step -- the one-output dict `_main_output` builds (L = 1: no loss_*_<l> keys, nothing stacked or concatenated, the
@@ -247,8 +266,8 @@ class HeadTrainer:
                  max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0,
                  train: Sequence[str] = ("class",), aux_loss: bool = False, bbox_loss_coef: float = 5.0, giou_loss_coef: float = 2.0):
         train = (train,) if isinstance(train, str) else tuple(train)
-        if not train or set(train) - set(TRAINABLE):
-            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of {TRAINABLE!r}")
+        if not train or set(train) - set(TRAINABLE_ALL):
+            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of {TRAINABLE_ALL!r}")
         if loss not in ("ctc", "set", "ctc+set"):
             raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
         if "box" in train and loss == "ctc":
@@ -258,10 +277,13 @@ class HeadTrainer:
         if "cross" in train and "tail" not in train:
             raise ValueError("HeadTrainer(train=('cross', ..)): 'cross' requires 'tail' -- the gradient of the cross-attention block passes "
                              "through the last FFN and the norms either way")
+        if "self" in train and "cross" not in train:
+            raise ValueError("HeadTrainer(train=('self', ..)): 'self' requires 'cross' -- the gradient of the self-attention block passes "
+                             "through the cross-attention block and the tail either way")
         if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
             raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
                                       "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
-        self.train = tuple(k for k in TRAINABLE if k in train)
+        self.train = tuple(k for k in TRAINABLE_ALL if k in train)
         self.aux_loss = bool(aux_loss)
         self.bbox_loss_coef, self.giou_loss_coef = float(bbox_loss_coef), float(giou_loss_coef)
         self.every_output = "box" in self.train or "tail" in self.train or self.aux_loss          # the step reads every decoder layer's states
@@ -301,6 +323,19 @@ class HeadTrainer:
             if geometry != (4, 8, 4):
                 raise NotImplementedError(f"HeadTrainer(train=('cross', ..)): written for dec_n_points 4, nheads 8, num_feature_levels 4 (every "
                                           f"shipped config), not {geometry}")
+        if "self" in self.train:
+            layers = model.transformer.decoder.layers
+            last = layers[len(layers) - 1]
+            if getattr(model.cfg, "transformer_activation", "relu") != "relu" or getattr(model.cfg, "dropout", 0.0) != 0.0:
+                raise NotImplementedError("HeadTrainer(train=('self', ..)): written for the ReLU FFN without dropout (every shipped config)")
+            if any(o.self_attn is last.self_attn or o.self_attn.in_proj_weight is last.self_attn.in_proj_weight
+                   or o.self_attn.out_proj.weight is last.self_attn.out_proj.weight or o.norm2.weight is last.norm2.weight for o in list(layers)[:-1]):
+                raise NotImplementedError("HeadTrainer(train=('self', ..)): the decoder layers share parameters -- the last layer's self-attention is "
+                                          "then not the block alone")
+            geometry = (getattr(model.cfg, "nheads", None), getattr(model.cfg, "hidden_dim", None))
+            if geometry != (8, 256):
+                raise NotImplementedError(f"HeadTrainer(train=('self', ..)): written for nheads 8 x 32 channels (hidden_dim 256: every shipped config), "
+                                          f"not nheads, hidden_dim = {geometry}")
         # the ONE table of what is trained: every slice of param / exp_avg / exp_avg_sq / grad below is a lookup in it
         self.groups: Dict[str, ParamGroup] = {}
         n = 0
@@ -314,9 +349,11 @@ class HeadTrainer:
             if name == "cross" and (tuple(g.shapes) != ops.CROSS_SHAPES or self.D != 256):
                 raise NotImplementedError("HeadTrainer(train=('cross', ..)): the block is not sampling_offsets [256,256], attention_weights [128,256], "
                                           "output_proj [256,256], norm1 [256]")
+            if name == "self" and (tuple(g.shapes) != ops.SELF_SHAPES or self.D != 256):
+                raise NotImplementedError("HeadTrainer(train=('self', ..)): the block is not in_proj [768,256], out_proj [256,256], norm2 [256]")
             self.groups[name] = g
             n += g.n
-        self.n_class, self.n_box, self.n_tail, self.n_cross = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE)
+        self.n_class, self.n_box, self.n_tail, self.n_cross, self.n_self = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE_ALL)
         dev = head.weight.device
         self.param = torch.cat([p.detach().float().reshape(-1) for g in self.groups.values() for p in g.params]).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -354,6 +391,11 @@ class HeadTrainer:
         includes "cross")"""
         return self._views("cross", "HeadTrainer: the cross-attention block is not trained (train lacks 'cross')")
 
+    def self_block(self) -> List[torch.Tensor]:
+        """the master self-attention block as views of the flat buffer: [in_proj.W, in_proj.b, out_proj.W, out_proj.b, norm2.w, norm2.b]
+        (train includes "self")"""
+        return self._views("self", "HeadTrainer: the self-attention block is not trained (train lacks 'self')")
+
     def _box_weights(self) -> List[torch.Tensor]:
         """the box MLP the forward runs: the master when it is trained, else the model's"""
         return self.box_head() if self.n_box else [p.detach().float() for p in _model_params(self.model, "box")]
@@ -383,7 +425,7 @@ class HeadTrainer:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         if self.every_output:
-            out = self.model(samples, per_line=per_line, return_hidden="cross" if self.n_cross else "tail" if self.n_tail else "all")
+            out = self.model(samples, per_line=per_line, return_hidden="self" if self.n_self else "cross" if self.n_cross else "tail" if self.n_tail else "all")
         else:                                                               # the class head on the main output: the last state is all the step reads
             o = self.model(samples, per_line=per_line, return_hidden=True)
             out = self._main_output(o["hs"], o["pred_logits"], o["pred_boxes"])
@@ -408,6 +450,9 @@ class HeadTrainer:
         return {"hs_all": [hs], "tgt_all": [None], "refs": [ref], "aux_outputs": [], "pred_logits": logits, "pred_boxes": boxes, **more}
 
     def _no_cache(self, what):
+        if "self" in self.train:
+            raise ValueError(f"HeadTrainer.{what}: the self-attention block reads the layer's input state and runs the whole last layer, which the "
+                             "cache does not hold -- use step()")
         if "cross" in self.train:
             raise ValueError(f"HeadTrainer.{what}: the cross-attention block reads the batch's value map, which the cache does not hold -- use step()")
         if "box" in self.train:
@@ -439,6 +484,8 @@ class HeadTrainer:
             self.last_states["tail_in"] = out["tail_in"]
         if self.n_cross:
             self.last_states["cross_in"] = out["cross_in"]
+        if self.n_self:
+            self.last_states["self_in"] = out["self_in"]
         match = r = None
         if self.loss == "ctc":                                                  # the CTC loss reaches the tail through dlogits alone
             result = {}
@@ -487,9 +534,20 @@ class HeadTrainer:
                 # the block below the tail: everything from the state after norm2 upward is recomputed in fp32 from the masters, the tail's
                 # chain starts from that u and hands back the gradient at it
                 ci = out["cross_in"]
-                rec = ops.cross_recompute(ci["s"], ci["qpos"], ci["ref_in"], ci["value"], ci["shapes"], ci["lsi"], self.cross())
+                s, qpos, rec_s = ci["s"], ci["qpos"], None
+                if self.n_self:
+                    # one block deeper: the state after norm2 is recomputed in fp32 from the layer's input and the masters, and the cross
+                    # block starts from that s (its query position embedding cast up: one dtype for both)
+                    si = out["self_in"]
+                    rec_s = ops.self_recompute(si["t"], si["qpos"], self.self_block())
+                    s, qpos = rec_s["s"].view(B, nq, self.D), qpos.float()
+                rec = ops.cross_recompute(s, qpos, ci["ref_in"], ci["value"], ci["shapes"], ci["lsi"], self.cross())
                 _, grad_u = ops.tail_grad(rec["u"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad), return_du=True)
-                ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad))
+                if rec_s is None:
+                    ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad))
+                else:
+                    _, grad_s = ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad), return_ds=True)
+                    ops.self_grad(si, rec_s, grad_s, self.self_block(), out=self.groups["self"].of(self.grad))
             else:
                 ops.tail_grad(out["tail_in"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad))
         clip = self.max_norm > 0
@@ -506,7 +564,8 @@ class HeadTrainer:
         "class" in train: the model's head and empty moments); "box_head" / "box_exp_avg" / "box_exp_avg_sq" and "tail" / "tail_exp_avg" /
         "tail_exp_avg_sq": the same of the box head [W0 | b0 | W1 | b1 | W2 | b2] and of the tail [W1 | b1 | W2 | b2 | norm3.w | norm3.b |
         dec_norm.w | dec_norm.b], present when they are trained; "cross" / "cross_exp_avg" / "cross_exp_avg_sq": likewise the cross-attention
-        block [so.W | so.b | aw.W | aw.b | out.W | out.b | norm1.w | norm1.b]."""
+        block [so.W | so.b | aw.W | aw.b | out.W | out.b | norm1.w | norm1.b]; "self" / "self_exp_avg" / "self_exp_avg_sq": the self-attention
+        block [in_proj.W | in_proj.b | out_proj.W | out_proj.b | norm2.w | norm2.b]."""
         t = {key: g.of(flat).detach().cpu().clone() for g in self.groups.values() for key, flat in zip(g.keys, (self.param, self.exp_avg, self.exp_avg_sq))}
         if not self.n_class:
             t.update(head=torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
@@ -583,7 +642,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--train", default="class", help="the heads to train, comma-separated: class (default), box (the shared box head; needs "
                                                      "--loss set or ctc+set and the full forward every step), tail (the last decoder "
                                                      "layer's FFN and norm3 and decoder.norm; any loss), cross (that layer's cross-attention "
-                                                     "and norm1; needs tail and the full forward every step), e.g. class,box,tail,cross")
+                                                     "and norm1; needs tail and the full forward every step), self (that layer's "
+                                                     "self-attention and norm2; needs cross), e.g. class,box,tail,cross,self")
     ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
@@ -643,8 +703,12 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     ap = build_parser()
     args = ap.parse_args(argv)
     train = tuple(k.strip() for k in args.train.split(",") if k.strip())
-    if not train or set(train) - set(TRAINABLE):
-        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail, cross")
+    if not train or set(train) - set(TRAINABLE_ALL):
+        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail, cross, self")
+    if "self" in train and "cross" not in train:
+        ap.error("--train self needs cross: the gradient of the self-attention block passes through the cross-attention block either way")
+    if "self" in train and args.cache_features:
+        ap.error("--cache-features cannot train the self-attention block: it runs the whole last decoder layer")
     if "cross" in train and "tail" not in train:
         ap.error("--train cross needs tail: the gradient of the cross-attention block passes through the last FFN either way")
     if "cross" in train and args.cache_features:

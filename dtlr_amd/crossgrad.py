@@ -134,11 +134,13 @@ def cross_dow(A, dA, dloc, ref_in):
     return doff, dlogit
 
 
-def cross_grad(cross_in: Dict, rec: Dict[str, torch.Tensor], du, cross: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None):
+def cross_grad(cross_in: Dict, rec: Dict[str, torch.Tensor], du, cross: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
+               return_ds: bool = False):
     """The chain of DESIGN.md section 23 below norm1's output.  cross_in: forward(return_hidden="cross")'s out["cross_in"]; rec:
     cross_recompute's result on it; du [M,256] fp32: the gradient at u (the tail's dy + da W1); cross: the eight fp32 masters ->
     the flat gradient [CROSS_FLOATS] fp32 in CROSS_NAMES' order (out: a buffer to fill).  The terms that land on s, qpos, ref_in and the
-    value map are dropped: they are frozen."""
+    value map are dropped: they are frozen.  return_ds: -> (the gradient, ds [M,256] fp32 = dx1 + doff Wso + dlogit Waw, the gradient at s:
+    what the block below starts from); without it the launches and the bits are as they were."""
     from . import ops
     wso, _, waw, _, wo, _, g1, _ = cross
     if out is None:
@@ -154,4 +156,8 @@ def cross_grad(cross_in: Dict, rec: Dict[str, torch.Tensor], du, cross: Sequence
     doff, dlogit = cross_dow(rec["A"], dA, dloc, cross_in["ref_in"])
     ops.head_grad(doff, rec["qin"], out=out[:n_so])                             # [dW | db] of sampling_offsets ..
     ops.head_grad(dlogit, rec["qin"], out=out[n_so:n_so + n_aw])                # .. and of attention_weights: the flat order keeps them apart
-    return out
+    if not return_ds:
+        return out
+    ds = head_dx(doff, wso)                                                     # s reaches x1 directly and through qin = s + p
+    head_dx(dlogit, waw, out=ds, accumulate=True)
+    return out, ds.add_(dx1)

@@ -534,6 +534,28 @@ class DTLREngine:
         self._put(q + "norm1.b", norm1[1].detach().clone(), torch.float32)
 
     @torch.no_grad()
+    def set_decoder_self(self, in_proj_weight, in_proj_bias, out_proj, norm2) -> None:
+        """Replace the LAST decoder layer's self-attention block -- its in-projection ([Wq ; Wk ; Wv] [3d,d] and its bias [3d]), its out_proj
+        and the norm2 after it, the last two each a (weight, bias) pair -- in the packed model without re-packing anything else:
+        set_decoder_cross's counterpart.  `dec{L-1}.sa.qk` (rows 0 .. 2d of the in-projection: q and k share their
+        input), `dec{L-1}.sa.v` and `dec{L-1}.sa.out` are swapped as _put_linear packs them (no scaling is folded into `sa.qk`: the attention
+        kernels scale the scores), `dec{L-1}.norm2` in fp32, and only the images derived from the three linears -- the ones dec_query_stage
+        packs among them -- are dropped, to be rebuilt by the next forward.  A forward after this equals, bit for bit, the forward of a fresh
+        engine built from the updated state dict."""
+        d, q = self.cfg.hidden_dim, f"dec{self.cfg.dec_layers - 1}."
+        want = [((3 * d, d), (3 * d,)), ((d, d), (d,)), ((d,), (d,))]
+        if [tuple(tuple(t.shape) for t in pair) for pair in ((in_proj_weight, in_proj_bias), out_proj, norm2)] != want:
+            raise ValueError(f"set_decoder_self: not in_proj_weight [{3 * d},{d}], in_proj_bias [{3 * d}], out_proj [{d},{d}] and norm2 [{d}], each with its bias")
+        for name in (q + "sa.qk", q + "sa.v", q + "sa.out"):                  # before the puts: a split engine's kept fp32 sources are (kind, name) entries too
+            self._drop_images(name)
+        W, Bi = in_proj_weight.detach().clone(), in_proj_bias.detach().clone()      # copies: the engine never aliases the caller's buffers
+        self._put_linear(q + "sa.qk", W[:2 * d], Bi[:2 * d])
+        self._put_linear(q + "sa.v", W[2 * d:], Bi[2 * d:])
+        self._put_linear(q + "sa.out", out_proj[0].detach().clone(), out_proj[1].detach().clone())
+        self._put(q + "norm2.w", norm2[0].detach().clone(), torch.float32)
+        self._put(q + "norm2.b", norm2[1].detach().clone(), torch.float32)
+
+    @torch.no_grad()
     def tail_forward(self, tail_in, ref_last) -> Dict[str, torch.Tensor]:
         """The main output from the last decoder layer's FFN input on (forward(return_hidden="tail")'s out["tail_in"], in the engine's
         dtype) and that layer's reference points out["refs"][dec_layers - 1]: _ffn + norm3 -> decoder.norm -> class head -> box head, the
@@ -1001,14 +1023,15 @@ class DTLREngine:
             return True
         return False
 
-    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None, tail_in=None, cross_in=None):
+    def decoder(self, memory, ts, g, want_aux=False, dbg=None, vall=None, per_line=False, tgt_all=None, tail_in=None, cross_in=None, self_in=None):
         """TransformerDecoder.forward + DeformableTransformerDecoderLayer
         (deformable_transformer.py:652-766, 882-997), batch-first.  vall: value_proj(memory) of all layers when the caller already
         computed it (forward() does, on a side stream under the two-stage selection).  per_line: the query position embedding is the
         sine of the UNscaled reference (alone the valid ratios are 1); the sampling still uses ref * valid_ratios.  tgt_all: a list that
         receives every layer's un-normed output (what the box head's refinement of the reference points reads).  tail_in: a list that
         receives the last layer's FFN input (its state after norm1: what the tail's gradient starts from).  cross_in: a dict that receives
-        the inputs of the last layer's cross-attention block (forward(return_hidden="cross"))."""
+        the inputs of the last layer's cross-attention block (forward(return_hidden="cross")).  self_in: a dict that receives the inputs of
+        the last layer's self-attention block (forward(return_hidden="self"))."""
         cfg = self.cfg
         B = memory.shape[0]
         ref = ts["ref_unsig"].sigmoid()
@@ -1037,6 +1060,8 @@ class DTLREngine:
                 # self attention (q = k = tgt + query_pos, v = tgt)
                 qk = self._lin(q + "sa.qk", tgt, a2=qpos)
                 v = self._lin(q + "sa.v", tgt)
+            if self_in is not None and n == cfg.dec_layers - 1:
+                self_in.update(t=tgt, qpos=qpos)
             a = ops.mha(qk, v, cfg.nheads, split=self.split)
             tgt = self._proj_ln(q + "sa.out", q + "norm2", a, tgt)
             # deformable cross attention
@@ -1196,7 +1221,9 @@ class DTLREngine:
         out["cross_in"], the inputs of the last decoder layer's cross-attention block: {"s": its state after norm2,
         "qpos": the query position embedding [B,nq,hidden], both in the engine's dtype; "ref_in": reference_points_input [B,nq,L,4] fp32;
         "value": that layer's slice of the projected value map [B,S,heads,hidden/heads], a view; "shapes", "lsi": the level shapes and
-        starts} -- tensors the forward already has, no extra launch."""
+        starts} -- tensors the forward already has, no extra launch.  return_hidden="self": "cross", and out["self_in"], the inputs of that
+        layer's self-attention block: {"t": the layer's input state, "qpos": its query position embedding, both
+        [B,nq,hidden] in the engine's dtype} -- again tensors the forward already has."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1251,14 +1278,16 @@ class DTLREngine:
         ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        if return_hidden not in (False, True, "all", "tail", "cross"):
-            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail', 'cross'")
+        if return_hidden not in (False, True, "all", "tail", "cross", "self"):
+            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail', 'cross', 'self'")
         every = isinstance(return_hidden, str)
         want_aux = want_aux or every
         tgt_all = [] if every else None
-        tail_in = [] if return_hidden in ("tail", "cross") else None
-        cross_in = {} if return_hidden == "cross" else None
-        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in, cross_in=cross_in)
+        tail_in = [] if return_hidden in ("tail", "cross", "self") else None
+        cross_in = {} if return_hidden in ("cross", "self") else None
+        self_in = {} if return_hidden == "self" else None
+        hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in, cross_in=cross_in,
+                                self_in=self_in)
         out = self.heads(hs, refs, ts, want_aux, bool(return_hidden))
         if every:
             out["hs_all"], out["tgt_all"], out["refs"] = list(hs), tgt_all, list(refs)
@@ -1266,6 +1295,8 @@ class DTLREngine:
             out["tail_in"] = tail_in[0]
         if cross_in is not None:
             out["cross_in"] = cross_in
+        if self_in is not None:
+            out["self_in"] = self_in
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

@@ -1861,3 +1861,5 @@ from .tailgrad import (TAIL_NAMES, box_mlp_dx, ffn_grad, ffn_recompute, head_dx,
                        tail_shapes)
 # the tenth header (include/dtlr_crossgrad.h), the same way: written in dtlr_amd/crossgrad.py (the last decoder layer's cross-attention gradient)
 from .crossgrad import CROSS_FLOATS, CROSS_NAMES, CROSS_SHAPES, cross_dow, cross_grad, cross_recompute, msda_query_grad          # noqa: E402,F401
+# the eleventh header (include/dtlr_selfgrad.h), the same way: written in dtlr_amd/selfgrad.py (the last decoder layer's self-attention gradient)
+from .selfgrad import SELF_FLOATS, SELF_NAMES, SELF_SHAPES, mha_grad, self_grad, self_recompute          # noqa: E402,F401
