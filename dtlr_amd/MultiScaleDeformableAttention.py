@@ -11,6 +11,7 @@ Same names, argument meaning and error behaviour as the reference wrapper
   * batch % min(batch, im2col_step) must be 0;
   * the result is a new tensor [N, Lq, M*D] enqueued on the current stream, no host sync.
 fp32 and fp64 as the reference dispatches (cu:64); bf16 value (fp32 loc/attn) is an extension.
+ms_deform_attn_backward returns the reference's triple for 8 heads x 32 channels, 4 levels, 4 points (fp32 / bf16 / fp16 value).
 """
 from __future__ import annotations
 
@@ -54,7 +55,39 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     return out
 
 
+def _geometry(value, spatial_shapes, sampling_loc):
+    """(M, D, L, P) as far as the arguments' shapes state them; None for what they do not"""
+    dim = lambda t, rank, i: int(t.shape[i]) if isinstance(t, torch.Tensor) and t.dim() == rank else None
+    return dim(value, 4, 2), dim(value, 4, 3), dim(spatial_shapes, 2, 0), dim(sampling_loc, 6, 4)
+
+
+@_lib.op
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
-    """The reference's backward kernels (cuh:301-921) are training-only and outside the inference
-    hot path."""
-    raise NotImplementedError("dtlr_amd is an inference engine: ms_deform_attn_backward is not provided")
+    """The reference's backward (ms_deform_attn.h:42-61, cu:83-156): -> (grad_value, grad_sampling_loc, grad_attn_weight) with the
+    shapes and dtypes of value, sampling_loc and attn_weight.  Provided for 8 heads x 32 channels, 4 levels, 4 points and an fp32 / bf16 /
+    fp16 value -- any other geometry, or an fp64 value, is NotImplementedError, stated before every other check.  For an fp32 value the
+    triple is ops.msda_value_grad and ops.msda_query_grad on the same arguments, bit for bit; for a 16-bit value (fp32 loc / attn: the
+    forward's extension) grad_value is rounded once to that dtype.  No atomics: reproducible run to run.  The
+    contract is ms_deform_attn_forward's: contiguous tensors on the GPU, batch % min(batch, im2col_step) == 0, the same messages."""
+    from .crossgrad import msda_query_grad
+    from .msdagrad import msda_value_grad, supported_geometry
+    M, D, L, P = _geometry(value, spatial_shapes, sampling_loc)
+    if None in (M, D, L, P) or not supported_geometry(M, D, L, P):
+        raise NotImplementedError(f"ms_deform_attn_backward is provided for 8 heads x 32 channels, 4 levels, 4 points; got {M} heads x {D} "
+                                  f"channels, {L} levels, {P} points")
+    if value.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"ms_deform_attn_backward is provided for an fp32 / bf16 / fp16 value; got {value.dtype}")
+    if not value.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")            # ms_deform_attn.h:60
+    for t, name in ((value, "value"), (spatial_shapes, "spatial_shapes"), (level_start_index, "level_start_index"),
+                    (sampling_loc, "sampling_loc"), (attn_weight, "attn_weight"), (grad_output, "grad_output")):
+        _assert(t.is_contiguous(), f"{name} tensor has to be contiguous")       # cu:93-98
+        _assert(t.is_cuda, f"{name} must be a CUDA tensor")                     # cu:100-105
+    N, S = int(value.shape[0]), int(value.shape[1])
+    step = min(N, int(im2col_step))
+    _assert(step > 0 and N % step == 0, f"batch({N}) must divide im2col_step({step})")   # cu:119
+    _assert(grad_output.dtype in (value.dtype, torch.float32), "grad_output dtype mismatch")
+    g = grad_output.float()                                                       # an fp32 gradient is passed as it is
+    grad_value = msda_value_grad(spatial_shapes, level_start_index, sampling_loc, attn_weight, g, S)
+    grad_loc, grad_attn = msda_query_grad(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, g)
+    return grad_value.to(value.dtype), grad_loc, grad_attn

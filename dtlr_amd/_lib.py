@@ -130,6 +130,9 @@ _CROSSGRAD_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, par
 # include/dtlr_selfgrad.h, the eleventh header (the last decoder layer's self-attention gradient, everything below it frozen): the same again
 _SELFGRAD_FUNCTIONS, _, SELFGRAD_CONSTANTS = _read_header_file("dtlr_selfgrad.h")
 _SELFGRAD_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _SELFGRAD_FUNCTIONS.items()}
+# include/dtlr_msdagrad.h, the twelfth header (the deformable attention's gradient with respect to value): the same again
+_MSDAGRAD_FUNCTIONS, _, MSDAGRAD_CONSTANTS = _read_header_file("dtlr_msdagrad.h")
+_MSDAGRAD_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _MSDAGRAD_FUNCTIONS.items()}
 globals().update(CONSTANTS)            # DTLR_OK, DTLR_EINVAL .. DTLR_ELAUNCH; the dtype codes DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S
 
 
@@ -147,7 +150,8 @@ def takes_stream(name: str) -> bool:
     """whether the entry point's last parameter is `void *stream` (it is then reached through launch())"""
     params = (_FUNCTIONS.get(name) or _LEXICON_FUNCTIONS.get(name) or _METRICS_FUNCTIONS.get(name) or _WORDBEAM_FUNCTIONS.get(name)
               or _LM_FUNCTIONS.get(name) or _PATTERN_FUNCTIONS.get(name) or _SETLOSS_FUNCTIONS.get(name) or _BOXGRAD_FUNCTIONS.get(name)
-              or _TAILGRAD_FUNCTIONS.get(name) or _CROSSGRAD_FUNCTIONS.get(name) or _SELFGRAD_FUNCTIONS[name])[1]
+              or _TAILGRAD_FUNCTIONS.get(name) or _CROSSGRAD_FUNCTIONS.get(name) or _SELFGRAD_FUNCTIONS.get(name)
+              or _MSDAGRAD_FUNCTIONS[name])[1]
     return bool(params) and params[-1] == (c_void_p, "stream")
 
 
@@ -159,7 +163,8 @@ def _load(path: str) -> ctypes.CDLL:
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_LEXICON_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items())
                               + list(_WORDBEAM_SIGNATURES.items()) + list(_LM_SIGNATURES.items()) + list(_PATTERN_SIGNATURES.items())
                               + list(_SETLOSS_SIGNATURES.items()) + list(_BOXGRAD_SIGNATURES.items()) + list(_TAILGRAD_SIGNATURES.items())
-                              + list(_CROSSGRAD_SIGNATURES.items()) + list(_SELFGRAD_SIGNATURES.items())):
+                              + list(_CROSSGRAD_SIGNATURES.items()) + list(_SELFGRAD_SIGNATURES.items())
+                              + list(_MSDAGRAD_SIGNATURES.items())):
         fn = getattr(L, name)          # AttributeError if the .so is stale -> loud
         fn.restype, fn.argtypes = res, args
     return L
@@ -222,7 +227,7 @@ def query(L, name: str, *args):
     return getattr(L, name)(*args)
 
 
-# What the bindings of the gradient headers (boxgrad.py, tailgrad.py, crossgrad.py, selfgrad.py) share: the dtype codes of their activations, the fp32 operand
+# What the bindings of the gradient headers (boxgrad.py, tailgrad.py, crossgrad.py, selfgrad.py, msdagrad.py) share: the dtype codes of their activations, the fp32 operand
 # check, and a workspace of whole 16-byte units (the entry points refuse a workspace that is not 16-byte aligned).
 DT = {torch.float32: CONSTANTS["DTLR_F32"], torch.bfloat16: CONSTANTS["DTLR_BF16"], torch.float16: CONSTANTS["DTLR_F16"]}
 

@@ -115,7 +115,8 @@ def new_class_head(model, num_classes: int, weight: Optional[torch.Tensor] = Non
 
 
 TRAINABLE = ("class", "box", "tail", "cross")        # the groups up to DESIGN.md section 23, in the flat buffer's order
-TRAINABLE_ALL = TRAINABLE + ("self",)                # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
+TRAINABLE_ALL = TRAINABLE + ("self",)                # the groups up to DESIGN.md section 24
+TRAINABLE_FULL = TRAINABLE_ALL + ("value",)          # what HeadTrainer(train=..) and --train may name, in the flat buffer's order
 
 
 @dataclass
@@ -147,13 +148,16 @@ def _model_params(model, name: str) -> List[torch.Tensor]:
     """group name -> the model's parameters in the flat order: the shared class head [W, b]; the shared box MLP [W0, b0, W1, b1, W2,
     b2]; the tail (ops.TAIL_NAMES): linear1, linear2 and norm3 of the last decoder layer, then transformer.decoder.norm; the cross block
     (ops.CROSS_NAMES): sampling_offsets, attention_weights and output_proj of the last decoder layer's cross_attn, then its norm1; the self
-    block (ops.SELF_NAMES): in_proj and out_proj of the last decoder layer's self_attn, then its norm2"""
+    block (ops.SELF_NAMES): in_proj and out_proj of the last decoder layer's self_attn, then its norm2; "value": the weight and bias of
+    the last decoder layer's cross_attn.value_proj"""
     if name == "class":
         return [model.class_embed[0].weight, model.class_embed[0].bias]
     if name == "box":
         return [p for l in model.bbox_embed[0].layers for p in (l.weight, l.bias)]
     dec = model.transformer.decoder
     last = dec.layers[len(dec.layers) - 1]
+    if name == "value":
+        return [last.cross_attn.value_proj.weight, last.cross_attn.value_proj.bias]
     if name == "self":
         a = last.self_attn
         return [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, last.norm2.weight, last.norm2.bias]
@@ -170,7 +174,8 @@ _GROUPS = {"class": (("head", "exp_avg", "exp_avg_sq"), lambda eng, v: eng.set_c
            "box": (("box_head", "box_exp_avg", "box_exp_avg_sq"), lambda eng, v: eng.set_box_head(v[0::2], v[1::2])),
            "tail": (("tail", "tail_exp_avg", "tail_exp_avg_sq"), lambda eng, v: eng.set_decoder_tail(v[0:2], v[2:4], v[4:6], v[6:8])),
            "cross": (("cross", "cross_exp_avg", "cross_exp_avg_sq"), lambda eng, v: eng.set_decoder_cross(v[0:2], v[2:4], v[4:6], v[6:8])),
-           "self": (("self", "self_exp_avg", "self_exp_avg_sq"), lambda eng, v: eng.set_decoder_self(v[0], v[1], v[2:4], v[4:6]))}
+           "self": (("self", "self_exp_avg", "self_exp_avg_sq"), lambda eng, v: eng.set_decoder_self(v[0], v[1], v[2:4], v[4:6])),
+           "value": (("value", "value_exp_avg", "value_exp_avg_sq"), lambda eng, v: eng.set_decoder_value(v))}
 
 
 def _cat(ts):
@@ -253,7 +258,15 @@ class HeadTrainer:
     block's chain starts from THIS recomputed state after norm2 and hands back the gradient at it (ops.cross_grad's return_ds), and the
     attention core's backward is ops.mha_grad.  The terms that land on the layer's input are dropped.  No cache / step_cached.
 
-    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", "cross", "self", in this order) to its ParamGroup: the model's
+    train may also name "value" (DESIGN.md section 25), with "self" (and so "cross" and "tail"): the weight and bias of the LAST decoder
+    layer's cross_attn.value_proj, 65,792 parameters -- with it every parameter of the last decoder layer is trained.  The flat buffer grows by
+    [value_proj.W | value_proj.b] at its end, under the same clip norm and AdamW launch.  Its inputs -- the decoder's memory and the flat
+    padding mask -- are the engine's (forward's return_hidden="value"); the layer's value map is recomputed in fp32 from the master
+    (memory Wv^T + bv, the rows under the mask zero), the cross block samples THAT map, hands back the gradient at the sampler's output
+    (ops.cross_grad's return_do), ops.msda_value_grad turns it into the gradient at the map, and the weight gradient is ops.head_grad of it
+    against memory.  The term that lands on memory is dropped.  No cache / step_cached.
+
+    How it is laid out.  `self.groups` maps each trained group ("class", "box", "tail", "cross", "self", "value", in this order) to its ParamGroup: the model's
     parameters in flat order, their shapes, the group's offset and length in the flat buffers (param, exp_avg, exp_avg_sq, grad), its
     state-dict keys and the engine setter it is handed to.  weight / bias / box_head() / tail() / cross() / self_block(), _engine(), the step's gradient slices,
     state_dict / load_state_dict and write_back read that table and nothing else knows an offset.  There is ONE step routine, `_update`,
@@ -266,8 +279,8 @@ class HeadTrainer:
                  max_norm: Optional[float] = 0.01, loss: str = "ctc", CTC_loss_coef: float = 1.0, cls_loss_coef: float = 1.0,
                  train: Sequence[str] = ("class",), aux_loss: bool = False, bbox_loss_coef: float = 5.0, giou_loss_coef: float = 2.0):
         train = (train,) if isinstance(train, str) else tuple(train)
-        if not train or set(train) - set(TRAINABLE_ALL):
-            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of {TRAINABLE_ALL!r}")
+        if not train or set(train) - set(TRAINABLE_FULL):
+            raise ValueError(f"HeadTrainer: train {train!r} is not a non-empty subset of {TRAINABLE_FULL!r}")
         if loss not in ("ctc", "set", "ctc+set"):
             raise ValueError(f"HeadTrainer: loss {loss!r} is not one of ctc, set, ctc+set")
         if "box" in train and loss == "ctc":
@@ -280,10 +293,13 @@ class HeadTrainer:
         if "self" in train and "cross" not in train:
             raise ValueError("HeadTrainer(train=('self', ..)): 'self' requires 'cross' -- the gradient of the self-attention block passes "
                              "through the cross-attention block and the tail either way")
+        if "value" in train and "self" not in train:
+            raise ValueError("HeadTrainer(train=('value', ..)): 'value' requires 'self' -- the gradient of the value projection passes through "
+                             "the cross-attention block, which then starts from the recomputed state of the self-attention block")
         if "box" in train and (getattr(model.cfg, "use_detached_boxes_dec_out", False) or not model.dec_pred_bbox_embed_share):
             raise NotImplementedError("HeadTrainer(train=('box', ..)): written for the shared box head with look-forward-twice "
                                       "(dec_pred_bbox_embed_share, use_detached_boxes_dec_out = False: every shipped config)")
-        self.train = tuple(k for k in TRAINABLE_ALL if k in train)
+        self.train = tuple(k for k in TRAINABLE_FULL if k in train)
         self.aux_loss = bool(aux_loss)
         self.bbox_loss_coef, self.giou_loss_coef = float(bbox_loss_coef), float(giou_loss_coef)
         self.every_output = "box" in self.train or "tail" in self.train or self.aux_loss          # the step reads every decoder layer's states
@@ -336,6 +352,12 @@ class HeadTrainer:
             if geometry != (8, 256):
                 raise NotImplementedError(f"HeadTrainer(train=('self', ..)): written for nheads 8 x 32 channels (hidden_dim 256: every shipped config), "
                                           f"not nheads, hidden_dim = {geometry}")
+        if "value" in self.train:
+            layers = model.transformer.decoder.layers
+            last = layers[len(layers) - 1]
+            if any(o.cross_attn is last.cross_attn or o.cross_attn.value_proj.weight is last.cross_attn.value_proj.weight for o in list(layers)[:-1]):
+                raise NotImplementedError("HeadTrainer(train=('value', ..)): the decoder layers share parameters -- the last layer's value projection "
+                                          "is then not the block alone")
         # the ONE table of what is trained: every slice of param / exp_avg / exp_avg_sq / grad below is a lookup in it
         self.groups: Dict[str, ParamGroup] = {}
         n = 0
@@ -351,9 +373,11 @@ class HeadTrainer:
                                           "output_proj [256,256], norm1 [256]")
             if name == "self" and (tuple(g.shapes) != ops.SELF_SHAPES or self.D != 256):
                 raise NotImplementedError("HeadTrainer(train=('self', ..)): the block is not in_proj [768,256], out_proj [256,256], norm2 [256]")
+            if name == "value" and (g.shapes != [(256, 256), (256,)] or self.D != 256):
+                raise NotImplementedError("HeadTrainer(train=('value', ..)): the block is not value_proj [256,256] with its bias [256]")
             self.groups[name] = g
             n += g.n
-        self.n_class, self.n_box, self.n_tail, self.n_cross, self.n_self = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE_ALL)
+        self.n_class, self.n_box, self.n_tail, self.n_cross, self.n_self, self.n_value = (self.groups[k].n if k in self.groups else 0 for k in TRAINABLE_FULL)
         dev = head.weight.device
         self.param = torch.cat([p.detach().float().reshape(-1) for g in self.groups.values() for p in g.params]).to(dev).contiguous()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -396,6 +420,10 @@ class HeadTrainer:
         (train includes "self")"""
         return self._views("self", "HeadTrainer: the self-attention block is not trained (train lacks 'self')")
 
+    def value_proj(self) -> List[torch.Tensor]:
+        """the master value projection as views of the flat buffer: [value_proj.W, value_proj.b] (train includes "value")"""
+        return self._views("value", "HeadTrainer: the value projection is not trained (train lacks 'value')")
+
     def _box_weights(self) -> List[torch.Tensor]:
         """the box MLP the forward runs: the master when it is trained, else the model's"""
         return self.box_head() if self.n_box else [p.detach().float() for p in _model_params(self.model, "box")]
@@ -425,7 +453,7 @@ class HeadTrainer:
         """One training step through the full forward (engine.train_one_epoch_CTC's loop body, engine.py:190-216)."""
         self._engine()
         if self.every_output:
-            out = self.model(samples, per_line=per_line, return_hidden="self" if self.n_self else "cross" if self.n_cross else "tail" if self.n_tail else "all")
+            out = self.model(samples, per_line=per_line, return_hidden="value" if self.n_value else "self" if self.n_self else "cross" if self.n_cross else "tail" if self.n_tail else "all")
         else:                                                               # the class head on the main output: the last state is all the step reads
             o = self.model(samples, per_line=per_line, return_hidden=True)
             out = self._main_output(o["hs"], o["pred_logits"], o["pred_boxes"])
@@ -450,6 +478,8 @@ class HeadTrainer:
         return {"hs_all": [hs], "tgt_all": [None], "refs": [ref], "aux_outputs": [], "pred_logits": logits, "pred_boxes": boxes, **more}
 
     def _no_cache(self, what):
+        if "value" in self.train:
+            raise ValueError(f"HeadTrainer.{what}: the value projection reads the decoder's memory, which the cache does not hold -- use step()")
         if "self" in self.train:
             raise ValueError(f"HeadTrainer.{what}: the self-attention block reads the layer's input state and runs the whole last layer, which the "
                              "cache does not hold -- use step()")
@@ -486,6 +516,8 @@ class HeadTrainer:
             self.last_states["cross_in"] = out["cross_in"]
         if self.n_self:
             self.last_states["self_in"] = out["self_in"]
+        if self.n_value:
+            self.last_states["value_in"] = out["value_in"]
         match = r = None
         if self.loss == "ctc":                                                  # the CTC loss reaches the tail through dlogits alone
             result = {}
@@ -541,13 +573,32 @@ class HeadTrainer:
                     si = out["self_in"]
                     rec_s = ops.self_recompute(si["t"], si["qpos"], self.self_block())
                     s, qpos = rec_s["s"].view(B, nq, self.D), qpos.float()
+                if self.n_value:
+                    # the layer's value map in fp32 from the master, the rows under the padding mask zero as the forward fills them: the
+                    # cross block samples THIS map, not the engine's slice
+                    vi = out["value_in"]
+                    Wv, bv = self.value_proj()
+                    mem = vi["memory"].reshape(-1, self.D).float()
+                    Vf = ops.head_dx(mem, Wv.t().contiguous()).add_(bv)
+                    if vi["mask"] is not None:
+                        Vf.masked_fill_(vi["mask"].reshape(-1, 1), 0.0)
+                    ci = dict(ci, value=Vf.view(B, -1, 8, self.D // 8))
                 rec = ops.cross_recompute(s, qpos, ci["ref_in"], ci["value"], ci["shapes"], ci["lsi"], self.cross())
                 _, grad_u = ops.tail_grad(rec["u"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad), return_du=True)
                 if rec_s is None:
                     ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad))
-                else:
+                elif not self.n_value:
                     _, grad_s = ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad), return_ds=True)
                     ops.self_grad(si, rec_s, grad_s, self.self_block(), out=self.groups["self"].of(self.grad))
+                else:
+                    _, grad_s, grad_o = ops.cross_grad(ci, rec, grad_u, self.cross(), out=self.groups["cross"].of(self.grad), return_ds=True,
+                                                       return_do=True)
+                    ops.self_grad(si, rec_s, grad_s, self.self_block(), out=self.groups["self"].of(self.grad))
+                    dV = ops.msda_value_grad(ci["shapes"], ci["lsi"], rec["loc"], rec["A"], grad_o.view(B, nq, self.D), int(Vf.shape[0]) // B)
+                    dV = dV.view(-1, self.D)
+                    if vi["mask"] is not None:
+                        dV.masked_fill_(vi["mask"].reshape(-1, 1), 0.0)
+                    ops.head_grad(dV, mem, out=self.groups["value"].of(self.grad))         # [dWv | dbv]: value_proj as a head of 256 "classes"
             else:
                 ops.tail_grad(out["tail_in"], t_below, dh, self.tail(), out=self.groups["tail"].of(self.grad))
         clip = self.max_norm > 0
@@ -565,7 +616,8 @@ class HeadTrainer:
         "tail_exp_avg_sq": the same of the box head [W0 | b0 | W1 | b1 | W2 | b2] and of the tail [W1 | b1 | W2 | b2 | norm3.w | norm3.b |
         dec_norm.w | dec_norm.b], present when they are trained; "cross" / "cross_exp_avg" / "cross_exp_avg_sq": likewise the cross-attention
         block [so.W | so.b | aw.W | aw.b | out.W | out.b | norm1.w | norm1.b]; "self" / "self_exp_avg" / "self_exp_avg_sq": the self-attention
-        block [in_proj.W | in_proj.b | out_proj.W | out_proj.b | norm2.w | norm2.b]."""
+        block [in_proj.W | in_proj.b | out_proj.W | out_proj.b | norm2.w | norm2.b]; "value" / "value_exp_avg" / "value_exp_avg_sq": the last
+        decoder layer's value projection [value_proj.W | value_proj.b]."""
         t = {key: g.of(flat).detach().cpu().clone() for g in self.groups.values() for key, flat in zip(g.keys, (self.param, self.exp_avg, self.exp_avg_sq))}
         if not self.n_class:
             t.update(head=torch.cat([self.weight.reshape(-1), self.bias.reshape(-1)]).detach().float().cpu().clone(),
@@ -643,7 +695,8 @@ def build_parser() -> argparse.ArgumentParser:
                                                      "--loss set or ctc+set and the full forward every step), tail (the last decoder "
                                                      "layer's FFN and norm3 and decoder.norm; any loss), cross (that layer's cross-attention "
                                                      "and norm1; needs tail and the full forward every step), self (that layer's "
-                                                     "self-attention and norm2; needs cross), e.g. class,box,tail,cross,self")
+                                                     "self-attention and norm2; needs cross), value (that layer's cross_attn.value_proj; "
+                                                     "needs self), e.g. class,box,tail,cross,self,value")
     ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
@@ -703,8 +756,12 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     ap = build_parser()
     args = ap.parse_args(argv)
     train = tuple(k.strip() for k in args.train.split(",") if k.strip())
-    if not train or set(train) - set(TRAINABLE_ALL):
-        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail, cross, self")
+    if not train or set(train) - set(TRAINABLE_FULL):
+        ap.error(f"--train {args.train}: a comma-separated subset of class, box, tail, cross, self, value")
+    if "value" in train and "self" not in train:
+        ap.error("--train value needs self: the gradient of the value projection passes through the cross-attention block either way")
+    if "value" in train and args.cache_features:
+        ap.error("--cache-features cannot train the value projection: it reads the decoder's memory")
     if "self" in train and "cross" not in train:
         ap.error("--train self needs cross: the gradient of the self-attention block passes through the cross-attention block either way")
     if "self" in train and args.cache_features:

@@ -49,7 +49,7 @@ def msda_query_grad(value, spatial_shapes, level_start_index, sampling_loc, attn
     """dtlr_msda_query_grad: outputs 2 and 3 of the deformable attention's backward -- (grad_sampling_loc [N,Lq,8,4,4,2], grad_attn_weight
     [N,Lq,8,4,4]) fp32 -- from value [N,S,8,32] (fp32 / bf16 / fp16), sampling_loc, attn_weight (fp32) and grad_output [N,Lq,256] fp32,
     the gradient at the operator's output.  The arguments are checked as ms_deform_attn_forward checks them; any shape but 8 heads x 32
-    channels, 4 levels, 4 points raises DTLRError.  The gradient with respect to `value` is not provided (a scatter: DESIGN.md section 23).
+    channels, 4 levels, 4 points raises DTLRError.  The gradient with respect to `value` is ops.msda_value_grad.
     Reproducible run to run."""
     if not value.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
@@ -135,12 +135,14 @@ def cross_dow(A, dA, dloc, ref_in):
 
 
 def cross_grad(cross_in: Dict, rec: Dict[str, torch.Tensor], du, cross: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
-               return_ds: bool = False):
+               return_ds: bool = False, return_do: bool = False):
     """The chain of DESIGN.md section 23 below norm1's output.  cross_in: forward(return_hidden="cross")'s out["cross_in"]; rec:
     cross_recompute's result on it; du [M,256] fp32: the gradient at u (the tail's dy + da W1); cross: the eight fp32 masters ->
     the flat gradient [CROSS_FLOATS] fp32 in CROSS_NAMES' order (out: a buffer to fill).  The terms that land on s, qpos, ref_in and the
     value map are dropped: they are frozen.  return_ds: -> (the gradient, ds [M,256] fp32 = dx1 + doff Wso + dlogit Waw, the gradient at s:
-    what the block below starts from); without it the launches and the bits are as they were."""
+    what the block below starts from); without it the launches and the bits are as they were.  return_do: the
+    result is followed by do [M,256] fp32 = dx1 Wo, the gradient at the sampler's output -- what ops.msda_value_grad starts from (DESIGN.md
+    section 25); the chain forms it either way, so this adds no launch.  cross_in["value"] must be the map rec was recomputed from."""
     from . import ops
     wso, _, waw, _, wo, _, g1, _ = cross
     if out is None:
@@ -157,7 +159,7 @@ def cross_grad(cross_in: Dict, rec: Dict[str, torch.Tensor], du, cross: Sequence
     ops.head_grad(doff, rec["qin"], out=out[:n_so])                             # [dW | db] of sampling_offsets ..
     ops.head_grad(dlogit, rec["qin"], out=out[n_so:n_so + n_aw])                # .. and of attention_weights: the flat order keeps them apart
     if not return_ds:
-        return out
+        return (out, g) if return_do else out
     ds = head_dx(doff, wso)                                                     # s reaches x1 directly and through qin = s + p
     head_dx(dlogit, waw, out=ds, accumulate=True)
-    return out, ds.add_(dx1)
+    return (out, ds.add_(dx1), g) if return_do else (out, ds.add_(dx1))

@@ -314,7 +314,8 @@ class DINO(nn.Module):
         per_line: every line gets the result it would get alone (DTLREngine.forward); the reference's padded-batch semantics otherwise.
         return_hidden: add out["hs"], the decoder states the class head multiplies; "all": also hs_all, tgt_all and refs of every decoder
         layer, with the auxiliary outputs; "tail": "all" and tail_in, the last decoder layer's FFN input; "cross": "tail" and cross_in, the inputs of that layer's
-        cross-attention block; "self": "cross" and self_in, the inputs of that layer's self-attention block (DTLREngine.forward)."""
+        cross-attention block; "self": "cross" and self_in, the inputs of that layer's self-attention block; "value": "self" and value_in, the
+        decoder's memory and its flat padding mask (DTLREngine.forward)."""
         if targets is not None:
             raise NotImplementedError("dtlr_amd.DINO is inference-only: targets must be None")
         if self.training:

@@ -355,9 +355,11 @@ class DTLREngine:
             self._put_linear(q + "sa.out", sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"])
             self._put_linear(q + "ff1", sd[p + "linear1.weight"], sd[p + "linear1.bias"])
             self._put_linear(q + "ff2", sd[p + "linear2.weight"], sd[p + "linear2.bias"])
-        self._put_linear("dec.value_all",
-                         torch.cat([sd[f"{t}decoder.layers.{n}.cross_attn.value_proj.weight"] for n in range(cfg.dec_layers)], 0),
-                         torch.cat([sd[f"{t}decoder.layers.{n}.cross_attn.value_proj.bias"] for n in range(cfg.dec_layers)], 0))
+        # the fp32 rows of all layers' value projections stay on the device (1.5 MB at six layers): set_decoder_value replaces one layer's
+        # rows and packs `dec.value_all` again from them, as this line does
+        self._value_all_f32 = tuple(torch.cat([sd[f"{t}decoder.layers.{n}.cross_attn.value_proj.{k}"] for n in range(cfg.dec_layers)], 0)
+                                    .to(device=self.device, dtype=f32).contiguous() for k in ("weight", "bias"))
+        self._put_linear("dec.value_all", *self._value_all_f32)
         norm_pack("dec.norm", t + "decoder.norm")
         for i in range(2):
             self._put_linear(f"dec.rph{i}", sd[f"{t}decoder.ref_point_head.layers.{i}.weight"], sd[f"{t}decoder.ref_point_head.layers.{i}.bias"])
@@ -554,6 +556,25 @@ class DTLREngine:
         self._put_linear(q + "sa.out", out_proj[0].detach().clone(), out_proj[1].detach().clone())
         self._put(q + "norm2.w", norm2[0].detach().clone(), torch.float32)
         self._put(q + "norm2.b", norm2[1].detach().clone(), torch.float32)
+
+    @torch.no_grad()
+    def set_decoder_value(self, value_proj) -> None:
+        """Replace the LAST decoder layer's cross_attn.value_proj, a (weight [d,d], bias [d]) pair, in the packed model without re-packing
+        anything else: set_decoder_self's counterpart (DESIGN.md section 25).  The engine projects memory through all layers' value
+        projections at once (`dec.value_all`, [layers x d, d]): rows (L-1) d .. L d of its fp32 rows are replaced, `dec.value_all` is packed
+        again from them as the constructor packs it, and only the images derived from it (`k256_slices`, `k256s_slices`, and the split
+        engine's kept fp32 source) are dropped, to be rebuilt by the next forward.  A forward after this equals, bit for bit, the forward of
+        a fresh engine built from the updated state dict.  Replacing rows of the packed weight in place would not be enough: a 16-bit
+        engine holds rounded rows only, the split engine releases its fp32 source once the `k256s_slices` image is built, and a `k256_slices`
+        image spans 384 rows, one and a half layers -- hence the fp32 rows the constructor keeps."""
+        d, L = self.cfg.hidden_dim, self.cfg.dec_layers
+        if len(value_proj) != 2 or tuple(value_proj[0].shape) != (d, d) or tuple(value_proj[1].shape) != (d,):
+            raise ValueError(f"set_decoder_value: not value_proj [{d},{d}] with its bias [{d}]")
+        W, b = self._value_all_f32
+        W[(L - 1) * d:L * d].copy_(value_proj[0].detach())                     # copies: the engine never aliases the caller's buffers
+        b[(L - 1) * d:L * d].copy_(value_proj[1].detach())
+        self._drop_images("dec.value_all")                                    # before the put: a split engine's kept fp32 source is a (kind, name) entry too
+        self._put_linear("dec.value_all", W.clone(), b.clone())
 
     @torch.no_grad()
     def tail_forward(self, tail_in, ref_last) -> Dict[str, torch.Tensor]:
@@ -1223,7 +1244,10 @@ class DTLREngine:
         "value": that layer's slice of the projected value map [B,S,heads,hidden/heads], a view; "shapes", "lsi": the level shapes and
         starts} -- tensors the forward already has, no extra launch.  return_hidden="self": "cross", and out["self_in"], the inputs of that
         layer's self-attention block: {"t": the layer's input state, "qpos": its query position embedding, both
-        [B,nq,hidden] in the engine's dtype} -- again tensors the forward already has."""
+        [B,nq,hidden] in the engine's dtype} -- again tensors the forward already has.  return_hidden="value": "self", and out["value_in"],
+        the inputs of the decoder's value projections: {"memory": the encoder's output [B,S,hidden] in the engine's
+        dtype, "mask": the flat padding mask [B,S] bool (True = padding: those rows of the value map are zero), or None for an unpadded
+        batch} -- tensors the forward already has."""
         ops.require_cuda(x, "images")
         cfg = self.cfg
         B = x.shape[0]
@@ -1278,14 +1302,14 @@ class DTLREngine:
         ts = self.two_stage(memory, g, forced_topk, per_line)
         if vall is not None:
             cur.wait_stream(side)
-        if return_hidden not in (False, True, "all", "tail", "cross", "self"):
-            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail', 'cross', 'self'")
+        if return_hidden not in (False, True, "all", "tail", "cross", "self", "value"):
+            raise ValueError(f"return_hidden {return_hidden!r} is not one of False, True, 'all', 'tail', 'cross', 'self', 'value'")
         every = isinstance(return_hidden, str)
         want_aux = want_aux or every
         tgt_all = [] if every else None
-        tail_in = [] if return_hidden in ("tail", "cross", "self") else None
-        cross_in = {} if return_hidden in ("cross", "self") else None
-        self_in = {} if return_hidden == "self" else None
+        tail_in = [] if return_hidden in ("tail", "cross", "self", "value") else None
+        cross_in = {} if return_hidden in ("cross", "self", "value") else None
+        self_in = {} if return_hidden in ("self", "value") else None
         hs, refs = self.decoder(memory, ts, g, want_aux, vall=vall, per_line=per_line, tgt_all=tgt_all, tail_in=tail_in, cross_in=cross_in,
                                 self_in=self_in)
         out = self.heads(hs, refs, ts, want_aux, bool(return_hidden))
@@ -1297,6 +1321,8 @@ class DTLREngine:
             out["cross_in"] = cross_in
         if self_in is not None:
             out["self_in"] = self_in
+        if return_hidden == "value":
+            out["value_in"] = {"memory": memory, "mask": g["mask_flat"] if g["has_padding"] else None}
         if return_debug:
             out["_debug"] = dict(memory=memory, topk_idx=ts["topk_idx"], topk_scores=ts["topk_scores"], src=src,
                                  feats=feats, geometry=g)

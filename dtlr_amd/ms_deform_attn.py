@@ -1,7 +1,9 @@
 """Operator-level API of the reference, backed by the HIP kernel:
   MSDeformAttnFunction  <- models/dino/ops/functions/ms_deform_attn_func.py:21-38
   MSDeformAttn          <- models/dino/ops/modules/ms_deform_attn.py:30-126
-Same constructor/forward signatures and state-dict keys; inference only (backward raises)."""
+Same constructor/forward signatures and state-dict keys.  MSDeformAttnFunction is differentiable for 8 heads x 32 channels, 4 levels,
+4 points (MultiScaleDeformableAttention.ms_deform_attn_backward); the MSDeformAttn module stays inference only (its forward runs under
+no_grad: the projections are ops.linear)."""
 from __future__ import annotations
 
 import math
@@ -10,6 +12,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import MultiScaleDeformableAttention as MSDA
 from . import ops
@@ -19,12 +22,19 @@ class MSDeformAttnFunction(Function):
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights, im2col_step):
         ctx.im2col_step = im2col_step
-        return MSDA.ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
-                                           sampling_locations, attention_weights, ctx.im2col_step)
+        output = MSDA.ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
+                                             sampling_locations, attention_weights, ctx.im2col_step)
+        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights)
+        return output
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_output):
-        return MSDA.ms_deform_attn_backward(None, None, None, None, None, grad_output, ctx.im2col_step)
+        value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights = ctx.saved_tensors
+        grad_value, grad_sampling_loc, grad_attn_weight = MSDA.ms_deform_attn_backward(
+            value, value_spatial_shapes, value_level_start_index, sampling_locations, attention_weights, grad_output.contiguous(),
+            ctx.im2col_step)
+        return grad_value, None, None, grad_sampling_loc, grad_attn_weight, None
 
 
 class MSDeformAttn(nn.Module):

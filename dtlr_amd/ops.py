@@ -1863,3 +1863,5 @@ from .tailgrad import (TAIL_NAMES, box_mlp_dx, ffn_grad, ffn_recompute, head_dx,
 from .crossgrad import CROSS_FLOATS, CROSS_NAMES, CROSS_SHAPES, cross_dow, cross_grad, cross_recompute, msda_query_grad          # noqa: E402,F401
 # the eleventh header (include/dtlr_selfgrad.h), the same way: written in dtlr_amd/selfgrad.py (the last decoder layer's self-attention gradient)
 from .selfgrad import SELF_FLOATS, SELF_NAMES, SELF_SHAPES, mha_grad, self_grad, self_recompute          # noqa: E402,F401
+# the twelfth header (include/dtlr_msdagrad.h), the same way: written in dtlr_amd/msdagrad.py (the deformable attention's gradient with respect to value)
+from .msdagrad import VGRAD_SEGMENTS, VGRAD_TILE, msda_value_grad          # noqa: E402,F401

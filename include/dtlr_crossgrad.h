@@ -40,7 +40,7 @@ extern "C" {
  *     grad_loc [.., l, p, 1] = attn H_l <g, (1 - lx)(v10 - v00) + lx (v11 - v01)>
  *   a point with px <= -1, py <= -1, px >= W_l or py >= H_l (or a NaN coordinate) gives exact zeros.  g: the head's 32 channels of
  *   grad_out.  The 32-channel dot products are summed over a head's adjacent lanes by a butterfly of fixed order.  The gradient with
- *   respect to `value` is a scatter and is not provided.  loc, attn, grad_out, grad_loc, grad_attn: 16-byte aligned.
+ *   respect to `value` is dtlr_msda_value_grad of dtlr_msdagrad.h.  loc, attn, grad_out, grad_loc, grad_attn: 16-byte aligned.
  *
  * dtlr_cross_recompute: the block's forward in fp32 from the masters.  s, p [M,256] (x_dtype: DTLR_F32 or the 16-bit format, cast up
  *   on load), M = N Lq ; R [M,4,4] fp32 (reference_points_input) ; Wow [384,256] / bow [384]: [sampling_offsets ; attention_weights] ;
