@@ -21,6 +21,7 @@
 // C row stride ldc >= N (column slices of a wider matrix: the six decoder value projections share one [T, 1536] buffer).
 // HBM-bound by construction: per CU and 64-token tile 64..80 KB of traffic against 64..96 MFMAs per wave.
 #include "gfx950_prims.h"
+#include "../../include/dtlr_k256multi.h"
 
 namespace dtlr {
 
@@ -408,6 +409,292 @@ __global__ __launch_bounds__(512, 2) void gemm_k256_vow_kernel(
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// All decoder layers' value projections of `memory` in ONE launch:   C[m, 0:N] = A[m, :] W^T + bias,   N = 256 L (L = decoder layers).
+// As launches of gemm_k256_kernel<3, false> over 384-channel slices, `memory` is read once per slice and every wave writes 96-byte
+// pieces of the rows.  Here the N channels are cut into COLUMN GROUPS of NRT x 128 channels (NRT <= 5: the 160 resident VGPRs of
+// gemm_k256_vow_kernel), blockIdx.y = group, and the tile loop is gemm_k256_vow_kernel's: a three-stage token ring, a 64-token tile
+// walked in four 16-token groups, each finished and stored before the next starts.
+//   * groups: units of 128 channels spread as evenly as they go over ceil(N / 640) groups (k256_multi_plan): L = 6 gives 3 x 512, so
+//     the three workgroups of a token tile do the same work, and a wave owns 64 channels = ONE 128-byte line of every token, written by
+//     two back-to-back 16-byte-per-lane stores.  Uneven splits (L = 7: 640 + 640 + 512) run the NRT - 1 body in their last groups.
+//   * placement: gridDim.x is a multiple of 8 and gridDim.x * gridDim.y <= CUs, so the workgroups (x, 0 .. groups - 1) are all resident,
+//     sit on XCD x % 8 and walk the same run of token tiles at the same pace: the tile comes from HBM once and from that XCD's L2 after.
+//   * bit-identical to the slice launches: zero accumulator, k-steps 0..7 on the same MFMA with the weight as the A operand, + bias,
+//     one rounding; rows with row_mask[m] != 0 written as zeros.
+// vmcnt by hand: E stores per wave and tile, 4 DMA instructions per token tile.  A ragged tile (fewer stores) is a workgroup's last.
+constexpr int KM_NS = 3;
+constexpr int KM_LDS = KM_NS * K2_STAGE;                    // 96 KB
+constexpr int KM_MAX_NRT = DTLR_K256_MULTI_MAX_UNITS;
+
+template <int NRT, bool MASK>
+__device__ __forceinline__ void k256_multi_body(
+    const uint16_t* __restrict__ A, const uint16_t* __restrict__ Wp, const float* __restrict__ bias, const uint8_t* __restrict__ row_mask,
+    uint16_t* __restrict__ C, int ldc, int M, int tiles_per_wg)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char k2_smem[];
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)k2_smem;
+    constexpr int E = 4 * (NRT / 2 + (NRT & 1));             // stores per wave and tile
+    static_assert(2 * E + 4 < 64, "vmcnt is a 6-bit counter");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = lane & 15, g = lane >> 4;
+    const int ntiles = (M + K2_TOK - 1) / K2_TOK;
+    // workgroup (x, y) runs on XCD x % 8 (gridDim.x % 8 == 0); logical ids are contiguous inside an XCD
+    const int q8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7;
+    const int logical = xcd * q8 + ((int)blockIdx.x >> 3);
+    const int t_begin = logical * tiles_per_wg;
+    const int t_end = min(t_begin + tiles_per_wg, ntiles);
+    if (t_begin >= t_end) return;
+    const int nt = t_end - t_begin;
+
+    const int dr = lane >> 3, dc = (lane & 7) ^ dr;           // row within a DMA block; SOURCE chunk that lands in slot (lane & 7)
+    auto issue = [&](int t, int slot) {                       // token tile: this wave's blocks j = 4 wave + u (as in gemm_k256_kernel)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
+            const long tok = min((long)t * K2_TOK + tt8 * 8 + dr, (long)M - 1);
+            glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * K2_STAGE + j * 1024));
+        }
+    };
+    issue(t_begin, 0);
+    if (nt > 1) issue(t_begin + 1, 1);
+    uint4 wf[NRT][8];
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) wf[rt][ks] = load16(Wp + ((long)((wave * NRT + rt) * 8 + ks) * 64 + lane) * 8);
+    float4 bv[NRT];
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+        bv[rt] = bias ? *reinterpret_cast<const float4*>(bias + (wave * NRT + rt) * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    wait_vm<0>();
+    // the compiler's own wait for the bias loads belongs HERE, not at their first use inside the ring loop
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) asm volatile("" : "+v"(bv[rt].x), "+v"(bv[rt].y), "+v"(bv[rt].z), "+v"(bv[rt].w));
+
+    const unsigned rd0 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + ((g ^ (n & 7)) * 16));
+    const unsigned rd1 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + (((4 + g) ^ (n & 7)) * 16));
+
+    int slot = 0;
+    for (int i = 0; i < nt; ++i) {
+        const int t = t_begin + i;
+        __builtin_amdgcn_s_barrier();                         // tile i published; stage (i + 2) % 3 no longer read
+        const bool more = i + 2 < nt;
+        const long trow = (long)t * K2_TOK;
+        unsigned msk[4] = {0, 0, 0, 0};
+        if constexpr (MASK) {                                 // older than the DMA group below: waited for with vmcnt(4)
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) msk[tt] = k2_load_u8(row_mask + min(trow + tt * 16 + n, (long)M - 1));
+        }
+        if (more) issue(t + 2, slot == 0 ? 2 : slot - 1);
+        const unsigned char* sb = k2_smem + slot * K2_STAGE;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            f32x4_t acc[NRT];
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) acc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const uint4 bf = *reinterpret_cast<const uint4*>(sb + ((ks & 1) ? rd1 : rd0) + tt * 8192 + (ks >> 1) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < NRT; ++rt) acc[rt] = mma16(wf[rt][ks], bf, acc[rt]);
+            }
+            if constexpr (MASK) {
+                if (tt == 0) {
+                    if (more) wait_vm<4>(); else wait_vm<0>();
+                    asm volatile("" : "+v"(msk[0]), "+v"(msk[1]), "+v"(msk[2]), "+v"(msk[3]));      // read only after the wait
+                }
+            }
+            const long tok = trow + tt * 16 + n;
+            const bool live = tok < M;
+            const bool zero = MASK && msk[tt] != 0;
+            // ---- + bias, padding rows, round, paired 16-byte stores (gemm_k256_kernel's !RES epilogue) ------------------------------
+            uint32_t pk_lo = 0, pk_hi = 0;
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+                float v[4] = {acc[rt][0] + bv[rt].x, acc[rt][1] + bv[rt].y, acc[rt][2] + bv[rt].z, acc[rt][3] + bv[rt].w};
+                if (zero) { v[0] = v[1] = v[2] = v[3] = 0.f; }
+                const uint32_t lo = pack_bf16x2(v[0], v[1]), hi = pack_bf16x2(v[2], v[3]);
+                if ((rt & 1) == 0 && rt + 1 < NRT) { pk_lo = lo; pk_hi = hi; }
+                else if (rt & 1) {
+                    // pair the row tiles (rt - 1, rt): exchange halves between lane rows g and g ^ 1 -> a lane owns 8 consecutive channels
+                    const auto s0 = __builtin_amdgcn_permlane16_swap(pk_lo, lo, false, false);
+                    const auto s1 = __builtin_amdgcn_permlane16_swap(pk_hi, hi, false, false);
+                    uint16_t* dst = C + tok * (long)ldc + (wave * NRT + rt - 1 + (g & 1)) * 16 + 8 * (g >> 1);
+                    if (live) *reinterpret_cast<uint4*>(dst) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                } else {                                      // odd NRT: the last row tile alone, 8-byte stores
+                    uint16_t* dst = C + tok * (long)ldc + (wave * NRT + rt) * 16 + 4 * g;
+                    if (live) *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+                }
+            }
+        }
+        // my pieces of tile i + 1 must have landed before the next barrier.  Issued after them: tile i - 1's stores, this iteration's
+        // DMA group (if any), this tile's stores (and, MASK, this tile's flags: waited for above, with everything older).
+        if (more) wait_vm<2 * E + 4>();
+        else if (i + 1 < nt) wait_vm<2 * E>();
+        slot = slot == 2 ? 0 : slot + 1;
+    }
+}
+
+// blockIdx.y = column group: the first n_hi groups hold NRT_HI units of 128 channels, the others NRT_HI - 1; the images and the columns
+// of the groups follow each other in that order (dtlr_k256_multi_pack_weights).
+template <int NRT_HI, bool MASK>
+__global__ __launch_bounds__(512, 2) void gemm_k256_multi_kernel(
+    const uint16_t* __restrict__ A, const uint16_t* __restrict__ Wp, const float* __restrict__ bias, const uint8_t* __restrict__ row_mask,
+    uint16_t* __restrict__ C, int ldc, int M, int tiles_per_wg, int n_hi)
+{
+    const int gi = (int)blockIdx.y;
+    const int col0 = 128 * (gi < n_hi ? gi * NRT_HI : n_hi * NRT_HI + (gi - n_hi) * (NRT_HI - 1));
+    Wp += (long)col0 * 256;
+    C += col0;
+    if (bias) bias += col0;
+    if constexpr (NRT_HI == KM_MAX_NRT) {                     // the only width an even number of units splits unevenly at
+        if (gi >= n_hi) { k256_multi_body<NRT_HI - 1, MASK>(A, Wp, bias, row_mask, C, ldc, M, tiles_per_wg); return; }
+    }
+    k256_multi_body<NRT_HI, MASK>(A, Wp, bias, row_mask, C, ldc, M, tiles_per_wg);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The weight-resident body with TWO token streams:   C[M, 384] = (A + A2)[M, 256] . W^T + bias      ([offsets | logits] of tgt + query_pos
+// in the decoder, of src + pos in a padded encoder batch; deformable_transformer.py:797-812, ms_deform_attn.py:97-98).
+// The tiled GEMM's A + A2 prologue (gemm.hip: GT<uint16_t>::add) forms every operand element as round16(float(a) + float(a2)); so does
+// this kernel, ONCE per element: the A and A2 tiles of 64 tokens are DMA'd side by side (64 KB per stage, two stages, proj_ln_k256's
+// ring), and each wave, as soon as ITS OWN DMA pieces of a tile have landed (vmcnt), adds its 4 KB of A2 into its 4 KB of A in place --
+// before the barrier that publishes the tile, so the sum costs no barrier of its own and 1/8 of the tile's additions per wave.  The MFMA
+// phase then reads the summed tile exactly as gemm_k256_kernel<3, false> reads A: same fragments, k-steps 0..7 from a zero accumulator,
+// + bias, one rounding -- bit-identical to the tiled kernel with the prologue.  A2 == nullptr: no second stream, no addition.
+constexpr int KA_STAGE = 2 * K2_STAGE;                      // A tile | A2 tile
+constexpr int KA_LDS = 2 * KA_STAGE;                        // 128 KB
+constexpr int KA_E = 8;                                     // stores per wave and tile: 4 groups x (one 16-byte + one 8-byte)
+
+__device__ __forceinline__ uint4 k2_add16(uint4 a, uint4 b) {            // gemm.hip's GT<uint16_t>::add
+    const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(h16_lo(x[i]) + h16_lo(y[i]), h16_hi(x[i]) + h16_hi(y[i]));
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <bool MASK>
+__global__ __launch_bounds__(512, 2) void gemm_k256_a2_kernel(
+    const uint16_t* __restrict__ A, const uint16_t* __restrict__ A2, const uint16_t* __restrict__ Wp, const float* __restrict__ bias,
+    const uint8_t* __restrict__ row_mask, uint16_t* __restrict__ C, int M, int tiles_per_wg)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char k2_smem[];
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)k2_smem;
+    constexpr int NRT = 3;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = lane & 15, g = lane >> 4;
+    const int ntiles = (M + K2_TOK - 1) / K2_TOK;
+    const int t_begin = (int)blockIdx.x * tiles_per_wg;
+    const int t_end = min(t_begin + tiles_per_wg, ntiles);
+    if (t_begin >= t_end) return;
+    const int nt = t_end - t_begin;
+    const bool two = A2 != nullptr;                           // wave-uniform: the DMA count per tile is 8 or 4
+    const int dr = lane >> 3, dc = (lane & 7) ^ dr;
+    auto issue = [&](int t, int slot) {                       // this wave's 4 blocks of the A tile, then of the A2 tile
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
+            const long tok = min((long)t * K2_TOK + tt8 * 8 + dr, (long)M - 1);
+            glds16(A + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * KA_STAGE + j * 1024));
+        }
+        if (two) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = 4 * wave + u, tt8 = j >> 2, kb = j & 3;
+                const long tok = min((long)t * K2_TOK + tt8 * 8 + dr, (long)M - 1);
+                glds16(A2 + tok * 256 + kb * 64 + dc * 8, lds_base + (unsigned)(slot * KA_STAGE + K2_STAGE + j * 1024));
+            }
+        }
+    };
+    // A <- round16(A + A2) on the 4 KB this wave DMA'd itself (landed: the caller waited on vmcnt); done before the publishing barrier
+    auto sum_own = [&](int slot) {
+        if (!two) return;
+        unsigned char* p = k2_smem + slot * KA_STAGE + wave * 4096 + lane * 16;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint4 a = *reinterpret_cast<const uint4*>(p + u * 1024), b = *reinterpret_cast<const uint4*>(p + K2_STAGE + u * 1024);
+            *reinterpret_cast<uint4*>(p + u * 1024) = k2_add16(a, b);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my LDS writes are done before I arrive at the barrier
+    };
+    issue(t_begin, 0);
+    uint4 wf[NRT][8];
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) wf[rt][ks] = load16(Wp + ((long)((wave * NRT + rt) * 8 + ks) * 64 + lane) * 8);
+    float4 bv[NRT];
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+        bv[rt] = bias ? *reinterpret_cast<const float4*>(bias + (wave * NRT + rt) * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    wait_vm<0>();
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) asm volatile("" : "+v"(bv[rt].x), "+v"(bv[rt].y), "+v"(bv[rt].z), "+v"(bv[rt].w));
+    sum_own(0);
+
+    const unsigned rd0 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + ((g ^ (n & 7)) * 16));
+    const unsigned rd1 = (unsigned)((n >> 3) * 4096 + (n & 7) * 128 + (((4 + g) ^ (n & 7)) * 16));
+
+    for (int i = 0; i < nt; ++i) {
+        const int t = t_begin + i;
+        const int slot = i & 1;
+        __builtin_amdgcn_s_barrier();                         // tile i summed and published; stage (i + 1) & 1 no longer read
+        const bool more = i + 1 < nt;
+        const long trow = (long)t * K2_TOK;
+        unsigned msk[4] = {0, 0, 0, 0};
+        if constexpr (MASK) {                                 // older than the DMA group below
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) msk[tt] = k2_load_u8(row_mask + min(trow + tt * 16 + n, (long)M - 1));
+        }
+        if (more) issue(t + 1, slot ^ 1);
+        const unsigned char* sb = k2_smem + slot * KA_STAGE;
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            f32x4_t acc[NRT];
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) acc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const uint4 bf = *reinterpret_cast<const uint4*>(sb + ((ks & 1) ? rd1 : rd0) + tt * 8192 + (ks >> 1) * 1024);
+#pragma unroll
+                for (int rt = 0; rt < NRT; ++rt) acc[rt] = mma16(wf[rt][ks], bf, acc[rt]);
+            }
+            if constexpr (MASK) {
+                if (tt == 0) {                                // the flags, and nothing newer than the DMA group issued after them
+                    if (!more) wait_vm<0>(); else if (two) wait_vm<8>(); else wait_vm<4>();
+                    asm volatile("" : "+v"(msk[0]), "+v"(msk[1]), "+v"(msk[2]), "+v"(msk[3]));
+                }
+            }
+            const long tok = trow + tt * 16 + n;
+            const bool live = tok < M;
+            const bool zero = MASK && msk[tt] != 0;
+            uint32_t lo[NRT], hi[NRT];
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+                float v[4] = {acc[rt][0] + bv[rt].x, acc[rt][1] + bv[rt].y, acc[rt][2] + bv[rt].z, acc[rt][3] + bv[rt].w};
+                if (zero) { v[0] = v[1] = v[2] = v[3] = 0.f; }
+                lo[rt] = pack_bf16x2(v[0], v[1]);
+                hi[rt] = pack_bf16x2(v[2], v[3]);
+            }
+            const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+            const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+            uint16_t* dst = C + tok * 384;
+            if (live) {
+                *reinterpret_cast<uint4*>(dst + (wave * 3 + (g & 1)) * 16 + 8 * (g >> 1)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                *reinterpret_cast<uint2*>(dst + (wave * 3 + 2) * 16 + 4 * g) = make_uint2(lo[2], hi[2]);
+            }
+        }
+        // my pieces of tile i + 1 (older than this tile's KA_E stores) must have landed: I add them up, then arrive at the barrier
+        if (more) { wait_vm<KA_E>(); sum_own(slot ^ 1); }
+    }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Output projection + residual + LayerNorm in the same weight-resident form:   Y = LayerNorm(R + A W^T + b),  all [M, 256] bf16.
 // (`src = norm1(src + self_attn(...))`, the last op of self_attn being output_proj: models/dino/deformable_transformer.py:810-815,
 // ops/modules/ms_deform_attn.py:124.)  ffn.hip's proj_ln_bf16_kernel keeps the TOKENS in registers and re-streams the 128 KB weight
@@ -641,4 +928,90 @@ extern "C" int dtlr_gemm_k256(const void* A, const void* Wp, const float* bias, 
     if (N == 256) { if (resid) K2_LAUNCH(2, true) else K2_LAUNCH(2, false) }
     else { if (resid) K2_LAUNCH(3, true) else K2_LAUNCH(3, false) }
 #undef K2_LAUNCH
+}
+
+// The column groups of dtlr_gemm_k256_multi for N = 256 L channels: N / 128 units over ceil(N / 640) groups, as evenly as they go; the
+// first n_hi groups hold nrt_hi units, the others nrt_hi - 1.  False: N is not a positive multiple of 256.
+static bool k256_multi_plan(int N, int* ngroups, int* nrt_hi, int* n_hi)
+{
+    if (N <= 0 || N % 256) return false;
+    const int units = N / 128;
+    *ngroups = (units + KM_MAX_NRT - 1) / KM_MAX_NRT;
+    *nrt_hi = (units + *ngroups - 1) / *ngroups;
+    *n_hi = units - (*nrt_hi - 1) * *ngroups;
+    return true;
+}
+
+// W [N, 256] row-major (host) -> the groups' dtlr_k256_pack_weights-style images one after the other (host, N * 256 elements): group gi
+// with nrt units starts at channel col0 (the units before it x 128), and its block ((wave * nrt + rt) * 8 + ks) = 64 lanes x 8 elements,
+// lane (m, g) <- W[col0 + (wave * nrt + rt) * 16 + m][32 ks + 8 g ..].
+extern "C" int dtlr_k256_multi_pack_weights(const unsigned short* w_host, unsigned short* wp_host, int N)
+{
+    if (!w_host || !wp_host) return DTLR_EINVAL;
+    int ngroups, nrt_hi, n_hi;
+    if (!k256_multi_plan(N, &ngroups, &nrt_hi, &n_hi)) return DTLR_ESHAPE;
+    int col0 = 0;
+    for (int gi = 0; gi < ngroups; ++gi) {
+        const int nrt = gi < n_hi ? nrt_hi : nrt_hi - 1;
+        unsigned short* img = wp_host + (long)col0 * 256;
+        for (int wave = 0; wave < 8; ++wave)
+            for (int rt = 0; rt < nrt; ++rt)
+                for (int ks = 0; ks < 8; ++ks)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int m = lane & 15, g = lane >> 4;
+                        const int row = col0 + (wave * nrt + rt) * 16 + m;
+                        for (int e = 0; e < 8; ++e)
+                            img[((long)((wave * nrt + rt) * 8 + ks) * 64 + lane) * 8 + e] = w_host[(long)row * 256 + ks * 32 + g * 8 + e];
+                    }
+        col0 += nrt * 128;
+    }
+    return DTLR_OK;
+}
+
+extern "C" int dtlr_gemm_k256_multi(const void* A, const void* Wp, const float* bias, const unsigned char* row_mask, void* C, int ldc,
+                                    int M, int N, int K, void* stream)
+{
+    clear_stale_error();
+    if (!A || !Wp || !C) return DTLR_EINVAL;
+    if (M <= 0 || N <= 0 || ldc < N || (ldc & 7)) return DTLR_EINVAL;
+    int ngroups, nrt_hi, n_hi;
+    if (K != 256 || !k256_multi_plan(N, &ngroups, &nrt_hi, &n_hi)) return DTLR_ESHAPE;
+    if (n_hi < ngroups && nrt_hi != KM_MAX_NRT) return DTLR_ESHAPE;      // (cannot happen for an even number of units)
+    const int ntiles = (M + K2_TOK - 1) / K2_TOK;
+    // every workgroup resident at once, one per CU, and the groups of a token run a multiple of 8 workgroup ids apart (same XCD)
+    int gx = k2_cu_count() / ngroups & ~7;
+    if (gx < 8) gx = 8;
+    const int per = (ntiles + gx - 1) / gx;
+    gx = ((ntiles + per - 1) / per + 7) & ~7;
+    hipStream_t st = (hipStream_t)stream;
+#define KM_LAUNCH(NRT, MASK)                                                                       \
+    return launch<gemm_k256_multi_kernel<NRT, MASK>>(dim3(gx, ngroups), dim3(512), KM_LDS, st, (const uint16_t*)A, (const uint16_t*)Wp, bias, \
+                                                     row_mask, (uint16_t*)C, ldc, M, per, n_hi);
+    switch (nrt_hi) {
+    case 2: if (row_mask) { KM_LAUNCH(2, true) } else { KM_LAUNCH(2, false) }
+    case 3: if (row_mask) { KM_LAUNCH(3, true) } else { KM_LAUNCH(3, false) }
+    case 4: if (row_mask) { KM_LAUNCH(4, true) } else { KM_LAUNCH(4, false) }
+    default: if (row_mask) { KM_LAUNCH(5, true) } else { KM_LAUNCH(5, false) }
+    }
+#undef KM_LAUNCH
+}
+
+extern "C" int dtlr_gemm_k256_a2(const void* A, const void* A2, const void* Wp, const float* bias, const unsigned char* row_mask, void* C,
+                                 int M, int N, int K, void* stream)
+{
+    clear_stale_error();
+    if (!A || !Wp || !C) return DTLR_EINVAL;
+    if (M <= 0) return DTLR_EINVAL;
+    if (N != 384 || K != 256) return DTLR_ESHAPE;
+    const int ntiles = (M + K2_TOK - 1) / K2_TOK;
+    const int ncu = k2_cu_count();
+    const int grid = ntiles < ncu ? ntiles : ncu;
+    const int per = (ntiles + grid - 1) / grid;
+    const int g2 = (ntiles + per - 1) / per;
+    hipStream_t st = (hipStream_t)stream;
+    if (row_mask)
+        return launch<gemm_k256_a2_kernel<true>>(dim3(g2), dim3(512), KA_LDS, st, (const uint16_t*)A, (const uint16_t*)A2, (const uint16_t*)Wp, bias,
+                                                 row_mask, (uint16_t*)C, M, per);
+    return launch<gemm_k256_a2_kernel<false>>(dim3(g2), dim3(512), KA_LDS, st, (const uint16_t*)A, (const uint16_t*)A2, (const uint16_t*)Wp, bias,
+                                              row_mask, (uint16_t*)C, M, per);
 }

@@ -59,7 +59,8 @@ _IMAGES = {
                               (e.w[n + ".c3.b"].float() + e.w[n + ".ds.b"].float()).contiguous()),
     # ops.kres_pack_bcast384: the encoder's [offsets | logits] projection with a row-broadcast residual (dtlr_gemm_kres_bcast384)
     "bcast384": lambda e, n: ops.kres_pack_bcast384(e.w[n + ".w"]),
-    # ops.k256_pack: a [256 | 384, 256] projection over all tokens (dtlr_gemm_k256)
+    # ops.k256_pack: a [256 | 384, 256] projection over all tokens (dtlr_gemm_k256); of a taller [256 L, 256] weight, the column-group
+    # image of dtlr_gemm_k256_multi (dec.value_all in one launch; the same image at L = 1)
     "k256": lambda e, n: ops.k256_pack(e.w[n + ".w"]),
     # ops.k256_pack of every 384 rows of a taller weight, as a list (dtlr_gemm_k256 into column slices: dec.value_all)
     "k256_slices": lambda e, n: [ops.k256_pack(e.w[n + ".w"][r0:r0 + 384]) for r0 in range(0, e.w[n + ".w"].shape[0], 384)],
@@ -149,6 +150,11 @@ class DTLREngine:
                                           #         3.45 -> 3.63 ms: the chain stays.  Fills between those, and counts above 256, are NOT measured.
         self.use_k256_fused = 1           # 16-bit, unpadded batch: an encoder layer's value and [offsets | logits] projections in ONE pass over src
                                           #         (ops.gemm_k256_vow: dtlr_gemm_k256, N = 640) instead of dtlr_gemm_k256 + dtlr_gemm_kres_bcast384; bit-identical either way
+        self.use_k256_multi = 1           # 16-bit: value_proj(memory) of ALL decoder layers in ONE launch over column groups (ops.gemm_k256_multi:
+                                          #         dtlr_gemm_k256_multi) instead of one dtlr_gemm_k256 launch per 384 channels; bit-identical either way
+        self.use_k256_a2 = 1              # 16-bit: [offsets | logits] of (x + pos) for a [384, 256] weight on the weight-resident kernel with two token
+        self.k256_a2_min_rows = 16384     #         streams (ops.gemm_k256_a2: dtlr_gemm_k256_a2) instead of the tiled GEMM's A + A2 prologue, from this many rows
+                                          #         on (the plain K = 256 projections' threshold; smaller calls are not measured); bit-identical either way
         self.use_l2_cat = True            # 16-bit: layer2.0's strided shortcut convolution as extra K columns of its tail GEMM
         self.head_ts_min_classes = 1024   # 16-bit engines: class heads with at least this many classes run on the token-stationary kernel (dtlr_head_ts)
         self.head_ts_scores = True        # ... and the two-stage selection scores (row maximum: no logits leave the chip) for EVERY charset: 142 -> 74 us at 166 classes
@@ -437,6 +443,11 @@ class DTLREngine:
         if self.use_k256_small and x.dtype in ops.H16 and not relu and residual is None and a2 is None and out_dtype in (None, x.dtype) \
                 and w.shape[1] == 256 and w.shape[0] in (256, 384) and x.numel() // 256 >= 16384 and x.is_contiguous():
             return ops.gemm_k256(x, self._image("k256", name), w.shape[0], self.w[name + ".b"], row_mask=row_mask)     # plain K = 256 projections
+        if getattr(self, "use_k256_a2", 0) and a2 is not None and x.dtype in ops.H16 and a2.dtype == x.dtype and not relu and residual is None \
+                and out_dtype in (None, x.dtype) and tuple(w.shape) == (384, 256) and a2.numel() == x.numel() \
+                and x.numel() // 256 >= self.k256_a2_min_rows:
+            # [offsets | logits] of tgt + query_pos (decoder) or src + pos (encoder, padded batch): the sum formed on chip, weights resident
+            return ops.gemm_k256_a2(x, a2, self._image("k256", name), self.w[name + ".b"], row_mask=row_mask)
         return ops.linear(x, w, self.w[name + ".b"], relu, residual, a2, row_mask, out_dtype)
 
     def _ln(self, name, x, residual=None):
@@ -562,7 +573,7 @@ class DTLREngine:
         """Replace the LAST decoder layer's cross_attn.value_proj, a (weight [d,d], bias [d]) pair, in the packed model without re-packing
         anything else: set_decoder_self's counterpart (DESIGN.md section 25).  The engine projects memory through all layers' value
         projections at once (`dec.value_all`, [layers x d, d]): rows (L-1) d .. L d of its fp32 rows are replaced, `dec.value_all` is packed
-        again from them as the constructor packs it, and only the images derived from it (`k256_slices`, `k256s_slices`, and the split
+        again from them as the constructor packs it, and only the images derived from it (`k256`, `k256_slices`, `k256s_slices`, and the split
         engine's kept fp32 source) are dropped, to be rebuilt by the next forward.  A forward after this equals, bit for bit, the forward of
         a fresh engine built from the updated state dict.  Replacing rows of the packed weight in place would not be enough: a 16-bit
         engine holds rounded rows only, the split engine releases its fp32 source once the `k256s_slices` image is built, and a `k256_slices`
@@ -1029,6 +1040,10 @@ class DTLREngine:
         C = self.cfg.hidden_dim
         rmask = g["mask_flat"] if g["has_padding"] else None
         Nall = self.w["dec.value_all.w"].shape[0]
+        if self.use_k256 and getattr(self, "use_k256_multi", 0) and memory.dtype in ops.H16 and C == 256 and Nall % 256 == 0:
+            # every layer's slice in one launch: memory comes from HBM once (padded and unpadded batches alike)
+            ops.gemm_k256_multi(memory, self._image("k256", "dec.value_all"), Nall, self.w["dec.value_all.b"], row_mask=rmask, out=vall)
+            return True
         if self.use_k256 and memory.dtype in ops.H16 and C == 256 and Nall % 384 == 0:
             # weight-resident streaming kernel, 384 output channels per launch, written as column slices of one [B, S, N] buffer
             for j, img in enumerate(self._image("k256_slices", "dec.value_all")):

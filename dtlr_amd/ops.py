@@ -210,9 +210,12 @@ def linear_resbcast(x, w, resid, b=None):
 def k256_pack(w):
     """[N, 256] weight (N = 256 or 384; any float dtype / device) -> the fragment-order bf16 image dtlr_gemm_k256 keeps in
     registers: block ((wave * NRT + rt) * 8 + ks) = 64 lanes x 8 elements, lane (m, g) <- W[(wave*NRT + rt)*16 + m][32 ks + 8 g ..]
-    (== dtlr_k256_pack_weights; done with tensor ops on the weight's own device)."""
+    (== dtlr_k256_pack_weights; done with tensor ops on the weight's own device).  A taller weight, N = 256 L: the column-group image
+    of dtlr_gemm_k256_multi (k256_multi_pack; at N = 256 the two are the same image)."""
     N, K = w.shape
-    assert K == 256 and N in (256, 384)
+    assert K == 256 and (N == 384 or N % 256 == 0)
+    if N > 384:
+        return k256_multi_pack(w)
     nrt = N // 128
     return w.detach().to(_hdt(w)).view(8, nrt, 16, 8, 4, 8).permute(0, 1, 3, 4, 2, 5).contiguous().view(-1)
 
@@ -1865,3 +1868,5 @@ from .crossgrad import CROSS_FLOATS, CROSS_NAMES, CROSS_SHAPES, cross_dow, cross
 from .selfgrad import SELF_FLOATS, SELF_NAMES, SELF_SHAPES, mha_grad, self_grad, self_recompute          # noqa: E402,F401
 # the twelfth header (include/dtlr_msdagrad.h), the same way: written in dtlr_amd/msdagrad.py (the deformable attention's gradient with respect to value)
 from .msdagrad import VGRAD_SEGMENTS, VGRAD_TILE, msda_value_grad          # noqa: E402,F401
+# the thirteenth header (include/dtlr_k256multi.h), the same way: written in dtlr_amd/k256multi.py (the K = 256 projection over column groups)
+from .k256multi import K256_MULTI_MAX_UNITS, gemm_k256_a2, gemm_k256_multi, k256_multi_pack, k256_multi_plan          # noqa: E402,F401
