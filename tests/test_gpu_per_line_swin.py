@@ -79,7 +79,7 @@ def _assert_lines_equal_crops(got, s, alone):
 
 # ------------------------------------------------------------------------------------------------ kernels
 @pytest.mark.parametrize("dtype", list(DTYPES))
-@pytest.mark.parametrize("window", [4, 7])
+@pytest.mark.parametrize("window", [4, 7, 12])
 @pytest.mark.parametrize("shifted", [False, True])
 def test_window_attn_ext_equals_the_whole_map_kernel_on_each_cropped_line(dtype, window, shifted):
     dt, nh = DTYPES[dtype], 2
