@@ -33,6 +33,12 @@ deformable attention's backward only the two gathers are needed (dtlr_cross_reco
 after it, where the character queries of a line talk to each other.  The layer's input state and the query position embedding are the
 constants of the frozen trunk; everything from there up is recomputed in fp32 from the masters (dtlr_self_recompute), the cross block then
 starts from THAT state after norm2, and the attention core's backward is dtlr_mha_grad.
+
+--augment default | full trains on the reference's augmented lines: make_coco_transforms("train")'s random erasing
+(and, with --aug-scales, its random resize per line) drawn on the host from (seed, epoch, line) and applied by the launch that resizes
+the line (dtlr_augment_lines).  --resident decodes every file once into one device buffer (transforms.DeviceLineSet) and feeds every step
+from it; --val-labels / --val-mode run the held-out, never augmented lines through the forward after every epoch and print val loss_CTC
+and val CER.  Without these flags the loop runs the launches it ran.
 """
 from __future__ import annotations
 
@@ -698,8 +704,31 @@ def build_parser() -> argparse.ArgumentParser:
                                                      "self-attention and norm2; needs cross), value (that layer's cross_attn.value_proj; "
                                                      "needs self), e.g. class,box,tail,cross,self,value")
     ap.add_argument("--aux-loss", action="store_true", help="set losses on every decoder output, as the reference weighs them (default: the main output)")
+    ap.add_argument("--augment", default="none", choices=["none", "default", "full"],
+                    help="the reference's training erasing, on the device (DESIGN.md section 26): none (default: the evaluation transform); default: "
+                         "4 x RandomErasing(p 0.5, scale 0.005-0.05, ratio 5-6); full: 5 full-height bars of 1-4 %% of the width in front of "
+                         "those (the reference's --random_erasing)")
+    ap.add_argument("--aug-scales", default=None, help="comma-separated short sides, one drawn per line and step (the reference's data_aug_scales); "
+                                                       "default: no random resize; needs --batching padded or ragged")
+    ap.add_argument("--aug-seed", type=int, default=None, help="seed of the augmentation draws (default: --seed); a line's draws depend on "
+                                                               "(seed, epoch, line) alone")
+    ap.add_argument("--resident", action="store_true", help="decode every line once into one device buffer and feed every step from it")
+    ap.add_argument("--resident-max-gb", type=float, default=16.0, help="refuse --resident beyond this many GB of pixels")
+    ap.add_argument("--val-labels", default=None, help="labels of held-out lines: val loss_CTC and val CER at the end of every epoch and of the run")
+    ap.add_argument("--val-mode", default=None, help="split of the held-out lines in a labels.pkl (default val; with no --val-labels: a split of --labels)")
+    ap.add_argument("--val-images", default=None, help="folder of the held-out lines' images (default: --images)")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
+
+
+def parse_scales(text: Optional[str]) -> Optional[List[int]]:
+    """--aug-scales: "480,512" -> [480, 512]; None stays None; ValueError for anything but positive integers"""
+    if text is None:
+        return None
+    scales = [int(t) for t in text.split(",") if t.strip()]
+    if not scales or min(scales) <= 0:
+        raise ValueError(text)
+    return scales
 
 
 def text_to_labels(text: str, charset: Sequence) -> List[int]:
@@ -776,11 +805,21 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         ap.error("--train box / --aux-loss need --loss set or ctc+set")
     if args.aux_loss and args.cache_features:
         ap.error("--cache-features keeps the last decoder layer's states only: not with --aux-loss")
+    try:
+        scales = parse_scales(args.aug_scales)
+    except ValueError:
+        ap.error(f"--aug-scales {args.aug_scales}: a comma-separated list of positive integers")
+    if scales is not None and args.batching == "exact":
+        ap.error("--aug-scales needs --batching padded or ragged: the lines of a batch no longer share one size")
+    if args.cache_features and (args.augment != "none" or scales is not None):
+        ap.error("--cache-features cannot train on augmented lines: the cached states are those of one fixed image")
+    if args.resident_max_gb <= 0:
+        ap.error("--resident-max-gb must be positive")
     from . import eval_harness as H
     from . import weights as W
     from .config import DTLRConfig
     from .dino import DINO
-    from .transforms import EvalTransform
+    from .transforms import ERASING_DEFAULT, ERASING_FULL, DeviceLineSet, EvalTransform, TrainTransform
     if not torch.cuda.is_available():
         raise SystemExit("dtlr_amd.adapt needs an MI355X (no CPU path)")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -813,14 +852,55 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     per_line = args.batching == "ragged"
     batches = H.plan_batches(sizes, args.batch, args.batching == "exact", args.size, args.max_size)
     tf = EvalTransform(args.size, args.max_size)
+    # the training transform: None is the evaluation transform, the path before augmentation
+    ttf = None
+    if args.augment != "none" or scales is not None:
+        ttf = TrainTransform(args.size, args.max_size, scales=scales, erasing={"none": (), "default": ERASING_DEFAULT, "full": ERASING_FULL}[args.augment],
+                             seed=args.seed if args.aug_seed is None else args.aug_seed)
+    val = None
+    if args.val_labels is not None or args.val_mode is not None:
+        vrows = H.load_labels(args.val_labels or args.labels, args.val_mode or "val")
+        vpaths = [H.find_image(args.val_images or args.images, name) for name, _ in vrows]
+        vsizes = [H.image_size(p) for p in vpaths]
+        val = {"paths": vpaths, "labels": [text_to_labels(t, charset) for _, t in vrows], "set": None,
+               "batches": H.plan_batches(vsizes, args.batch, args.batching == "exact", args.size, args.max_size)}
+    lines = None
+    if args.resident:
+        cap = int(args.resident_max_gb * 1e9)
+        need = sum(h * w * 3 for h, w in sizes + (vsizes if val else []))
+        if need > cap:
+            raise SystemExit(f"--resident: the lines hold {need / 1e9:.3f} GB of pixels, more than --resident-max-gb {args.resident_max_gb:g}")
+        lines = DeviceLineSet([H.read_rgb(p) for p in paths], device=dev, max_bytes=cap)
+        if val:
+            val["set"] = DeviceLineSet([H.read_rgb(p) for p in val["paths"]], device=dev, max_bytes=cap - lines.nbytes)
+
+    def eval_lines(idx):
+        """the batch `idx` under the evaluation transform: from the resident set, or from the files"""
+        return lines.eval_batch(idx, args.size, args.max_size) if lines is not None else tf([H.read_rgb(paths[i]) for i in idx], device=dev)
+
+    def train_lines(idx, epoch):
+        if ttf is None:
+            return eval_lines(idx)
+        return lines.train_batch(idx, ttf, epoch) if lines is not None else ttf([H.read_rgb(paths[i]) for i in idx], idx, epoch, device=dev)
+
+    def validate():
+        """the held-out lines, never augmented, through the forward with the parameters as they stand: (loss_CTC, CER) over the lines"""
+        trainer._engine()
+        loss = cer = n = 0.0
+        for idx in val["batches"]:
+            x = val["set"].eval_batch(idx, args.size, args.max_size) if val["set"] is not None else tf([H.read_rgb(val["paths"][i]) for i in idx], device=dev)
+            with torch.no_grad():
+                ev = E.evaluate_ctc_step(trainer.model(x, per_line=per_line), [val["labels"][i] for i in idx])
+            loss, cer, n = loss + ev["loss_CTC"] * ev["n"], cer + ev["cer_sum"], n + ev["n"]
+        return loss / max(n, 1), cer / max(n, 1)
+
     char_boxes: Dict[int, torch.Tensor] = {}
     if args.loss != "ctc":
-        char_boxes, batches = load_char_boxes(args, trainer, rows, labels, batches, lambda idx: tf([H.read_rgb(paths[i]) for i in idx], device=dev),
-                                              per_line)
+        char_boxes, batches = load_char_boxes(args, trainer, rows, labels, batches, eval_lines, per_line)      # aligned on the un-augmented lines
     total = args.max_steps if args.max_steps is not None else (args.epochs if args.epochs is not None else 1) * len(batches)
     rng = np.random.Generator(np.random.PCG64(args.seed))
     cached: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
-    step, last = 0, {}
+    step, last, epoch = 0, {}, 0
     while step < total:
         for bi in rng.permutation(len(batches)):
             if step >= total:
@@ -830,16 +910,21 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
             tb = [char_boxes[i] for i in idx] if args.loss != "ctc" else None
             if args.cache_features:
                 if int(bi) not in cached:
-                    cached[int(bi)] = trainer.cache(tf([H.read_rgb(paths[i]) for i in idx], device=dev), per_line=per_line)
+                    cached[int(bi)] = trainer.cache(eval_lines(idx), per_line=per_line)
                 r = trainer.step_cached(*cached[int(bi)], tl, tb)
             else:
-                r = trainer.step(tf([H.read_rgb(paths[i]) for i in idx], device=dev), tl, per_line=per_line, target_boxes=tb)
+                r = trainer.step(train_lines(idx, epoch), tl, per_line=per_line, target_boxes=tb)
             step += 1
             if step % max(args.log_every, 1) == 0 or step == total:
                 ev = E.evaluate_ctc_step(trainer.last_outputs, tl)            # the batch's loss and CER before this step's update
                 last = {"step": step, **{k: float(v.item()) for k, v in r.items()}, "cer": ev["cer_sum"] / max(ev["n"], 1)}
                 shown = "  ".join(f"{k} {last[k]:.6f}" for k in ("loss_CTC", "loss_ce", "loss_bbox", "loss_giou") if k in last)
                 print(f"step {step}/{total}  {shown}  train CER {last['cer']:.4f}", flush=True)
+        epoch += 1
+        if val is not None:                                                   # the end of an epoch, or of the run inside one
+            vloss, vcer = validate()
+            last.update(val_loss_CTC=vloss, val_cer=vcer)
+            print(f"epoch {epoch} (step {step}/{total})  val loss_CTC {vloss:.6f}  val CER {vcer:.4f}", flush=True)
     trainer.write_back()
     save_checkpoint(args.out, model, charset, trainer)
     print(f"wrote {args.out}", file=sys.stderr)

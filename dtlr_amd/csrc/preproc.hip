@@ -12,7 +12,13 @@
 // One thread per canvas pixel.  A thread's horizontal weights live in its own LDS column (computed once, used for every source
 // row it touches); the few vertical weights are recomputed per thread (a handful of double operations).  The source is uint8:
 // a 128 x 2048 line is 0.8 MB against the 1.3 MB fp32 tensor it produces, so the kernel is bound by its fp32 canvas writes.
+//
+// The training transform (include/dtlr_augment.h) is the same kernel with erasing rectangles (RECTS): the reference erases with value 0
+// AFTER Normalize, so an erased pixel is +0.0f and is never resampled.  A line's table is the same for the whole workgroup (blockIdx.z),
+// and so is the row (blockIdx.y): the table is read through uniform addresses, and a rectangle that misses the row is dropped by a
+// uniform branch before any lane looks at its column.
 #include "dtlr_common.h"
+#include "../../include/dtlr_augment.h"
 
 namespace dtlr {
 
@@ -51,8 +57,11 @@ __device__ __forceinline__ int pp_clip8(int v) { v >>= PP_BITS; return v < 0 ? 0
 struct PPNorm { float mean[3], std[3]; };
 
 // src: the images back to back, each [h, w, 3] uint8 ; offsets [B] bytes ; dims [B][4] = (h, w, oh, ow)
+// RECTS: rects [B][R][4] = (i, j, h, w) in the resized line's pixels, 0 < R <= DTLR_AUG_MAX_RECTS (without RECTS neither is looked at)
+template <bool RECTS>
 __global__ __launch_bounds__(256) void preprocess_lines_kernel(const unsigned char* __restrict__ src, const long* __restrict__ offsets,
-                                                               const int* __restrict__ dims, float* __restrict__ canvas,
+                                                               const int* __restrict__ dims, const int* __restrict__ rects, int R,
+                                                               float* __restrict__ canvas,
                                                                unsigned char* __restrict__ mask, int Hc, int Wc, PPNorm nrm)
 {
     __shared__ int kh[PP_MAXT][256];
@@ -65,6 +74,23 @@ __global__ __launch_bounds__(256) void preprocess_lines_kernel(const unsigned ch
         out[0] = 0.f; out[plane] = 0.f; out[2 * plane] = 0.f;
         mask[(long)b * plane + (long)yy * Wc + xx] = 1;
         return;
+    }
+    if constexpr (RECTS) {
+        const int* tab = rects + (long)b * R * 4;                    // uniform: scalar loads
+        bool erased = false;
+        for (int r = 0; r < R; ++r) {
+            const int ri = tab[4 * r], rj = tab[4 * r + 1], rh = tab[4 * r + 2], rw = tab[4 * r + 3];
+            if (rh <= 0 || rw <= 0) continue;
+            // clipped to the extent; the far edges in 64 bits (i + h of a hostile table does not fit 32)
+            const long i1 = (long)ri + rh, j1 = (long)rj + rw;
+            if (yy < ri || yy >= i1) continue;                       // the row test: uniform over the block
+            erased = erased || (xx >= rj && xx < j1);
+        }
+        if (erased) {                                               // RandomErasing(value=0) after Normalize: +0.0, not resampled
+            out[0] = 0.f; out[plane] = 0.f; out[2 * plane] = 0.f;
+            mask[(long)b * plane + (long)yy * Wc + xx] = 0;
+            return;
+        }
     }
     // horizontal weights of output column xx
     double cx, sx;
@@ -105,11 +131,10 @@ __global__ __launch_bounds__(256) void preprocess_lines_kernel(const unsigned ch
 
 using namespace dtlr;
 
-extern "C" int dtlr_preprocess_lines(const unsigned char* src, const long* offsets, const int* dims, int B, int Hc, int Wc,
-                                     float max_downscale, const float* mean3, const float* std3,
-                                     float* canvas, unsigned char* mask, void* stream)
+// the two entries' common body: R == 0 launches the form without rectangles
+static int preprocess_entry(const unsigned char* src, const long* offsets, const int* dims, const int* rects, int R, int B, int Hc, int Wc,
+                            float max_downscale, const float* mean3, const float* std3, float* canvas, unsigned char* mask, void* stream)
 {
-    clear_stale_error();
     if (!src || !offsets || !dims || !canvas || !mask || !mean3 || !std3) return DTLR_EINVAL;
     if (B <= 0 || Hc <= 0 || Wc <= 0) return DTLR_EINVAL;
     // horizontal taps = ceil(max(scale, 1)) * 2 + 1 must fit the per-thread LDS column
@@ -118,5 +143,26 @@ extern "C" int dtlr_preprocess_lines(const unsigned char* src, const long* offse
     PPNorm n;
     for (int c = 0; c < 3; ++c) { n.mean[c] = mean3[c]; n.std[c] = std3[c]; }
     const dim3 grid((Wc + 255) / 256, Hc, B);
-    return launch<preprocess_lines_kernel>(grid, dim3(256), 0, (hipStream_t)stream, src, offsets, dims, canvas, mask, Hc, Wc, n);
+    if (R > 0)
+        return launch<preprocess_lines_kernel<true>>(grid, dim3(256), 0, (hipStream_t)stream, src, offsets, dims, rects, R, canvas, mask, Hc, Wc, n);
+    return launch<preprocess_lines_kernel<false>>(grid, dim3(256), 0, (hipStream_t)stream, src, offsets, dims, (const int*)nullptr, 0, canvas,
+                                                  mask, Hc, Wc, n);
+}
+
+extern "C" int dtlr_preprocess_lines(const unsigned char* src, const long* offsets, const int* dims, int B, int Hc, int Wc,
+                                     float max_downscale, const float* mean3, const float* std3,
+                                     float* canvas, unsigned char* mask, void* stream)
+{
+    clear_stale_error();
+    return preprocess_entry(src, offsets, dims, nullptr, 0, B, Hc, Wc, max_downscale, mean3, std3, canvas, mask, stream);
+}
+
+extern "C" int dtlr_augment_lines(const unsigned char* src, const long* offsets, const int* dims, const int* rects, int R, int B, int Hc,
+                                  int Wc, float max_downscale, const float* mean3, const float* std3,
+                                  float* canvas, unsigned char* mask, void* stream)
+{
+    clear_stale_error();
+    if (R < 0 || R > DTLR_AUG_MAX_RECTS) return DTLR_ESHAPE;
+    if (R > 0 && !rects) return DTLR_EINVAL;
+    return preprocess_entry(src, offsets, dims, rects, R, B, Hc, Wc, max_downscale, mean3, std3, canvas, mask, stream);
 }

@@ -1870,3 +1870,5 @@ from .selfgrad import SELF_FLOATS, SELF_NAMES, SELF_SHAPES, mha_grad, self_grad,
 from .msdagrad import VGRAD_SEGMENTS, VGRAD_TILE, msda_value_grad          # noqa: E402,F401
 # the thirteenth header (include/dtlr_k256multi.h), the same way: written in dtlr_amd/k256multi.py (the K = 256 projection over column groups)
 from .k256multi import K256_MULTI_MAX_UNITS, gemm_k256_a2, gemm_k256_multi, k256_multi_pack, k256_multi_plan          # noqa: E402,F401
+# the fourteenth header (include/dtlr_augment.h), the same way: written in dtlr_amd/augment.py (the training transform: preprocessing with erasing rectangles)
+from .augment import AUG_MAX_RECTS, augment_lines          # noqa: E402,F401
