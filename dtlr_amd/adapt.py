@@ -39,6 +39,12 @@ starts from THAT state after norm2, and the attention core's backward is dtlr_mh
 the line (dtlr_augment_lines).  --resident decodes every file once into one device buffer (transforms.DeviceLineSet) and feeds every step
 from it; --val-labels / --val-mode run the held-out, never augmented lines through the forward after every epoch and print val loss_CTC
 and val CER.  Without these flags the loop runs the launches it ran.
+
+--synth-fonts A.ttf,B.ttf | builtin (or --synth-atlas atlas.npz) with --synth-lines N trains on synthetic lines rendered on the device
+(dtlr_amd/synthlines.py, dtlr_synth_lines): no --images / --labels, every character carries the box its layout
+gave it (--loss set / ctc+set take them without --boxes), and the start of every epoch renders fresh lines into the same resident
+pool.  --augment, --batching, --val-* (real held-out lines) and every --train group work as on a resident set.  Without these flags the
+loop runs the launches it ran.
 """
 from __future__ import annotations
 
@@ -670,8 +676,8 @@ def build_parser() -> argparse.ArgumentParser:
                                  description="train the class head of a pretrained DTLR checkpoint for a new charset (CTC loss, AdamW), on the GPU")
     ap.add_argument("--config", default="latin", help="a reference config file (config/*.py) or a preset: latin | chinese | tiny")
     ap.add_argument("--weights", required=True, help="the pretrained checkpoint.pth")
-    ap.add_argument("--images", required=True, help="folder with the line images (<id>.jpg / .png)")
-    ap.add_argument("--labels", required=True, help="labels.pkl (reference layout), .json or .tsv")
+    ap.add_argument("--images", default=None, help="folder with the line images (<id>.jpg / .png); required unless the lines are synthetic")
+    ap.add_argument("--labels", default=None, help="labels.pkl (reference layout), .json or .tsv; required unless the lines are synthetic")
     ap.add_argument("--mode", default="train", help="split of a labels.pkl")
     ap.add_argument("--charset", required=True, help="the NEW charset (.json list / .pkl list)")
     ap.add_argument("--old-charset", default=None, help="charset of the checkpoint (--smart-mapping; default: the package's default_charset.json)")
@@ -717,8 +723,49 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--val-labels", default=None, help="labels of held-out lines: val loss_CTC and val CER at the end of every epoch and of the run")
     ap.add_argument("--val-mode", default=None, help="split of the held-out lines in a labels.pkl (default val; with no --val-labels: a split of --labels)")
     ap.add_argument("--val-images", default=None, help="folder of the held-out lines' images (default: --images)")
+    ap.add_argument("--synth-fonts", default=None, help="train on synthetic lines rendered on the device (DESIGN.md section 27): comma-separated "
+                                                        ".ttf / .otf paths, or builtin (Pillow's default face); every character carries its box")
+    ap.add_argument("--synth-atlas", default=None, help="the same from a glyph atlas written by synthlines.GlyphAtlas.save (no font needed)")
+    ap.add_argument("--synth-text", default=None, help="a text file, one line a line (default: 1-5 random words over --charset)")
+    ap.add_argument("--synth-lines", type=int, default=None, help="lines of the synthetic set; every epoch renders fresh ones")
+    ap.add_argument("--synth-font-sizes", default=None, help="a size or a range of sizes (default 30-50, the reference's)")
+    ap.add_argument("--synth-backgrounds", default=None, help="folder of background images kept on the device (default: procedural backgrounds)")
+    ap.add_argument("--synth-seed", type=int, default=None, help="seed of the generator's draws (default: --seed); a line's draws depend on "
+                                                                 "(seed, epoch, line) alone")
     ap.add_argument("--out", required=True, help="the adapted checkpoint ({'model': state_dict, 'charset', 'trainer'})")
     return ap
+
+
+def check_synth_args(ap: argparse.ArgumentParser, args) -> Optional[List[int]]:
+    """The --synth-* flags against each other and the rest: None without them (--images / --labels are then demanded), otherwise the
+    font sizes.  Every refusal is the parser's error, before anything is loaded."""
+    synth = args.synth_fonts is not None or args.synth_atlas is not None
+    if not synth:
+        for name in ("synth_text", "synth_lines", "synth_font_sizes", "synth_backgrounds", "synth_seed"):
+            if getattr(args, name) is not None:
+                ap.error(f"--{name.replace('_', '-')} needs --synth-fonts or --synth-atlas")
+        if args.images is None or args.labels is None:
+            ap.error("the following arguments are required: --images, --labels (or --synth-fonts / --synth-atlas for synthetic lines)")
+        return None
+    if args.synth_fonts is not None and args.synth_atlas is not None:
+        ap.error("--synth-fonts and --synth-atlas exclude each other")
+    if args.images is not None or args.labels is not None or args.limit:
+        ap.error("synthetic lines have no files: not with --images, --labels or --limit (held-out real lines: --val-images, --val-labels)")
+    if args.synth_lines is None or args.synth_lines <= 0:
+        ap.error("--synth-lines must be given and positive")
+    if args.cache_features:
+        ap.error("--cache-features cannot train on synthetic lines: every epoch renders fresh ones")
+    if args.boxes_from != "labels" or args.boxes is not None:
+        ap.error("synthetic lines carry the generator's boxes: not with --boxes or --boxes-from align")
+    if args.val_mode is not None and args.val_labels is None:
+        ap.error("--val-mode needs --val-labels with synthetic lines: there is no --labels file to take a split of")
+    if (args.val_labels is not None) and args.val_images is None:
+        ap.error("--val-labels needs --val-images with synthetic lines: there is no --images folder")
+    from .synthlines import parse_range
+    try:
+        return parse_range(args.synth_font_sizes or "30-50")
+    except ValueError:
+        ap.error(f"--synth-font-sizes {args.synth_font_sizes}: a size or a range such as 30-50")
 
 
 def parse_scales(text: Optional[str]) -> Optional[List[int]]:
@@ -815,6 +862,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         ap.error("--cache-features cannot train on augmented lines: the cached states are those of one fixed image")
     if args.resident_max_gb <= 0:
         ap.error("--resident-max-gb must be positive")
+    synth_sizes = check_synth_args(ap, args)
     from . import eval_harness as H
     from . import weights as W
     from .config import DTLRConfig
@@ -843,12 +891,25 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
     trainer = HeadTrainer(model, lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_max_norm, loss=args.loss,
                           train=train, aux_loss=args.aux_loss)
 
-    rows = H.load_labels(args.labels, args.mode)
-    if args.limit:
-        rows = rows[: args.limit]
-    paths = [H.find_image(args.images, name) for name, _ in rows]
-    labels = [text_to_labels(t, charset) for _, t in rows]
-    sizes = [H.image_size(p) for p in paths]
+    synth = None
+    if synth_sizes is not None:
+        # synthetic lines: the set is rendered on the device, the labels and boxes come from its layout, and the
+        # loop below renders fresh lines at the start of every epoch
+        from . import synthlines as SL
+        seed = args.seed if args.synth_seed is None else args.synth_seed
+        synth = SL.SyntheticLineSet(SL.atlas_from_args(args.synth_fonts, args.synth_atlas, charset, synth_sizes, seed=seed),
+                                    SL.SynthRecipe(font_size=(synth_sizes[0], synth_sizes[-1])), args.synth_lines, SL.read_text(args.synth_text),
+                                    SL.load_backgrounds(args.synth_backgrounds), device=dev, max_bytes=int(args.resident_max_gb * 1e9), charset=charset,
+                                    seed=seed, epoch=0)
+        rows, paths = [(f"{i:06d}", None) for i in range(len(synth))], []
+        labels, sizes = [synth.labels(i) for i in range(len(synth))], list(synth.hw)
+    else:
+        rows = H.load_labels(args.labels, args.mode)
+        if args.limit:
+            rows = rows[: args.limit]
+        paths = [H.find_image(args.images, name) for name, _ in rows]
+        labels = [text_to_labels(t, charset) for _, t in rows]
+        sizes = [H.image_size(p) for p in paths]
     per_line = args.batching == "ragged"
     batches = H.plan_batches(sizes, args.batch, args.batching == "exact", args.size, args.max_size)
     tf = EvalTransform(args.size, args.max_size)
@@ -864,8 +925,11 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         vsizes = [H.image_size(p) for p in vpaths]
         val = {"paths": vpaths, "labels": [text_to_labels(t, charset) for _, t in vrows], "set": None,
                "batches": H.plan_batches(vsizes, args.batch, args.batching == "exact", args.size, args.max_size)}
-    lines = None
-    if args.resident:
+    lines = synth
+    if synth is not None:
+        if args.resident and val:
+            val["set"] = DeviceLineSet([H.read_rgb(p) for p in val["paths"]], device=dev, max_bytes=int(args.resident_max_gb * 1e9))
+    elif args.resident:
         cap = int(args.resident_max_gb * 1e9)
         need = sum(h * w * 3 for h, w in sizes + (vsizes if val else []))
         if need > cap:
@@ -895,13 +959,21 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict:
         return loss / max(n, 1), cer / max(n, 1)
 
     char_boxes: Dict[int, torch.Tensor] = {}
-    if args.loss != "ctc":
+    if args.loss != "ctc" and synth is not None:
+        char_boxes = {i: synth.boxes(i) for i in range(len(synth))}
+    elif args.loss != "ctc":
         char_boxes, batches = load_char_boxes(args, trainer, rows, labels, batches, eval_lines, per_line)      # aligned on the un-augmented lines
     total = args.max_steps if args.max_steps is not None else (args.epochs if args.epochs is not None else 1) * len(batches)
     rng = np.random.Generator(np.random.PCG64(args.seed))
     cached: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
     step, last, epoch = 0, {}, 0
     while step < total:
+        if synth is not None and epoch > 0:                                   # fresh lines: sizes, labels and boxes follow the new layout
+            synth.render(epoch)
+            labels, sizes = [synth.labels(i) for i in range(len(synth))], list(synth.hw)
+            batches = H.plan_batches(sizes, args.batch, args.batching == "exact", args.size, args.max_size)
+            if args.loss != "ctc":
+                char_boxes = {i: synth.boxes(i) for i in range(len(synth))}
         for bi in rng.permutation(len(batches)):
             if step >= total:
                 break

@@ -1872,3 +1872,6 @@ from .msdagrad import VGRAD_SEGMENTS, VGRAD_TILE, msda_value_grad          # noq
 from .k256multi import K256_MULTI_MAX_UNITS, gemm_k256_a2, gemm_k256_multi, k256_multi_pack, k256_multi_plan          # noqa: E402,F401
 # the fourteenth header (include/dtlr_augment.h), the same way: written in dtlr_amd/augment.py (the training transform: preprocessing with erasing rectangles)
 from .augment import AUG_MAX_RECTS, augment_lines          # noqa: E402,F401
+# the fifteenth header (include/dtlr_synth.h), the same way: written in dtlr_amd/synthop.py (synthetic text lines rendered from a glyph atlas)
+from .synthop import (SYNTH_LINE_WORDS, SYNTH_MAX_GLYPHS, SYNTH_MAX_H, SYNTH_MAX_R, SYNTH_MAX_STAINS, SYNTH_MAX_W, SYNTH_STRIP,          # noqa: E402,F401
+                      synth_lines)

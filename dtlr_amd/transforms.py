@@ -295,6 +295,26 @@ class DeviceLineSet:
             self.pool[off: off + im.numel()].copy_(im.reshape(-1))
         self.offsets = torch.tensor(self.offs, dtype=torch.int64).to(self.device)
 
+    @classmethod
+    def from_pool(cls, pool, offs: Sequence[int], hw: Sequence[Tuple[int, int]]) -> "DeviceLineSet":
+        """A set over pixels that already lie on the device: `pool` uint8 [n] CUDA, image i its h x w x 3 bytes at byte offset offs[i]
+        (synthlines.SyntheticLineSet renders into such a pool).  Nothing is copied; ValueError for an image outside the pool."""
+        self = cls.__new__(cls)
+        self._adopt(pool, offs, hw)
+        return self
+
+    def _adopt(self, pool, offs: Sequence[int], hw: Sequence[Tuple[int, int]]) -> None:
+        if not (pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()):
+            raise ValueError("DeviceLineSet: the pool must be a contiguous uint8 vector on the GPU")
+        hw, offs = [(int(h), int(w)) for h, w in hw], [int(o) for o in offs]
+        if len(hw) == 0 or len(hw) != len(offs):
+            raise ValueError(f"DeviceLineSet: {len(hw)} sizes, {len(offs)} offsets")
+        if any(h <= 0 or w <= 0 or o < 0 or o + h * w * 3 > pool.numel() for o, (h, w) in zip(offs, hw)):
+            raise ValueError("DeviceLineSet: an image is empty or lies outside the pool")
+        self.device, self.hw, self.offs, self.pool = pool.device, hw, offs, pool
+        self.nbytes = sum(h * w * 3 for h, w in hw)
+        self.offsets = torch.tensor(offs, dtype=torch.int64).to(pool.device)
+
     def __len__(self) -> int:
         return len(self.hw)
 
