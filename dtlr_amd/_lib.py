@@ -142,6 +142,9 @@ _AUGMENT_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, param
 # include/dtlr_synth.h, the fifteenth header (synthetic text lines rendered from a glyph atlas): the same again
 _SYNTH_FUNCTIONS, _, SYNTH_CONSTANTS = _read_header_file("dtlr_synth.h")
 _SYNTH_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _SYNTH_FUNCTIONS.items()}
+# include/dtlr_convnext.h, the sixteenth header (the ConvNeXt backbone: depthwise 7x7 + LayerNorm, LayerNorm + 2x2 regrouping, stem): the same again
+_CONVNEXT_FUNCTIONS, _, CONVNEXT_CONSTANTS = _read_header_file("dtlr_convnext.h")
+_CONVNEXT_SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in _CONVNEXT_FUNCTIONS.items()}
 globals().update(CONSTANTS)            # DTLR_OK, DTLR_EINVAL .. DTLR_ELAUNCH; the dtype codes DTLR_F32, DTLR_F64, DTLR_BF16, DTLR_F16, DTLR_F32S
 
 
@@ -160,7 +163,8 @@ def takes_stream(name: str) -> bool:
     params = (_FUNCTIONS.get(name) or _LEXICON_FUNCTIONS.get(name) or _METRICS_FUNCTIONS.get(name) or _WORDBEAM_FUNCTIONS.get(name)
               or _LM_FUNCTIONS.get(name) or _PATTERN_FUNCTIONS.get(name) or _SETLOSS_FUNCTIONS.get(name) or _BOXGRAD_FUNCTIONS.get(name)
               or _TAILGRAD_FUNCTIONS.get(name) or _CROSSGRAD_FUNCTIONS.get(name) or _SELFGRAD_FUNCTIONS.get(name)
-              or _MSDAGRAD_FUNCTIONS.get(name) or _K256MULTI_FUNCTIONS.get(name) or _AUGMENT_FUNCTIONS.get(name) or _SYNTH_FUNCTIONS[name])[1]
+              or _MSDAGRAD_FUNCTIONS.get(name) or _K256MULTI_FUNCTIONS.get(name) or _AUGMENT_FUNCTIONS.get(name) or _SYNTH_FUNCTIONS.get(name)
+              or _CONVNEXT_FUNCTIONS[name])[1]
     return bool(params) and params[-1] == (c_void_p, "stream")
 
 
@@ -174,7 +178,8 @@ def _load(path: str) -> ctypes.CDLL:
                               + list(_SETLOSS_SIGNATURES.items()) + list(_BOXGRAD_SIGNATURES.items()) + list(_TAILGRAD_SIGNATURES.items())
                               + list(_CROSSGRAD_SIGNATURES.items()) + list(_SELFGRAD_SIGNATURES.items())
                               + list(_MSDAGRAD_SIGNATURES.items()) + list(_K256MULTI_SIGNATURES.items())
-                              + list(_AUGMENT_SIGNATURES.items()) + list(_SYNTH_SIGNATURES.items())):
+                              + list(_AUGMENT_SIGNATURES.items()) + list(_SYNTH_SIGNATURES.items())
+                              + list(_CONVNEXT_SIGNATURES.items())):
         fn = getattr(L, name)          # AttributeError if the .so is stale -> loud
         fn.restype, fn.argtypes = res, args
     return L

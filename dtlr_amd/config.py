@@ -49,6 +49,15 @@ class DTLRConfig:
     swin_depths: tuple = ()
     swin_num_heads: tuple = ()
     swin_window: int = 0
+    # ConvNeXt backbones (models/dino/backbone.py:206-208 -> convnext.py:237-242): the named variant below, or "convnext_custom" with
+    # convnext_depths / convnext_dims (test-sized networks)
+    convnext_depths: tuple = ()
+    convnext_dims: tuple = ()
+
+    def __post_init__(self):
+        # resnet101 is resnet50 with 23 blocks in layer3 (torchvision); an explicit non-default table (tiny test configs) wins
+        if self.backbone == "resnet101" and tuple(self.backbone_blocks) == (3, 4, 6, 3):
+            self.backbone_blocks = (3, 4, 23, 3)
 
     @property
     def head_dim(self) -> int:
@@ -73,8 +82,24 @@ class DTLRConfig:
                         window_size=self.swin_window)
         return dict(self.SWIN_VARIANTS[self.backbone])
 
+    CONVNEXT_VARIANTS = {   # convnext.py:237-242, the one name build_backbone accepts (backbone.py:206)
+        "convnext_xlarge_22k": dict(depths=(3, 3, 27, 3), dims=(256, 512, 1024, 2048)),
+    }
+
+    @property
+    def is_convnext(self) -> bool:
+        return self.backbone.startswith("convnext_")
+
+    def convnext_params(self) -> dict:
+        """depths / dims of the configured ConvNeXt backbone."""
+        if self.backbone == "convnext_custom":
+            return dict(depths=tuple(self.convnext_depths), dims=tuple(self.convnext_dims))
+        return dict(self.CONVNEXT_VARIANTS[self.backbone])
+
     @property
     def backbone_channels(self) -> List[int]:
+        if self.is_convnext:                                          # dims[1:] (backbone.py:208)
+            return list(self.convnext_params()["dims"][1:])
         if self.is_swin:                                              # num_features[1:] (backbone.py:204, swin_transformer.py:521)
             e = self.swin_params()["embed_dim"]
             return [2 * e, 4 * e, 8 * e]
@@ -82,9 +107,20 @@ class DTLRConfig:
 
     def validate(self) -> None:
         """Reject configurations outside the hot path."""
-        if self.backbone != "resnet50" and not (self.backbone in self.SWIN_VARIANTS or self.backbone == "swin_custom"):
-            raise NotImplementedError(f"backbone {self.backbone!r}: resnet50 (every shipped reference config, config/*.py:26) and the "
-                                      "Swin variants of models/dino/backbone.py:172 are built; resnet101 / convnext are not")
+        self.__post_init__()                  # a backbone named after construction gets its block table too
+        known = ("resnet50", "resnet101", "swin_custom", "convnext_custom") + tuple(self.SWIN_VARIANTS) + tuple(self.CONVNEXT_VARIANTS)
+        if self.backbone not in known:
+            raise NotImplementedError(f"backbone {self.backbone!r} is not one of {', '.join(known)} (models/dino/backbone.py:167-210 "
+                                      "builds no other)")
+        if self.is_convnext:
+            cp = self.convnext_params()
+            if len(cp["depths"]) != 4 or len(cp["dims"]) != 4 or any(int(n) <= 0 for n in cp["depths"]):
+                raise ValueError("convnext backbone: 4 stages with convnext_depths / convnext_dims set")
+            if any(int(c) <= 0 or int(c) % 32 for c in cp["dims"]):
+                raise NotImplementedError("convnext backbone: every dim must be a positive multiple of 32 (the depthwise kernel's lanes "
+                                          "run along channels in groups of 32)")
+            if cp["dims"][0] > 512 or max(cp["dims"]) > 4096 or max(cp["dims"][:3]) > 2048:
+                raise NotImplementedError("convnext backbone: dims[0] <= 512, dims[1..2] <= 2048, dims[3] <= 4096 (include/dtlr_convnext.h)")
         if self.is_swin:
             sp = self.swin_params()
             if len(sp["depths"]) != 4 or len(sp["num_heads"]) != 4 or sp["window_size"] <= 0 or sp["embed_dim"] <= 0:

@@ -187,6 +187,40 @@ class _SwinBackbone(nn.Module):
         self.num_channels = cfg.backbone_channels
 
 
+class _CnxLayerNorm(nn.Module):
+    def __init__(self, n):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(n))
+        self.bias = nn.Parameter(torch.zeros(n))
+
+
+class _CnxBlock(nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = _CnxLayerNorm(dim)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Parameter(torch.ones(dim))
+
+
+class _ConvNeXtBackbone(nn.Module):
+    """Parameter container with the state-dict layout of models/dino/convnext.py:77-107 (`backbone.0.*`).  All four norm{i} exist,
+    as in the reference, whatever return_interm_indices is: a strict load takes norm0, nothing uses it."""
+
+    def __init__(self, cfg: DTLRConfig):
+        super().__init__()
+        cp = cfg.convnext_params()
+        depths, dims = cp["depths"], cp["dims"]
+        self.downsample_layers = nn.ModuleList([nn.Sequential(nn.Conv2d(3, dims[0], kernel_size=4, stride=4), _CnxLayerNorm(dims[0]))])
+        for i in range(3):
+            self.downsample_layers.append(nn.Sequential(_CnxLayerNorm(dims[i]), nn.Conv2d(dims[i], dims[i + 1], kernel_size=2, stride=2)))
+        self.stages = nn.ModuleList(nn.Sequential(*[_CnxBlock(dims[i]) for _ in range(depths[i])]) for i in range(4))
+        for i in range(4):
+            setattr(self, f"norm{i}", _CnxLayerNorm(dims[i]))
+        self.num_channels = cfg.backbone_channels
+
+
 class MLP(nn.Module):
     """models/dino/utils.py:110-122 (container)."""
 
@@ -266,7 +300,8 @@ class DINO(nn.Module):
         proj = [nn.Sequential(nn.Conv2d(c, d, kernel_size=1), nn.GroupNorm(32, d)) for c in cfg.backbone_channels]
         proj.append(nn.Sequential(nn.Conv2d(cfg.backbone_channels[-1], d, kernel_size=3, stride=2, padding=1), nn.GroupNorm(32, d)))
         self.input_proj = nn.ModuleList(proj)
-        self.backbone = nn.Sequential(_SwinBackbone(cfg) if cfg.is_swin else _Backbone(cfg.backbone_blocks))
+        self.backbone = nn.Sequential(_ConvNeXtBackbone(cfg) if cfg.is_convnext else _SwinBackbone(cfg) if cfg.is_swin
+                                      else _Backbone(cfg.backbone_blocks))
         self.transformer = _Transformer(cfg)
         self.aux_loss = True
         self.dec_pred_class_embed_share = cfg.dec_pred_class_embed_share

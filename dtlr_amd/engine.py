@@ -290,9 +290,81 @@ class DTLREngine:
                 x = ops.linear(padk(ops.swin_patch_merge(x, w[q + "ln.w"], w[q + "ln.b"], ext=ext, s=2 + i), q + "w"), w[q + "w"], None)
         return outs
 
+    def _pack_convnext(self, sd):
+        """backbone.0.* of a ConvNeXt backbone (models/dino/convnext.py): the depthwise taps tap-major [49, C] fp32; the stem's weight
+        k-major [48, E] fp32; a downsample convolution as a GEMM weight [C', (dy, dx, c)] (the order dtlr_cnx_ln_gather2x2 writes);
+        gamma folded into pwconv2: gamma * (W h + b) = (gamma . W) h + gamma . b, so the layer scale and the residual ride the existing
+        GEMM epilogue (one rounding moves: the 16-bit engines round gamma . W once at pack time, where the reference multiplies the
+        rounded product by gamma -- DESIGN.md section 28).  norm0 is in the state dict and unused unless stage 0 is returned."""
+        cfg, f32 = self.cfg, torch.float32
+        cp = cfg.convnext_params()
+        depths, dims = cp["depths"], cp["dims"]
+        kpad = (lambda k: -(-k // 64) * 64) if self.dtype in ops.H16 else (lambda k: k)      # the 16-bit GEMM's 64-element K slab, as _pack_swin
+        b = "backbone.0."
+        self._put("cnx.stem.w", sd[b + "downsample_layers.0.0.weight"].float().reshape(dims[0], 48).t(), f32)      # [48, E], k-major
+        self._put("cnx.stem.b", sd[b + "downsample_layers.0.0.bias"], f32)
+        self._put("cnx.stem.ln.w", sd[b + "downsample_layers.0.1.weight"], f32)
+        self._put("cnx.stem.ln.b", sd[b + "downsample_layers.0.1.bias"], f32)
+        for i in range(4):
+            C = dims[i]
+            if i > 0:
+                p, q = f"{b}downsample_layers.{i}.", f"cnx.{i}.down."
+                self._put(q + "ln.w", sd[p + "0.weight"], f32)
+                self._put(q + "ln.b", sd[p + "0.bias"], f32)
+                self._put_linear(q[:-1], sd[p + "1.weight"].float().permute(0, 2, 3, 1).reshape(C, 4 * dims[i - 1]), sd[p + "1.bias"])
+            for j in range(depths[i]):
+                p, q = f"{b}stages.{i}.{j}.", f"cnx.{i}.{j}."
+                self._put(q + "dw.k", sd[p + "dwconv.weight"].float().reshape(C, 49).t(), f32)                       # [49, C], tap-major
+                self._put(q + "dw.b", sd[p + "dwconv.bias"], f32)
+                self._put(q + "ln.w", sd[p + "norm.weight"], f32)
+                self._put(q + "ln.b", sd[p + "norm.bias"], f32)
+                w1 = sd[p + "pwconv1.weight"].float()
+                if kpad(C) != C:
+                    w1 = torch.nn.functional.pad(w1, (0, kpad(C) - C))
+                self._put_linear(q + "pw1", w1, sd[p + "pwconv1.bias"])
+                g = sd[p + "gamma"].float()
+                self._put_linear(q + "pw2", g[:, None] * sd[p + "pwconv2.weight"].float(), g * sd[p + "pwconv2.bias"].float())
+            if i in cfg.return_interm_indices:
+                self._put(f"cnx.norm{i}.w", sd[f"{b}norm{i}.weight"], f32)
+                self._put(f"cnx.norm{i}.b", sd[f"{b}norm{i}.bias"], f32)
+
+    def backbone_convnext(self, x_nchw) -> List[torch.Tensor]:
+        """ConvNeXt.forward_features (models/dino/convnext.py:121-131) -> the NHWC maps of return_interm_indices after norm{i}.
+        Stage i runs on (floor(H / 2^(2+i)), floor(W / 2^(2+i))): the stem and the downsample convolutions are unpadded, so a trailing
+        partial patch is dropped -- where the ResNet and Swin paths give ceil.  A block is three launches: depthwise 7x7 + LayerNorm,
+        pwconv1 + GELU, pwconv2 (gamma folded in) + residual."""
+        cfg, w = self.cfg, self.w
+        cp = cfg.convnext_params()
+        if x_nchw.shape[2] < 32 or x_nchw.shape[3] < 32:
+            raise ValueError(f"convnext backbone: a {x_nchw.shape[2]} x {x_nchw.shape[3]} canvas leaves no pixel at stride 32 (sizes floor)")
+        x = ops.cnx_stem(x_nchw, w["cnx.stem.w"], w["cnx.stem.b"], w["cnx.stem.ln.w"], w["cnx.stem.ln.b"], self.dtype, 1e-6)
+
+        def padk(t, wname):                       # zero-pad the last dim to the packed weight's K (16-bit engines: see _pack_convnext)
+            kp = w[wname].shape[1]
+            if kp == t.shape[-1]:
+                return t
+            tp = t.new_zeros(t.shape[:-1] + (kp,))
+            tp[..., : t.shape[-1]] = t
+            return tp
+        outs = []
+        for i in range(4):
+            if i > 0:
+                q = f"cnx.{i}.down"
+                x = ops.linear(ops.cnx_ln_gather2x2(x, w[q + ".ln.w"], w[q + ".ln.b"], 1e-6), w[q + ".w"], w[q + ".b"])
+            for j in range(cp["depths"][i]):
+                q = f"cnx.{i}.{j}."
+                y = ops.cnx_dwconv_ln(x, w[q + "dw.k"], w[q + "dw.b"], w[q + "ln.w"], w[q + "ln.b"], 1e-6)
+                hdn = ops.linear(padk(y, q + "pw1.w"), w[q + "pw1.w"], w[q + "pw1.b"], relu=3)
+                x = ops.linear(hdn, w[q + "pw2.w"], w[q + "pw2.b"], residual=x)
+            if i in cfg.return_interm_indices:
+                outs.append(ops.layernorm(x, w[f"cnx.norm{i}.w"], w[f"cnx.norm{i}.b"], 1e-6))
+        return outs
+
     def _pack(self, sd):
         cfg, f32 = self.cfg, torch.float32
-        if cfg.is_swin:
+        if cfg.is_convnext:
+            self._pack_convnext(sd)
+        elif cfg.is_swin:
             self._pack_swin(sd)
         else:
             self._pack_resnet(sd)
@@ -323,6 +395,10 @@ class DTLREngine:
         cfg, f32 = self.cfg, torch.float32
         for l in range(cfg.num_feature_levels):
             w, bias = sd[f"input_proj.{l}.0.weight"].float(), sd[f"input_proj.{l}.0.bias"].float()
+            if cfg.is_convnext and self.dtype in ops.H16 and w.shape[1] % 64:
+                # test-sized ConvNeXt dims (96, 160) on the 16-bit engines: input channels zero-padded to the GEMM's 64-element K slab, the
+                # maps padded to match where they are consumed (_padc); no named variant has such a dim
+                w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, -w.shape[1] % 64))
             if l < cfg.num_feature_levels - 1:
                 self._put_linear(f"ip{l}", w.flatten(1), bias)            # 1x1 conv == linear on NHWC tokens
             else:
@@ -449,6 +525,17 @@ class DTLREngine:
             # [offsets | logits] of tgt + query_pos (decoder) or src + pos (encoder, padded batch): the sum formed on chip, weights resident
             return ops.gemm_k256_a2(x, a2, self._image("k256", name), self.w[name + ".b"], row_mask=row_mask)
         return ops.linear(x, w, self.w[name + ".b"], relu, residual, a2, row_mask, out_dtype)
+
+    def _padc(self, name, x):
+        """x [..., C] zero-padded along C to the input channels of weight `name` (ConvNeXt test dims on the 16-bit engines, _pack_rest);
+        x itself whenever the widths agree, which is every other case"""
+        w = self.w[name + ".w"]
+        kp = w.shape[1] if w.dim() == 2 else w.shape[3]
+        if kp == x.shape[-1]:
+            return x
+        xp = x.new_zeros(x.shape[:-1] + (kp,))
+        xp[..., : x.shape[-1]] = x
+        return xp
 
     def _ln(self, name, x, residual=None):
         return ops.layernorm(x, self.w[name + ".w"], self.w[name + ".b"], 1e-5, residual)
@@ -1126,11 +1213,15 @@ class DTLREngine:
     def features(self, x, ext=None):
         """backbone maps (NHWC) + the extra stride-2 level's convolution (dino.py:290-311) and the level sizes.
         ext (per-line batches): the backbone's extent handling, and the last map zeroed outside the extents before the 3x3/s2 conv."""
-        feats = self.backbone_swin(x.float(), ext) if self.cfg.is_swin else self.backbone(x.float(), ext)
+        if self.cfg.is_convnext:
+            assert ext is None                    # forward() refuses per-line batches for ConvNeXt
+            feats = self.backbone_convnext(x.float())
+        else:
+            feats = self.backbone_swin(x.float(), ext) if self.cfg.is_swin else self.backbone(x.float(), ext)
         level_hw = [(f.shape[1], f.shape[2]) for f in feats]
         if ext is not None:
             ops.zero_outside_extent(feats[-1], ext, 2 + len(feats))
-        last = self._conv(f"ip{len(feats)}", feats[-1], 2, 1)
+        last = self._conv(f"ip{len(feats)}", self._padc(f"ip{len(feats)}", feats[-1]), 2, 1)
         level_hw.append((last.shape[1], last.shape[2]))
         return feats, last, level_hw
 
@@ -1195,7 +1286,7 @@ class DTLREngine:
         src = torch.empty((B, S_tot, self.cfg.hidden_dim), dtype=self.dtype, device=last.device)
         off = 0
         for l, f in enumerate(list(feats) + [last]):
-            t = self._lin(f"ip{l}", f.flatten(1, 2)) if l < len(feats) else f.flatten(1, 2)
+            t = self._lin(f"ip{l}", self._padc(f"ip{l}", f).flatten(1, 2)) if l < len(feats) else f.flatten(1, 2)
             T_l = t.shape[1]
             if ext is not None:
                 ops.groupnorm_tokens_ext(t, level_hw[l], ext, 3 + l, 32, self.w[f"ip{l}.gn.w"], self.w[f"ip{l}.gn.b"], out=src[:, off:off + T_l])
@@ -1268,6 +1359,10 @@ class DTLREngine:
         B = x.shape[0]
         ext = None
         if per_line:
+            if cfg.is_convnext:
+                raise NotImplementedError("per_line (ragged batching) with a ConvNeXt backbone: its levels are floor(h / 2^s) of a line's "
+                                          "size, and the extent machinery (extent.hip, the MSDA extent forms, the level masks) is built on "
+                                          "ceil(h / 2^s) throughout -- use exact or padded batching")
             if cfg.num_feature_levels != 4 or len(cfg.backbone_blocks) != 4:
                 raise NotImplementedError("per_line: written for the 4-level ResNet configuration")
             if sizes is not None:
@@ -1283,7 +1378,7 @@ class DTLREngine:
             # forward then allocates nothing and dispatches exactly as an eager one (dtlr_hip.h, dtlr_workspace_reserve)
             ops.workspace_reserve(self.dtype)
             self._ws_streams.add(st)
-        overlap = self.overlap_streams and not cfg.is_swin and not per_line
+        overlap = self.overlap_streams and not cfg.is_swin and not cfg.is_convnext and not per_line
         src = None
         if overlap:
             feats, last, level_hw, src = self._features_tokens_overlapped(x)

@@ -1875,3 +1875,5 @@ from .augment import AUG_MAX_RECTS, augment_lines          # noqa: E402,F401
 # the fifteenth header (include/dtlr_synth.h), the same way: written in dtlr_amd/synthop.py (synthetic text lines rendered from a glyph atlas)
 from .synthop import (SYNTH_LINE_WORDS, SYNTH_MAX_GLYPHS, SYNTH_MAX_H, SYNTH_MAX_R, SYNTH_MAX_STAINS, SYNTH_MAX_W, SYNTH_STRIP,          # noqa: E402,F401
                       synth_lines)
+# the sixteenth header (include/dtlr_convnext.h), the same way: written in dtlr_amd/convnextop.py (the ConvNeXt backbone: depthwise 7x7 + LayerNorm, LayerNorm + 2x2 regrouping, stem)
+from .convnextop import CNX_GATHER_MAX_C, CNX_MAX_C, CNX_STEM_MAX_E, cnx_dwconv_ln, cnx_ln_gather2x2, cnx_stem, cnx_tile          # noqa: E402,F401

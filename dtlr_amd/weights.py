@@ -195,9 +195,11 @@ def synthetic_state_dict(cfg: DTLRConfig, seed: int = 0, version: int = GENERATO
 
     if cfg.is_swin:
         _swin(sd, cfg, seed)
+    if cfg.is_convnext:
+        _convnext(sd, cfg, seed)
     # ---- backbone.0.body.* : ResNet-50 v1.5 with FrozenBN -----------------------------------
     b = "backbone.0.body."
-    if not cfg.is_swin:
+    if not cfg.is_swin and not cfg.is_convnext:
         _resnet(sd, cfg, seed)
     _rest(sd, cfg, seed, d, C, ff, version)
     return sd
@@ -236,6 +238,41 @@ def _swin(sd, cfg: DTLRConfig, seed: int):
             sd[p + "reduction.weight"] = _normal(p + "reduction.weight", seed, (2 * C, 4 * C), 1.0 / math.sqrt(4 * C))
         if i in cfg.return_interm_indices:
             _norm(sd, f"{b}norm{i}", C, seed)
+
+
+def _cnx_norm(sd, name, n, seed):
+    # LayerNorm of a ConvNeXt backbone: weights around 1, biases around 0, both with a spread a test can see
+    sd[name + ".weight"] = _uniform(name + ".weight", seed, (n,), 0.7, 1.3)
+    sd[name + ".bias"] = _normal(name + ".bias", seed, (n,), 0.1)
+
+
+def _convnext(sd, cfg: DTLRConfig, seed: int):
+    """backbone.0.* of a ConvNeXt backbone (models/dino/convnext.py:77-107: downsample_layers, stages.{i}.{j}, norm{0..3}).  gamma is
+    drawn of order one, NOT at the reference's initial 1e-6: with 1e-6 every block is the identity to seven digits and no comparison
+    would see the block body.  New names only: no tensor of another backbone moves (GENERATOR_VERSION stays)."""
+    cp = cfg.convnext_params()
+    depths, dims = cp["depths"], cp["dims"]
+    b = "backbone.0."
+    _conv(sd, b + "downsample_layers.0.0.weight", dims[0], 3, 4, seed, gain=1.0)
+    sd[b + "downsample_layers.0.0.bias"] = _normal(b + "downsample_layers.0.0.bias", seed, (dims[0],), 0.02)
+    _cnx_norm(sd, b + "downsample_layers.0.1", dims[0], seed)
+    for i in range(3):
+        p = f"{b}downsample_layers.{i + 1}."
+        _cnx_norm(sd, p + "0", dims[i], seed)
+        _conv(sd, p + "1.weight", dims[i + 1], dims[i], 2, seed, gain=1.0)
+        sd[p + "1.bias"] = _normal(p + "1.bias", seed, (dims[i + 1],), 0.02)
+    for i in range(4):
+        C = dims[i]
+        for j in range(depths[i]):
+            p = f"{b}stages.{i}.{j}."
+            sd[p + "dwconv.weight"] = _normal(p + "dwconv.weight", seed, (C, 1, 7, 7), 1.0 / 7.0)
+            sd[p + "dwconv.bias"] = _normal(p + "dwconv.bias", seed, (C,), 0.1)
+            _cnx_norm(sd, p + "norm", C, seed)
+            _linear(sd, p + "pwconv1", 4 * C, C, seed, gain=math.sqrt(2.0))
+            _linear(sd, p + "pwconv2", C, 4 * C, seed, gain=0.5)
+            sd[p + "gamma"] = _uniform(p + "gamma", seed, (C,), 0.5, 1.5)
+    for i in range(4):
+        _cnx_norm(sd, f"{b}norm{i}", dims[i], seed)
 
 
 def _resnet(sd, cfg: DTLRConfig, seed: int):

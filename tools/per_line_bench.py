@@ -59,7 +59,8 @@ def main():
     crops, resized = iam_like_sizes(args.lines, args.seed)
     lines = [synth.stroke_lines(1, h, w, seed=1000 + i)[0].cuda() for i, (h, w) in enumerate(resized)]
     plans = {"exact": H.plan_batches(crops, args.batch, True, 800, 1333), "padded": H.plan_batches(crops, args.batch, False, 800, 1333)}
-    plans["ragged"] = plans["padded"]
+    if not cfg.is_convnext:                   # ragged batching is not built for ConvNeXt (floor level sizes)
+        plans["ragged"] = plans["padded"]
     for eng in args.engines.split(","):
         m = DINO(cfg, compute_dtype={"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "f32s": "f32s"}[eng])
         m.load_state_dict(sd)
@@ -79,9 +80,10 @@ def main():
             can = sum(len(b) * max(resized[i][0] for i in b) * max(resized[i][1] for i in b) for b in plan)
             rec[mode] = {"lines_per_s": round(args.lines / best, 1), "mean_batch": round(args.lines / len(plan), 2),
                          "canvas_fill": round(pix / can, 4)}
-        rec["ragged_over_padded"] = round(rec["ragged"]["lines_per_s"] / rec["padded"]["lines_per_s"], 3)
-        rec["ragged_over_exact"] = round(rec["ragged"]["lines_per_s"] / rec["exact"]["lines_per_s"], 3)
-        for mode in ("ragged", "padded"):
+        if "ragged" in plans:
+            rec["ragged_over_padded"] = round(rec["ragged"]["lines_per_s"] / rec["padded"]["lines_per_s"], 3)
+            rec["ragged_over_exact"] = round(rec["ragged"]["lines_per_s"] / rec["exact"]["lines_per_s"], 3)
+        for mode in [m_ for m_ in ("ragged", "padded") if m_ in plans]:
             dl = max((a[0] - b[0]).abs().max().item() for a, b in zip(outs[mode], outs["exact"]))
             db = max((a[1] - b[1]).abs().max().item() for a, b in zip(outs[mode], outs["exact"]))
             ds = sum(decode_blank({"pred_logits": a[0][None].float(), "pred_boxes": a[1][None].float()}) !=
