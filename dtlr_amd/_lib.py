@@ -243,7 +243,7 @@ def query(L, name: str, *args):
 
 
 # What the bindings of the gradient headers (boxgrad.py, tailgrad.py, crossgrad.py, selfgrad.py, msdagrad.py) share: the dtype codes of their activations, the fp32 operand
-# check, and a workspace of whole 16-byte units (the entry points refuse a workspace that is not 16-byte aligned).
+# check, the master-weight check, and a workspace of whole 16-byte units (the entry points refuse a workspace that is not 16-byte aligned).
 DT = {torch.float32: CONSTANTS["DTLR_F32"], torch.bfloat16: CONSTANTS["DTLR_BF16"], torch.float16: CONSTANTS["DTLR_F16"]}
 
 
@@ -255,6 +255,14 @@ def gpu(t, what):
 
 def f32(t, what):
     return gpu(t, what).float().contiguous()
+
+
+def masters(params, shapes, device, message):
+    """the master weights of a block -> contiguous; ValueError(message) unless they are fp32 on `device` with exactly `shapes`"""
+    ws = [w.contiguous() for w in params]
+    if tuple(tuple(w.shape) for w in ws) != tuple(shapes) or any(w.dtype != torch.float32 or w.device != device for w in ws):
+        raise ValueError(message)
+    return ws
 
 
 def workspace(nbytes, dev, what):

@@ -76,14 +76,6 @@ def msda_query_grad(value, spatial_shapes, level_start_index, sampling_loc, attn
     return gl, ga
 
 
-def _masters(cross, dev, what):
-    ws = [w.contiguous() for w in cross]
-    if len(ws) != 8 or tuple(tuple(w.shape) for w in ws) != CROSS_SHAPES or any(w.dtype != torch.float32 or w.device != dev for w in ws):
-        raise ValueError(f"{what}: the masters must be fp32 on {dev}: sampling_offsets [256,256] / [256], attention_weights [128,256] / [128], "
-                         "output_proj [256,256] / [256], norm1 [256] / [256]")
-    return ws
-
-
 @_lib.op
 def cross_recompute(s, qpos, ref_in, value, spatial_shapes, level_start_index, cross: Sequence[torch.Tensor], eps: float = LN_EPS) -> Dict[str, torch.Tensor]:
     """dtlr_cross_recompute: the last decoder layer's cross-attention block in fp32 from the masters.  s, qpos [N,Lq,256] (fp32 / bf16 /
@@ -103,7 +95,8 @@ def cross_recompute(s, qpos, ref_in, value, spatial_shapes, level_start_index, c
     vstride = _value_view(_lib.gpu(value, "value"), "cross_recompute")
     s, qpos, ref_in = s.contiguous(), qpos.contiguous(), _lib.f32(ref_in, "ref_in")
     spatial_shapes, level_start_index = _lib.gpu(spatial_shapes, "spatial_shapes").contiguous(), _lib.gpu(level_start_index, "level_start_index").contiguous()
-    wso, bso, waw, baw, wo, bo, g1, b1 = _masters(cross, dev, "cross_recompute")
+    wso, bso, waw, baw, wo, bo, g1, b1 = _lib.masters(cross, CROSS_SHAPES, dev, f"cross_recompute: the masters must be fp32 on {dev}: sampling_offsets "
+                                                      "[256,256] / [256], attention_weights [128,256] / [128], output_proj [256,256] / [256], norm1 [256] / [256]")
     wow, bow = torch.cat([wso, waw]), torch.cat([bso, baw])                  # the 384 x 256 projection the forward runs
     M = N * Lq
     f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)

@@ -251,16 +251,16 @@ extern "C" int dtlr_box_mlp_grad(const void* x_ptrs, const void* dy_ptrs, const 
     if (!x_ptrs || !dy_ptrs || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !grad || !workspace) return DTLR_EINVAL;
     if (A < 1 || M <= 0 || (rows && R <= 0)) return DTLR_EINVAL;
     if (A > DTLR_BOX_GRAD_MAX_APPS) return DTLR_ESHAPE;
-    if (x_dtype != DTLR_F32 && x_dtype != DTLR_H16) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(x_dtype)) return DTLR_EDTYPE;
     const BgPlan q = bg_plan(A, M, rows ? R : 0);
     if (!q.ok) return DTLR_ESHAPE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return DTLR_EINVAL;
+    if (misaligned(workspace, 15)) return DTLR_EINVAL;
     BgApps apps{};
     for (int a = 0; a < A; ++a) {
         apps.x[a] = static_cast<const void* const*>(x_ptrs)[a];
         apps.dy[a] = static_cast<const float* const*>(dy_ptrs)[a];
-        if (!apps.x[a] || !apps.dy[a] || (reinterpret_cast<uintptr_t>(apps.dy[a]) & 15)) return DTLR_EINVAL;
-        if (reinterpret_cast<uintptr_t>(apps.x[a]) & (x_dtype == DTLR_F32 ? 3 : 1)) return DTLR_EINVAL;
+        if (!apps.x[a] || !apps.dy[a] || misaligned(apps.dy[a], 15)) return DTLR_EINVAL;
+        if (misaligned(apps.x[a], x_dtype == DTLR_F32 ? 3 : 1)) return DTLR_EINVAL;
     }
     const BgWs w = bg_ws(static_cast<float*>(workspace), q.Rp, q.splits);
     const hipStream_t st = (hipStream_t)stream;

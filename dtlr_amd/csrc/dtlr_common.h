@@ -96,6 +96,10 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) { return (uint16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// ---- argument checks of the gradient entry points (host) ----------------------------------------------------------------
+inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+inline bool is_f32_or_h16(int dt) { return dt == DTLR_F32 || dt == DTLR_H16; }      // an activation's dtype code: fp32 or this build's 16-bit format
+
 // ---- A/B switches of the measurement builds.  The product libraries are compiled WITHOUT -DDTLR_EXPERIMENT: every switch below is then
 // its default, a compile-time constant, and no environment variable can change what a kernel launch does.  `python -m dtlr_amd.build
 // --instr` (never loaded by the product) defines DTLR_EXPERIMENT and reads them from the environment, once per process.

@@ -1,7 +1,11 @@
-// The 32-row x 256-column tile product shared by the row kernels of dtlr_box_mlp_grad (box_grad.hip) and of the decoder tail's gradient
-// (tail_grad.hip: tg_rows_gemm_kernel, tg_box_dx_kernel): thread n owns one output column for the tile's 32 rows, the activations lie in
+// The 32-row x 256-column tile product shared by the row kernels of dtlr_box_mlp_grad (box_grad.hip), of the decoder tail's gradient
+// (tail_grad.hip: tg_rows_gemm_kernel, tg_box_dx_kernel) and of grad_rows.hip (gr_rows_gemm256_kernel): thread n owns one output column for the tile's 32 rows, the activations lie in
 // LDS transposed ([k][row], pitch GR_LD) and are broadcast from there, the weight is read k-major, coalesced over n.  Plain fp32 FMAs,
-// 32 terms a stage in an fp32 accumulator; the stages are added in order into an accumulator of the caller's type.  No launches here.
+// 32 terms a stage in an fp32 accumulator; the stages are added in order into an accumulator of the caller's type.
+// Below it, the three launches that several gradient files make, each kernel defined once in grad_rows.hip: the 32 x 32 transpose
+// (tail_grad.hip, cross_grad.hip, self_grad.hip), the LayerNorm forward over rows of 256 and the K = 256 two-stream row product
+// (cross_grad.hip, self_grad.hip).  tg_rows_gemm_kernel (runtime K, long weight index, ReLU / mask / accumulate epilogue) has one user
+// and stays in tail_grad.hip.
 #pragma once
 #include "dtlr_common.h"
 
@@ -44,5 +48,23 @@ __device__ __forceinline__ void gr_mac(const float* __restrict__ Wt, Idx ldw, in
         for (int r = 0; r < GR_TR; ++r) acc[r] += (Acc)c[r];
     }
 }
+
+// the 32-row tiles of M rows: the x extent of every row product's grid
+inline unsigned gr_tiles(long M) { return (unsigned)((M + GR_TR - 1) / GR_TR); }
+
+// out[m][n] = sum_k (A[m][k] + A2[m][k]) Wt[k][n] + bias[n] + res[m][n], K = 256, m < M, n < N.  A, A2 (optional; both 16-bit when
+// a_h16) and res (optional; row pitch N, 16-bit when res_h16) in fp32 or the 16-bit format ; Wt k-major with row pitch ldw ; out has row
+// pitch ldo, out2 (optional, row pitch ldo2) receives the same values ; xsum (optional) receives A + A2 in fp32, [M,256].
+struct GrRows256 {
+    const void* A; const void* A2; int a_h16; long M;
+    const float* Wt; int ldw; int N; const float* bias;
+    const void* res; int res_h16;
+    float* out; int ldo; float* out2; int ldo2; float* xsum;
+};
+
+// Each enqueues one launch on `stream` and returns DTLR_OK or DTLR_ELAUNCH (defined in grad_rows.hip).
+int gr_transpose(const float* src, float* dst, int R, int C, hipStream_t stream);                     // dst[c][r] = src[r][c], src [R, C]
+int gr_layernorm256(const float* x, const float* gamma, const float* beta, float* out, long M, float eps, hipStream_t stream);
+int gr_rows_gemm256(const GrRows256& g, hipStream_t stream);
 
 }  // namespace dtlr

@@ -98,7 +98,7 @@ extern "C" int dtlr_head_grad(const float* G, const float* X, float* dW, float* 
     if (!G || !X || !dW || !db || !workspace) return DTLR_EINVAL;
     if (M <= 0 || C <= 0 || D <= 0) return DTLR_EINVAL;
     if (D % HG_TD) return DTLR_ESHAPE;
-    if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(workspace)) & 15) return DTLR_EINVAL;
+    if (misaligned(X, 15) || misaligned(workspace, 15)) return DTLR_EINVAL;
     const HgPlan p = hg_plan(M, C, D);
     const long nW = (long)C * D;
     float* part = workspace;
@@ -115,7 +115,7 @@ extern "C" int dtlr_grad_norm_scale(const float* grad, long n, float max_norm, f
 {
     clear_stale_error();
     if (!grad || !scale_out || !workspace || n <= 0) return DTLR_EINVAL;
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) return DTLR_EINVAL;
+    if (misaligned(workspace, 7)) return DTLR_EINVAL;
     long nb = (n + 255) / 256;
     if (nb > GN_BLOCKS) nb = GN_BLOCKS;
     if (int rc = launch<sumsq_partial_kernel>(dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, grad, n, (double*)workspace)) return rc;

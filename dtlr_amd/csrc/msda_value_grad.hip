@@ -5,12 +5,13 @@
 //   lane      = one pixel, its 32 channel sums in registers
 //   wavefront = one fixed quarter of the queries, [w ceil(Lq / 4), (w + 1) ceil(Lq / 4))
 // For each level the tile meets, a wavefront walks its queries' samples of that level in ascending (q, p), 64 at a time: every lane takes
-// one sample, forms cross_grad.hip's geometry for it and tests its corners against the tile; a ballot gives the hits.  The hits are taken
+// one sample, forms msda_grad_geo.h's point for it (the one cross_grad.hip's kernels form) and tests its corners against the tile; a
+// ballot gives the hits.  The hits are taken
 // in ascending order: the sample's (y0, x0, ly, lx, attn) are broadcast, its grad_out row is read through a wavefront-uniform address, and
 // every lane adds weight x row, the weight being zero unless the lane's pixel is one of the four corners.  The four wavefronts' sums meet
 // in LDS and are added in segment order by the first, which stores each row once.  No atomics; the order of every sum depends on Lq alone.
 #include "gfx950_prims.h"
-#include "dtlr_common.h"
+#include "msda_grad_geo.h"
 #include "../../include/dtlr_msdagrad.h"
 
 namespace dtlr {
@@ -18,7 +19,6 @@ namespace dtlr {
 constexpr int VG_TILE = DTLR_VGRAD_TILE, VG_SEG = DTLR_VGRAD_SEGMENTS, VG_HD = 32, VG_ROW = 256;
 static_assert(VG_TILE == 64 && VG_SEG == 4, "a lane a pixel, a wavefront a segment, 256 threads");
 
-__device__ __forceinline__ long vg_clamp(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int vg_bcast(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 __device__ __forceinline__ float vg_bcast(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 
@@ -43,9 +43,9 @@ __global__ __launch_bounds__(256) void vg_value_grad_kernel(const long* __restri
     bool owned = false;                                             // a row belongs to the first level that claims it
 #pragma unroll 1
     for (int l = 0; l < 4; ++l) {
-        // the level table, made safe as cross_grad.hip makes it: 1 <= H, W <= 2^15, 0 <= start <= S - 1 (S < 2^23: all of this fits an int)
-        const int H = (int)vg_clamp(shapes[2 * l], 1, 32768), W = (int)vg_clamp(shapes[2 * l + 1], 1, 32768);
-        const int st = (int)vg_clamp(lsi[l], 0, (long)S - 1);
+        // the level's entry of the table, made safe as geo_levels makes it: 1 <= H, W <= 2^15, 0 <= start <= S - 1 (S < 2^23: all of this fits an int)
+        const int H = (int)geo_clamp(shapes[2 * l], 1, 32768), W = (int)geo_clamp(shapes[2 * l + 1], 1, 32768);
+        const int st = (int)geo_clamp(lsi[l], 0, (long)S - 1);
         const int HW = H * W;
         const bool mine = !owned && (unsigned)(f - st) < (unsigned)HW;
         owned = owned || mine;
@@ -59,13 +59,8 @@ __global__ __launch_bounds__(256) void vg_value_grad_kernel(const long* __restri
             const int lp = l * 4 + (j & 3);
             const float2 c = *reinterpret_cast<const float2*>(loc + si * 32 + lp * 2);
             const float a = attn[si * 16 + lp];
-            // cross_grad.hip's cg_geo: px = loc_x W - 0.5, clamped to [-1, size] (a NaN becomes -1), the reference's test on the unclamped point
-            const float fh = c.y * (float)H - 0.5f, fw = c.x * (float)W - 0.5f;
-            const bool inside = fh > -1.f && fw > -1.f && fh < (float)H && fw < (float)W;
-            const float h_im = __builtin_amdgcn_fmed3f(fh, -1.f, (float)H), w_im = __builtin_amdgcn_fmed3f(fw, -1.f, (float)W);
-            const float hf = floorf(h_im), wf = floorf(w_im);
-            const float lh = h_im - hf, lw = w_im - wf;
-            const int y0 = (int)hf, x0 = (int)wf;
+            const GeoPoint pt = geo_point(c.x, c.y, H, W);
+            const int y0 = pt.y0, x0 = pt.x0;
             bool hit = false;
 #pragma unroll
             for (int cy = 0; cy < 2; ++cy)
@@ -74,12 +69,12 @@ __global__ __launch_bounds__(256) void vg_value_grad_kernel(const long* __restri
                     const int yy = y0 + cy, xx = x0 + cx;
                     hit = hit || ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W && (unsigned)(st + yy * W + xx - f0) < (unsigned)VG_TILE);
                 }
-            unsigned long long m = __ballot(hit && have && inside);
+            unsigned long long m = __ballot(hit && have && pt.inside);
             while (m) {                                             // wavefront-uniform: ascending samples
                 const int i = __builtin_ctzll(m);
                 m &= m - 1;
                 const int sy0 = vg_bcast(y0, i), sx0 = vg_bcast(x0, i);
-                const float slh = vg_bcast(lh, i), slw = vg_bcast(lw, i), sa = vg_bcast(a, i);
+                const float slh = vg_bcast(pt.lh, i), slw = vg_bcast(pt.lw, i), sa = vg_bcast(a, i);
                 const int qi = __builtin_amdgcn_readfirstlane((base + i) >> 2);
                 const float* __restrict__ g = go + ((long)n * Lq + qi) * VG_ROW + h * VG_HD;
                 const int dy = ypix - sy0, dx = xpix - sx0;
@@ -106,8 +101,6 @@ __global__ __launch_bounds__(256) void vg_value_grad_kernel(const long* __restri
     for (int k = 0; k < VG_HD / 4; ++k) out[k] = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
 }
 
-static inline bool vg_mis(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 }  // namespace dtlr
 
 using namespace dtlr;
@@ -123,7 +116,7 @@ extern "C" int dtlr_msda_value_grad(const long* shapes, const long* lsi, const f
     const int tiles = (S + VG_TILE - 1) / VG_TILE;
     const long blocks = (long)N * 8 * tiles;
     if (blocks >= (1l << 31)) return DTLR_ESHAPE;
-    if (vg_mis(loc) || vg_mis(attn) || vg_mis(grad_out) || vg_mis(grad_value)) return DTLR_EINVAL;
+    if (misaligned(loc, 15) || misaligned(attn, 15) || misaligned(grad_out, 15) || misaligned(grad_value, 15)) return DTLR_EINVAL;
     return launch<vg_value_grad_kernel>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, shapes, lsi, loc, attn, grad_out, S, Lq, tiles,
                                         grad_value);
 }

@@ -13,7 +13,8 @@
 // layout of the second, so the probabilities go from one to the other in registers; the other operand of the second product is read
 // transposed (a lane reads one float, 16 lanes a 64-byte piece of a row).  S and dP are formed by the same MFMA chain in all three
 // kernels, so that P = exp2(S c - m) never exceeds 1 and, at L = 1, dS is exactly zero.  No LDS, no atomics; every sum in a fixed order.
-// The two row products are grad_rows.h's 32-row tile product (exact fp32 FMAs, 32 terms in fp32, the stages in fp64).
+// The weight transposes, the three row products and norm2 are grad_rows.h's launches (gr_transpose, gr_rows_gemm256, gr_layernorm256: the
+// kernels cross_grad.hip runs too).
 #include "gfx950_prims.h"
 #include "grad_rows.h"
 #include "../../include/dtlr_selfgrad.h"
@@ -22,84 +23,6 @@ namespace dtlr {
 
 static_assert(GR_D == DTLR_SELF_HIDDEN && DTLR_SELF_HEADS * DTLR_SELF_HEAD_DIM == DTLR_SELF_HIDDEN, "8 heads x 32 channels");
 constexpr int SG_QKV = 3 * GR_D;                                    // [Q | K | V]
-
-// ------------------------------------------------------------------------------------------------------------ the row products
-// out[m][n] = sum_k (A[m][k] + A2[m][k]) Wt[k][n] + bias[n] + res[m][n], K = 256 ; A, A2 (optional), res (optional) in fp32 or the 16-bit
-// format ; out has row pitch ldo, out2 (optional, row pitch ldo2) receives the same values ; xsum (optional): receives A + A2 in fp32.
-// grid (ceil(M / 32), ceil(N / 256)).
-__global__ __launch_bounds__(256) void sg_rows_gemm_kernel(const void* __restrict__ A, const void* __restrict__ A2, int a_h16, long M,
-                                                           const float* __restrict__ Wt, int ldw, int N, const float* __restrict__ bias,
-                                                           const void* __restrict__ res, int res_h16, float* __restrict__ out, int ldo,
-                                                           float* __restrict__ out2, int ldo2, float* __restrict__ xsum)
-{
-    __shared__ __attribute__((aligned(16))) float As[32 * GR_LD];
-    const long m0 = (long)blockIdx.x * GR_TR;
-    const int n = (int)blockIdx.y * 256 + threadIdx.x;
-    const bool nvalid = n < N;
-    const int sr = threadIdx.x >> 3, sk = (threadIdx.x & 7) * 4;
-    const long sm = m0 + sr;
-    double acc[GR_TR];
-#pragma unroll
-    for (int r = 0; r < GR_TR; ++r) acc[r] = 0.0;
-    for (int kc = 0; kc < GR_D; kc += 32) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = kc + sk + j;
-            float v = 0.f;
-            if (sm < M) {
-                v = gr_load(A, a_h16, sm * GR_D + k);
-                if (A2) v += gr_load(A2, a_h16, sm * GR_D + k);
-                if (xsum && blockIdx.y == 0) xsum[sm * GR_D + k] = v;
-            }
-            As[(sk + j) * GR_LD + sr] = v;
-        }
-        __syncthreads();
-        gr_mac<double, true, int>(Wt + (long)kc * ldw, ldw, n, nvalid, As, 32, GR_D - kc, acc);
-    }
-    if (!nvalid) return;
-    const double bn = (double)bias[n];
-#pragma unroll
-    for (int r = 0; r < GR_TR; ++r) {
-        const long m = m0 + r;
-        if (m >= M) continue;
-        double v = acc[r] + bn;
-        if (res) v += (double)gr_load(res, res_h16, m * N + n);
-        out[m * ldo + n] = (float)v;
-        if (out2) out2[m * ldo2 + n] = (float)v;
-    }
-}
-
-// dst[c][r] = src[r][c], src [R, C]
-__global__ __launch_bounds__(256) void sg_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int C)
-{
-    __shared__ float t[32][33];
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int j = ty; j < 32; j += 8)
-        if (r0 + j < R && c0 + tx < C) t[j][tx] = src[(long)(r0 + j) * C + c0 + tx];
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (c0 + j < C && r0 + tx < R) dst[(long)(c0 + j) * R + r0 + tx] = t[tx][j];
-}
-
-// s = LayerNorm(x) over rows of 256: one wavefront a row, statistics fp32 two-pass (as dtlr_ln_backward takes them)
-__global__ __launch_bounds__(256) void sg_ln_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float* __restrict__ s, long M, float eps)
-{
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;                                           // wavefront-uniform
-    const float4 t = *reinterpret_cast<const float4*>(x + row * GR_D + 4 * lane);
-    float v[4] = {t.x, t.y, t.z, t.w};
-    const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / GR_D);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] -= mean; q += v[j] * v[j]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / GR_D) + eps);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = v[j] * rstd * gamma[4 * lane + j] + beta[4 * lane + j];      // views of a flat buffer: no alignment
-    *reinterpret_cast<float4*>(s + row * GR_D + 4 * lane) = make_float4(v[0], v[1], v[2], v[3]);
-}
 
 // ------------------------------------------------------------------------------------------------------------ the attention core's backward
 // 8 contiguous floats of a row
@@ -288,7 +211,6 @@ __global__ __launch_bounds__(256) void sg_mha_dkv_kernel(const float* __restrict
     }
 }
 
-static inline bool sg_mis(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 static inline long sg_lp(long L) { return (L + 15) / 16 * 16; }
 
 }  // namespace dtlr
@@ -312,8 +234,8 @@ extern "C" int dtlr_mha_grad(const float* q, const float* k, const float* v, int
     const int C = H * 32;
     const long ld = row_stride > 0 ? row_stride : C;
     if (ld < C || (ld & 3) || (long)B * L * ld >= (1l << 33)) return DTLR_ESHAPE;
-    if (sg_mis(q, 15) || sg_mis(k, 15) || sg_mis(v, 15) || sg_mis(grad_out, 15) || sg_mis(dq, 15) || sg_mis(dk, 15) || sg_mis(dv, 15) ||
-        sg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(q, 15) || misaligned(k, 15) || misaligned(v, 15) || misaligned(grad_out, 15) || misaligned(dq, 15) || misaligned(dk, 15) || misaligned(dv, 15) ||
+        misaligned(workspace, 15)) return DTLR_EINVAL;
     const int Lp = (int)sg_lp(L);
     const long plane = (long)B * H * Lp;
     float* stats = static_cast<float*>(workspace);
@@ -339,11 +261,11 @@ extern "C" int dtlr_self_recompute(const void* t, const void* p, int x_dtype, in
     clear_stale_error();
     if (!t || !p || !Win || !bin || !Wo || !bo || !gamma2 || !beta2 || !x || !qkv || !a || !x0 || !s || !workspace) return DTLR_EINVAL;
     if (B <= 0 || L <= 0) return DTLR_EINVAL;
-    if (x_dtype != DTLR_F32 && x_dtype != DTLR_H16) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(x_dtype)) return DTLR_EDTYPE;
     if (!dtlr_self_recompute_workspace_bytes(B, L)) return DTLR_ESHAPE;
     const long M = (long)B * L;
-    if (sg_mis(t, x_dtype == DTLR_F32 ? 3 : 1) || sg_mis(p, x_dtype == DTLR_F32 ? 3 : 1) || sg_mis(x, 15) || sg_mis(qkv, 15) || sg_mis(a, 15) ||
-        sg_mis(x0, 15) || sg_mis(s, 15) || sg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(t, x_dtype == DTLR_F32 ? 3 : 1) || misaligned(p, x_dtype == DTLR_F32 ? 3 : 1) || misaligned(x, 15) || misaligned(qkv, 15) || misaligned(a, 15) ||
+        misaligned(x0, 15) || misaligned(s, 15) || misaligned(workspace, 15)) return DTLR_EINVAL;
     float* WinT = static_cast<float*>(workspace);                   // [256][768]
     float* WoT = WinT + (long)GR_D * SG_QKV;                         // [256][256]
     float* qk = WoT + (long)GR_D * GR_D;                             // [M][512]: the image dtlr_mha_forward reads
@@ -351,15 +273,15 @@ extern "C" int dtlr_self_recompute(const void* t, const void* p, int x_dtype, in
     float* vt = vv + M * GR_D;                                       // dtlr_mha_forward's workspace
     const hipStream_t st = (hipStream_t)stream;
     const int h16 = x_dtype != DTLR_F32;
-    const unsigned tiles = (unsigned)((M + GR_TR - 1) / GR_TR);
-    if (int rc = launch<sg_transpose_kernel>(dim3(GR_D / 32, SG_QKV / 32), dim3(256), 0, st, Win, WinT, SG_QKV, GR_D)) return rc;
-    if (int rc = launch<sg_transpose_kernel>(dim3(GR_D / 32, GR_D / 32), dim3(256), 0, st, Wo, WoT, GR_D, GR_D)) return rc;
-    if (int rc = launch<sg_rows_gemm_kernel>(dim3(tiles, 2), dim3(256), 0, st, t, p, h16, M, (const float*)WinT, SG_QKV, 2 * GR_D, bin,
-                                             (const void*)nullptr, 0, qkv, SG_QKV, qk, 2 * GR_D, x)) return rc;
-    if (int rc = launch<sg_rows_gemm_kernel>(dim3(tiles, 1), dim3(256), 0, st, t, (const void*)nullptr, h16, M, (const float*)(WinT + 2 * GR_D), SG_QKV,
-                                             GR_D, bin + 2 * GR_D, (const void*)nullptr, 0, qkv + 2 * GR_D, SG_QKV, vv, GR_D, (float*)nullptr)) return rc;
+    if (int rc = gr_transpose(Win, WinT, SG_QKV, GR_D, st)) return rc;
+    if (int rc = gr_transpose(Wo, WoT, GR_D, GR_D, st)) return rc;
+    // [Q | K] of t + p, then V of t: both into qkv and into the images dtlr_mha_forward reads
+    if (int rc = gr_rows_gemm256({.A = t, .A2 = p, .a_h16 = h16, .M = M, .Wt = WinT, .ldw = SG_QKV, .N = 2 * GR_D, .bias = bin, .out = qkv,
+                                  .ldo = SG_QKV, .out2 = qk, .ldo2 = 2 * GR_D, .xsum = x}, st)) return rc;
+    if (int rc = gr_rows_gemm256({.A = t, .a_h16 = h16, .M = M, .Wt = WinT + 2 * GR_D, .ldw = SG_QKV, .N = GR_D, .bias = bin + 2 * GR_D,
+                                  .out = qkv + 2 * GR_D, .ldo = SG_QKV, .out2 = vv, .ldo2 = GR_D}, st)) return rc;
     if (int rc = dtlr_mha_forward(qk, vv, vt, a, B, L, DTLR_SELF_HEADS, DTLR_SELF_HEAD_DIM, DTLR_F32, stream)) return rc;
-    if (int rc = launch<sg_rows_gemm_kernel>(dim3(tiles, 1), dim3(256), 0, st, (const void*)a, (const void*)nullptr, 0, M, (const float*)WoT, GR_D, GR_D,
-                                             bo, t, h16, x0, GR_D, (float*)nullptr, 0, (float*)nullptr)) return rc;
-    return launch<sg_ln_kernel>(dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const float*)x0, gamma2, beta2, s, M, eps);
+    if (int rc = gr_rows_gemm256({.A = a, .M = M, .Wt = WoT, .ldw = GR_D, .N = GR_D, .bias = bo, .res = t, .res_h16 = h16, .out = x0, .ldo = GR_D}, st))
+        return rc;
+    return gr_layernorm256(x0, gamma2, beta2, s, M, eps, st);
 }

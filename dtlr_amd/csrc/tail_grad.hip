@@ -10,7 +10,8 @@
 //   * tg_rows_gemm_kernel: out[M, N] = epilogue(A[M, K] Wt[K, N]), one workgroup a tile of 32 rows x 256 columns, thread n one column for
 //     the 32 rows.  A goes to LDS 32 k at a time, transposed ([k][row]), and is broadcast from there; the weight is read k-major,
 //     coalesced over n (W of the class head, W2 of the FFN and W0 / W1 of the box MLP ARE k-major for their input gradients; the
-//     forward products read transposes made in the workspace).  32 terms in an fp32 accumulator, those stages in an fp64 one.
+//     forward products read transposes made in the workspace by grad_rows.h's gr_transpose, the kernel the cross-attention and
+//     self-attention gradients use too).  32 terms in an fp32 accumulator, those stages in an fp64 one.
 //     The products are plain fp32 FMAs: exact fp32 products, the reason DESIGN section 11 gives.
 //   * hg_partial_tile / hg_reduce (head_grad_tile.h) for the two d^T x products of the FFN, whose reduction runs over M.
 // The LayerNorm backward is one wavefront a row; its column sums are taken 32 rows at a time in fp32 by each wavefront, then in fp64,
@@ -64,18 +65,6 @@ __global__ __launch_bounds__(256) void tg_rows_gemm_kernel(const void* __restric
         if (accumulate) f += out[m * ldo + n];
         out[m * ldo + n] = f;
     }
-}
-
-// dst[c][r] = src[r][c], src [R, C]
-__global__ __launch_bounds__(256) void tg_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int C)
-{
-    __shared__ float t[32][33];
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int j = ty; j < 32; j += 8)
-        if (r0 + j < R && c0 + tx < C) t[j][tx] = src[(long)(r0 + j) * C + c0 + tx];
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (c0 + j < C && r0 + tx < R) dst[(long)(c0 + j) * R + r0 + tx] = t[tx][j];
 }
 
 __global__ __launch_bounds__(256) void tg_cast_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, long n)
@@ -273,9 +262,6 @@ __global__ __launch_bounds__(256) void tg_ffn_reduce_kernel(TgProb p0, TgProb p1
 }
 
 static inline bool tg_ffn_ok(long M, int F) { return M > 0 && M <= 0x7fffffffl && F >= 64 && F <= DTLR_TAIL_MAX_FFN && F % 64 == 0; }
-static inline bool tg_dtype_ok(int dt) { return dt == DTLR_F32 || dt == DTLR_H16; }
-static inline bool tg_mis(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-static inline unsigned tg_tiles(long M) { return (unsigned)((M + GR_TR - 1) / GR_TR); }
 
 // the workspace of dtlr_ffn_grad
 struct FgWs { float *da, *u32, *part0, *part1; double *pb0, *pb1; long bytes; };
@@ -303,7 +289,7 @@ extern "C" int dtlr_head_dx(const float* G, const float* W, float* dh, long M, i
     clear_stale_error();
     if (!G || !W || !dh || M <= 0 || C <= 0) return DTLR_EINVAL;
     if (C > DTLR_TAIL_MAX_CLASSES || M > 0x7fffffffl) return DTLR_ESHAPE;
-    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, (hipStream_t)stream, (const void*)G, 0, M, C, W, (long)GR_D, GR_D,
+    return launch<tg_rows_gemm_kernel>(dim3(gr_tiles(M), 1), dim3(256), 0, (hipStream_t)stream, (const void*)G, 0, M, C, W, (long)GR_D, GR_D,
                                        (const float*)nullptr, (const void*)nullptr, 0, (const float*)nullptr, dh, (long)GR_D, 0, accumulate != 0);
 }
 
@@ -326,23 +312,23 @@ extern "C" int dtlr_box_mlp_dx(const void* x_ptrs, const void* dz_ptrs, const vo
     clear_stale_error();
     if (!x_ptrs || !dz_ptrs || !dh_ptrs || !W0 || !b0 || !W1 || !b1 || !W2 || !workspace) return DTLR_EINVAL;
     if (A < 1 || M <= 0 || (rows && R <= 0)) return DTLR_EINVAL;
-    if (!tg_dtype_ok(x_dtype)) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(x_dtype)) return DTLR_EDTYPE;
     const long rpad = tg_box_rpad(A, M, rows ? R : 0);
     if (!rpad) return DTLR_ESHAPE;
-    if (tg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(workspace, 15)) return DTLR_EINVAL;
     TgApps apps{};
     for (int a = 0; a < A; ++a) {
         apps.x[a] = static_cast<const void* const*>(x_ptrs)[a];
         apps.dz[a] = static_cast<const float* const*>(dz_ptrs)[a];
         apps.dh[a] = static_cast<float* const*>(dh_ptrs)[a];
-        if (!apps.x[a] || !apps.dz[a] || !apps.dh[a] || tg_mis(apps.dz[a], 15) || tg_mis(apps.dh[a], 3)) return DTLR_EINVAL;
-        if (tg_mis(apps.x[a], x_dtype == DTLR_F32 ? 3 : 1)) return DTLR_EINVAL;
+        if (!apps.x[a] || !apps.dz[a] || !apps.dh[a] || misaligned(apps.dz[a], 15) || misaligned(apps.dh[a], 3)) return DTLR_EINVAL;
+        if (misaligned(apps.x[a], x_dtype == DTLR_F32 ? 3 : 1)) return DTLR_EINVAL;
     }
     float* W0T = static_cast<float*>(workspace);
     float* W1T = W0T + GR_D * GR_D;
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W0, W0T, GR_D, GR_D)) return rc;
-    if (int rc = launch<tg_transpose_kernel>(dim3(8, 8), dim3(256), 0, st, W1, W1T, GR_D, GR_D)) return rc;
+    if (int rc = gr_transpose(W0, W0T, GR_D, GR_D, st)) return rc;
+    if (int rc = gr_transpose(W1, W1T, GR_D, GR_D, st)) return rc;
     const size_t lds = (size_t)2 * GR_D * GR_LD * sizeof(float);
     return launch<tg_box_dx_kernel>(dim3((unsigned)((long)A * rpad / GR_TR)), dim3(256), lds, st, apps, rows, M, rows ? (long)R : M, rpad,
                                     (int)(x_dtype != DTLR_F32), (const float*)W0T, b0, (const float*)W1T, b1, W0, W1, W2);
@@ -359,9 +345,9 @@ extern "C" int dtlr_ln_backward(const void* x, int x_dtype, const float* gamma, 
 {
     clear_stale_error();
     if (!x || !gamma || !g || !dgamma || !dbeta || !workspace || M <= 0 || dx_row0 < 0) return DTLR_EINVAL;
-    if (!tg_dtype_ok(x_dtype)) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(x_dtype)) return DTLR_EDTYPE;
     if (M > (1l << 40)) return DTLR_ESHAPE;
-    if (tg_mis(x, x_dtype == DTLR_F32 ? 15 : 7) || tg_mis(gamma, 3) || tg_mis(g, 15) || tg_mis(dx, 15) || tg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(x, x_dtype == DTLR_F32 ? 15 : 7) || misaligned(gamma, 3) || misaligned(g, 15) || misaligned(dx, 15) || misaligned(workspace, 15)) return DTLR_EINVAL;
     const LnPlan p = ln_plan(M);
     const hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -383,24 +369,24 @@ extern "C" int dtlr_ffn_recompute(const void* u, int u_dtype, const float* W1, c
 {
     clear_stale_error();
     if (!u || !W1 || !b1 || !W2 || !b2 || !h || !y || !workspace || M <= 0 || F <= 0) return DTLR_EINVAL;
-    if (!tg_dtype_ok(u_dtype)) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(u_dtype)) return DTLR_EDTYPE;
     if (!tg_ffn_ok(M, F)) return DTLR_ESHAPE;
-    if (tg_mis(u, u_dtype == DTLR_F32 ? 3 : 1) || tg_mis(h, 3) || tg_mis(y, 3) || tg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(u, u_dtype == DTLR_F32 ? 3 : 1) || misaligned(h, 3) || misaligned(y, 3) || misaligned(workspace, 15)) return DTLR_EINVAL;
     float* W1T = static_cast<float*>(workspace);                   // [256][F]
     float* W2T = W1T + (long)F * GR_D;                              // [F][256]
     const hipStream_t st = (hipStream_t)stream;
     const int h16 = u_dtype != DTLR_F32;
-    if (int rc = launch<tg_transpose_kernel>(dim3(GR_D / 32, (unsigned)(F / 32)), dim3(256), 0, st, W1, W1T, F, GR_D)) return rc;
-    if (int rc = launch<tg_transpose_kernel>(dim3((unsigned)(F / 32), GR_D / 32), dim3(256), 0, st, W2, W2T, GR_D, F)) return rc;
-    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, u, h16, M, GR_D, (const float*)W1T,
+    if (int rc = gr_transpose(W1, W1T, F, GR_D, st)) return rc;
+    if (int rc = gr_transpose(W2, W2T, GR_D, F, st)) return rc;
+    if (int rc = launch<tg_rows_gemm_kernel>(dim3(gr_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, u, h16, M, GR_D, (const float*)W1T,
                                              (long)F, F, b1, (const void*)nullptr, 0, (const float*)nullptr, h, (long)F, 1, 0)) return rc;
-    return launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), 1), dim3(256), 0, st, (const void*)h, 0, M, F, (const float*)W2T, (long)GR_D, GR_D, b2,
+    return launch<tg_rows_gemm_kernel>(dim3(gr_tiles(M), 1), dim3(256), 0, st, (const void*)h, 0, M, F, (const float*)W2T, (long)GR_D, GR_D, b2,
                                        u, h16, (const float*)nullptr, y, (long)GR_D, 0, 0);
 }
 
 extern "C" long dtlr_ffn_grad_workspace_bytes(long M, int F, int u_dtype)
 {
-    if (!tg_ffn_ok(M, F) || !tg_dtype_ok(u_dtype)) return 0;
+    if (!tg_ffn_ok(M, F) || !is_f32_or_h16(u_dtype)) return 0;
     return fg_ws(nullptr, M, F, u_dtype != DTLR_F32, hg_plan(M, F, GR_D).splits).bytes;
 }
 
@@ -409,15 +395,15 @@ extern "C" int dtlr_ffn_grad(const void* u, int u_dtype, const float* h, const f
 {
     clear_stale_error();
     if (!u || !h || !dy || !W2 || !grad || !workspace || M <= 0 || F <= 0) return DTLR_EINVAL;
-    if (!tg_dtype_ok(u_dtype)) return DTLR_EDTYPE;
+    if (!is_f32_or_h16(u_dtype)) return DTLR_EDTYPE;
     if (!tg_ffn_ok(M, F)) return DTLR_ESHAPE;
-    if (tg_mis(u, u_dtype == DTLR_F32 ? 15 : 1) || tg_mis(h, 15) || tg_mis(dy, 15) || tg_mis(grad, 3) || tg_mis(workspace, 15)) return DTLR_EINVAL;
+    if (misaligned(u, u_dtype == DTLR_F32 ? 15 : 1) || misaligned(h, 15) || misaligned(dy, 15) || misaligned(grad, 3) || misaligned(workspace, 15)) return DTLR_EINVAL;
     const bool cast = u_dtype != DTLR_F32;
     const HgPlan hp = hg_plan(M, F, GR_D);                          // tiles_c tiles_d = 4 F / 64 for both products: one plan
     const FgWs w = fg_ws(static_cast<float*>(workspace), M, F, cast, hp.splits);
     const hipStream_t st = (hipStream_t)stream;
     // da = [h > 0] (dy W2): W2 [256][F] is k-major for this product
-    if (int rc = launch<tg_rows_gemm_kernel>(dim3(tg_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, (const void*)dy, 0, M, GR_D, W2, (long)F,
+    if (int rc = launch<tg_rows_gemm_kernel>(dim3(gr_tiles(M), (unsigned)((F + 255) / 256)), dim3(256), 0, st, (const void*)dy, 0, M, GR_D, W2, (long)F,
                                              F, (const float*)nullptr, (const void*)nullptr, 0, h, w.da, (long)F, 0, 0)) return rc;
     const float* u32 = static_cast<const float*>(u);
     if (cast) {

@@ -67,13 +67,6 @@ def mha_grad(q, k, v, grad_out, n_heads: int):
     return dq, dk, dv
 
 
-def _masters(params, dev, what):
-    ws = [w.contiguous() for w in params]
-    if len(ws) != 6 or tuple(tuple(w.shape) for w in ws) != SELF_SHAPES or any(w.dtype != torch.float32 or w.device != dev for w in ws):
-        raise ValueError(f"{what}: the masters must be fp32 on {dev}: in_proj [768,256] / [768], out_proj [256,256] / [256], norm2 [256] / [256]")
-    return ws
-
-
 @_lib.op
 def self_recompute(t, qpos, self_params: Sequence[torch.Tensor], eps: float = LN_EPS) -> Dict[str, torch.Tensor]:
     """dtlr_self_recompute: the last decoder layer's self-attention block in fp32 from the masters.  t, qpos [B,L,256] (fp32 / bf16 / fp16:
@@ -87,7 +80,8 @@ def self_recompute(t, qpos, self_params: Sequence[torch.Tensor], eps: float = LN
     B, L = int(t.shape[0]), int(t.shape[1])
     dev = t.device
     t, qpos = t.contiguous(), qpos.contiguous()
-    win, bin_, wo, bo, g2, b2 = _masters(self_params, dev, "self_recompute")
+    win, bin_, wo, bo, g2, b2 = _lib.masters(self_params, SELF_SHAPES, dev, f"self_recompute: the masters must be fp32 on {dev}: in_proj [768,256] / [768], "
+                                             "out_proj [256,256] / [256], norm2 [256] / [256]")
     M = B * L
     f = lambda n: torch.empty((M, n), dtype=torch.float32, device=dev)
     out = {"x": f(SELF_HIDDEN), "qkv": f(3 * SELF_HIDDEN), "a": f(SELF_HIDDEN), "x0": f(SELF_HIDDEN), "s": f(SELF_HIDDEN)}

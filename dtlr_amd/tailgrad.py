@@ -97,20 +97,14 @@ def ln_backward(x, gamma, g, dx_row0: Optional[int] = 0, eps: float = LN_EPS, dg
     return dx, dgamma, dbeta
 
 
-def _ffn_weights(weights, dev, what):
-    ws_ = [w.contiguous() for w in weights]
-    F = int(ws_[0].shape[0]) if ws_ and ws_[0].dim() == 2 else 0
-    if len(ws_) != 4 or [tuple(w.shape) for w in ws_] != list(tail_shapes(F)[:4]) or any(w.dtype != torch.float32 or w.device != dev for w in ws_):
-        raise ValueError(f"{what}: the weights must be fp32 (W1 [F,256], b1 [F], W2 [256,F], b2 [256]) on {dev}")
-    return ws_, F
-
-
 @_lib.op
 def ffn_recompute(u, weights: Sequence[torch.Tensor]):
     """dtlr_ffn_recompute: u [M,256] (fp32 / bf16 / fp16: the last decoder layer's state after norm1), the fp32 masters (W1, b1, W2, b2)
     -> (h [M,F] fp32 = relu(W1 u + b1), y [M,256] fp32 = u + W2 h + b2)."""
     u, M = _rows(u, "ffn_recompute: u")
-    (w1, b1, w2, b2), F = _ffn_weights(weights, u.device, "ffn_recompute")
+    F = int(weights[0].shape[0]) if len(weights) and weights[0].dim() == 2 else 0
+    w1, b1, w2, b2 = _lib.masters(weights, tail_shapes(F)[:4], u.device,
+                                  f"ffn_recompute: the weights must be fp32 (W1 [F,256], b1 [F], W2 [256,F], b2 [256]) on {u.device}")
     L = _lib.lib(u.dtype)
     ws = _lib.workspace(_lib.query(L, "dtlr_ffn_recompute_workspace_bytes", M, F), u.device, f"dtlr_ffn_recompute M={M} F={F}")
     h = torch.empty((M, F), dtype=torch.float32, device=u.device)

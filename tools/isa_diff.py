@@ -2,6 +2,8 @@
 """Which kernels of a .hip file changed between a git revision and the working tree -- at the instruction level (no GPU).
     python tools/isa_diff.py dtlr_amd/csrc/msda_enc.hip [--rev HEAD] [--defs=-DDTLR_HALF_IS_F16]
     python tools/isa_diff.py --all [--rev HEAD] [--defs=...] [-j N]        every csrc/*.hip: one line per kernel plus a total
+    python tools/isa_diff.py --all --moved sg_ln_kernel=gr_layernorm256_kernel ..       a kernel that was renamed or moved to another file:
+                                                                           MOVED-SAME (not counted as changed) or MOVED-CHANGED
 Compiles both versions for gfx950 with --save-temps and compares every kernel's instruction stream (basic-block label numbers
 normalised).  The old side is compiled inside a copy of the REVISION's dtlr_amd/csrc and include (git archive), so a header that
 changed between the two does not leak into it.  Use: adding a variant / template instantiation next to a verified kernel, or moving
@@ -41,10 +43,14 @@ def kernels(tree, name, defs):
     return out
 
 
-def diff_file(old_tree, name, defs):
-    """(report lines, kernels compared, kernels that differ) for one file; a file the revision does not have is all NEW."""
+def diff_file(old_tree, name, defs, gone=None, came=None):
+    """(report lines, kernels compared, kernels that differ) for one file; a file the revision does not have is all NEW.  gone / came:
+    dicts that receive the bodies of the REMOVED / NEW kernels (for --moved)."""
     a = kernels(old_tree, name, defs) if os.path.exists(f"{old_tree}/{CSRC}/{name}") else {}
-    b = kernels(ROOT, name, defs)
+    b = kernels(ROOT, name, defs) if os.path.exists(f"{ROOT}/{CSRC}/{name}") else {}
+    if gone is not None:
+        gone.update({k: a[k] for k in a if k not in b})
+        came.update({k: b[k] for k in b if k not in a})
     rep, changed = [], 0
     for k in sorted(set(a) | set(b)):
         if k not in a:
@@ -67,6 +73,8 @@ def main():
     ap.add_argument("--rev", default="HEAD")
     ap.add_argument("--defs", default="")
     ap.add_argument("-j", type=int, default=8, help="files compiled at a time with --all")
+    ap.add_argument("--moved", action="append", default=[], metavar="OLD=NEW", help="with --all: a REMOVED kernel whose symbol contains OLD is "
+                    "compared with the NEW kernel whose symbol contains NEW (a kernel renamed or moved to another file); repeatable")
     args = ap.parse_args()
     if bool(args.source) == args.all:
         ap.error("give one source file or --all")
@@ -82,13 +90,26 @@ def main():
             print("\n".join(rep))
             sys.exit(1 if changed else 0)
         names = sorted({os.path.basename(p) for t in (ROOT, old_tree) for p in glob.glob(f"{t}/{CSRC}/*.hip")})
-        total = changed = new = 0
+        total = changed = new = moved = 0
+        gone, came = {}, {}
         with concurrent.futures.ThreadPoolExecutor(args.j) as pool:
-            for name, (rep, n, c) in zip(names, pool.map(lambda f: diff_file(old_tree, f, defs), names)):
-                for line in rep:
-                    print(f"{name:16s} {line}")
-                total, changed, new = total + n, changed + c, new + sum(x.startswith("NEW") for x in rep)
-        print(f"TOTAL    {len(names)} files, {total} kernels: {total - changed - new} SAME, {new} NEW, {changed} CHANGED or REMOVED  (rev {args.rev}, defs '{args.defs}')")
+            reports = list(zip(names, pool.map(lambda f: diff_file(old_tree, f, defs, gone, came), names)))
+        verdict = {}                                     # REMOVED symbol -> its line as a moved kernel
+        for old, new_ in (m.split("=", 1) for m in args.moved):
+            for k in (k for k in gone if old in k):
+                to = [n for n in came if new_ in n]
+                if len(to) != 1:
+                    sys.exit(f"--moved {old}={new_}: {len(to)} NEW kernels contain '{new_}'")
+                same = gone[k] == came[to[0]]
+                verdict[k] = f"MOVED-{'SAME' if same else 'CHANGED'}  {k} -> {to[0]}  ({len(gone[k])} -> {len(came[to[0]])})"
+                moved += same
+        for name, (rep, n, c) in reports:
+            for line in rep:
+                print(f"{name:16s} {verdict.get(line.split()[1], line) if line.startswith('REMOVED') else line}")
+            total, changed, new = total + n, changed + c, new + sum(x.startswith("NEW") for x in rep)
+        changed -= moved
+        print(f"TOTAL    {len(names)} files, {total} kernels: {total - changed - new - moved} SAME, {new} NEW, {moved} MOVED-SAME, {changed} CHANGED or REMOVED  "
+              f"(rev {args.rev}, defs '{args.defs}')")
         sys.exit(1 if changed else 0)
 
 
